@@ -10,10 +10,14 @@ N=8 12.5 M per GPU = BASELINE.json configs[2], 100 M pairs over the node), the i
 collective is the all-reduce of the six HitCounters per step (RCCL over xGMI).  `python bench.py --gpus N` without a
 launcher re-executes itself under torch.distributed.run with N ranks.
 
-Prints ONE JSON line on rank 0 (see the driver contract) with `roofline` and `cpu_baseline` objects.  At N=1 the same
-line also carries, under `other_configs`, bounded legs of configs[3] (the -p index: BooPHF walked on the device, and the
-same index expanded into the bucket table at load) and configs[4] (-s), each with its own value, kernel time, roofline
-and parity against the oracle, and under `pcie_inclusive` / `end_to_end` what a caller with host buffers / FASTQ files sees.
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run does only what that line's headline needs: it sets
+up (the index comes from the cache that build() prepares), warms up, times the K steps and prints the line, with
+`cpu_baseline` null and the roofline drawn from the recorded bytes per pair.  `--dump-outputs DIR` also writes what the
+last timed step computed (a fixed, seeded sample of the hits) as .npy files.  `--full` adds everything else: at N=1 the
+`cpu_baseline` and `roofline` objects and the parity of a sample against the oracle, under `other_configs` bounded legs of
+configs[3] (the -p index: BooPHF walked on the device, and the same index expanded into the bucket table at load) and
+configs[4] (-s), each with its own value, kernel time, roofline and parity against the oracle, under `input_variants` other
+input distributions, and under `pcie_inclusive` / `end_to_end` what a caller with host buffers / FASTQ files sees.
 """
 import argparse
 import ctypes
@@ -132,8 +136,19 @@ class BackgroundBuilds:
                 p.wait()
 
 
+def default_cache():
+    """where the synthetic indices live: $QMAP_BENCH_CACHE, else the user's cache directory (build() prepares the headline's
+    index there, so that a plain run does not spend its first minute building it)"""
+    if os.environ.get("QMAP_BENCH_CACHE"):
+        return os.environ["QMAP_BENCH_CACHE"]
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    return os.path.join(base, "rapmap_amd", "bench")
+
+
 def spec_args(spec):
-    """'ph' | 'par<frac>,<family>' -> keyword arguments of build_or_reuse_index"""
+    """'dense' | 'ph' | 'par<frac>,<family>' -> keyword arguments of build_or_reuse_index"""
+    if spec == "dense":
+        return {}
     if spec == "ph":
         return dict(perfect_hash=True)
     a, b = spec[3:].split(",")
@@ -277,7 +292,8 @@ class Oracles:
 
 def timed_steps(mp, opts, ptr, n, L, steps, warmup, world, device, qd, host=None):
     """W untimed + K timed passes of the hot path, bracketed by barrier + synchronize; max over ranks.
-    host = (packed1, off, exc1, packed2, exc2): --reads-from-host, the batch comes up from page-locked host memory in every step"""
+    host = (packed1, off, exc1, packed2, exc2): --reads-from-host, the batch comes up from page-locked host memory in every step
+    -> (seconds, kernel ms per step, counters summed over the steps and ranks, the last step's MapResult)"""
     def step():
         if host is not None:
             r = mp.map_pairs_prepacked(host[0], host[1], host[2], host[3], host[1], host[4], opts=opts, fetch=False)
@@ -311,7 +327,35 @@ def timed_steps(mp, opts, ptr, n, L, steps, warmup, world, device, qd, host=None
     tt = torch.tensor([el], dtype=torch.float64, device=device)
     if dist.is_initialized():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-    return float(tt.item()), kernel_ms, tot
+    return float(tt.item()), kernel_ms, tot, r
+
+
+DUMP_SEED = 20261016
+DUMP_PAIRS = 1 << 16
+DUMP_BUDGET = 60_000_000      # bytes of array data; the .npy headers stay well inside 64 MB
+
+
+def dump_outputs(out_dir, ra, qd, mp, r, n):
+    """what the last timed step computed, as a caller of qm_map_device receives it (hit_offsets, the hit records, the six
+    HitCounters), downloaded after the timed region and written as float64 .npy files: the counters whole, the hits of a fixed
+    seeded sample of DUMP_PAIRS pairs (every field of HIT_DTYPE in a file of its own, the pairs in ascending order, each
+    pair's hits in the order the path returned them).  When the sample holds more hits than DUMP_BUDGET allows, its first pairs
+    up to the budget give theirs; hits_per_pair covers the whole sample either way."""
+    os.makedirs(out_dir, exist_ok=True)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    hits = np.zeros(max(r.n_hits, 0), dtype=ra.api.HIT_DTYPE)
+    ra.api._check(ra.api.lib().qm_fetch_hits(mp._h, offs.ctypes.data, hits.ctypes.data if r.n_hits else None))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_PAIRS), replace=False))
+    cnt = offs[pick + 1] - offs[pick]
+    per_hit = 8 * len(ra.api.HIT_DTYPE.names)
+    room = max(0, DUMP_BUDGET - 8 * (2 * pick.size + len(qd.COUNTER_KEYS))) // per_hit
+    keep = int(np.searchsorted(np.cumsum(cnt), room, side="right"))
+    sel = np.concatenate([np.arange(offs[p], offs[p + 1]) for p in pick[:keep]]) if keep else np.zeros(0, dtype=np.int64)
+    arrays = {"counters": np.array([r.counters[k] for k in qd.COUNTER_KEYS]), "pair_index": pick, "hits_per_pair": cnt}
+    arrays.update(("hit_" + f, hits[f][sel]) for f in ra.api.HIT_DTYPE.names)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log("outputs of the last timed step -> %s (%d of %d sampled pairs with their %d hits)" % (out_dir, keep, pick.size, sel.size))
 
 
 def cpu_and_parity(orc, mp, opts, oopts, s1, s2, off, ptr, n, L, cpu_seconds, sweep=True):
@@ -508,6 +552,11 @@ def main():
     ap.add_argument("--genes", type=int, default=40000, help="synthetic genes (40000 ~ 200k transcripts, 3e8 bases)")
     ap.add_argument("--pairs", type=int, default=None, help="read pairs per GPU per step (default: 10 M = configs[1]; "
                     "12.5 M at 8 GPUs = configs[2], 100 M pairs over the node)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: cpu_baseline, roofline and "
+                    "parity against the oracle, and at N=1 the other_configs / input_variants / side legs (each can still be left out "
+                    "with its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (counters, hits of a "
+                    "fixed seeded sample of pairs) to DIR/<name>.npy as float64")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="N=1: skip the bounded legs of configs[3] and configs[4]")
@@ -527,13 +576,16 @@ def main():
                     "never the contract's `value` (the line says so in config.reads_from_host)")
     ap.add_argument("--build-only", default=None, help=argparse.SUPPRESS)      # (BackgroundBuilds' child: build these indices and exit)
     ap.add_argument("--read-len", type=int, default=100, help="read length (BASELINE.json: 100; 129..256 runs the NS=4 kernels)")
-    ap.add_argument("--cache", default=os.environ.get("QMAP_BENCH_CACHE", "/dev/shm" if os.path.isdir("/dev/shm") else "/tmp"))
+    ap.add_argument("--cache", default=default_cache(), help="where the synthetic indices are built and kept")
     ap.add_argument("--e2e-dir", default=os.environ.get("QMAP_BENCH_E2E_DIR", "/tmp"), help="where the end_to_end leg puts its FASTQ files")
     ap.add_argument("--e2e-threads", type=int, default=24, help="ingest workers of the end_to_end leg (the engine alone peaks at 16-32 on this host, pinned to the socket that holds the files: profiles/r04/ingest_after_pin.log)")
     ap.add_argument("--gz-leg", type=int, default=0, help="N=1: also map the first GZ_LEG pairs from ordinary `gzip -6` files (end_to_end_gzip; opt-in: writing the files takes about a minute per 4 M pairs)")
     ap.add_argument("--e2e-copies", type=int, default=4, help="the end_to_end leg's FASTQ files hold the batch this many times (4 x 10 M = 40 M pairs)")
     ap.add_argument("--compat-pairs", type=int, default=8_000_000, help="pairs of the batch the compat_face leg runs through the reference's call surface")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    checks = args.full and not args.no_cpu_baseline     # the oracle legs (cpu_baseline, parity, and at N=1 the legs behind them)
 
     if args.build_only:
         os.nice(5)
@@ -591,7 +643,7 @@ def main():
     k, L = 31, args.read_len
     plain_head = not args.perfect_hash and not args.sel_aln and L == 100 and not args.paralogs and not args.repeat_family
     bg_specs = []
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and plain_head:
+    if rank == 0 and world == 1 and checks and plain_head:
         if not args.no_other_configs:
             bg_specs.append("ph")
         if not args.no_input_variants:
@@ -623,8 +675,10 @@ def main():
         host = (ra.api.pinned_copy(p1[0]), ra.api.pinned_copy(hoff), ra.api.pinned_copy(p1[2]) if len(p1[2]) else p1[2], ra.api.pinned_copy(p2[0]),
                 ra.api.pinned_copy(p2[2]) if len(p2[2]) else p2[2])
     with bg.quiet():
-        el, kernel_ms, tot = timed_steps(mp, opts, ptr, n, L, args.steps, args.warmup, world, device, qd, host=host)
+        el, kernel_ms, tot, last = timed_steps(mp, opts, ptr, n, L, args.steps, args.warmup, world, device, qd, host=host)
     head_stats = kernel_stats(mp, n)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ra, qd, mp, last, n)
     total_pairs = n * world * args.steps
     value = total_pairs / el / 1e6
 
@@ -657,7 +711,7 @@ def main():
                              if grouped else None)
 
     # ---- cpu_baseline + roofline counters: rank 0, N=1 only, bounded sample of the same workload
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and checks:
         from oracle import oracle
         oracles = Oracles()
         orc = oracles.get(idx_dir)
@@ -734,7 +788,7 @@ def main():
                 log("input_variants failed: %r" % (ex,))
         bg.close()
     elif rank == 0:
-        # N>1 (or --no-cpu-baseline): no oracle leg.  The roofline of rank 0's kernel still uses the algorithmic bytes
+        # N>1 (or a plain run, or --no-cpu-baseline): no oracle leg.  The roofline of rank 0's kernel still uses the algorithmic bytes
         # per pair of this workload: recorded by an N=1 run on this box, else the committed figure of the default workload.
         out["cpu_baseline"] = None
         out["roofline"] = None
@@ -798,7 +852,7 @@ def input_variant_legs(args, ra, qd, oracles, oracle, qi, idx_dir, mp, text, sta
         torch.cuda.synchronize()
         ptr = (s1.data_ptr(), off.data_ptr(), s2.data_ptr(), off.data_ptr())
         with bg.quiet():
-            el, kms, tot = timed_steps(mapper, opts, ptr, m, L, 3, 1, 1, device, qd)
+            el, kms, tot, _ = timed_steps(mapper, opts, ptr, m, L, 3, 1, 1, device, qd)
         val = m * 3 / el / 1e6
         ks = kernel_stats(mapper, m)
         h1 = s1[: par * L].cpu().numpy(); h2 = s2[: par * L].cpu().numpy(); ho = off[: par + 1].cpu().numpy()
@@ -968,7 +1022,7 @@ def other_configs(oc, args, ra, qd, oracles, oracle, qi, idx_dir, mp, s1, s2, of
     def leg(name, mapper, o, key, bpp, w, cp, workload, extra=None, whole_step=False):
         ph_thread.join()                                     # (no timed step beside a thread of this process that holds the interpreter lock for long stretches)
         with args._bg.quiet():
-            el, kms, tot = timed_steps(mapper, o, ptr, n, L, steps, warm, 1, device, qd)
+            el, kms, tot, _ = timed_steps(mapper, o, ptr, n, L, steps, warm, 1, device, qd)
         val = n * steps / el / 1e6
         km = float(np.mean(kms))
         oc[name] = {"workload": workload, "value": round(val, 4), "unit": "M read-pairs/s", "steps": steps, "warmup": warm,

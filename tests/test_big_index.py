@@ -91,31 +91,42 @@ def test_suffix_array_and_hash_intervals_against_the_text(big_index):
 
 
 def test_hash_file_loads_in_the_references_container(big_index):
+    """the reference's own spp::sparse_hash_map (oracle/_ref) finds every record of this hash.bin and none of 200 000 absent keys;
+    where oracle/_ref cannot be built, its recorded verdict on these very bytes (tests/golden/reference_answers/)"""
     import rapmap_amd as ra
-    refso = os.path.join(ROOT, "oracle", "_ref", "libqm_ref.so")
-    if not os.path.exists(refso):
-        pytest.skip("oracle/_ref/libqm_ref.so not built (the reference tree is not on this box)")
+    import test_oracle_ref as tor
     qi = ra.QuasiIndex(big_index)
     try:
         h = qi.raw("hash")
-        R = C.CDLL(refso)
-        R.ref_spp_load.restype = C.c_void_p; R.ref_spp_load.argtypes = [C.c_char_p]
-        R.ref_spp_size.restype = C.c_int64; R.ref_spp_size.argtypes = [C.c_void_p]
-        R.ref_spp_find.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        R.ref_spp_free.argtypes = [C.c_void_p]
-        hd = R.ref_spp_load(os.path.join(big_index, "hash.bin").encode())
-        assert hd, "the reference's sparse_hash_map could not unserialize hash.bin"
         keys = np.ascontiguousarray(h["key"]); K = keys.size
-        assert int(R.ref_spp_size(hd)) == K
-        found = np.zeros(K, np.uint8); fl = np.zeros(K, np.int32); fu = np.zeros(K, np.int32)
-        R.ref_spp_find(hd, keys.ctypes.data, K, found.ctypes.data, fl.ctypes.data, fu.ctypes.data)
-        assert ((found == 1) & (fl.view(np.uint32) == h["lb"]) & (fu.view(np.uint32) == h["ub"])).all()
+        path = os.path.join(big_index, "hash.bin")
+        data = open(path, "rb").read()
         rng = np.random.default_rng(2)
         absent = rng.integers(0, 1 << 62, size=200_000, dtype=np.uint64)
         absent = absent[~np.isin(absent, keys)]
-        fa_ = np.zeros(absent.size, np.uint8); x = np.zeros(absent.size, np.int32); y = np.zeros(absent.size, np.int32)
-        R.ref_spp_find(hd, absent.ctypes.data, absent.size, fa_.ctypes.data, x.ctypes.data, y.ctypes.data)
-        R.ref_spp_free(hd)
-        assert fa_.sum() == 0
+
+        def live(R):
+            R.ref_spp_load.restype = C.c_void_p; R.ref_spp_load.argtypes = [C.c_char_p]
+            R.ref_spp_size.restype = C.c_int64; R.ref_spp_size.argtypes = [C.c_void_p]
+            R.ref_spp_find.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+            R.ref_spp_free.argtypes = [C.c_void_p]
+            hd = R.ref_spp_load(path.encode())
+            assert hd, "the reference's sparse_hash_map could not unserialize hash.bin"
+            try:
+                found = np.zeros(K, np.uint8); fl = np.zeros(K, np.int32); fu = np.zeros(K, np.int32)
+                R.ref_spp_find(hd, keys.ctypes.data, K, found.ctypes.data, fl.ctypes.data, fu.ctypes.data)
+                fa_ = np.zeros(absent.size, np.uint8); x = np.zeros(absent.size, np.int32); y = np.zeros(absent.size, np.int32)
+                R.ref_spp_find(hd, absent.ctypes.data, absent.size, fa_.ctypes.data, x.ctypes.data, y.ctypes.data)
+                return {"sha256": tor.sha256(data), "size": R.ref_spp_size(hd), "keys_found": tor.sha256(found.tobytes() + fl.tobytes() + fu.tobytes()),
+                        "absent": absent.size, "absent_found": int(fa_.sum())}
+            finally:
+                R.ref_spp_free(hd)
+        a = tor.answers("spp_big_index_hash", live, tor._ref())
+        assert str(a["sha256"]) == str(tor.sha256(data)), "not the hash.bin the reference's container read"
+        assert int(a["size"]) == K
+        # every key found, with the interval bounds our loader sees (as the container's int32 bytes)
+        want = np.ones(K, np.uint8).tobytes() + np.asarray(h["lb"], np.uint32).tobytes() + np.asarray(h["ub"], np.uint32).tobytes()
+        assert str(a["keys_found"]) == str(tor.sha256(want))
+        assert int(a["absent"]) == absent.size and int(a["absent_found"]) == 0
     finally:
         qi.close()

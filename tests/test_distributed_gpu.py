@@ -74,7 +74,7 @@ def test_bench_one_rank_on_the_nccl_backend(tmp_path):
     e = dict(os.environ)
     e["QMAP_BENCH_CACHE"] = str(tmp_path); e.pop("QMAP_BENCH_REHEARSAL", None)
     r = _launch(1, [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--genes", "800", "--pairs", "200000",
-                    "--cpu-seconds", "2", "--no-other-configs", "--no-side-legs"], env=e)
+                    "--cpu-seconds", "2", "--full", "--no-other-configs", "--no-side-legs"], env=e)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["collective"]["backend"] == "nccl" and out["collective"]["world_size"] == 1
@@ -139,13 +139,13 @@ def test_bench_spawns_its_own_ranks(tmp_path):
 
 
 def test_bench_single_gpu_line_has_the_contract_fields(tmp_path):
-    """the N=1 line on a small workload: metric fields, roofline, cpu_baseline, parity against the oracle"""
+    """the N=1 line of a --full run on a small workload: metric fields, roofline, cpu_baseline, parity against the oracle"""
     e = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     e["QMAP_BENCH_CACHE"] = str(tmp_path)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--genes", "800",
-                        "--pairs", "100000", "--cpu-seconds", "2"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=1500)
+                        "--pairs", "100000", "--cpu-seconds", "2", "--full"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -154,3 +154,32 @@ def test_bench_single_gpu_line_has_the_contract_fields(tmp_path):
     assert out["n_gpus"] == 1 and out["parity"]["bit_identical_to_oracle"] is True
     assert out["roofline"]["bound"] == "hbm" and 0 < out["roofline"]["frac"] < 1
     assert out["cpu_baseline"]["kind"] in ("port", "reference") and out["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """a plain N=1 run (no --full): the contract fields, no oracle leg, exactly --steps timed steps; --dump-outputs writes the
+    last timed step's counters and sampled hits as float64 .npy files, identical from one run to the next"""
+    e = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        e.pop(k, None)
+    e["QMAP_BENCH_CACHE"] = str(tmp_path / "cache")
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--genes", "800",
+                            "--pairs", "100000", "--dump-outputs", str(d)], cwd=ROOT, env=e, capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, r.stderr[-4000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert out["cpu_baseline"] is None and "parity" not in out and "other_configs" not in out
+        files = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64_000_000
+        assert all(a.dtype == np.float64 for a in files.values())
+        assert files["counters"][3] == 100000                      # numReads of the last step: every pair of the batch
+        assert files["hits_per_pair"].sum() == files["hit_tid"].size > 0
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

@@ -2,8 +2,13 @@
 image (oracle/Makefile.ref -> oracle/_ref/libqm_ref.so, built from /root/reference in place; see oracle/ref_harness.cpp):
 ksw2pp's KSW2Aligner + ksw_extz2_sse (row a17), the Kmer<32,1> codec (a1), boomphf::mphf load + lookup (a3) and rank9b (a8).
 This is what pins those four restatements; the collector / searcher / hit manager templates cannot be compiled here (they
-include the un-vendored cereal) and stay corroborated by the reference's SAM fixtures only."""
+include the un-vendored cereal) and stay corroborated by the reference's SAM fixtures only.
+
+Where oracle/_ref cannot be built (no reference tree on the machine), every question goes to the reference's recorded answers
+under tests/golden/reference_answers/ instead (answers() below); where it is built, the live answers must still equal the record.
+A question about a file our own code writes records that file's SHA-256 too: the recorded answers hold for those bytes only."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 import tarfile
@@ -14,16 +19,45 @@ import pytest
 from conftest import GOLD, ROOT
 
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libqm_ref.so")
+ANSWERS = os.path.join(GOLD, "reference_answers")
+
+
+def answers(name, live, ref):
+    """the reference's answers to one fixed set of questions, as a dict of arrays: live(ref) when the harness library is there
+    (compared with the record, or written to it with QM_RECORD_REFERENCE=1), else the record tests/golden/reference_answers/<name>.npz"""
+    path = os.path.join(ANSWERS, name + ".npz")
+    if ref is None:
+        assert os.path.exists(path), "no reference harness here and no recorded answers " + path
+        with np.load(path) as z:
+            return {k: z[k] for k in z.files}
+    got = {k: np.asarray(v) for k, v in live(ref).items()}
+    if os.environ.get("QM_RECORD_REFERENCE") == "1":
+        os.makedirs(ANSWERS, exist_ok=True)
+        np.savez_compressed(path, **got)
+    else:
+        with np.load(path) as z:
+            assert sorted(z.files) == sorted(got) and all(np.array_equal(z[k], got[k]) for k in got), "live answers differ from " + path
+    return got
+
+
+def sha256(data):
+    return np.array(hashlib.sha256(data).hexdigest())
+
+
+def _load_ref():
+    """the harness library, built by oracle/Makefile.ref where the reference tree it names is present; None where it is not"""
+    if not os.path.exists(REF_SO):
+        if subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "Makefile.ref"], capture_output=True).returncode:
+            return None
+    return C.CDLL(REF_SO)
 
 
 @pytest.fixture(scope="module")
 def ref():
-    if not os.path.exists(REF_SO):
-        if os.path.isdir("/root/reference/src/ksw2pp"):
-            subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "Makefile.ref"])
-        else:
-            pytest.skip("oracle/_ref not built and the reference tree is not here")
-    L = C.CDLL(REF_SO)
+    """the live harness library with its signatures, or None: the tests then read the recorded answers"""
+    L = _load_ref()
+    if L is None:
+        return None
     L.ref_ksw_extension.restype = C.c_int
     L.ref_ksw_extension.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int] + [C.c_int] * 5
     L.ref_kmer.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
@@ -38,33 +72,36 @@ def ref():
 
 def _ref():
     """the harness library for tests outside this module (None when it is neither built nor buildable here)"""
-    if not os.path.exists(REF_SO):
-        if not os.path.isdir("/root/reference/src/ksw2pp"):
-            return None
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "Makefile.ref"])
-    return C.CDLL(REF_SO)
+    return _load_ref()
 
 
-def check_spp64(L, blob, expect):
-    """`blob` (a serialised spp::sparse_hash_map<int64_t, int64_t>) loads in the reference's container and holds exactly `expect`"""
+def check_spp64(L, blob, expect, name):
+    """`blob` (a serialised spp::sparse_hash_map<int64_t, int64_t>) loads in the reference's container and holds exactly `expect`
+    (L None: the container's recorded answers for the blob of that SHA-256)"""
     import tempfile
-    L.ref_spp64_load.restype = C.c_void_p; L.ref_spp64_load.argtypes = [C.c_char_p]
-    L.ref_spp64_size.restype = C.c_int64; L.ref_spp64_size.argtypes = [C.c_void_p]
-    L.ref_spp64_find.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.ref_spp64_free.argtypes = [C.c_void_p]
-    with tempfile.NamedTemporaryFile(suffix=".spp") as f:
-        f.write(blob); f.flush()
-        h = L.ref_spp64_load(f.name.encode())
-    assert h
-    try:
-        assert L.ref_spp64_size(h) == len(expect)
-        keys = np.array(sorted(expect) + [max(expect) + 1, -5, 1 << 40], dtype=np.int64)
-        found = np.zeros(keys.size, dtype=np.uint8); val = np.zeros(keys.size, dtype=np.int64)
-        L.ref_spp64_find(h, keys.ctypes.data, keys.size, found.ctypes.data, val.ctypes.data)
-        assert found[:-3].all() and not found[-3:].any()
-        assert [int(v) for v in val[:-3]] == [expect[int(k)] for k in keys[:-3]]
-    finally:
-        L.ref_spp64_free(h)
+    keys = np.array(sorted(expect) + [max(expect) + 1, -5, 1 << 40], dtype=np.int64)
+
+    def live(L):
+        L.ref_spp64_load.restype = C.c_void_p; L.ref_spp64_load.argtypes = [C.c_char_p]
+        L.ref_spp64_size.restype = C.c_int64; L.ref_spp64_size.argtypes = [C.c_void_p]
+        L.ref_spp64_find.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.ref_spp64_free.argtypes = [C.c_void_p]
+        with tempfile.NamedTemporaryFile(suffix=".spp") as f:
+            f.write(blob); f.flush()
+            h = L.ref_spp64_load(f.name.encode())
+        assert h
+        try:
+            found = np.zeros(keys.size, dtype=np.uint8); val = np.zeros(keys.size, dtype=np.int64)
+            L.ref_spp64_find(h, keys.ctypes.data, keys.size, found.ctypes.data, val.ctypes.data)
+            return {"sha256": sha256(blob), "keys": keys, "size": L.ref_spp64_size(h), "found": found, "val": val}
+        finally:
+            L.ref_spp64_free(h)
+    a = answers(name, live, L)
+    assert str(a["sha256"]) == str(sha256(blob)) and np.array_equal(a["keys"], keys), "not the map the reference's container read"
+    assert int(a["size"]) == len(expect)
+    found, val = a["found"], a["val"]
+    assert found[:-3].all() and not found[-3:].any()
+    assert [int(v) for v in val[:-3]] == [expect[int(k)] for k in keys[:-3]]
 
 
 @pytest.fixture(scope="module")
@@ -88,12 +125,14 @@ def test_ksw2_extension_score_equals_the_references(ref, oracle_mod, scheme):
     ol = oracle_mod._lib()
     ol.qo_ksw_extz2.restype = C.c_int
     lut = np.frombuffer(b"ACGTN", dtype=np.uint8)
+    cases = list(_cases(777 + w, 600))
+    score = answers("ksw2_extension_%d_%d_%d_%d_%d" % scheme, lambda L: {"score": [
+        L.ref_ksw_extension(lut[q].tobytes(), len(q), lut[t].tobytes(), len(t), a, b, q_, e_, w) for q, t in cases]}, ref)["score"]
     bad = []
-    for q, t in _cases(777 + w, 600):
-        want = ref.ref_ksw_extension(lut[q].tobytes(), len(q), lut[t].tobytes(), len(t), a, b, q_, e_, w)
+    for (q, t), want in zip(cases, score):
         got = ol.qo_ksw_extz2(len(q), q.ctypes.data_as(C.c_void_p), len(t), t.ctypes.data_as(C.c_void_p), a, b, q_, e_, w)
         if got != want:
-            bad.append((len(q), len(t), want, got))
+            bad.append((len(q), len(t), int(want), got))
     assert not bad, "%d of 600 differ, first %r" % (len(bad), bad[:5])
 
 
@@ -107,14 +146,17 @@ def test_ksw2_long_and_dirty_inputs(ref, oracle_mod):
         nt4[c] = i; nt4[c + 32] = i
     nt4[:4] = [0, 1, 2, 3]
     alphabet = np.frombuffer(b"ACGTacgtNnRYKM", dtype=np.uint8)
+    cases = []
     for it in range(300):
         ql = int(rng.integers(200, 257)); tl = min(276, ql + 20 - int(rng.integers(0, 17)))
         q = alphabet[rng.choice(len(alphabet), ql, p=[.2, .2, .2, .2] + [.02] * 10)]
         t = q[:tl].copy() if tl <= ql else np.concatenate([q, alphabet[rng.integers(0, 4, tl - ql)]])
         m = rng.random(tl) < 0.04
         t[m] = alphabet[rng.integers(0, 4, int(m.sum()))]
-        w = [15, 33, 60, -1][it % 4]
-        want = ref.ref_ksw_extension(q.tobytes(), ql, t.tobytes(), tl, 2, -4, 4, 2, w)
+        cases.append((q, ql, t, tl, [15, 33, 60, -1][it % 4]))
+    score = answers("ksw2_long_and_dirty", lambda L: {"score": [
+        L.ref_ksw_extension(q.tobytes(), ql, t.tobytes(), tl, 2, -4, 4, 2, w) for q, ql, t, tl, w in cases]}, ref)["score"]
+    for it, ((q, ql, t, tl, w), want) in enumerate(zip(cases, score)):
         qc = nt4[q]; tc = nt4[t]
         got = ol.qo_ksw_extz2(ql, qc.ctypes.data_as(C.c_void_p), tl, tc.ctypes.data_as(C.c_void_p), 2, -4, 4, 2, w)
         assert got == want, (it, ql, tl, w, want, got)
@@ -127,19 +169,29 @@ def test_kmer_codec_equals_the_references(ref, oracle_mod):
     ol.qo_kmer_homopolymer.argtypes = [C.c_uint64, C.c_int]
     rng = np.random.default_rng(11)
     alphabet = np.frombuffer(b"ACGTacgtNnUuRY$", dtype=np.uint8)
+    cases = []
     for k in (31, 21, 5, 1):
         for it in range(3000):
             p = [.22] * 4 + [.02] * 4 + [.01] * 7
             p = np.array(p) / sum(p)
-            s = alphabet[rng.choice(len(alphabet), k, p=p)].tobytes() if it % 7 else bytes([b"ACGT"[it % 4]]) * k
+            cases.append((k, alphabet[rng.choice(len(alphabet), k, p=p)].tobytes() if it % 7 else bytes([b"ACGT"[it % 4]]) * k))
+
+    def live(L):
+        out = np.zeros((len(cases), 4), dtype=np.uint64)        # fromChars' return value, the word, its reverse complement, homopolymer
+        for i, (k, s) in enumerate(cases):
             w, rc, hp = C.c_uint64(), C.c_uint64(), C.c_int()
-            ok = ref.ref_kmer(s, k, C.byref(w), C.byref(rc), C.byref(hp))
-            v = C.c_int()
-            ow = ol.qo_kmer_encode(s, len(s), k, C.byref(v))
-            assert v.value == ok and ow == w.value, (k, s, ok, v.value, hex(w.value), hex(ow))
-            if ok:
-                assert ol.qo_kmer_rc(ow, k) == rc.value, (k, s)
-                assert ol.qo_kmer_homopolymer(ow, k) == hp.value, (k, s)
+            ok = L.ref_kmer(s, k, C.byref(w), C.byref(rc), C.byref(hp))
+            out[i] = (ok, w.value, rc.value, hp.value)
+        return {"kmer": out}
+    rec = answers("kmer_codec", live, ref)["kmer"]
+    for (k, s), (ok, w, rc, hp) in zip(cases, rec):
+        ok, w, rc, hp = int(ok), int(w), int(rc), int(hp)
+        v = C.c_int()
+        ow = ol.qo_kmer_encode(s, len(s), k, C.byref(v))
+        assert v.value == ok and ow == w, (k, s, ok, v.value, hex(w), hex(ow))
+        if ok:
+            assert ol.qo_kmer_rc(ow, k) == rc, (k, s)
+            assert ol.qo_kmer_homopolymer(ow, k) == hp, (k, s)
 
 
 def test_boophf_lookup_equals_the_references(ref, ref_index):
@@ -147,19 +199,25 @@ def test_boophf_lookup_equals_the_references(ref, ref_index):
     the .bph the reference wrote: every indexed k-mer and 20 000 k-mers that are not in the index"""
     from oracle import q5, q5ph
     path = os.path.join(ref_index["perfect"], "hash_info.bph")
-    h = ref.ref_mphf_load(path.encode())
-    assert h
     boo = q5ph.BooPHF(path)
     ix = q5.load(ref_index["dense"])
     keys = np.ascontiguousarray(ix.hkeys, dtype=np.uint64)
     rng = np.random.default_rng(3)
     other = rng.integers(0, 1 << 62, 20000, dtype=np.uint64)
     allk = np.concatenate([keys, other])
-    out = np.zeros(allk.size, dtype=np.uint64)
-    ref.ref_mphf_lookup(h, allk.ctypes.data, allk.size, out.ctypes.data)
+
+    def live(L):
+        h = L.ref_mphf_load(path.encode())
+        assert h
+        out = np.zeros(allk.size, dtype=np.uint64)
+        L.ref_mphf_lookup(h, allk.ctypes.data, allk.size, out.ctypes.data)
+        L.ref_mphf_free(h)
+        return {"keys": allk, "lookup": out}
+    a = answers("boophf_lookup", live, ref)
+    assert np.array_equal(a["keys"], allk)
+    out = a["lookup"]
     NOT_FOUND = (1 << 64) - 1                                # mphf::lookup returns ULLONG_MAX for a key the final hash does not hold
     mine = np.array([NOT_FOUND if (v := boo.lookup(int(x))) is None else v for x in allk], dtype=np.uint64)
-    ref.ref_mphf_free(h)
     assert np.array_equal(out, mine)
     inidx = out[: keys.size]
     assert inidx.max() < keys.size and np.unique(inidx).size == keys.size          # a minimal perfect hash on its own keys
@@ -172,13 +230,19 @@ def test_rank_equals_the_references(ref, ref_index, oracle_mod):
     raw = open(os.path.join(ref_index["dense"], "rsd.bin"), "rb").read()
     nbits = int(np.frombuffer(raw[:8], dtype="<u8")[0])
     bits = np.frombuffer(raw[8:], dtype=np.uint8).copy()
-    h = ref.ref_rank_create(bits.ctypes.data, nbits)
     ix = q5.load(ref_index["dense"])
     orc = oracle.Oracle(ix)
     pos = np.concatenate([np.arange(0, min(nbits, 3000)), np.random.default_rng(1).integers(0, nbits, 20000)]).astype(np.uint64)
-    out = np.zeros(pos.size, dtype=np.uint64)
-    ref.ref_rank_query(h, pos.ctypes.data, pos.size, out.ctypes.data)
-    ref.ref_rank_free(h)
+
+    def live(L):
+        h = L.ref_rank_create(bits.ctypes.data, nbits)
+        out = np.zeros(pos.size, dtype=np.uint64)
+        L.ref_rank_query(h, pos.ctypes.data, pos.size, out.ctypes.data)
+        L.ref_rank_free(h)
+        return {"pos": pos, "rank": out}
+    a = answers("rank9b", live, ref)
+    assert np.array_equal(a["pos"], pos)
+    out = a["rank"]
     ol = oracle_mod._lib()
     mine = np.array([ol.qo_rank(orc.h, int(p)) for p in pos], dtype=np.uint64)
     assert np.array_equal(out, mine)
@@ -208,6 +272,32 @@ def _spp_dump(ref, path):
     return h, keys, lb, ub
 
 
+def spp_answers(name, ref, path, probes=()):
+    """what the reference's spp::sparse_hash_map says about the hash.bin at `path`: its records in container order (keys, lb,
+    ub) and, for every probe array returned by probes(keys), find's (found, lb, ub).  Recorded with the file's SHA-256: the
+    record answers for those bytes only."""
+    data = open(path, "rb").read()
+
+    def live(L):
+        _spp(L)
+        h, keys, lb, ub = _spp_dump(L, path)
+        out = {"sha256": sha256(data), "keys": keys, "lb": lb, "ub": ub}
+        try:
+            for i, pr in enumerate(probes(keys) if probes else ()):
+                pr = np.ascontiguousarray(pr, dtype=np.uint64)
+                f = np.zeros(len(pr), dtype=np.uint8); fl = np.zeros(len(pr), dtype=np.int32); fu = np.zeros(len(pr), dtype=np.int32)
+                L.ref_spp_find(h, pr.ctypes.data, len(pr), f.ctypes.data, fl.ctypes.data, fu.ctypes.data)
+                out.update({"probe%d" % i: pr, "found%d" % i: f, "lb%d" % i: fl, "ub%d" % i: fu})
+        finally:
+            L.ref_spp_free(h)
+        return out
+    a = answers(name, live, ref)
+    assert str(a["sha256"]) == str(sha256(data)), path + " is not the file the reference's container read"
+    for i, pr in enumerate(probes(a["keys"]) if probes else ()):
+        assert np.array_equal(a["probe%d" % i], pr)
+    return a
+
+
 def test_dense_hash_file_equals_the_references_container(ref, ref_index, oracle_mod):
     """hash.bin written by the reference, read back by the reference's own spp::sparse_hash_map::unserialize
     (include/sparsepp/spp.h:2355-2429 through include/SparseHashSerializer.hpp:31-47, as RapMapSAIndex::load does,
@@ -215,30 +305,25 @@ def test_dense_hash_file_equals_the_references_container(ref, ref_index, oracle_
     oracle's find (what every parity test's lookups go through) must answer like the container's find, for present and absent keys"""
     from oracle import q5
     from conftest import load_oracle
-    _spp(ref)
     d = ref_index["dense"]
-    h, keys, lb, ub = _spp_dump(ref, os.path.join(d, "hash.bin"))
-    try:
-        k2, l2, u2 = q5.read_dense_hash(d)
-        assert len(keys) == len(k2) == 18902
-        o1 = np.argsort(keys); o2 = np.argsort(k2)
-        assert np.array_equal(keys[o1], k2[o2]) and np.array_equal(lb[o1], l2[o2]) and np.array_equal(ub[o1], u2[o2])
-        assert np.array_equal(keys, k2)                       # even the record order: the reader walks the file like the container
-        ix, orc = load_oracle(d)
-        rng = np.random.default_rng(3)
-        probe = np.concatenate([keys, rng.integers(0, 1 << 62, 20000, dtype=np.uint64), keys ^ np.uint64(1)])
-        found = np.zeros(len(probe), dtype=np.uint8); fl = np.zeros(len(probe), dtype=np.int32); fu = np.zeros(len(probe), dtype=np.int32)
-        ref.ref_spp_find(h, probe.ctypes.data, len(probe), found.ctypes.data, fl.ctypes.data, fu.ctypes.data)
-        assert found[: len(keys)].all() and not found[len(keys): len(keys) + 20000].any()
-        ol = oracle_mod._lib()
-        out = (C.c_int32 * 2)()
-        for i in range(0, len(probe), 7):                    # every 7th probe through the oracle's own find
-            got = ol.qo_hash_find(orc.h, int(probe[i]), out)
-            assert bool(got) == bool(found[i])
-            if got:
-                assert (out[0], out[1]) == (fl[i], fu[i])
-    finally:
-        ref.ref_spp_free(h)
+    a = spp_answers("spp_reference_hash", ref, os.path.join(d, "hash.bin"), lambda keys: [np.concatenate(
+        [keys, np.random.default_rng(3).integers(0, 1 << 62, 20000, dtype=np.uint64), keys ^ np.uint64(1)])])
+    keys, lb, ub = a["keys"], a["lb"], a["ub"]
+    k2, l2, u2 = q5.read_dense_hash(d)
+    assert len(keys) == len(k2) == 18902
+    o1 = np.argsort(keys); o2 = np.argsort(k2)
+    assert np.array_equal(keys[o1], k2[o2]) and np.array_equal(lb[o1], l2[o2]) and np.array_equal(ub[o1], u2[o2])
+    assert np.array_equal(keys, k2)                       # even the record order: the reader walks the file like the container
+    ix, orc = load_oracle(d)
+    probe, found, fl, fu = a["probe0"], a["found0"], a["lb0"], a["ub0"]
+    assert found[: len(keys)].all() and not found[len(keys): len(keys) + 20000].any()
+    ol = oracle_mod._lib()
+    out = (C.c_int32 * 2)()
+    for i in range(0, len(probe), 7):                    # every 7th probe through the oracle's own find
+        got = ol.qo_hash_find(orc.h, int(probe[i]), out)
+        assert bool(got) == bool(found[i])
+        if got:
+            assert (out[0], out[1]) == (fl[i], fu[i])
 
 
 def test_our_hash_file_loads_in_the_references_container(ref, sample_data, lib_built):
@@ -246,38 +331,37 @@ def test_our_hash_file_loads_in_the_references_container(ref, sample_data, lib_b
     reference's find -- XXH64 + its own probing over the slots we chose -- returns every record: the file is a container the
     reference can use, not just the same map"""
     from oracle import q5
-    _spp(ref)
     d = sample_data["idx"]
-    h, keys, lb, ub = _spp_dump(ref, os.path.join(d, "hash.bin"))
-    try:
-        k2, l2, u2 = q5.read_dense_hash(d)
-        assert np.array_equal(keys, k2) and np.array_equal(lb, l2) and np.array_equal(ub, u2) and len(keys) > 1000
-        found = np.zeros(len(keys), dtype=np.uint8); fl = np.zeros(len(keys), dtype=np.int32); fu = np.zeros(len(keys), dtype=np.int32)
-        ref.ref_spp_find(h, keys.ctypes.data, len(keys), found.ctypes.data, fl.ctypes.data, fu.ctypes.data)
-        assert found.all() and np.array_equal(fl, lb) and np.array_equal(fu, ub)
-    finally:
-        ref.ref_spp_free(h)
+    a = spp_answers("spp_our_hash", ref, os.path.join(d, "hash.bin"), lambda keys: [keys])
+    keys, lb, ub = a["keys"], a["lb"], a["ub"]
+    k2, l2, u2 = q5.read_dense_hash(d)
+    assert np.array_equal(keys, k2) and np.array_equal(lb, l2) and np.array_equal(ub, u2) and len(keys) > 1000
+    found, fl, fu = a["found0"], a["lb0"], a["ub0"]
+    assert found.all() and np.array_equal(fl, lb) and np.array_equal(fu, ub)
 
 
 def test_xxh64_equals_the_references(ref, lib_built):
     """the index builder's XXH64 (slot placement in hash.bin, duplicate filter) == src/xxhash.c, every length class of the
     algorithm (< 4, < 8, < 32, >= 32 bytes, unaligned tails), several seeds"""
     import rapmap_amd as ra
-    _spp(ref)
     L = ra.api.lib()
     L.qm_xxh64.restype = C.c_uint64; L.qm_xxh64.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     rng = np.random.default_rng(11)
     buf = rng.integers(0, 256, 4096, dtype=np.uint8)
-    for ln in list(range(0, 100)) + [127, 128, 129, 1000, 4095]:
-        for seed in (0, 1, 0x9E3779B97F4A7C15):
-            for shift in (0, 1, 3):
-                p = buf.ctypes.data + shift
-                if shift + ln > buf.size:
-                    continue
-                assert L.qm_xxh64(p, ln, seed) == ref.ref_xxh64(p, ln, seed), (ln, seed, shift)
+    cases = [(shift, ln, seed) for ln in list(range(0, 100)) + [127, 128, 129, 1000, 4095] for seed in (0, 1, 0x9E3779B97F4A7C15)
+             for shift in (0, 1, 3) if shift + ln <= buf.size]
     keys = rng.integers(0, 1 << 62, 5000, dtype=np.uint64)
+
+    def live(R):
+        _spp(R)
+        return {"buf": np.array([R.ref_xxh64(buf.ctypes.data + shift, ln, seed) for shift, ln, seed in cases], dtype=np.uint64),
+                "keys": np.array([R.ref_xxh64(keys[i:].ctypes.data, 8, 0) for i in range(len(keys))], dtype=np.uint64)}
+    a = answers("xxh64", live, ref)
+    for (shift, ln, seed), want in zip(cases, a["buf"]):
+        assert L.qm_xxh64(buf.ctypes.data + shift, ln, seed) == int(want), (ln, seed, shift)
+    assert len(a["buf"]) == len(cases) and len(a["keys"]) == len(keys)
     for i in range(len(keys)):
-        assert L.qm_xxh64(keys[i:].ctypes.data, 8, 0) == ref.ref_xxh64(keys[i:].ctypes.data, 8, 0)
+        assert L.qm_xxh64(keys[i:].ctypes.data, 8, 0) == int(a["keys"][i])
 
 
 @pytest.mark.gpu
@@ -288,46 +372,40 @@ def test_device_lookup_answers_like_the_references_container(ref, ref_index, lib
     a read of exactly k characters, must come back as the interval khash.find returns; random k-mers that the container does
     not hold (neither strand) must come back empty"""
     import rapmap_amd as ra
-    _spp(ref)
-    h, keys, lb, ub = _spp_dump(ref, os.path.join(ref_index["dense"], "hash.bin"))
-    try:
-        k = 31
-        def decode(words):
-            sh = np.arange(k - 1, -1, -1, dtype=np.uint64) * np.uint64(2)
-            return np.frombuffer(b"ACGT", dtype=np.uint8)[((words[:, None] >> sh[None, :]) & np.uint64(3)).astype(np.int64)]
-        def rc(words):
-            c = decode(words)[:, ::-1]
-            m = np.zeros(256, dtype=np.uint64); m[ord("A")] = 3; m[ord("C")] = 2; m[ord("G")] = 1; m[ord("T")] = 0
-            sh = np.arange(k - 1, -1, -1, dtype=np.uint64) * np.uint64(2)
-            return (m[c] << sh[None, :]).sum(axis=1).astype(np.uint64)
-        rng = np.random.default_rng(5)
-        absent = rng.integers(0, 1 << 62, 30000, dtype=np.uint64)
-        f1 = np.zeros(len(absent), dtype=np.uint8); f2 = np.zeros(len(absent), dtype=np.uint8); t = np.zeros(len(absent), dtype=np.int32)
-        ra_ = rc(absent)
-        ref.ref_spp_find(h, absent.ctypes.data, len(absent), f1.ctypes.data, t.ctypes.data, t.ctypes.data)
-        ref.ref_spp_find(h, ra_.ctypes.data, len(ra_), f2.ctypes.data, t.ctypes.data, t.ctypes.data)
-        absent = absent[(f1 == 0) & (f2 == 0)]
-        words = np.concatenate([keys, absent])
-        seq = decode(words).reshape(-1).copy(); off = np.arange(len(words) + 1, dtype=np.int64) * k
-        qi = ra.QuasiIndex(ref_index[kind]); mp = ra.QuasiMapper(qi, 0, ph_compact=compact)
-        found, ioff, ints = mp.collect_reads(seq, off)
-        cnt = np.diff(ioff)
-        assert not cnt[len(keys):].any() and not found[len(keys):].any()
-        checked = 0
-        for i in range(len(keys)):
-            if not (0 < ub[i] - lb[i] < 1000):
-                continue                                    # the collector does not record intervals of >= maxInterval suffixes
-            g = ints[ioff[i]:ioff[i + 1]]
-            fw = g[(g["query_rc"] == 0) & (g["query_pos"] == 0)]
-            if len(fw) == 0:                               # homopolymer k-mers are never probed (include/SACollector.hpp:176-181)
-                w = int(keys[i]); assert w in (0, (1 << 62) - 1) or len(set(decode(keys[i:i + 1])[0].tolist())) == 1, hex(w)
-                continue
-            assert len(fw) == 1 and (int(fw["begin"][0]), int(fw["end"][0]), int(fw["len"][0])) == (int(lb[i]), int(ub[i]), k), i
-            checked += 1
-        assert checked > 18000
-        mp.close(); qi.close()
-    finally:
-        ref.ref_spp_free(h)
+    k = 31
+    def decode(words):
+        sh = np.arange(k - 1, -1, -1, dtype=np.uint64) * np.uint64(2)
+        return np.frombuffer(b"ACGT", dtype=np.uint8)[((words[:, None] >> sh[None, :]) & np.uint64(3)).astype(np.int64)]
+    def rc(words):
+        c = decode(words)[:, ::-1]
+        m = np.zeros(256, dtype=np.uint64); m[ord("A")] = 3; m[ord("C")] = 2; m[ord("G")] = 1; m[ord("T")] = 0
+        sh = np.arange(k - 1, -1, -1, dtype=np.uint64) * np.uint64(2)
+        return (m[c] << sh[None, :]).sum(axis=1).astype(np.uint64)
+    def probes(keys):
+        absent = np.random.default_rng(5).integers(0, 1 << 62, 30000, dtype=np.uint64)
+        return [absent, rc(absent)]
+    a = spp_answers("spp_reference_hash_absent", ref, os.path.join(ref_index["dense"], "hash.bin"), probes)
+    keys, lb, ub = a["keys"], a["lb"], a["ub"]
+    absent = a["probe0"][(a["found0"] == 0) & (a["found1"] == 0)]
+    words = np.concatenate([keys, absent])
+    seq = decode(words).reshape(-1).copy(); off = np.arange(len(words) + 1, dtype=np.int64) * k
+    qi = ra.QuasiIndex(ref_index[kind]); mp = ra.QuasiMapper(qi, 0, ph_compact=compact)
+    found, ioff, ints = mp.collect_reads(seq, off)
+    cnt = np.diff(ioff)
+    assert not cnt[len(keys):].any() and not found[len(keys):].any()
+    checked = 0
+    for i in range(len(keys)):
+        if not (0 < ub[i] - lb[i] < 1000):
+            continue                                    # the collector does not record intervals of >= maxInterval suffixes
+        g = ints[ioff[i]:ioff[i + 1]]
+        fw = g[(g["query_rc"] == 0) & (g["query_pos"] == 0)]
+        if len(fw) == 0:                               # homopolymer k-mers are never probed (include/SACollector.hpp:176-181)
+            w = int(keys[i]); assert w in (0, (1 << 62) - 1) or len(set(decode(keys[i:i + 1])[0].tolist())) == 1, hex(w)
+            continue
+        assert len(fw) == 1 and (int(fw["begin"][0]), int(fw["end"][0]), int(fw["len"][0])) == (int(lb[i]), int(ub[i]), k), i
+        checked += 1
+    assert checked > 18000
+    mp.close(); qi.close()
 
 
 def _ref_fastx(ref, p1, p2=None):
@@ -339,6 +417,33 @@ def _ref_fastx(ref, p1, p2=None):
         return [l.split(b"\t") for l in C.string_at(out, n).split(b"\n")[:-1]]
     finally:
         ref.ref_free(out)
+
+
+def _records_sha(recs):
+    return sha256(b"\n".join(b"\t".join(r) for r in recs))
+
+
+def fastx_answers(name, ref, *paths):
+    """what the reference's FastxParser reads from these files: (number of records, SHA-256 of the records, one per line with
+    their fields tab-joined), recorded with the SHA-256 of each file's decompressed content"""
+    import gzip as gz
+
+    def content(p):
+        with (gz.open(p, "rb") if p.endswith(".gz") else open(p, "rb")) as f:
+            return sha256(f.read())
+    files = np.array([str(content(p)) for p in paths])
+
+    def live(L):
+        recs = _ref_fastx(L, *paths)
+        return {"files": files, "n": len(recs), "records": _records_sha(recs)}
+    a = answers(name, live, ref)
+    assert np.array_equal(a["files"], files), "not the files the reference's parser read"
+    return int(a["n"]), str(a["records"])
+
+
+def assert_reads(name, ref, got, *paths):
+    n, sha = fastx_answers(name, ref, *paths)
+    assert len(got) == n and str(_records_sha(got)) == sha, (name, len(got), n)
 
 
 def test_ingest_engine_reads_what_the_references_parser_reads(ref, lib_built, tmp_path):
@@ -364,9 +469,10 @@ def test_ingest_engine_reads_what_the_references_parser_reads(ref, lib_built, tm
         return out
 
     g1 = os.path.join(GOLD, "sample_data", "reads_1.fastq.gz"); g2 = os.path.join(GOLD, "sample_data", "reads_2.fastq.gz")
-    want = _ref_fastx(ref, g1, g2)
-    assert len(want) == 10000 and ours(g1, g2, 777, 3) == want
-    assert ours(g1, None, 4096, 2) == _ref_fastx(ref, g1)
+    got = ours(g1, g2, 777, 3)
+    assert len(got) == 10000
+    assert_reads("fastx_sample_pair", ref, got, g1, g2)
+    assert_reads("fastx_sample_single", ref, ours(g1, None, 4096, 2), g1)
     rnd = random.Random(7)
     p1 = str(tmp_path / "a.fq"); p2 = str(tmp_path / "b.fq")
     with open(p1, "wb") as f1, open(p2, "wb") as f2:
@@ -382,14 +488,15 @@ def test_ingest_engine_reads_what_the_references_parser_reads(ref, lib_built, tm
         got = ours(p1, p2, 1000, 6)
     finally:
         del os.environ["QM_INGEST_CHUNK"]
-    want = _ref_fastx(ref, p1, p2)
-    assert len(want) == 20000 and got == want
+    assert len(got) == 20000
+    assert_reads("fastx_ragged_pair", ref, got, p1, p2)
     # the same pair as BGZF files (independent gzip members, inflated by helper threads side by side here; one multi-member gzip
     # stream to the reference's kseq / gzread)
     from util import write_bgzf
     b1 = str(tmp_path / "a.bgzf.fq.gz"); b2 = str(tmp_path / "b.bgzf.fq.gz")
     write_bgzf(b1, open(p1, "rb").read(), block=5000); write_bgzf(b2, open(p2, "rb").read(), block=65280)
-    assert _ref_fastx(ref, b1, b2) == want and ours(b1, b2, 3000, 4) == want
+    assert_reads("fastx_ragged_pair_bgzf", ref, ours(b1, b2, 3000, 4), b1, b2)
+    assert ours(b1, b2, 3000, 4) == got
     fa = str(tmp_path / "t.fa.gz")
     with gz.open(fa, "wt") as f:
         for i in range(3000):
@@ -397,4 +504,4 @@ def test_ingest_engine_reads_what_the_references_parser_reads(ref, lib_built, tm
             f.write(">t%d gene=%d\n" % (i, i // 3))
             for j in range(0, len(sq), 60):
                 f.write(sq[j:j + 60] + "\n")
-    assert ours(fa, None, 257, 4) == _ref_fastx(ref, fa)
+    assert_reads("fastx_multiline_fasta", ref, ours(fa, None, 257, 4), fa)
