@@ -772,12 +772,8 @@ static DevIndex dev_index(const qm_ctx* c) {
 
 // ---- stage A: one wavefront per read (collector + hits->mappings, or one of the two alone), with its retries: the per-read
 // lists or the interval output outgrew their buffers (grow, redo), -s reads left on the slow queue (second, small launch).
-// the longest read a call takes: QM_MAX_LONG_READ_LEN; with -s only while the band's ring edition of the alignment kernel has a
-// long-image form (--dpBandwidth 0 .. 97; the full-band ring holds every column of a 512-base alignment and no more)
-static int len_limit(const qm_opts* o) {
-  (void)o;                                                   // (round 4: with -s too, whatever the band -- a band beyond 97 takes the device-memory edition of the alignment kernel)
-  return QM_MAX_LONG_READ_LEN;
-}
+// The longest read a call takes is QM_MAX_LONG_READ_LEN, with -s too, whatever the band: a --dpBandwidth beyond 97 takes the
+// device-memory edition of the alignment kernel.
 
 // The wide extension table (SaExt2: 224 characters behind every suffix's k-mer, 64 bytes per suffix-array entry) for the one-read-per-
 // wavefront lean kernel: built by the first call that has reads of 129 .. 256 characters, shared by the replica's contexts; a replica
@@ -805,6 +801,24 @@ static bool ensure_saext2(qm_ctx* c) {
   return c->d_saext2 != nullptr;
 }
 
+// The -s extension table (sanext_entry: a capped MMP extension becomes one trip; 4 bytes per suffix-array entry, built from text and SA as
+// they sit in HBM): built by the first -s call on a replica, shared by every context of the replica.
+static int ensure_sanext(qm_ctx* c) {
+  if (c->d_sanext || c->ix->nSA <= 0 || !c->rep) return QM_OK;
+  Replica& R = *c->rep;
+  std::lock_guard<std::mutex> lk(R.sanextMu);
+  if (!R.d_sanext) {
+    unsigned int* p = nullptr;
+    HIPCHK(hipMalloc((void**)&p, (size_t)c->ix->nSA * sizeof(unsigned int)));
+    hipError_t e = qmk_build_sanext(c->d_text, c->ix->n, c->d_SA, c->ix->nSA, c->ix->k, p, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { hipFree(p); return fail(QM_E_NOGPU, "building the -s extension table: %s", hipGetErrorString(e)); }
+    R.d_sanext = p; R.devBytes += c->ix->nSA * 4;
+  }
+  c->d_sanext = R.d_sanext; c->devBytes = R.devBytes;
+  return QM_OK;
+}
+
 // The general kernels' per-wave scratch in device memory (QM_GSCR_U64 words, 112 KB) for a launch of `grid` blocks: one per launched
 // wave while that is no more than the waves that can be resident at once (64 per CU, generously); beyond that -- the oversubscribed
 // grids -- one per SLOT, and the waves take and return slots as they start and end (ReadBatch::gslots).  Returns the flags, or null.
@@ -824,17 +838,24 @@ static int gscr_for(qm_ctx* c, int grid, unsigned*& slots, int& nslots) {
   return QM_OK;
 }
 
-static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n, const void* d_seq1, const void* d_off1, const void* d_seq2,
-                       const void* d_off2, int ns, ChunkFeeder* feeder, u64* hscal) {
-  int rc;
-  const bool paired = d_seq2 != nullptr;
-  const int64_t nreads = paired ? 2 * n : n;
-  const int phc = c->d_ph ? 1 : 0;                        // (the compact -p image: its kernels take a larger grid)
-  int grid = qmk_map_grid_ex(nreads, c->numCU, phc);
-  if ((rc = ensure(c->d_lcnt, c->capLcnt, nreads + 1))) return rc;
-  if ((rc = ensure(c->d_loff, c->capLoff, nreads + 1))) return rc;
+// What a call of stage A runs, decided once (plan_stage_a): which kernels, over what grid, writing which outputs.
+enum { SK_GENERAL, SK_LEAN, SK_DUO, SK_LEAN_SEL, SK_H2M };
+struct StagePlan {
+  int first;                // the first launch.  SK_GENERAL: the general kernels (fused, or the collector alone: QM_RUN_COLLECT, the first half of twoPass); SK_LEAN: qm_lean_kernel;
+                            // SK_DUO: the pair kernel; SK_LEAN_SEL: qm_lean_kernel's -s edition as the collector of twoPass; SK_H2M: hits -> mappings alone (QM_RUN_FROM_INTERVALS)
+  bool leanWide, duoMerge;  // the lean kernels' one-read-per-wavefront edition (reads of 129 .. 256 characters); the pair kernel merges the pairs it maps (pair_cnt)
+  bool twoPass, wantIv, wantFound;   // fused -s: a collector, then the list kernels; the SA-interval records / the foundHit flags are written
+  bool paired; int ns, phc; int64_t n, nreads;
+  int grid; unsigned* gslots; int ngslots;   // blocks of a launch of the general kernels over the whole batch (reserve_stage_a lowers it when their scratch does not fit) and the flags of their scratch slots, if any (gscr_for)
+};
+static bool lean_first(const StagePlan& p) { return p.first == SK_LEAN || p.first == SK_DUO; }   // the fused default call: lists from a kernel that owns no scratch in device memory
+
+static int plan_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, bool paired, int64_t n, int ns, StagePlan& p) {
+  p.paired = paired; p.n = n; p.nreads = paired ? 2 * n : n; p.ns = ns;
+  p.phc = c->d_ph ? 1 : 0;                                // (the compact -p image: its kernels take a larger grid)
+  p.grid = qmk_map_grid_ex(p.nreads, c->numCU, p.phc); p.gslots = nullptr; p.ngslots = 0;
   // The lean kernel (qm_lean.inl: two reads per wavefront and iteration, reads of up to 128 clean characters) takes the fused default
-  // call on a dense table; the reads it marks instead of mapping go through the general kernel in a second, small launch below.
+  // call on a dense table; the reads it marks instead of mapping go through the general kernel in a second, small launch (pass_lean_leftovers).
   // It owns no per-wave scratch in device memory: that is only reserved -- for the small grid -- when the second launch happens.
   static const bool leanOff = [] { const char* e = getenv("QM_NO_LEAN"); return e && atoi(e) != 0; }();
   // Reads of 129 .. 256 characters (slot classes 3 and 4) take its wide edition -- one read per wavefront -- once the replica holds the
@@ -842,8 +863,8 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   static const bool wideOff = [] { const char* e = getenv("QM_NO_LEAN_WIDE"); return e && atoi(e) != 0; }();
   const bool leanBase = !leanOff && rq.mode == QM_RUN_FUSED && o->sensitive && (c->d_slots || c->d_ph) && c->d_saext && c->ix->k <= 31;
   // (a call that keeps the SA-interval records takes the general kernel: the lean kernels do not write them; foundHit they do -- stage views without intervals)
-  const bool leanWide = leanBase && !wideOff && (ns == 3 || ns == 4) && (o->sel_aln || !rq.keepIntervals) && ensure_saext2(c);
-  const bool useLean = leanBase && !o->sel_aln && (ns == 2 || leanWide) && !rq.keepIntervals;
+  p.leanWide = leanBase && !wideOff && (ns == 3 || ns == 4) && (o->sel_aln || !rq.keepIntervals) && ensure_saext2(c);
+  const bool useLean = leanBase && !o->sel_aln && (ns == 2 || p.leanWide) && !rq.keepIntervals;
   // Pairs of such reads take the pair kernel (qm_duo.inl): the two mates walked in lockstep by the two halves of a wavefront, and -- in a
   // plain fused call -- merged there (pair_cnt: stage B's count pass finds the pair done, its write pass expands the records)
   static const bool duoOff = [] { const char* e = getenv("QM_NO_DUO"); return e && atoi(e) != 0; }();
@@ -853,291 +874,310 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   const bool useDuo = useLean && !duoOff && !rq.noDuo && !(c->flags & QM_CTX_NO_PAIR_KERNEL) && paired && ns == 2 && (!c->d_ph || duoPh);
   // (qm_lean_kernel holds both mates of a pair in one wavefront too, but merging there was measured and dropped: that kernel is bound by the CU's scalar unit and
   // the merge's bookkeeping cost it 1.3 ms per 10 M pairs -- 62 instead of 28 spilled scalar registers -- where stage B saved 0.5: profiles/r06/exp_mix.txt)
-  const bool duoMerge = useDuo && !rq.mergeOnly && !rq.stageView;
-  if (duoMerge) { if ((rc = ensure(c->d_cnt, c->capCnt, n + 1))) return rc; }
-  unsigned* gslots = nullptr; int ngslots = 0;
-  if (!useLean) {
-    // the general kernels' scratch (gscr_for); when even that does not fit next to the index, the launch falls back to the resident grid
-    rc = gscr_for(c, grid, gslots, ngslots);
-    if (rc == QM_E_NOMEM) { grid = qmk_resident_grid(nreads, c->numCU); rc = gscr_for(c, grid, gslots, ngslots); }
-    if (rc) return rc;
-  }
-  // ... and its -s edition stands in for the chain-scoring collector of a fused -s call (intervals and foundHit out; the list kernels
-  // that follow are the same)
-  const bool useLeanSel = leanBase && o->sel_aln && (ns == 2 || leanWide);
-  if (rq.mode != QM_RUN_COLLECT) {
-    int64_t wantLists = nreads * 4 + (int64_t)grid * 4 * QM_CHUNK * 2;   // chunked bump allocator: up to one open chunk per wave
-    if (c->capLists < wantLists) { if ((rc = ensure(c->d_lists, c->capLists, wantLists))) return rc; }
-  }
+  p.duoMerge = useDuo && !rq.mergeOnly && !rq.stageView;
   // A fused -s call runs stage A as two launches: the chain-scoring collector alone (its memory-bound walk, at the default
   // kernel's occupancy: without the chaining code it needs half the registers and no LDS scratch) leaves every read's
   // SA-interval hits in HBM, then one wavefront per read turns them into the read's list (sort, slack intersection, chaining).
-  const bool twoPass = rq.mode == QM_RUN_FUSED && o->sel_aln != 0;
-  const bool wantIv = rq.keepIntervals || rq.mode == QM_RUN_COLLECT || twoPass;
-  if (wantIv) {
-    if ((rc = ensure(c->d_ivcnt, c->capIvCnt, nreads + 1))) return rc;
-    if ((rc = ensure(c->d_ivoff, c->capIvOff, nreads + 1))) return rc;
-    const int64_t want = nreads * (o->sel_aln ? 16 : 4) + (int64_t)grid * 4 * QM_IVCHUNK * 2;   // chunked allocator: up to one open chunk per wave
-    if (c->capIv < want) { if ((rc = ensure(c->d_iv, c->capIv, want))) return rc; }
+  p.twoPass = rq.mode == QM_RUN_FUSED && o->sel_aln != 0;
+  p.wantIv = rq.keepIntervals || rq.mode == QM_RUN_COLLECT || p.twoPass;
+  p.wantFound = rq.keepFound || rq.mode == QM_RUN_COLLECT || p.twoPass;
+  // ... and the lean kernel's -s edition stands in for that collector (intervals and foundHit out; the list kernels that follow are the same); every collector of a -s call reads the -s extension table
+  if (o->sel_aln && rq.mode != QM_RUN_FROM_INTERVALS) { const int rc = ensure_sanext(c); if (rc) return rc; }
+  const bool useLeanSel = leanBase && o->sel_aln && (ns == 2 || p.leanWide) && c->d_sanext;
+  p.first = useDuo ? SK_DUO : useLean ? SK_LEAN : useLeanSel ? SK_LEAN_SEL : rq.mode == QM_RUN_FROM_INTERVALS ? SK_H2M : SK_GENERAL;
+  return QM_OK;
+}
+
+// The work buffers of a call, sized from the plan.
+static int reserve_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, StagePlan& p) {
+  int rc;
+  if ((rc = ensure(c->d_lcnt, c->capLcnt, p.nreads + 1))) return rc;
+  if ((rc = ensure(c->d_loff, c->capLoff, p.nreads + 1))) return rc;
+  if (p.duoMerge && (rc = ensure(c->d_cnt, c->capCnt, p.n + 1))) return rc;
+  if (!lean_first(p)) {
+    // the general kernels' scratch (gscr_for); when even that does not fit next to the index, the launch falls back to the resident grid
+    rc = gscr_for(c, p.grid, p.gslots, p.ngslots);
+    if (rc == QM_E_NOMEM) { p.grid = qmk_resident_grid(p.nreads, c->numCU); rc = gscr_for(c, p.grid, p.gslots, p.ngslots); }
+    if (rc) return rc;
   }
-  const bool wantFound = rq.keepFound || rq.mode == QM_RUN_COLLECT || twoPass;
-  if (wantFound) { if ((rc = ensure(c->d_found, c->capFound, nreads + 1))) return rc; }
-  if (o->sel_aln && rq.mode != QM_RUN_FROM_INTERVALS && !c->d_sanext && c->ix->nSA > 0 && c->rep) {
-    // first -s call on this replica: the table that turns a capped MMP extension into one trip (sanext_entry); 4 bytes per
-    // suffix-array entry, built from text and SA as they sit in HBM, shared by every context of the replica
-    Replica& R = *c->rep;
-    std::lock_guard<std::mutex> lk(R.sanextMu);
-    if (!R.d_sanext) {
-      unsigned int* p = nullptr;
-      HIPCHK(hipMalloc((void**)&p, (size_t)c->ix->nSA * sizeof(unsigned int)));
-      hipError_t e = qmk_build_sanext(c->d_text, c->ix->n, c->d_SA, c->ix->nSA, c->ix->k, p, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { hipFree(p); return fail(QM_E_NOGPU, "building the -s extension table: %s", hipGetErrorString(e)); }
-      R.d_sanext = p; R.devBytes += c->ix->nSA * 4;
+  // lists and interval records come from chunked bump allocators: up to one open chunk per wave
+  if (rq.mode != QM_RUN_COLLECT && (rc = ensure(c->d_lists, c->capLists, p.nreads * 4 + (int64_t)p.grid * 4 * QM_CHUNK * 2))) return rc;
+  if (p.wantIv) {
+    if ((rc = ensure(c->d_ivcnt, c->capIvCnt, p.nreads + 1))) return rc;
+    if ((rc = ensure(c->d_ivoff, c->capIvOff, p.nreads + 1))) return rc;
+    if ((rc = ensure(c->d_iv, c->capIv, p.nreads * (o->sel_aln ? 16 : 4) + (int64_t)p.grid * 4 * QM_IVCHUNK * 2))) return rc;
+  }
+  if (p.wantFound && (rc = ensure(c->d_found, c->capFound, p.nreads + 1))) return rc;
+  // -s: per-wave scratch for chaining (qm_sel.inl; the list kernels' grids stay within residency)
+  if (o->sel_aln && (rc = ensure(c->d_selscr, c->capSelScr, (int64_t)qmk_resident_grid(p.nreads, c->numCU) * 4 * (int64_t)qmk_sel_scratch_bytes()))) return rc;
+  return QM_OK;
+}
+
+// The first launch's view of the batch; the follow-up passes copy it and point the copy at their queue.
+static void fill_batch(const qm_ctx* c, const qm_opts* o, const RunReq& rq, const StagePlan& p, const void* d_seq1, const void* d_off1,
+                       const void* d_seq2, const void* d_off2, ReadBatch& B) {
+  memset(&B, 0, sizeof(B));
+  B.seq1 = (const unsigned char*)d_seq1; B.off1 = (const long long*)d_off1;
+  B.seq2 = (const unsigned char*)d_seq2; B.off2 = (const long long*)d_off2; B.nreads = p.nreads;
+  B.lcnt = c->d_lcnt; B.loff = c->d_loff; B.lists = c->d_lists; B.cursor = c->d_scal; B.lists_cap = c->capLists;
+  B.status = (int*)(c->d_scal + QM_SC_STATUS); B.gscratch = c->d_gscr; B.gslots = p.gslots; B.ngslots = p.ngslots; B.gxcd = xcds_of(c); B.skiplist = c->d_skip;
+  B.lean_wide = p.leanWide ? 1 : 0;
+  if (p.duoMerge) { B.pair_cnt = c->d_cnt; B.max_num_hits = o->max_num_hits; B.no_orphans = o->no_orphans; B.no_dovetail = o->no_dovetail; }
+  if (p.wantIv) { B.iv_out = c->d_iv; B.iv_cnt = c->d_ivcnt; B.iv_off = c->d_ivoff; B.iv_cap = c->capIv; }
+  if (p.wantFound) B.found_out = c->d_found;
+  B.iv_in = rq.ivIn; B.iv_in_off = rq.ivInOff; B.len_in = rq.lenIn; B.found_in = rq.foundIn;
+  B.strict_check = o->strict_check; B.max_interval = o->max_interval; B.quasi_cov = o->quasi_cov; B.sensitive = o->sensitive; B.fuzzy = p.paired ? o->fuzzy : 0;
+  if (rq.mode == QM_RUN_FROM_INTERVALS) B.fuzzy = o->fuzzy;   // the caller says what kind of list it wants (both orientations kept or not)
+  if (o->sel_aln) {                                   // -s: chain scoring + per-wave scratch for chaining (qm_sel.inl)
+    B.selscr = (SelScratch*)c->d_selscr;
+    B.max_mmp_ext = o->max_mmp_extension > 0 ? o->max_mmp_extension : 7;
+    const float cs = (float)o->consensus_slack;        // MappingOpts::consensusSlack is a float (RapMapSAMapper.cpp:138,184-185)
+    B.consensus_fraction = cs < 0 ? -cs : ((cs == 0.0) ? 1.0 : (1.0 - cs));   // negative: MappingConfig::consensusFraction itself (qmap_mi355.h)
+  }
+}
+
+// The first launch: one per chunk behind its own upload (ChunkFeeder), or the whole resident batch as the one chunk.  A launch sees its chunk through
+// shifted pointers (offsets are absolute, the per-read / per-unit arrays start at the chunk), the bump allocators, the counters and the status word are shared.
+static int launch_first(qm_ctx* c, const StagePlan& p, const RunReq& rq, const DevIndex& ix, const ReadBatch& B, ChunkFeeder* feeder) {
+  int rc;
+  const int64_t chunk = feeder ? feeder->chunk : p.n;
+  for (int64_t u0 = 0; u0 < p.n; u0 += chunk) {
+    const int64_t u1 = u0 + chunk < p.n ? u0 + chunk : p.n;
+    if (feeder) {
+      if ((rc = feeder->upload(feeder->self, u0, u1))) return rc;
+      HIPCHK(hipEventRecord(c->evCopy, c->copyStream));
+      HIPCHK(hipStreamWaitEvent(c->stream, c->evCopy, 0));
     }
-    c->d_sanext = R.d_sanext; c->devBytes = R.devBytes;
+    ReadBatch C = B;
+    const int64_t r0 = p.paired ? 2 * u0 : u0, r1 = p.paired ? 2 * u1 : u1;
+    C.off1 = B.off1 + u0; if (p.paired) C.off2 = B.off2 + u0;
+    C.nreads = r1 - r0; C.lcnt = B.lcnt + r0; C.loff = B.loff + r0;
+    if (C.iv_cnt) { C.iv_cnt = B.iv_cnt + r0; C.iv_off = B.iv_off + r0; }
+    if (C.found_out) C.found_out = B.found_out + r0;
+    if (C.pair_cnt) C.pair_cnt = B.pair_cnt + u0;
+    C.read_base = r0;                                 // (what the launch calls read 0: for the skip list)
+    const int g = feeder ? qmk_map_grid_ex(r1 - r0, c->numCU, p.phc) : p.grid;
+    if (p.first == SK_DUO) HIPCHK(qmk_launch_duo(&ix, &C, c->numCU, c->stream));
+    else if (p.first == SK_LEAN || p.first == SK_LEAN_SEL) HIPCHK(qmk_launch_lean(&ix, &C, c->numCU, c->stream));
+    else if (p.first == SK_H2M) HIPCHK(qmk_h2m(&ix, &C, g, c->numCU, c->stream));
+    else if (p.twoPass) HIPCHK(qmk_map_reads_ex(&ix, &C, p.ns, 1, g, c->numCU, c->stream));
+    else HIPCHK(qmk_map_reads(&ix, &C, rq.mode == QM_RUN_COLLECT ? -1 : p.ns, g, c->numCU, c->stream));
   }
+  return QM_OK;
+}
+
+// The status word of the scalar block.  1: the list allocator ran out, 16: the interval allocator did (both: grow and redo the batch);
+// 2: an SA-interval list beyond QM_GCAP, 4: a read beyond the longest any kernel takes (both: the call fails).  A batch with one of the
+// four is redone or refused as a whole (stage_verdict), so no follow-up pass runs over it.  (8, 64: internal errors, reported there too.)
+static bool stage_ok(const u64* hscal) { return !(hscal[QM_SC_STATUS] & (1 | 2 | 4 | 16)); }
+// The scalar block as everything queued so far leaves it: the host round trip of stage A.  timedMs: the pass recorded evP0 .. evP1 around
+// its launch, and that span is added to the call's kernel time (for the N-aware pass also where it runs inside the call's ev0 .. ev1, as ever).
+static int read_scalars(qm_ctx* c, u64* hscal, float* timedMs = nullptr) {
+  HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  float t = 0; if (timedMs && hipEventElapsedTime(&t, c->evP0, c->evP1) == hipSuccess) *timedMs += t;
+  return QM_OK;
+}
+
+// The reads of the batch whose lcnt word is `mark` (QM_LCNT_LEAN, QM_LCNT_SLOW), gathered into d_slowq; Q: B pointed at that queue.  nq is the kernels' own count of
+// such reads (a scalar slot): the queue is sized for it and the gather writes no more, whatever lcnt holds.  QM_SC_SLOWQ is the gather's cursor; nothing else reads it.
+static int gather_queue(qm_ctx* c, unsigned mark, int64_t nq, const ReadBatch& B, ReadBatch& Q) {
+  int rc;
+  if ((rc = ensure(c->d_slowq, c->capSlowq, nq))) return rc;
+  HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));
+  HIPCHK(qmk_collect_marked(c->d_lcnt, B.nreads, mark, c->d_slowq, nq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
+  Q = B; Q.slowq = c->d_slowq; Q.nreads = nq;
+  return QM_OK;
+}
+
+// The N-aware pass (round 6).  The first-pass kernels leave every read with a character outside A C G T; when many of a batch's reads are
+// there for that reason (sequencers write N where a base call failed), qm_lean_kernel's N-aware edition goes over the queue of what was
+// left before the general kernel does: reads whose odd characters are all N are mapped at its rate (lean_iter<..., NQ>: k-mers with an N
+// are stepped over, MMPs end at one), the others are marked again and counted anew.  hscal: the scalars after the first pass -> after this one.
+static int pass_n_aware(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const ReadBatch& B, u64* hscal, float& extraMs) {
+  const char* npe = getenv("QM_NPASS_MIN");                      // (read per call: tests switch it; negative: never)
+  const long long minDirty = npe ? atoll(npe) : 2048LL;
+  if (p.leanWide || minDirty < 0 || p.nreads <= 0) return QM_OK;
+#ifndef QM_TIMING
+  const int64_t nq = (int64_t)hscal[QM_SC_LEANQ], dirtyReads = (int64_t)hscal[QM_SC_DEFER0];
+#else
+  const int64_t nq = (int64_t)hscal[QM_SC_LEANQ], dirtyReads = nq;   // (the phase sums sit in the slots of the four reasons, QM_SC_DEFER0 ..)
+#endif
+  if (nq <= 0 || dirtyReads < minDirty || !stage_ok(hscal)) return QM_OK;
+  int rc; ReadBatch Q;
+  if ((rc = gather_queue(c, QM_LCNT_LEAN, nq, B, Q))) return rc;
+  HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_LEANQ, 0, sizeof(u64), c->stream));
+#ifndef QM_TIMING
+  HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_DEFER0, 0, 4 * sizeof(u64), c->stream));
+#endif
+  HIPCHK(hipEventRecord(c->evP0, c->stream));
+  HIPCHK(qmk_launch_lean_nq(&ix, &Q, c->numCU, c->stream));
+  HIPCHK(hipEventRecord(c->evP1, c->stream));
+  if ((rc = read_scalars(c, hscal, &extraMs))) return rc;
+  c->lastNPass = nq - (int64_t)hscal[QM_SC_LEANQ];
+  return QM_OK;
+}
+
+// What a lean kernel marked instead of taking (a character that is not A C G T, a long run of one base, a read beyond 128 characters, a
+// wide interval, hits on both strands ...): gathered into a queue and taken by the general kernel that does the same job; everything it
+// writes goes where the first launch would have put it, and the reads it sets aside in turn (beyond its slot class) take the long-read pass.
+static int pass_lean_leftovers(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const ReadBatch& B, u64* hscal, float& extraMs) {
+#ifndef QM_TIMING
+  for (int i = 0; i < 4; ++i) c->lastDefer[i] = (int64_t)hscal[QM_SC_DEFER0 + i];   // why they were left, as the N-aware pass has it now
+#endif
+  if (p.duoMerge) c->lastDuoMerged = (int64_t)hscal[4];        // (numReads so far: the pairs the pair kernel merged; stage B's count pass adds the others)
+  const int64_t nq = (int64_t)hscal[QM_SC_LEANQ];
+  if (nq <= 0 || !stage_ok(hscal)) return QM_OK;
+  int rc; ReadBatch Q;
+  if ((rc = gather_queue(c, QM_LCNT_LEAN, nq, B, Q))) return rc;
+  c->lastLeanDeferred = nq;
+  if (p.first == SK_LEAN_SEL) {
+    // -s: the general chain-scoring collector, before the list kernels go over all reads and inside the call's ev0 .. ev1; its scalars come
+    // down with theirs.  It borrows the scratch reserved for the first launch (p.grid blocks), so it stays within that grid.
+    const int g2 = qmk_map_grid_ex(nq, c->numCU, p.phc);
+    HIPCHK(qmk_map_reads_ex(&ix, &Q, p.ns, 1, g2 < p.grid ? g2 : p.grid, c->numCU, c->stream));
+    return QM_OK;
+  }
+  // the default call: the general kernels' scratch does not exist yet (B was filled in without it) and is reserved for this launch's own
+  // grid -- the dense table's, on the compact -p image too.  The launch comes after ev1: timed by itself.
+  const int g2 = qmk_map_grid_ex(nq, c->numCU, 0);
+  if ((rc = gscr_for(c, g2, Q.gslots, Q.ngslots))) return rc;
+  Q.gscratch = c->d_gscr;
+  HIPCHK(hipEventRecord(c->evP0, c->stream));
+  HIPCHK(qmk_map_reads(&ix, &Q, p.ns, g2, c->numCU, c->stream));
+  HIPCHK(hipEventRecord(c->evP1, c->stream));
+  return read_scalars(c, hscal, &extraMs);
+}
+
+// Reads longer than the slot class of the first launch (always: longer than QM_MAX_READ_LEN) were set aside (map_read): gathered and
+// mapped by the 32-slot kernels (ns32: 32; -32: their collector alone) -- a second, small launch; everything it writes (lists, intervals,
+// foundHit) goes where the first pass would have put it.
+static int pass_long_reads(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const ReadBatch& B, u64* hscal, int ns32) {
+  const int64_t nl = (int64_t)hscal[QM_SC_SLOWCNT];
+  if (nl <= 0 || !stage_ok(hscal)) return QM_OK;
+  int rc; ReadBatch Q;
+  if ((rc = gather_queue(c, QM_LCNT_SLOW, nl, B, Q))) return rc;
+  c->lastSlowReads = nl;
+  // the launch uses the scratch of the first one, so it stays within its grid; after a lean kernel, which has none, the scratch is reserved here
+  const int g2 = qmk_map_grid_ex(nl, c->numCU, p.phc), g = g2 < p.grid ? g2 : p.grid;
+  if (lean_first(p)) { if ((rc = gscr_for(c, g, Q.gslots, Q.ngslots))) return rc; Q.gscratch = c->d_gscr; }
+  HIPCHK(qmk_map_reads(&ix, &Q, ns32, g, c->numCU, c->stream));
+  if (!p.twoPass) return read_scalars(c, hscal);
+  // fused -s: the list kernels run next; their own slow queue (reads whose intervals overflow their scratch: pass_sel_slow) starts from zero
+  static_assert(QM_SC_SLOWMAX == QM_SC_SLOWCNT + 1, "the queue's count and its largest entry: one memset");
+  HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWCNT, 0, 2 * sizeof(u64), c->stream));
+  return QM_OK;
+}
+
+// The list kernels of a fused -s call over H, the collectors' intervals.
+static int run_list_kernels(qm_ctx* c, const StagePlan& p, const RunReq& rq, const DevIndex& ix, const ReadBatch& H) {
+  if (!p.twoPass || p.nreads <= 0) return QM_OK;
+  const char* pe = getenv("QM_SEL_PACK");              // 0: the one-read-per-wavefront list kernel for every read (A/B timing, tests)
+  if (pe && atoi(pe) == 0) { HIPCHK(qmk_h2m(&ix, &H, p.grid, c->numCU, c->stream)); return QM_OK; }
+  int rc;
+  // several reads per wavefront first (qm_selpack.inl); what that kernel cannot take -- hits on both strands, more than 64
+  // intervals or suffixes -- it queues, and the one-read-per-wavefront kernel runs over the queue (its length stays on the device)
+  if ((rc = ensure(c->d_todoq, c->capTodoq, p.nreads))) return rc;
+  // ... then the wide edition (256 lanes' worth per batch: reads of 150 bp and more) over that queue, which leaves one of its own.
+  // A batch of reads beyond 192 characters goes to the wide edition directly: hardly any of them fits the narrow one's 64 lanes
+  if ((rc = ensure(c->d_todoq2, c->capTodoq2, p.nreads))) return rc;
+  static const int wideFrom = [] { const char* e = getenv("QM_SEL_WIDE_FROM"); return e ? atoi(e) : 192; }();   // (tuning knob)
+  if (rq.shortLen > wideFrom) HIPCHK(qmk_h2m_packw(&ix, &H, nullptr, nullptr, c->d_todoq2, p.grid, c->numCU, c->stream));
+  else {
+    HIPCHK(qmk_h2m_pack(&ix, &H, c->d_todoq, p.grid, c->numCU, c->stream));
+    HIPCHK(qmk_h2m_packw(&ix, &H, c->d_todoq, (const unsigned long long*)(c->d_scal + QM_SC_TODO), c->d_todoq2, p.grid, c->numCU, c->stream));
+  }
+  ReadBatch T = H; T.slowq = c->d_todoq2; T.nreads_dev = c->d_scal + QM_SC_TODO2;
+  HIPCHK(qmk_h2m(&ix, &T, p.grid, c->numCU, c->stream));
+  return QM_OK;
+}
+
+// -s: reads whose SA intervals hold more suffixes than a wave's scratch (repeats, low-complexity reads) were left on the slow queue: gathered, a few waves given
+// scratch sized for the largest, and mapped by the one-read-per-wavefront list kernel (qmk_h2m: what the first launch of a QM_RUN_FROM_INTERVALS call runs too) over its view H
+static int pass_sel_slow(qm_ctx* c, const qm_opts* o, const RunReq& rq, const DevIndex& ix, const ReadBatch& H, u64* hscal) {
+  if (!o->sel_aln || rq.mode == QM_RUN_COLLECT) return QM_OK;
+  const int64_t ns_ = (int64_t)hscal[QM_SC_SLOWCNT];
+  if (ns_ <= 0 || !stage_ok(hscal)) return QM_OK;
+  int rc; ReadBatch Q;
+  const int64_t need = (((int64_t)hscal[QM_SC_SLOWMAX] + 63) / 64) * 64 + 64;
+  if ((rc = gather_queue(c, QM_LCNT_SLOW, ns_, H, Q))) return rc;
+  const unsigned long long per = (qmk_sel_dyn_bytes(need) + 255) & ~255ULL;
+  int64_t waves = ns_ < 256 ? ns_ : 256;
+  while (waves > 4 && (unsigned long long)waves * per > (8ULL << 30)) waves /= 2;      // at most 8 GB of scratch
+  const int sgrid = (int)((waves + 3) / 4);
+  if ((rc = ensure(c->d_dynmem, c->capDynMem, (int64_t)((unsigned long long)sgrid * 4 * per)))) return rc;
+  const size_t sb = qmk_sel_dyn_struct_bytes();
+  std::vector<unsigned char> hd((size_t)sgrid * 4 * sb);
+  for (int w = 0; w < sgrid * 4; ++w) qmk_sel_dyn_bind(hd.data() + (size_t)w * sb, c->d_dynmem + (unsigned long long)w * per, need);
+  if ((rc = ensure(c->d_dyn, c->capDyn, (int64_t)hd.size()))) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_dyn, hd.data(), hd.size(), hipMemcpyHostToDevice, c->stream));
+  Q.dyn = (SelScratchDyn*)c->d_dyn; Q.iv_out = nullptr; Q.found_out = nullptr;   // (intervals and foundHit: already written by the first pass)
+  HIPCHK(qmk_h2m(&ix, &Q, sgrid, c->numCU, c->stream));
+  if ((rc = read_scalars(c, hscal))) return rc;           // (hd is a local: the copy above is done)
+  c->lastSlowReads = ns_;
+  return QM_OK;
+}
+
+// What the final status word means for the call: QM_OK, an error, or QM_STAGE_RETRY after a bump allocator ran out and its buffer was grown.
+enum { QM_STAGE_RETRY = 1 };
+static int stage_verdict(qm_ctx* c, const StagePlan& p, const u64* hscal) {
+  const int status = (int)(hscal[QM_SC_STATUS] & 0xffffffffu); int rc;
+  if (status & 4) return fail(QM_E_TOOLONG, "a read is longer than %d characters (-s: the alignment kernels are sized for that; otherwise the long-read pass takes up to %d)", QM_MAX_LONG_READ_LEN, QM_MAX_LONG_READ_LEN);
+  if (status & 2) return fail(QM_E_UNSUPPORTED, "an SA-interval list exceeded %d entries (max_interval too large)", QM_GCAP);
+  if (status & 8) return fail(QM_E_STATE, "selective alignment: a read overflowed the scratch sized for it (internal error)");
+  if (status & 64) return fail(QM_E_STATE, "a wavefront found no free scratch slot on its XCD (internal error)");
+  if (!(status & 17)) return QM_OK;
+  if (status & 1) {
+    int64_t want = (int64_t)hscal[0] + p.nreads + (int64_t)p.grid * 4 * QM_CHUNK;
+    if (want < c->capLists * 2) want = c->capLists * 2;
+    if ((rc = ensure(c->d_lists, c->capLists, want))) return rc;
+  }
+  if (status & 16) {
+    int64_t want = (int64_t)hscal[QM_SC_IVCUR] + p.nreads + (int64_t)p.grid * 4 * QM_IVCHUNK;
+    if (want < c->capIv * 2) want = c->capIv * 2;
+    if ((rc = ensure(c->d_iv, c->capIv, want))) return rc;
+  }
+  c->lastRelaunches += 1;
+  return QM_STAGE_RETRY;
+}
+
+static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n, const void* d_seq1, const void* d_off1, const void* d_seq2,
+                       const void* d_off2, int ns, ChunkFeeder* feeder, u64* hscal) {
+  int rc; StagePlan p;
+  if ((rc = plan_stage_a(c, o, rq, d_seq2 != nullptr, n, ns, p))) return rc;
+  if ((rc = reserve_stage_a(c, o, rq, p))) return rc;
   const DevIndex ix = dev_index(c);
-  c->lastRelaunches = 0; c->lastSlowReads = 0; c->lastIvTotal = 0; c->lastLeanReads = useLean ? nreads : -1; c->lastLeanDeferred = 0;
-  c->lastDuoPairs = useDuo ? n : -1; c->lastDuoMerged = 0;
+  const int64_t nreads = p.nreads;
+  c->lastRelaunches = 0; c->lastSlowReads = 0; c->lastIvTotal = 0; c->lastLeanReads = lean_first(p) ? nreads : -1; c->lastLeanDeferred = 0;
+  c->lastDuoPairs = p.first == SK_DUO ? n : -1; c->lastDuoMerged = 0;
   for (int i = 0; i < 4; ++i) c->lastDefer[i] = 0;
   c->lastNPass = 0;
-  float leanExtraMs = 0;
+  float extraMs = 0;                                     // the passes timed by themselves (read_scalars' timedMs), over all retries
   while (true) {
-    ReadBatch B; memset(&B, 0, sizeof(B));
-    B.seq1 = (const unsigned char*)d_seq1; B.off1 = (const long long*)d_off1;
-    B.seq2 = (const unsigned char*)d_seq2; B.off2 = (const long long*)d_off2; B.nreads = nreads;
-    B.lcnt = c->d_lcnt; B.loff = c->d_loff; B.lists = c->d_lists; B.cursor = c->d_scal; B.lists_cap = c->capLists;
-    B.status = (int*)(c->d_scal + QM_SC_STATUS); B.gscratch = c->d_gscr; B.gslots = gslots; B.ngslots = ngslots; B.gxcd = xcds_of(c); B.skiplist = c->d_skip;
-    B.lean_wide = leanWide ? 1 : 0;
-    if (duoMerge) { B.pair_cnt = c->d_cnt; B.max_num_hits = o->max_num_hits; B.no_orphans = o->no_orphans; B.no_dovetail = o->no_dovetail; }
-    if (wantIv) { B.iv_out = c->d_iv; B.iv_cnt = c->d_ivcnt; B.iv_off = c->d_ivoff; B.iv_cap = c->capIv; }
-    if (wantFound) B.found_out = c->d_found;
-    B.iv_in = rq.ivIn; B.iv_in_off = rq.ivInOff; B.len_in = rq.lenIn; B.found_in = rq.foundIn;
-    B.strict_check = o->strict_check; B.max_interval = o->max_interval; B.quasi_cov = o->quasi_cov; B.sensitive = o->sensitive; B.fuzzy = paired ? o->fuzzy : 0;
-    if (rq.mode == QM_RUN_FROM_INTERVALS) B.fuzzy = o->fuzzy;   // the caller says what kind of list it wants (both orientations kept or not)
-    if (o->sel_aln) {                                   // -s: chain scoring + per-wave scratch for chaining (qm_sel.inl)
-      if ((rc = ensure(c->d_selscr, c->capSelScr, (int64_t)qmk_resident_grid(nreads, c->numCU) * 4 * (int64_t)qmk_sel_scratch_bytes()))) return rc;   // (the list kernels' grids stay within residency)
-      B.selscr = (SelScratch*)c->d_selscr;
-      B.max_mmp_ext = o->max_mmp_extension > 0 ? o->max_mmp_extension : 7;
-      const float cs = (float)o->consensus_slack;        // MappingOpts::consensusSlack is a float (RapMapSAMapper.cpp:138,184-185)
-      B.consensus_fraction = cs < 0 ? -cs : ((cs == 0.0) ? 1.0 : (1.0 - cs));   // negative: MappingConfig::consensusFraction itself (qmap_mi355.h)
-    }
-    HIPCHK(hipMemsetAsync(c->d_scal, 0, QM_SC_WORDS * sizeof(u64), c->stream));
-    if (rq.mode == QM_RUN_COLLECT || twoPass) HIPCHK(hipMemsetAsync(c->d_lcnt, 0, (size_t)(nreads + 1) * sizeof(uint32_t), c->stream));   // collector-only kernels write no list lengths: the array only carries the long-read marks
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    auto launch = [&](const ReadBatch& X, int g) -> hipError_t {
-      if (useDuo) return qmk_launch_duo(&ix, &X, c->numCU, c->stream);
-      if (useLean || (useLeanSel && ix.sanext)) return qmk_launch_lean(&ix, &X, c->numCU, c->stream);
-      if (rq.mode == QM_RUN_FROM_INTERVALS) return qmk_h2m(&ix, &X, g, c->numCU, c->stream);
-      if (twoPass) return qmk_map_reads_ex(&ix, &X, ns, 1, g, c->numCU, c->stream);
-      return qmk_map_reads(&ix, &X, rq.mode == QM_RUN_COLLECT ? -1 : ns, g, c->numCU, c->stream);
-    };
-    // The N-aware pass (round 6).  The first-pass kernels leave every read with a character outside A C G T; when many of a batch's reads are
-    // there for that reason (sequencers write N where a base call failed), qm_lean_kernel's N-aware edition goes over the queue of what was
-    // left before the general kernel does: reads whose odd characters are all N are mapped at its rate (lean_iter<..., NQ>: k-mers with an N
-    // are stepped over, MMPs end at one), the others are marked again and counted anew.  hscal: the scalars after the first pass -> after this one.
-    auto n_pass = [&]() -> int {
-      const char* npe = getenv("QM_NPASS_MIN");                      // (read per call: tests switch it; negative: never)
-      const long long minDirty = npe ? atoll(npe) : 2048LL;
-      if (leanWide || minDirty < 0 || nreads <= 0) return QM_OK;
-      const int64_t nq = (int64_t)hscal[QM_SC_LEANQ];
-#ifndef QM_TIMING
-      const int64_t dirtyReads = (int64_t)hscal[QM_SC_DEFER0];
-#else
-      const int64_t dirtyReads = nq;
-#endif
-      if (nq <= 0 || dirtyReads < minDirty || ((int)(hscal[QM_SC_STATUS] & 0xffffffffu) & 23)) return QM_OK;
-      int r;
-      if ((r = ensure(c->d_slowq, c->capSlowq, nq))) return r;
-      HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));
-      HIPCHK(qmk_collect_lean(c->d_lcnt, nreads, c->d_slowq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
-      HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_LEANQ, 0, sizeof(u64), c->stream));
-#ifndef QM_TIMING
-      HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_DEFER0, 0, 4 * sizeof(u64), c->stream));
-#endif
-      ReadBatch Q = B;
-      Q.slowq = c->d_slowq; Q.nreads = nq;
-      HIPCHK(hipEventRecord(c->evP0, c->stream));
-      HIPCHK(qmk_launch_lean_nq(&ix, &Q, c->numCU, c->stream));
-      HIPCHK(hipEventRecord(c->evP1, c->stream));
-      HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));
-      HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      float t = 0; if (hipEventElapsedTime(&t, c->evP0, c->evP1) == hipSuccess) leanExtraMs += t;
-      c->lastNPass = nq - (int64_t)hscal[QM_SC_LEANQ];
-      return QM_OK;
-    };
-    // second pass of a two-pass -s call (also the slow pass's kernel): intervals -> lists
+    ReadBatch B;
+    fill_batch(c, o, rq, p, d_seq1, d_off1, d_seq2, d_off2, B);
+    // the list kernels' view of a two-pass -s call (also the slow pass's): the collectors' intervals in (they stay valid, kept for the caller or not), nothing of theirs out
     ReadBatch H = B;
-    if (twoPass) {
-      H.iv_in = c->d_iv; H.iv_in_off = c->d_ivoff; H.iv_in_cnt = c->d_ivcnt; H.found_in = c->d_found;
-      if (!rq.keepIntervals) { }                       // the interval output stays valid either way: it is this pass's input
-      H.iv_out = nullptr; H.found_out = nullptr;
-    }
-    if (feeder && n > 0) {
-      // first pass over host buffers: one launch per chunk, each behind its own upload.  A launch sees its chunk through
-      // shifted pointers (offsets are absolute, the per-read / per-unit arrays start at the chunk), the bump allocators,
-      // the counters and the status word are shared.
-      for (int64_t u0 = 0; u0 < n; u0 += feeder->chunk) {
-        const int64_t u1 = u0 + feeder->chunk < n ? u0 + feeder->chunk : n;
-        if ((rc = feeder->upload(feeder->self, u0, u1))) return rc;
-        HIPCHK(hipEventRecord(c->evCopy, c->copyStream));
-        HIPCHK(hipStreamWaitEvent(c->stream, c->evCopy, 0));
-        ReadBatch C = B;
-        const int64_t r0 = paired ? 2 * u0 : u0, r1 = paired ? 2 * u1 : u1;
-        C.off1 = B.off1 + u0; if (paired) C.off2 = B.off2 + u0;
-        C.nreads = r1 - r0; C.lcnt = B.lcnt + r0; C.loff = B.loff + r0;
-        if (C.iv_cnt) { C.iv_cnt = B.iv_cnt + r0; C.iv_off = B.iv_off + r0; }
-        if (C.found_out) C.found_out = B.found_out + r0;
-        if (C.pair_cnt) C.pair_cnt = B.pair_cnt + u0;
-        C.read_base = r0;                                 // (what the launch calls read 0: for the skip list)
-        HIPCHK(launch(C, qmk_map_grid_ex(r1 - r0, c->numCU, phc)));
-      }
-      feeder = nullptr;                                   // a retry finds everything resident
-    } else if (nreads > 0) HIPCHK(launch(B, grid));
-    if (useLeanSel && ix.sanext && nreads > 0) {
-      // what the lean collector marked instead of walking: gathered and walked by the general chain-scoring collector, before the
-      // list kernels go over all reads
-      HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      if ((rc = n_pass())) return rc;
-      const int st0 = (int)(hscal[QM_SC_STATUS] & 0xffffffffu);
-#ifndef QM_TIMING
-      for (int i = 0; i < 4; ++i) c->lastDefer[i] = (int64_t)hscal[QM_SC_DEFER0 + i];
-#endif
-      if (hscal[QM_SC_LEANQ] > 0 && !(st0 & 23)) {
-        const int64_t nq = (int64_t)hscal[QM_SC_LEANQ];
-        if ((rc = ensure(c->d_slowq, c->capSlowq, nq))) return rc;
-        HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));
-        HIPCHK(qmk_collect_lean(c->d_lcnt, nreads, c->d_slowq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
-        ReadBatch S2 = B;
-        S2.slowq = c->d_slowq; S2.nreads = nq;
-        const int g2 = qmk_map_grid_ex(nq, c->numCU, phc);
-        HIPCHK(qmk_map_reads_ex(&ix, &S2, ns, 1, g2 < grid ? g2 : grid, c->numCU, c->stream));
-        HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));   // (the passes below gather with the same counter)
-        c->lastLeanDeferred = nq;
-      }
+    if (p.twoPass) { H.iv_in = c->d_iv; H.iv_in_off = c->d_ivoff; H.iv_in_cnt = c->d_ivcnt; H.found_in = c->d_found; H.iv_out = nullptr; H.found_out = nullptr; }
+    HIPCHK(hipMemsetAsync(c->d_scal, 0, QM_SC_WORDS * sizeof(u64), c->stream));
+    if (rq.mode == QM_RUN_COLLECT || p.twoPass) HIPCHK(hipMemsetAsync(c->d_lcnt, 0, (size_t)(nreads + 1) * sizeof(uint32_t), c->stream));   // collector-only kernels write no list lengths: the array only carries the long-read marks
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    if ((rc = launch_first(c, p, rq, ix, B, feeder))) return rc;
+    feeder = nullptr;                                     // a retry finds everything resident
+    if (p.first == SK_LEAN_SEL && nreads > 0) {          // -s: what the lean collector left reaches the general one before the list kernels run
+      if ((rc = read_scalars(c, hscal)) || (rc = pass_n_aware(c, p, ix, B, hscal, extraMs)) || (rc = pass_lean_leftovers(c, p, ix, B, hscal, extraMs))) return rc;
       c->lastLeanReads = nreads;
     }
-    if (twoPass && rq.longReads && nreads > 0) {
-      // -s with reads beyond QM_MAX_READ_LEN in the batch: the collector set them aside (map_read); their intervals come from a
-      // second, small launch of the 32-slot chain-scoring collector, before the list kernel goes over all reads
-      HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      const int st1 = (int)(hscal[QM_SC_STATUS] & 0xffffffffu);
-      if (hscal[QM_SC_SLOWCNT] > 0 && !(st1 & 23)) {
-        const int64_t nl_ = (int64_t)hscal[QM_SC_SLOWCNT];
-        if ((rc = ensure(c->d_slowq, c->capSlowq, nl_))) return rc;
-        HIPCHK(qmk_collect_slow(c->d_lcnt, nreads, c->d_slowq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
-        ReadBatch S2 = B;
-        S2.slowq = c->d_slowq; S2.nreads = nl_;
-        const int g2 = qmk_map_grid_ex(nl_, c->numCU, phc);
-        HIPCHK(qmk_map_reads(&ix, &S2, -32, g2 < grid ? g2 : grid, c->numCU, c->stream));
-        // the list kernel's own slow queue (reads whose intervals overflow its scratch) starts from zero
-        HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWCNT, 0, 3 * sizeof(u64), c->stream));
-        c->lastSlowReads = nl_;
-      }
-    }
-    if (twoPass && nreads > 0) {
-      const char* pe = getenv("QM_SEL_PACK");              // 0: the one-read-per-wavefront list kernel for every read (A/B timing, tests)
-      const bool packed = !(pe && atoi(pe) == 0);
-      if (packed) {
-        // several reads per wavefront first (qm_selpack.inl); what that kernel cannot take -- hits on both strands, more than 64
-        // intervals or suffixes -- it queues, and the one-read-per-wavefront kernel runs over the queue (its length stays on the device)
-        if ((rc = ensure(c->d_todoq, c->capTodoq, nreads))) return rc;
-        // ... then the wide edition (256 lanes' worth per batch: reads of 150 bp and more) over that queue, which leaves one of its own.
-        // A batch of reads beyond 192 characters goes to the wide edition directly: hardly any of them fits the narrow one's 64 lanes
-        if ((rc = ensure(c->d_todoq2, c->capTodoq2, nreads))) return rc;
-        static const int wideFrom = [] { const char* e = getenv("QM_SEL_WIDE_FROM"); return e ? atoi(e) : 192; }();   // (tuning knob)
-        if (rq.shortLen > wideFrom) HIPCHK(qmk_h2m_packw(&ix, &H, nullptr, nullptr, c->d_todoq2, grid, c->numCU, c->stream));
-        else {
-          HIPCHK(qmk_h2m_pack(&ix, &H, c->d_todoq, grid, c->numCU, c->stream));
-          HIPCHK(qmk_h2m_packw(&ix, &H, c->d_todoq, (const unsigned long long*)(c->d_scal + QM_SC_TODO), c->d_todoq2, grid, c->numCU, c->stream));
-        }
-        ReadBatch T = H; T.slowq = c->d_todoq2; T.nreads_dev = c->d_scal + QM_SC_TODO2;
-        HIPCHK(qmk_h2m(&ix, &T, grid, c->numCU, c->stream));
-      } else HIPCHK(qmk_h2m(&ix, &H, grid, c->numCU, c->stream));
-    }
+    // fused -s with reads beyond QM_MAX_READ_LEN in the batch: the counts come down once more, so that the 32-slot collector has their intervals ready for the list kernels
+    if (p.twoPass && rq.longReads && nreads > 0 && ((rc = read_scalars(c, hscal)) || (rc = pass_long_reads(c, p, ix, B, hscal, -32)))) return rc;
+    if ((rc = run_list_kernels(c, p, rq, ix, H))) return rc;
     HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (useLean && (rc = n_pass())) return rc;
-    int status = (int)(hscal[QM_SC_STATUS] & 0xffffffffu);
-#ifndef QM_TIMING
-    if (useLean) for (int i = 0; i < 4; ++i) c->lastDefer[i] = (int64_t)hscal[QM_SC_DEFER0 + i];
-#endif
-    if (duoMerge) c->lastDuoMerged = (int64_t)hscal[4];        // (numReads so far: the pairs the pair kernel merged; stage B's count pass adds the others)
-    if (useLean && hscal[QM_SC_LEANQ] > 0 && !(status & 23)) {
-      // what the lean kernel marked instead of mapping (a character that is not A C G T, a long run of one base, a read beyond 128
-      // characters, a wide interval, hits on both strands ...): gathered into a queue and mapped by the general kernel; everything it
-      // writes goes where the first launch would have put it, and the reads it sets aside in turn (beyond its slot class) take the
-      // long-read pass below
-      const int64_t nq = (int64_t)hscal[QM_SC_LEANQ];
-      if ((rc = ensure(c->d_slowq, c->capSlowq, nq))) return rc;
-      const int g2 = qmk_map_grid_ex(nq, c->numCU, 0);
-      unsigned* gs2 = nullptr; int ngs2 = 0;
-      if ((rc = gscr_for(c, g2, gs2, ngs2))) return rc;
-      HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));
-      HIPCHK(qmk_collect_lean(c->d_lcnt, nreads, c->d_slowq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
-      ReadBatch S2 = B;
-      S2.slowq = c->d_slowq; S2.nreads = nq; S2.gscratch = c->d_gscr; S2.gslots = gs2; S2.ngslots = ngs2;      // (B was filled in before the scratch existed)
-      HIPCHK(hipEventRecord(c->evP0, c->stream));
-      HIPCHK(qmk_map_reads(&ix, &S2, ns, g2, c->numCU, c->stream));
-      HIPCHK(hipEventRecord(c->evP1, c->stream));
-      HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));   // (the long-read pass gathers with the same counter)
-      HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      status = (int)(hscal[QM_SC_STATUS] & 0xffffffffu);
-      float t = 0; if (hipEventElapsedTime(&t, c->evP0, c->evP1) == hipSuccess) leanExtraMs += t;
-      c->lastLeanDeferred = nq;
-    }
-    if ((!o->sel_aln || rq.mode == QM_RUN_COLLECT) && rq.mode != QM_RUN_FROM_INTERVALS && hscal[QM_SC_SLOWCNT] > 0 && !(status & 23)) {
-      // reads longer than the slot class of this launch (always: longer than QM_MAX_READ_LEN) were set aside: gather them
-      // and map them with the 32-slot kernels -- a second, small launch; everything it writes (lists, intervals, foundHit)
-      // goes where the first pass would have put it
-      const int64_t nl_ = (int64_t)hscal[QM_SC_SLOWCNT];
-      if ((rc = ensure(c->d_slowq, c->capSlowq, nl_))) return rc;
-      HIPCHK(qmk_collect_slow(c->d_lcnt, nreads, c->d_slowq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
-      ReadBatch S2 = B;
-      S2.slowq = c->d_slowq; S2.nreads = nl_;
-      const int g2 = qmk_map_grid_ex(nl_, c->numCU, phc);
-      if (useLean) { unsigned* gs3 = nullptr; int ngs3 = 0; if ((rc = gscr_for(c, g2 < grid ? g2 : grid, gs3, ngs3))) return rc; S2.gscratch = c->d_gscr; S2.gslots = gs3; S2.ngslots = ngs3; }
-      HIPCHK(qmk_map_reads(&ix, &S2, rq.mode == QM_RUN_COLLECT ? -32 : 32, g2 < grid ? g2 : grid, c->numCU, c->stream));
-      HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      status = (int)(hscal[QM_SC_STATUS] & 0xffffffffu);
-      c->lastSlowReads = nl_;
-    }
-    if (o->sel_aln && rq.mode != QM_RUN_COLLECT && hscal[QM_SC_SLOWCNT] > 0 && !(status & 23)) {
-      // -s: reads whose SA intervals hold more suffixes than a wave's scratch (repeats, low-complexity reads) were left on
-      // the slow queue: gather them, give a few waves scratch sized for the largest, and map them with the same kernel
-      const int64_t ns_ = (int64_t)hscal[QM_SC_SLOWCNT];
-      const int64_t need = (((int64_t)hscal[QM_SC_SLOWMAX] + 63) / 64) * 64 + 64;
-      if ((rc = ensure(c->d_slowq, c->capSlowq, ns_))) return rc;
-      HIPCHK(qmk_collect_slow(c->d_lcnt, nreads, c->d_slowq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
-      const unsigned long long per = (qmk_sel_dyn_bytes(need) + 255) & ~255ULL;
-      int64_t waves = ns_ < 256 ? ns_ : 256;
-      while (waves > 4 && (unsigned long long)waves * per > (8ULL << 30)) waves /= 2;      // at most 8 GB of scratch
-      const int sgrid = (int)((waves + 3) / 4);
-      if ((rc = ensure(c->d_dynmem, c->capDynMem, (int64_t)((unsigned long long)sgrid * 4 * per)))) return rc;
-      const size_t sb = qmk_sel_dyn_struct_bytes();
-      std::vector<unsigned char> hd((size_t)sgrid * 4 * sb);
-      for (int w = 0; w < sgrid * 4; ++w) qmk_sel_dyn_bind(hd.data() + (size_t)w * sb, c->d_dynmem + (unsigned long long)w * per, need);
-      if ((rc = ensure(c->d_dyn, c->capDyn, (int64_t)hd.size()))) return rc;
-      HIPCHK(hipMemcpyAsync(c->d_dyn, hd.data(), hd.size(), hipMemcpyHostToDevice, c->stream));
-      ReadBatch S2 = twoPass ? H : B;
-      S2.slowq = c->d_slowq; S2.dyn = (SelScratchDyn*)c->d_dyn; S2.nreads = ns_;
-      S2.iv_out = nullptr; S2.found_out = nullptr;            // already written by the first pass
-      if (twoPass) HIPCHK(qmk_h2m(&ix, &S2, sgrid, c->numCU, c->stream));
-      else HIPCHK(launch(S2, sgrid));
-      HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));                 // hd is a local
-      status = (int)(hscal[QM_SC_STATUS] & 0xffffffffu);
-      c->lastSlowReads = ns_;
-    }
+    if ((rc = read_scalars(c, hscal))) return rc;
+    if (lean_first(p) && ((rc = pass_n_aware(c, p, ix, B, hscal, extraMs)) || (rc = pass_lean_leftovers(c, p, ix, B, hscal, extraMs)))) return rc;
+    if ((!o->sel_aln || rq.mode == QM_RUN_COLLECT) && rq.mode != QM_RUN_FROM_INTERVALS && (rc = pass_long_reads(c, p, ix, B, hscal, rq.mode == QM_RUN_COLLECT ? -32 : 32))) return rc;
+    if ((rc = pass_sel_slow(c, o, rq, ix, H, hscal))) return rc;
 #ifdef QM_TIMING
-    {
+    {                                                    // the phase sums of the -DQM_TIMING kernels: stage A's, qm_h2m_kernel's, the packed list kernels'
       static const char* nm[7] = {"read->LDS", "strand setup", "probe windows", "extension", "collector rest", "hits->mappings", "write-out+loop"};
       double tot = 0; for (int i = 0; i < 7; ++i) tot += (double)hscal[20 + i];
       for (int i = 0; i < 7; ++i) fprintf(stderr, "[qm timing] %-16s %6.2f %%  %10.0f clk/read\n", nm[i], 100.0 * hscal[20 + i] / tot, (double)hscal[20 + i] / (double)nreads);
@@ -1149,24 +1189,8 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
       if (pt > 0) for (int i = 0; i < 8; ++i) fprintf(stderr, "[qm timing pack] %-16s %6.2f %%  %10.0f clk/read\n", pm[i], 100.0 * hscal[40 + i] / pt, (double)hscal[40 + i] / (double)nreads);
     }
 #endif
-    if (status & 4) return fail(QM_E_TOOLONG, "a read is longer than %d characters (-s: the alignment kernels are sized for that; otherwise the long-read pass takes up to %d)", len_limit(o), QM_MAX_LONG_READ_LEN);
-    if (status & 2) return fail(QM_E_UNSUPPORTED, "an SA-interval list exceeded %d entries (max_interval too large)", QM_GCAP);
-    if (status & 8) return fail(QM_E_STATE, "selective alignment: a read overflowed the scratch sized for it (internal error)");
-    if (status & 64) return fail(QM_E_STATE, "a wavefront found no free scratch slot on its XCD (internal error)");
-    if (status & 17) {           // a bump allocator ran out: grow and redo the batch
-      if (status & 1) {
-        int64_t want = (int64_t)hscal[0] + nreads + (int64_t)grid * 4 * QM_CHUNK;
-        if (want < c->capLists * 2) want = c->capLists * 2;
-        if ((rc = ensure(c->d_lists, c->capLists, want))) return rc;
-      }
-      if (status & 16) {
-        int64_t want = (int64_t)hscal[QM_SC_IVCUR] + nreads + (int64_t)grid * 4 * QM_IVCHUNK;
-        if (want < c->capIv * 2) want = c->capIv * 2;
-        if ((rc = ensure(c->d_iv, c->capIv, want))) return rc;
-      }
-      c->lastRelaunches += 1;
-      continue;
-    }
+    if ((rc = stage_verdict(c, p, hscal)) == QM_STAGE_RETRY) continue;
+    if (rc) return rc;
     break;
   }
   // reads that were skipped, not mapped (beyond QM_MAX_LONG_READ_LEN characters; interval lists beyond the scratch): their list
@@ -1175,12 +1199,23 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
     c->skipList.resize((size_t)(c->lastSkipped < QM_SKIP_CAP ? c->lastSkipped : QM_SKIP_CAP));
     HIPCHK(hipMemcpy(c->skipList.data(), c->d_skip, c->skipList.size() * sizeof(u64), hipMemcpyDeviceToHost));
   }
-  c->lastIvTotal = wantIv ? (int64_t)hscal[QM_SC_IVCUR] : 0;
-  c->lastIvReads = wantIv ? nreads : -1;
-  c->lastFoundReads = wantFound ? nreads : -1;
-  c->lastListReads = (rq.mode != QM_RUN_COLLECT && !duoMerge) ? nreads : -1;   // (pairs the pair kernel merged have no per-read lists)
+  c->lastIvTotal = p.wantIv ? (int64_t)hscal[QM_SC_IVCUR] : 0;
+  c->lastIvReads = p.wantIv ? nreads : -1;
+  c->lastFoundReads = p.wantFound ? nreads : -1;
+  c->lastListReads = (rq.mode != QM_RUN_COLLECT && !p.duoMerge) ? nreads : -1;   // (pairs the pair kernel merged have no per-read lists)
   c->lastListWords = (int64_t)hscal[0];
-  float ms = 0; hipEventElapsedTime(&ms, c->ev0, c->ev1); c->lastMapMs = ms + leanExtraMs;
+  float ms = 0; hipEventElapsedTime(&ms, c->ev0, c->ev1); c->lastMapMs = ms + extraMs;
+  return QM_OK;
+}
+
+// the temporary storage of the device scans (qmk_scan_counts) over `items` counts
+static int ensure_scan_tmp(qm_ctx* c, int64_t items) {
+  const size_t stb = qmk_scan_temp_bytes(items);
+  if (stb <= c->scanTmpBytes && c->d_scanTmp) return QM_OK;
+  if (c->d_scanTmp) hipFree(c->d_scanTmp);
+  c->d_scanTmp = nullptr; c->scanTmpBytes = 0;
+  HIPCHK(hipMalloc(&c->d_scanTmp, stb ? stb : 16));
+  c->scanTmpBytes = stb;
   return QM_OK;
 }
 
@@ -1190,13 +1225,7 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   int rc;
   if ((rc = ensure(c->d_cnt, c->capCnt, n + 1))) return rc;
   if ((rc = ensure(c->d_offs, c->capOffs, n + 1))) return rc;
-  size_t stb = qmk_scan_temp_bytes(n + 1);
-  if (stb > c->scanTmpBytes || !c->d_scanTmp) {
-    if (c->d_scanTmp) hipFree(c->d_scanTmp);
-    c->d_scanTmp = nullptr; c->scanTmpBytes = 0;
-    HIPCHK(hipMalloc(&c->d_scanTmp, stb ? stb : 16));
-    c->scanTmpBytes = stb;
-  }
+  if ((rc = ensure_scan_tmp(c, n + 1))) return rc;
   PairBatch P; memset(&P, 0, sizeof(P));
   P.n = n; P.paired = paired ? 1 : 0; P.off1 = (const long long*)d_off1; P.off2 = (const long long*)d_off2;
   P.lcnt = c->d_lcnt; P.loff = c->d_loff; P.lists = c->d_lists; P.cnt = c->d_cnt; P.offs = c->d_offs;
@@ -1315,7 +1344,7 @@ static int map_device_impl(qm_ctx* c, const qm_opts* o, int64_t n, const void* d
   int rc = check_opts(o);
   if (rc) return rc;
   if ((d_seq2 == nullptr) != (d_off2 == nullptr)) return fail(QM_E_ARG, "seq2/off2 must both be given or both be null");
-  // (a read beyond len_limit() is skipped, not mapped: qm_fetch_skipped)
+  // (a read beyond QM_MAX_LONG_READ_LEN is skipped, not mapped: qm_fetch_skipped)
   HIPCHK(hipSetDevice(c->device));
   // 64-character slots per read: picks the kernel instantiation.  `short_read_len` (host callers: the longest read that is not
   // beyond QM_MAX_READ_LEN) picks it when the batch also holds long reads -- those are set aside by the launch whatever its
@@ -1342,13 +1371,7 @@ static int map_device_impl(qm_ctx* c, const qm_opts* o, int64_t n, const void* d
     if ((rc = ensure(c->d_ivcsr, c->capIvcsr, nreads + 1))) return rc;
     if ((rc = ensure(c->d_lcsr, c->capLcsr, nreads + 1))) return rc;
     if (!c->h_tot) HIPCHK(hipHostMalloc((void**)&c->h_tot, 2 * sizeof(long long), hipHostMallocDefault));
-    const size_t stb = qmk_scan_temp_bytes(nreads + 1);
-    if (stb > c->scanTmpBytes || !c->d_scanTmp) {
-      if (c->d_scanTmp) hipFree(c->d_scanTmp);
-      c->d_scanTmp = nullptr; c->scanTmpBytes = 0;
-      HIPCHK(hipMalloc(&c->d_scanTmp, stb ? stb : 16));
-      c->scanTmpBytes = stb;
-    }
+    if ((rc = ensure_scan_tmp(c, nreads + 1))) return rc;
     if (!r2.keepIntervals) {
       // a stage view without the SA-interval records (QM_STAGES_NO_INTERVALS): every read's count is zero
       if ((rc = ensure(c->d_ivcnt, c->capIvCnt, nreads + 1))) return rc;
@@ -1540,7 +1563,6 @@ static int map_host(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq1, co
   if ((rc = check_opts(o))) return rc;
   if ((rc = stage_offsets(c, n, off1, c->d_seq1, c->capSeq1, c->d_off1, c->capOff1, maxLen, maxShort))) return rc;
   if (seq2 && (rc = stage_offsets(c, n, off2, c->d_seq2, c->capSeq2, c->d_off2, c->capOff2, maxLen, maxShort))) return rc;
-  const int32_t lim = len_limit(o);
   // the characters follow chunk by chunk, each chunk's kernel behind its own copy (ChunkFeeder); QM_HOST_CHUNK = units per chunk
   HostFeed hf = {c, seq1, off1, seq2, off2};
   const char* ce = getenv("QM_HOST_CHUNK");
@@ -1726,9 +1748,6 @@ static int upload(qm_ctx* c, void* dst, const void* src, size_t bytes) {
   return QM_OK;
 }
 
-static int map_host(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq1, const int64_t* off1, const char* seq2,
-                    const int64_t* off2, int64_t* n_hits, qm_counters* counters, const RunReq& rq);
-
 int qm_collect_reads(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq, const int64_t* off, int64_t* n_intervals) {
   if (!c || n < 0 || (n > 0 && (!seq || !off))) return fail(QM_E_ARG, "bad argument");
   int rc = check_opts(o);
@@ -1738,7 +1757,7 @@ int qm_collect_reads(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq, co
   if (n == 0) off = &zero;
   int32_t maxLen = 0;
   for (int64_t i = 0; i < n; ++i) { const int64_t l = off[i + 1] - off[i]; if (l < 0) return fail(QM_E_ARG, "offsets not monotone"); if (l > maxLen) maxLen = (int32_t)(l > 0x7fffffff ? 0x7fffffff : l); }
-  if (maxLen > (len_limit(o))) return fail(QM_E_TOOLONG, "read length %d > %d", maxLen, len_limit(o));
+  if (maxLen > QM_MAX_LONG_READ_LEN) return fail(QM_E_TOOLONG, "read length %d > %d", maxLen, QM_MAX_LONG_READ_LEN);
   if ((rc = ensure(c->d_seq1, c->capSeq1, off[n] + 64))) return rc;
   if ((rc = ensure(c->d_off1, c->capOff1, n + 1))) return rc;
   if ((rc = upload(c, c->d_off1, off, (size_t)(n + 1) * 8))) return rc;
@@ -1776,7 +1795,7 @@ int qm_hits_to_mappings(qm_ctx* c, const qm_opts* o, int64_t n, const int32_t* r
   if (ni > 0 && !ints) return fail(QM_E_ARG, "null intervals");
   for (int64_t i = 0; i < n; ++i) {
     if (int_offsets[i + 1] < int_offsets[i]) return fail(QM_E_ARG, "interval offsets not monotone");
-    if (read_len[i] < 0 || read_len[i] > (len_limit(o))) return fail(QM_E_TOOLONG, "read length %d > %d", read_len[i], len_limit(o));
+    if (read_len[i] < 0 || read_len[i] > QM_MAX_LONG_READ_LEN) return fail(QM_E_TOOLONG, "read length %d > %d", read_len[i], QM_MAX_LONG_READ_LEN);
     int nf = 0, nr = 0; bool seenRc = false;
     for (int64_t j = int_offsets[i]; j < int_offsets[i + 1]; ++j) {
       if (ints[j].query_rc) { ++nr; seenRc = true; } else { ++nf; if (seenRc) return fail(QM_E_ARG, "read %lld: forward-strand intervals must precede the reverse-complement ones", (long long)i); }

@@ -158,6 +158,7 @@ __global__ __launch_bounds__(256) void qm_pair_count_kernel(PairBatch P) {
 // hit and lane to 64 different lines (1.05 ms per 5 M pairs at 1.6 TB/s; profiles/r06/timeline.sh).  A wavefront whose units hold more
 // than the stage takes the direct path.
 #define QM_PW_CAP 320
+static_assert(sizeof(qm_hit) == 32, "the staged write passes (qm_pair_write_kernel, qm_sel_compact_kernel) copy a hit as two uint4");
 __global__ __launch_bounds__(256) void qm_pair_write_kernel(PairBatch P) {
   __shared__ __attribute__((aligned(16))) qm_hit stage[4][QM_PW_CAP];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63u);
@@ -368,8 +369,9 @@ __global__ __launch_bounds__(256) void qm_sel_merge_kernel(PairBatch P, SelBatch
   sel_flush_counters(sc, uc, P.counters);
 }
 
-// -s: the reads stage A left on the slow queue (lcnt == QM_LCNT_SLOW), gathered into q[0 .. *count)
-__global__ __launch_bounds__(256) void qm_collect_slow_kernel(const u32* lcnt, long long nreads, long long* q, u64* count, u32 mark) {
+// the reads stage A set aside (lcnt == mark: QM_LCNT_SLOW, QM_LCNT_LEAN), gathered into q[0 .. min(*count, cap)): the host sizes the queue
+// from the kernels' own counters, and a mark those counters do not know of (a stale word in lcnt) is dropped here instead of written
+__global__ __launch_bounds__(256) void qm_collect_slow_kernel(const u32* lcnt, long long nreads, long long* q, u64* count, u32 mark, unsigned long long cap) {
   const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool m = r < nreads && lcnt[r] == mark;
   // one addition per wavefront (a batch with N's queues a tenth of its reads: 380 k additions to ONE address were 0.75 ms of a 9 ms step),
@@ -380,7 +382,8 @@ __global__ __launch_bounds__(256) void qm_collect_slow_kernel(const u32* lcnt, l
     unsigned long long base = 0;
     if (lane == lead) base = atomicAdd((unsigned long long*)count, (unsigned long long)__builtin_popcountll(b));
     base = __shfl(base, lead);
-    if (m) q[base + (unsigned long long)__builtin_popcountll(b & ((1ULL << lane) - 1ULL))] = r;
+    const unsigned long long at = base + (unsigned long long)__builtin_popcountll(b & ((1ULL << lane) - 1ULL));
+    if (m && at < cap) q[at] = r;
   }
 }
 
@@ -855,15 +858,9 @@ size_t qmk_sel_dyn_struct_bytes(void) { return sizeof(SelScratchDyn); }
 unsigned long long qmk_sel_dyn_bytes(long long n) { return SelScratchDyn::bytes_for(n); }
 // host image of wave w's SelScratchDyn over device memory at `base`
 void qmk_sel_dyn_bind(void* host_struct, void* dev_base, long long n) { ((SelScratchDyn*)host_struct)->bind((unsigned char*)dev_base, n); }
-hipError_t qmk_collect_slow(const unsigned int* lcnt, long long nreads, long long* q, unsigned long long* count, hipStream_t st) {
+hipError_t qmk_collect_marked(const unsigned int* lcnt, long long nreads, unsigned int mark, long long* q, long long cap, unsigned long long* count, hipStream_t st) {
   if (nreads <= 0) return hipSuccess;
-  hipLaunchKernelGGL(qm_collect_slow_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, st, lcnt, nreads, q, (u64*)count, (u32)QM_LCNT_SLOW);
-  return hipGetLastError();
-}
-// the same for the reads qm_lean_kernel marked (QM_LCNT_LEAN)
-hipError_t qmk_collect_lean(const unsigned int* lcnt, long long nreads, long long* q, unsigned long long* count, hipStream_t st) {
-  if (nreads <= 0) return hipSuccess;
-  hipLaunchKernelGGL(qm_collect_slow_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, st, lcnt, nreads, q, (u64*)count, (u32)QM_LCNT_LEAN);
+  hipLaunchKernelGGL(qm_collect_slow_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, st, lcnt, nreads, q, (u64*)count, (u32)mark, (unsigned long long)(cap > 0 ? cap : 0));
   return hipGetLastError();
 }
 hipError_t qmk_sel_slots(const void* pp, hipStream_t st) {

@@ -137,7 +137,7 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
 #undef QE_CALL
     }
     if (!o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & 1)) {
-      // the long-read pass (see qm_host.hip): reads beyond the slot count of the first pass again, on the 32-slot kernels
+      // the long-read pass (pass_long_reads in qm_host.hip): reads beyond the slot count of the first pass again, on the 32-slot kernels
       std::vector<long long> q;
       for (long long r = 0; r < nreads; ++r) if (lcnt[r] == QM_LCNT_SLOW) q.push_back(r);
       ReadBatch S2 = B; S2.slowq = q.data(); S2.nreads = (long long)q.size();
@@ -156,7 +156,7 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
       return off[unit + 1] - off[unit];
     };
     if (o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & 1)) {
-      // -s, reads beyond the slot class (the device: the 32-slot chain-scoring collector, then the list kernel; here the fused
+      // -s, reads beyond the slot class (the device, pass_long_reads before the list kernels: the 32-slot chain-scoring collector, then the list kernel; here the fused
       // 32-slot kernel).  A read whose intervals overflow the scratch is queued again, for the slow pass below.
       std::vector<long long> q;
       for (long long r = 0; r < nreads; ++r) if (lcnt[r] == QM_LCNT_SLOW && rawLen(r) > 64 * ns) q.push_back(r);
@@ -172,7 +172,7 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
       }
     }
     if (o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & (1 | 4))) {
-      // the slow pass of -s (see qm_host.hip): the queued reads again, on scratch sized for the largest of them
+      // the slow pass of -s (pass_sel_slow in qm_host.hip): the queued reads again, on scratch sized for the largest of them
       const long long need = (((long long)scal[QM_SC_SLOWMAX] + 63) / 64) * 64 + 64;
       std::vector<unsigned char> dmem((size_t)SelScratchDyn::bytes_for(need));
       SelScratchDyn dyn; dyn.bind(dmem.data(), need);
