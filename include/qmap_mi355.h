@@ -333,6 +333,35 @@ int qm_build_index_ex(const char* fasta_path, const char* out_dir, int32_t k, in
  * duplicate-transcript filter.  (Diagnostics: tests hold it against the reference's src/xxhash.c.) */
 uint64_t qm_xxh64(const void* data, uint64_t len, uint64_t seed);
 
+/* ---- equivalence classes on the device ---------------------------------------------------------------------------------
+ * What a RapMap / Salmon-style caller does with a fragment's hit list: take the set of transcripts it maps to and add one to the
+ * count of that set, its equivalence class (Salmon's eq_classes.txt).  A unit's LABEL is the ascending list of the DISTINCT
+ * qm_hit.tid values of its hit list hits[hit_offsets[u] .. hit_offsets[u + 1]) -- hit lists are neither sorted nor free of
+ * repeats (an orphan unit is the left mate's run followed by the right mate's, include/RapMapUtils.hpp:1257-1262; -f and -s may
+ * repeat a transcript) --; a unit without hits contributes nothing.  A qm_eqc maps every label to the unsigned 64-bit number of
+ * units (or sum of weights) that carried it; identity is the full label, never its hash.  No cap on the length of a list.
+ * The batch is folded where it lies, in device memory: a run that wants classes brings a few megabytes to the host once instead
+ * of 32 bytes per hit and batch.  A table is not thread-safe (one per context / host thread; merge with qm_eqc_add_labels). */
+typedef struct qm_eqc qm_eqc;   /* a label -> count table in the device memory of ctx's GPU */
+/* flags bits 8..15: keep only that many low bits of the 64-bit key (0 = all; tests: forces collisions) */
+int qm_eqc_create(qm_ctx* ctx, int64_t expected_classes, uint32_t flags, qm_eqc** out);
+int qm_eqc_destroy(qm_eqc* t);
+int qm_eqc_clear(qm_eqc* t);
+/* fold the result of ctx's last map call (what qm_result_device names), on ctx's stream, before anything can overwrite it.
+ * QM_E_STATE without a result, QM_E_ARG when table and context are on different devices. */
+int qm_eqc_add(qm_eqc* t, qm_ctx* ctx);
+/* fold n lists of tids held in HOST memory, any order, duplicates allowed; weights NULL = 1 each.  The one merge primitive: a
+ * table fetched from another context, device or rank is folded in with its counts as weights. */
+int qm_eqc_add_labels(qm_eqc* t, int64_t n, const int64_t* offsets, const uint32_t* tids, const uint64_t* weights);
+int qm_eqc_size(qm_eqc* t, int64_t* n_classes, int64_t* n_tids, uint64_t* total_count);
+/* canonical order: labels ascending, compared lexicographically as uint32 sequences */
+int qm_eqc_fetch(qm_eqc* t, int64_t* label_offsets /*[n_classes+1]*/, uint32_t* tids, uint64_t* counts);
+/* since creation / the last clear: how often the table was rebuilt larger, published slots a probing unit found to hold another
+ * label, units of more than 8 hits (labelled by the queue launch), probe launches; QM_EQC_STAT_LAST_FOLD_US: the last fold (qm_eqc_add, the
+ * last part of qm_eqc_add_labels) from its first launch to its last read-back, in microseconds, by HIP events on its stream */
+enum { QM_EQC_STAT_GROWTHS = 0, QM_EQC_STAT_COLLISION_PROBES = 1, QM_EQC_STAT_LONG_UNITS = 2, QM_EQC_STAT_ROUNDS = 3, QM_EQC_STAT_LAST_FOLD_US = 4 };
+int qm_eqc_stat(const qm_eqc* t, int which, int64_t* value);
+
 /* ---- host-side callers of the path -------------------------------------------
  * Read ingest: replaces fastx_parser::FastxParser<ReadPair|ReadSeq> (include/FastxParser.hpp:62-66,
  * src/FastxParser.cpp:229-328: one kseq producer thread, per-record std::strings).  FASTA/FASTQ, plain or
@@ -373,6 +402,11 @@ int qm_stream_open(const qm_index* ix, int device_id, uint32_t ctx_flags, const 
 /* ... on the devices devices[0..n_devices).  stream_flags: QM_STREAM_NO_NAMES -- read names are not kept (names* / name_off*
  * of the batches are NULL): for callers that only want hits. */
 #define QM_STREAM_NO_NAMES 1u
+/* QM_STREAM_EQ_CLASSES -- every map context owns a qm_eqc and folds each batch into it after mapping; qm_stream_eqc_finish merges
+ * them.  QM_STREAM_NO_HITS (only together with QM_STREAM_EQ_CLASSES) -- the hits are not brought to the host: hit_offsets and
+ * hits of a batch are NULL; n_hits, counters, gpu_ms and device stay as they are. */
+#define QM_STREAM_EQ_CLASSES 2u
+#define QM_STREAM_NO_HITS 4u
 int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devices, uint32_t ctx_flags, const qm_opts* opts,
                       const char* path1, const char* path2, int64_t batch_units, int32_t reader_threads, uint32_t stream_flags,
                       qm_stream** out);
@@ -383,11 +417,16 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
  * stream of 2^18-pair batches of 2 x 100 bp reads.  Optional: without it a stream pins its own slots while it starts. */
 int qm_stream_reserve(int64_t bytes);
 int qm_stream_next(qm_stream* s, qm_stream_batch* batch);
+/* Once qm_stream_next has returned the end of the input: merges the contexts' tables, across devices, into the first one (through
+ * qm_eqc_add_labels) and reports its size; qm_stream_eqc_fetch then hands it out as qm_eqc_fetch does. */
+int qm_stream_eqc_finish(qm_stream* s, int64_t* n_classes, int64_t* n_tids);
+int qm_stream_eqc_fetch(qm_stream* s, int64_t* label_offsets, uint32_t* tids, uint64_t* counts);
 void qm_stream_close(qm_stream* s);
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
- * buffers; qm_stream_stats_ex(n <= 12) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
- * [8] copy tasks, [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall) */
+ * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 15) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
+ * [8] copy tasks, [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that went
+ * to the device 2-bit packed, [13] qm_eqc_add of the batches (summed over the contexts), [14] contexts that folded at least one batch */
 int qm_stream_stats(qm_stream* s, double* out6);
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n);
 const char* qm_stream_last_error(void);

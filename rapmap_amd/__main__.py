@@ -71,6 +71,9 @@ def _quasimap(argv):
     ap.add_argument("--device", type=int, default=0, help="GPU to use")
     ap.add_argument("--devices", default="", help="comma-separated GPUs to use, or 'all': the read batches are dealt round-robin to the devices "
                     "(each holds its own index replica), results come back in input order")
+    ap.add_argument("--eqClasses", default="", metavar="FILE", help="write the equivalence classes of the run (the sets of transcripts the "
+                    "fragments map to, with their counts) to FILE in the format of Salmon's eq_classes.txt; they are built on the GPU, "
+                    "and with -n no hit leaves the device")
     ap.add_argument("--chunk", type=int, default=1 << 18, help="read pairs per GPU batch")
     a = ap.parse_args(argv)
 
@@ -170,9 +173,12 @@ def _quasimap(argv):
     # one context per device lives for the whole run: the index replica stays resident between the files of a multi-file run
     # (a stream's own contexts share it)
     keep = [ra.QuasiMapper(qi, d) for d in sorted(set(devices))]
+    # --eqClasses: every stream folds its batches on the devices; the streams' merged tables (one per file) meet in this one
+    classes = ra.EqClasses(keep[0]) if a.eqClasses else None
     for f1, f2 in pairs:
         os.environ.setdefault("QM_INGEST_PIN", "1")   # a whole-machine job with one ingest engine: its workers on the NUMA node that holds the files' pages
-        st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None)
+        st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None,
+                             eq_classes=classes is not None, hits=out is not None or classes is None)
         for b in st:
             gpu_ms += b.gpu_ms
             for kk in tot:
@@ -185,8 +191,14 @@ def _quasimap(argv):
             if paired:
                 log("saw %d reads : pe / read = %.4f : se / read = %.4f" % (
                     tot["numReads"], tot["peHits"] / max(1, tot["numReads"]), tot["seHits"] / max(1, tot["numReads"])))
+        if classes is not None:
+            classes.add_labels(*st.eq_classes())
         log("stream: " + ", ".join("%s %.3f" % kv for kv in st.stats().items()))
         st.close()
+    if classes is not None:
+        classes.write(a.eqClasses, qi.txp_names)
+        log("wrote %d equivalence classes (%d fragments) to %s" % (classes.n_classes, classes.total, a.eqClasses))
+        classes.close()
     for k_ in keep:
         k_.close()
     if writer is not None:

@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "qm_map_pairs_stages", "qm_map_pairs_stages_ex", "qm_map_pairs_stages_packed", "qm_stage_bytes", "qm_fetch_stages", "qm_pinned_alloc", "qm_pinned_free", "qm_ctx_create_ex", "qm_fetch_hits_pinned", "qm_xxh64",
     "qm_stream_open", "qm_stream_open_ex", "qm_stream_reserve", "qm_stream_next", "qm_stream_close", "qm_stream_last_error", "qm_stream_stats", "qm_stream_stats_ex",
     "qm_reader_open", "qm_reader_next", "qm_reader_close", "qm_io_last_error", "qm_sam_header", "qm_sam_records",
+    "qm_eqc_create", "qm_eqc_destroy", "qm_eqc_clear", "qm_eqc_add", "qm_eqc_add_labels", "qm_eqc_size", "qm_eqc_fetch", "qm_eqc_stat",
+    "qm_stream_eqc_finish", "qm_stream_eqc_fetch",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
 ]
 
@@ -174,6 +176,16 @@ def lib():
     L.qm_sam_writer_put.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 10
     L.qm_sam_writer_close.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.qm_buf_free.argtypes = [C.c_void_p]
+    L.qm_eqc_create.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.qm_eqc_destroy.argtypes = [C.c_void_p]
+    L.qm_eqc_clear.argtypes = [C.c_void_p]
+    L.qm_eqc_add.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_eqc_add_labels.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_eqc_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+    L.qm_eqc_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_eqc_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_stream_eqc_finish.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.qm_stream_eqc_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -520,6 +532,119 @@ class QuasiMapper:
             pass
 
 
+def write_eq_classes(path, txp_names, label_offsets, tids, counts):
+    """Salmon's eq_classes.txt: the number of transcripts, the number of classes, one transcript name per line, then per class
+    (in the order given: EqClasses.fetch's canonical one) `k<TAB>t1<TAB>...<TAB>tk<TAB>count`"""
+    label_offsets = np.asarray(label_offsets, dtype=np.int64); tids = np.asarray(tids, dtype=np.uint32); counts = np.asarray(counts, dtype=np.uint64)
+    nc = len(label_offsets) - 1
+    with open(path, "w") as f:
+        f.write("%d\n%d\n" % (len(txp_names), nc))
+        for nm in txp_names:
+            f.write(nm + "\n")
+        out = []
+        for i in range(nc):
+            a, b = int(label_offsets[i]), int(label_offsets[i + 1])
+            out.append("\t".join([str(b - a)] + [str(int(t)) for t in tids[a:b]] + [str(int(counts[i]))]))
+            if len(out) >= 65536:
+                f.write("\n".join(out) + "\n"); out = []
+        if out:
+            f.write("\n".join(out) + "\n")
+
+
+def read_eq_classes(path):
+    """the inverse of write_eq_classes: (txp_names, label_offsets int64[nc + 1], tids uint32[], counts uint64[nc])"""
+    with open(path) as f:
+        nt = int(f.readline()); nc = int(f.readline())
+        names = [f.readline().rstrip("\n") for _ in range(nt)]
+        off = np.zeros(nc + 1, dtype=np.int64); tids = []; counts = np.zeros(nc, dtype=np.uint64)
+        for i in range(nc):
+            w = f.readline().split("\t")
+            k = int(w[0])
+            if len(w) != k + 2:
+                raise ValueError("%s: class %d has %d fields, %d expected" % (path, i, len(w), k + 2))
+            tids.extend(int(x) for x in w[1:1 + k]); counts[i] = int(w[1 + k]); off[i + 1] = off[i] + k
+    return names, off, np.array(tids, dtype=np.uint32), counts
+
+
+class EqClasses:
+    """qm_eqc_*: a label -> count table in the device memory of a mapper's GPU.  A unit's label is the ascending list of the
+    distinct transcripts of its hit list; add(mapper) folds the mapper's last result where it lies (no hit crosses PCIe),
+    add_labels folds lists held on the host (the merge primitive: another table's fetch() with its counts as weights).
+    expected: classes to size the table for (it grows by itself); hash_bits: keep only that many bits of the 64-bit key (tests)."""
+
+    GROWTHS, COLLISION_PROBES, LONG_UNITS, ROUNDS, LAST_FOLD_US = 0, 1, 2, 3, 4
+
+    def __init__(self, mapper, expected=1 << 16, hash_bits=0):
+        self._h = C.c_void_p()
+        if not 0 <= int(hash_bits) <= 63:
+            raise ValueError("hash_bits must be 0 .. 63")
+        _check(lib().qm_eqc_create(mapper._h, int(expected), int(hash_bits) << 8, C.byref(self._h)))
+        self.device = mapper.device
+
+    def add(self, mapper):
+        """fold the result of the mapper's last map call"""
+        _check(lib().qm_eqc_add(self._h, mapper._h))
+
+    def add_labels(self, offsets, tids, weights=None):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64); tids = np.ascontiguousarray(tids, dtype=np.uint32)
+        n = len(offsets) - 1
+        if n < 0:
+            raise ValueError("offsets needs n + 1 entries")
+        if n and int(offsets[-1]) > tids.size:
+            raise ValueError("offsets point beyond tids")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.uint64)
+            if weights.size != n:
+                raise ValueError("one weight per list")
+        _check(lib().qm_eqc_add_labels(self._h, n, offsets.ctypes.data, tids.ctypes.data if tids.size else None,
+                                       weights.ctypes.data if weights is not None and n else None))
+
+    def _size(self):
+        nc, nt, tot = C.c_int64(), C.c_int64(), C.c_uint64()
+        _check(lib().qm_eqc_size(self._h, C.byref(nc), C.byref(nt), C.byref(tot)))
+        return nc.value, nt.value, tot.value
+
+    @property
+    def n_classes(self):
+        return self._size()[0]
+
+    @property
+    def total(self):
+        """sum of all counts: the units (weights) folded so far that had a hit"""
+        return self._size()[2]
+
+    def fetch(self):
+        """(label_offsets int64[n_classes + 1], tids uint32[], counts uint64[n_classes]), labels ascending (lexicographic)"""
+        nc, nt, _ = self._size()
+        off = np.zeros(nc + 1, dtype=np.int64); tids = np.zeros(nt + 1, dtype=np.uint32); cnt = np.zeros(nc + 1, dtype=np.uint64)
+        _check(lib().qm_eqc_fetch(self._h, off.ctypes.data, tids.ctypes.data, cnt.ctypes.data))
+        return off, tids[:nt], cnt[:nc]
+
+    def stat(self, which):
+        """qm_eqc_stat: GROWTHS, COLLISION_PROBES, LONG_UNITS, ROUNDS, LAST_FOLD_US (the last fold by HIP events on its stream)"""
+        v = C.c_int64()
+        _check(lib().qm_eqc_stat(self._h, int(which), C.byref(v)))
+        return v.value
+
+    def clear(self):
+        _check(lib().qm_eqc_clear(self._h))
+
+    def write(self, path, txp_names):
+        off, tids, cnt = self.fetch()
+        write_eq_classes(path, txp_names, off, tids, cnt)
+
+    def close(self):
+        if self._h:
+            lib().qm_eqc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 PACK_EXC_DTYPE = np.dtype([("pos", "<u4"), ("ch", "<u4")])
 
 
@@ -643,20 +768,27 @@ class MappedStream:
     into pinned slots, two device contexts per device, results in pinned memory.  `device` may be one id or a list of ids
     (consecutive batches go to different devices; batches still come back in input order).  Iterating yields ReadBatch
     objects that also carry hit_offsets / hits / counters / device; every array is a zero-copy view that stays valid until
-    the next batch is taken.  names=False: read names are not kept (hits-only callers)."""
+    the next batch is taken.  names=False: read names are not kept (hits-only callers).  eq_classes=True: every batch is folded
+    into equivalence classes on its device (eq_classes() after the last batch); with hits=False on top the hits stay on the
+    device -- hit_offsets / hits of a batch are None, n_hits and counters as ever."""
 
     def __init__(self, index: QuasiIndex, path1, path2=None, opts=None, device=0, batch_units=1 << 20, threads=None, ph_compact=False,
-                 names=True):
+                 names=True, eq_classes=False, hits=True):
         self._h = C.c_void_p()
         self.paired = path2 is not None
         self.names = bool(names)
+        self.with_hits = bool(hits)
+        self._eqc = bool(eq_classes)
+        if not hits and not eq_classes:
+            raise ValueError("hits=False needs eq_classes=True")
         opts = opts or default_opts()
         devs = [int(d) for d in device] if isinstance(device, (list, tuple)) else [int(device)]
         self.devices = devs
         darr = (C.c_int32 * len(devs))(*devs)
         rc = lib().qm_stream_open_ex(index._h, darr, len(devs), 1 if ph_compact else 0, C.byref(opts), os.fsencode(path1),
                                      os.fsencode(path2) if path2 else None, int(batch_units),
-                                     int(threads or min(32, os.cpu_count() or 1)), 0 if names else 1, C.byref(self._h))
+                                     int(threads or min(32, os.cpu_count() or 1)),
+                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4), C.byref(self._h))
         if rc != 0:
             raise QmError("qm_stream_open failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
         self._index = index
@@ -681,20 +813,36 @@ class MappedStream:
                 if self.names:
                     b.name_off2 = arr(sb.name_off2, n + 1, np.int64); b.names2 = arr(sb.names2, int(b.name_off2[-1]), np.uint8)
             b.device = sb.device
-            b.hit_offsets = arr(sb.hit_offsets, n + 1, np.int64)
             b.n_hits = sb.n_hits
-            b.hits = arr(sb.hits, sb.n_hits, HIT_DTYPE) if sb.n_hits else np.zeros(0, dtype=HIT_DTYPE)
+            if self.with_hits:
+                b.hit_offsets = arr(sb.hit_offsets, n + 1, np.int64)
+                b.hits = arr(sb.hits, sb.n_hits, HIT_DTYPE) if sb.n_hits else np.zeros(0, dtype=HIT_DTYPE)
+            else:
+                b.hit_offsets = b.hits = None
             b.counters = sb.counters.as_dict()
             b.gpu_ms = sb.gpu_ms
             yield b
 
+    def eq_classes(self):
+        """after the last batch: the classes of the whole input, merged over the stream's contexts and devices --
+        (label_offsets, tids, counts) as EqClasses.fetch gives them"""
+        nc, nt = C.c_int64(), C.c_int64()
+        rc = lib().qm_stream_eqc_finish(self._h, C.byref(nc), C.byref(nt))
+        if rc != 0:
+            raise QmError("qm_stream_eqc_finish failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        off = np.zeros(nc.value + 1, dtype=np.int64); tids = np.zeros(nt.value + 1, dtype=np.uint32); cnt = np.zeros(nc.value + 1, dtype=np.uint64)
+        rc = lib().qm_stream_eqc_fetch(self._h, off.ctypes.data, tids.ctypes.data, cnt.ctypes.data)
+        if rc != 0:
+            raise QmError("qm_stream_eqc_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        return off, tids[:nt.value], cnt[:nc.value]
+
     def stats(self):
         """seconds: read_s = open to the last batch packed (wall), map_s / fetch_s = upload + kernels / download summed over the
         contexts, parse_cpu_s / copy_cpu_s = the ingest workers' task time summed over the workers"""
-        a = (C.c_double * 13)()
-        _check(lib().qm_stream_stats_ex(self._h, a, 13))
+        a = (C.c_double * 15)()
+        _check(lib().qm_stream_stats_ex(self._h, a, 15))
         return dict(zip(("read_s", "map_s", "fetch_s", "caller_wait_s", "open_s", "alloc_s", "first_batch_s", "parse_cpu_s", "copy_cpu_s",
-                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches"), [float(x) for x in a]))
+                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts"), [float(x) for x in a]))
 
     def close(self):
         if self._h:

@@ -77,4 +77,11 @@ hipError_t qmk_scan_counts_masked(void* temp, size_t temp_bytes, const unsigned 
 hipError_t qmk_stage_gather(long long nreads, const unsigned int* ivcnt, const long long* ivoff, const void* iv, const long long* ivcsr, void* iv_out,
                             const unsigned int* lcnt, const long long* loff, const unsigned long long* lists, const long long* lcsr,
                             unsigned long long* words_out, hipStream_t st);
+// the equivalence-class table (qm_eqc.inl; src / table / set: EqcSrc, EqcTable, EqcSet by address)
+hipError_t qmk_eqc_label(const void* src, hipStream_t st);
+hipError_t qmk_eqc_label_queued(const void* src, long long nq, hipStream_t st);
+hipError_t qmk_eqc_probe(const void* table, const void* set, const unsigned long long* qin, long long nin, unsigned long long* qout, int aggregate, hipStream_t st);
+hipError_t qmk_eqc_publish(const void* table, const void* set, const unsigned long long* q, long long nq, hipStream_t st);
+hipError_t qmk_eqc_reset_probes(unsigned long long* q, long long n, hipStream_t st);
+hipError_t qmk_eqc_sum(const unsigned long long* count, const unsigned long long* key, long long cap, unsigned long long* out, hipStream_t st);
 }

@@ -1,0 +1,267 @@
+// qm_eqc_host.inl -- host driver of the equivalence-class table (device code: qm_eqc.inl, kernels: qm_kernels_eqc.hip).
+// Included at the end of qm_host.hip: qm_eqc_add reads the context's last result where it lies in device memory.
+//
+// A fold = label launch (+ queue launch for the units of more than EQC_GROUP hits), then rounds of probe / publish until the
+// pending queue is empty; the host reads the scalar block once per round.  When slots or pool run out (counted by the kernels,
+// nothing written) the table is rebuilt four times as large -- the old table's slots go through the same probe / publish
+// launches as units whose weights are their counts -- and the pending units start over.
+#include <algorithm>
+#include "qm_eqc.inl"
+
+struct qm_eqc {
+  int device = 0; hipStream_t stream = nullptr; u64 keyMask = ~0ULL; int aggregate = 1;
+  EqcTable T{}; u64* d_scal = nullptr; u64 h[EQC_SC_WORDS] = {0};
+  // a fold's scratch
+  u32* d_lab = nullptr; u32* d_len = nullptr; u64* d_key = nullptr; u64* d_q[2] = {nullptr, nullptr}; long long* d_longq = nullptr;
+  int64_t capLab = 0, capLen = 0, capKey = 0, capQ[2] = {0, 0}, capLongq = 0;
+  u64* d_gq[2] = {nullptr, nullptr}; int64_t capGq[2] = {0, 0};       // the queues of a rebuild
+  long long* d_inOff = nullptr; u32* d_inTids = nullptr; u64* d_inW = nullptr; int64_t capInOff = 0, capInTids = 0, capInW = 0;   // qm_eqc_add_labels
+  int64_t growths = 0, longUnits = 0, rounds = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr; int64_t lastFoldUs = 0;   // around the last fold on its stream (QM_EQC_STAT_LAST_FOLD_US)
+};
+
+static void eqc_free_table(EqcTable& T) {
+  void* p[] = {T.key, T.claim, T.loff, T.llen, T.count, T.pool};
+  for (void* q : p) if (q) hipFree(q);
+  T.key = T.claim = T.count = nullptr; T.loff = nullptr; T.llen = nullptr; T.pool = nullptr;
+}
+static int eqc_alloc_table(qm_eqc* t, u64 cap, u64 poolCap, hipStream_t st, EqcTable& T) {
+  T = EqcTable{};
+  const bool ok = hipMalloc((void**)&T.key, cap * 8) == hipSuccess && hipMalloc((void**)&T.claim, cap * 8) == hipSuccess && hipMalloc((void**)&T.loff, cap * 8) == hipSuccess &&
+                  hipMalloc((void**)&T.llen, cap * 4) == hipSuccess && hipMalloc((void**)&T.count, cap * 8) == hipSuccess && hipMalloc((void**)&T.pool, poolCap * 4) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); eqc_free_table(T); return fail(QM_E_NOMEM, "no device memory for an equivalence-class table of %llu slots", (unsigned long long)cap); }
+  T.mask = cap - 1; T.maxClasses = cap / 2; T.poolCap = poolCap; T.scal = t->d_scal;
+  HIPCHK(hipMemsetAsync(T.key, 0, cap * 8, st));
+  HIPCHK(hipMemsetAsync(T.llen, 0, cap * 4, st));
+  HIPCHK(hipMemsetAsync(T.count, 0, cap * 8, st));
+  HIPCHK(hipMemsetAsync(T.claim, 0xff, cap * 8, st));
+  return QM_OK;
+}
+static int eqc_read_scalars(qm_eqc* t, hipStream_t st) {
+  HIPCHK(hipMemcpyAsync(t->h, t->d_scal, sizeof(t->h), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return QM_OK;
+}
+
+static int eqc_insert(qm_eqc* t, const EqcSet& S, hipStream_t st, u64** q, bool mayGrow);
+static int eqc_grow(qm_eqc* t, hipStream_t st) {
+  EqcTable old = t->T;
+  const u64 oldCap = old.mask + 1;
+  const bool slots = t->h[EQC_SC_SLOT_OVF] || t->h[EQC_SC_FULL];
+  // unit and slot indices travel as 32-bit numbers (queue entries, claim words)
+  if (slots && oldCap >= (1ULL << 31)) return fail(QM_E_UNSUPPORTED, "equivalence-class table: more than 2^30 classes (a table cannot grow beyond 2^31 slots)");
+  const u64 cap = slots ? (oldCap * 4 > (1ULL << 31) ? (1ULL << 31) : oldCap * 4) : oldCap, poolCap = t->h[EQC_SC_POOL_OVF] ? old.poolCap * 4 : old.poolCap;
+  int rc;
+  EqcTable T;
+  if ((rc = eqc_alloc_table(t, cap, poolCap, st, T))) return rc;
+  HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_FULL, 0, 6 * sizeof(u64), st));     // FULL, TICKETS, POOL, CLASSES and the two overflow counts
+  t->T = T;
+  if ((rc = ensure(t->d_gq[0], t->capGq[0], (int64_t)oldCap)) || (rc = ensure(t->d_gq[1], t->capGq[1], (int64_t)oldCap))) { eqc_free_table(old); return rc; }
+  const EqcSet R{old.pool, old.loff, old.llen, old.key, old.count, (long long)oldCap};     // empty slots have length 0: skipped like units without hits
+  rc = eqc_insert(t, R, st, t->d_gq, false);
+  eqc_free_table(old);
+  t->growths++;
+  return rc;
+}
+
+// every unit of S into the table; q: two queues of S.n entries each
+static int eqc_insert(qm_eqc* t, const EqcSet& S, hipStream_t st, u64** q, bool mayGrow) {
+  const u64* qin = nullptr; long long nin = S.n; int cur = 0, rc;
+  for (long long guard = 0;; ++guard) {
+    if (guard > (1LL << 40)) return fail(QM_E_STATE, "equivalence-class insert does not end");
+    HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_PEND, 0, 2 * sizeof(u64), st));   // PEND, FULL
+    HIPCHK(qmk_eqc_probe(&t->T, &S, (const unsigned long long*)qin, nin, (unsigned long long*)q[cur], t->aggregate, st));
+    t->rounds++;
+    if ((rc = eqc_read_scalars(t, st))) return rc;
+    const long long pend = (long long)t->h[EQC_SC_PEND];
+    if (!pend) return QM_OK;
+    if (t->h[EQC_SC_SLOT_OVF] || t->h[EQC_SC_POOL_OVF] || t->h[EQC_SC_FULL]) {
+      if (!mayGrow) return fail(QM_E_STATE, "equivalence-class table overflowed while it was rebuilt");
+      if ((rc = eqc_grow(t, st))) return rc;
+      HIPCHK(qmk_eqc_reset_probes((unsigned long long*)q[cur], pend, st));
+    }
+    else HIPCHK(qmk_eqc_publish(&t->T, &S, (const unsigned long long*)q[cur], pend, st));
+    qin = q[cur]; nin = pend; cur ^= 1;
+  }
+}
+
+// S: tids, stride, off, n filled in; nTids = off[n] (off[0] = 0)
+static int eqc_fold(qm_eqc* t, EqcSrc S, int64_t nTids, const u64* d_w, hipStream_t st) {
+  if (S.n <= 0 || nTids <= 0) return QM_OK;
+  if (S.n >= (1LL << 32)) return fail(QM_E_ARG, "more than 2^32 - 1 units in one fold");
+  int rc;
+  if ((rc = ensure(t->d_lab, t->capLab, nTids)) || (rc = ensure(t->d_len, t->capLen, S.n)) || (rc = ensure(t->d_key, t->capKey, S.n)) ||
+      (rc = ensure(t->d_q[0], t->capQ[0], S.n)) || (rc = ensure(t->d_q[1], t->capQ[1], S.n)) || (rc = ensure(t->d_longq, t->capLongq, std::max<int64_t>(1024, S.n / 16)))) return rc;
+  S.lab = t->d_lab; S.len = t->d_len; S.key = t->d_key; S.scal = t->d_scal; S.keyMask = t->keyMask;
+  HIPCHK(hipEventRecord(t->ev0, st));
+  int64_t nl = 0;
+  for (int pass = 0;; ++pass) {
+    S.longq = t->d_longq; S.longCap = (u64)t->capLongq;
+    HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_LONGQ, 0, sizeof(u64), st));
+    HIPCHK(qmk_eqc_label(&S, st));
+    if ((rc = eqc_read_scalars(t, st))) return rc;
+    nl = (int64_t)t->h[EQC_SC_LONGQ];
+    if (nl <= t->capLongq) break;
+    if (pass) return fail(QM_E_STATE, "long-unit queue overflowed twice");
+    if ((rc = ensure(t->d_longq, t->capLongq, nl))) return rc;       // counted, not written: a larger queue and the launch again
+  }
+  HIPCHK(qmk_eqc_label_queued(&S, nl, st));
+  t->longUnits += nl;
+  const EqcSet set{S.lab, S.off, S.len, S.key, d_w, S.n};
+  if ((rc = eqc_insert(t, set, st, t->d_q, true))) return rc;
+  HIPCHK(hipEventRecord(t->ev1, st));
+  HIPCHK(hipEventSynchronize(t->ev1));                           // (the stream is idle: the insert ended with a read-back)
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, t->ev0, t->ev1) == hipSuccess) t->lastFoldUs = (int64_t)(ms * 1000.0f + 0.5f);
+  return QM_OK;
+}
+
+extern "C" {
+
+int qm_eqc_create(qm_ctx* c, int64_t expected_classes, uint32_t flags, qm_eqc** out) {
+  if (!c || !out || expected_classes < 0 || (flags & ~0xff00u)) return fail(QM_E_ARG, "qm_eqc_create: bad argument");
+  const int bits = (int)((flags >> 8) & 0xff);
+  if (bits > 63) return fail(QM_E_ARG, "qm_eqc_create: at most 63 key bits");
+  HIPCHK(hipSetDevice(c->device));
+  qm_eqc* t = new qm_eqc();
+  t->device = c->device; t->keyMask = bits ? ((1ULL << bits) - 1) : ~0ULL;
+  { const char* e = getenv("QM_EQC_NO_AGGREGATE"); t->aggregate = !(e && atoi(e) != 0); }   // (A/B timing of the per-wavefront aggregation: INTEGRATION.md, environment)
+  u64 cap = 16; while (cap < 2 * (u64)expected_classes && cap < (1ULL << 31)) cap <<= 1;
+  int rc = QM_OK;
+  if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&t->d_scal, sizeof(t->h)) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: stream / scalars");
+  if (!rc && (hipEventCreate(&t->ev0) != hipSuccess || hipEventCreate(&t->ev1) != hipSuccess)) rc = fail(QM_E_NOGPU, "qm_eqc_create: events");
+  if (!rc && hipMemsetAsync(t->d_scal, 0, sizeof(t->h), t->stream) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: memset");
+  if (!rc) rc = eqc_alloc_table(t, cap, std::max<u64>(64, 8 * (u64)expected_classes), t->stream, t->T);
+  if (!rc && hipStreamSynchronize(t->stream) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: synchronize");
+  if (rc) { qm_eqc_destroy(t); return rc; }
+  *out = t;
+  return QM_OK;
+}
+
+int qm_eqc_destroy(qm_eqc* t) {
+  if (!t) return QM_OK;
+  hipSetDevice(t->device);
+  if (t->stream) hipStreamSynchronize(t->stream);
+  eqc_free_table(t->T);
+  void* p[] = {t->d_scal, t->d_lab, t->d_len, t->d_key, t->d_q[0], t->d_q[1], t->d_longq, t->d_gq[0], t->d_gq[1], t->d_inOff, t->d_inTids, t->d_inW};
+  for (void* q : p) if (q) hipFree(q);
+  if (t->ev0) hipEventDestroy(t->ev0);
+  if (t->ev1) hipEventDestroy(t->ev1);
+  if (t->stream) hipStreamDestroy(t->stream);
+  delete t;
+  return QM_OK;
+}
+
+int qm_eqc_clear(qm_eqc* t) {
+  if (!t) return fail(QM_E_ARG, "null table");
+  HIPCHK(hipSetDevice(t->device));
+  const u64 cap = t->T.mask + 1;
+  HIPCHK(hipMemsetAsync(t->T.key, 0, cap * 8, t->stream));
+  HIPCHK(hipMemsetAsync(t->T.llen, 0, cap * 4, t->stream));
+  HIPCHK(hipMemsetAsync(t->T.count, 0, cap * 8, t->stream));
+  HIPCHK(hipMemsetAsync(t->T.claim, 0xff, cap * 8, t->stream));
+  HIPCHK(hipMemsetAsync(t->d_scal, 0, sizeof(t->h), t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  memset(t->h, 0, sizeof(t->h));
+  t->growths = t->longUnits = t->rounds = 0;
+  return QM_OK;
+}
+
+int qm_eqc_add(qm_eqc* t, qm_ctx* c) {
+  if (!t || !c) return fail(QM_E_ARG, "qm_eqc_add: null argument");
+  if (c->lastUnits < 0) return fail(QM_E_STATE, "no mapping result to fold");
+  if (c->device != t->device) return fail(QM_E_ARG, "table on device %d, context on device %d", t->device, c->device);
+  HIPCHK(hipSetDevice(t->device));
+  EqcSrc S{};
+  S.tids = (const unsigned char*)c->d_hits; S.stride = (int)sizeof(qm_hit); S.off = c->d_offs; S.n = c->lastUnits;
+  return eqc_fold(t, S, c->lastHits, nullptr, c->stream);
+}
+
+int qm_eqc_add_labels(qm_eqc* t, int64_t n, const int64_t* offsets, const uint32_t* tids, const uint64_t* weights) {
+  if (!t || n < 0 || (n > 0 && !offsets)) return fail(QM_E_ARG, "qm_eqc_add_labels: bad argument");
+  for (int64_t i = 0; i < n; ++i) if (offsets[i + 1] < offsets[i]) return fail(QM_E_ARG, "qm_eqc_add_labels: offsets decrease at list %lld", (long long)i);
+  if (n > 0 && offsets[n] > offsets[0] && !tids) return fail(QM_E_ARG, "qm_eqc_add_labels: null tids");
+  HIPCHK(hipSetDevice(t->device));
+  const int64_t maxUnits = 1 << 22, maxTids = 1 << 25;          // a part: what is uploaded and folded in one go
+  std::vector<long long> off;
+  int rc;
+  for (int64_t u0 = 0; u0 < n;) {
+    int64_t u1 = u0 + 1;
+    while (u1 < n && u1 - u0 < maxUnits && offsets[u1 + 1] - offsets[u0] <= maxTids) ++u1;
+    const int64_t nu = u1 - u0, nt = offsets[u1] - offsets[u0];
+    off.resize((size_t)nu + 1);
+    for (int64_t i = 0; i <= nu; ++i) off[(size_t)i] = offsets[u0 + i] - offsets[u0];
+    if ((rc = ensure(t->d_inOff, t->capInOff, nu + 1)) || (rc = ensure(t->d_inTids, t->capInTids, std::max<int64_t>(nt, 1))) || (weights && (rc = ensure(t->d_inW, t->capInW, nu)))) return rc;
+    HIPCHK(hipMemcpyAsync(t->d_inOff, off.data(), (size_t)(nu + 1) * 8, hipMemcpyHostToDevice, t->stream));
+    if (nt > 0) HIPCHK(hipMemcpyAsync(t->d_inTids, tids + offsets[u0], (size_t)nt * 4, hipMemcpyHostToDevice, t->stream));
+    if (weights) HIPCHK(hipMemcpyAsync(t->d_inW, weights + u0, (size_t)nu * 8, hipMemcpyHostToDevice, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));                    // (the host vector is reused)
+    EqcSrc S{};
+    S.tids = (const unsigned char*)t->d_inTids; S.stride = 4; S.off = t->d_inOff; S.n = nu;
+    if ((rc = eqc_fold(t, S, nt, weights ? t->d_inW : nullptr, t->stream))) return rc;
+    u0 = u1;
+  }
+  return QM_OK;
+}
+
+int qm_eqc_size(qm_eqc* t, int64_t* n_classes, int64_t* n_tids, uint64_t* total_count) {
+  if (!t) return fail(QM_E_ARG, "null table");
+  HIPCHK(hipSetDevice(t->device));
+  if (total_count) {
+    HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_SUM, 0, sizeof(u64), t->stream));
+    HIPCHK(qmk_eqc_sum((const unsigned long long*)t->T.count, (const unsigned long long*)t->T.key, (long long)(t->T.mask + 1), (unsigned long long*)(t->d_scal + EQC_SC_SUM), t->stream));
+  }
+  int rc;
+  if ((rc = eqc_read_scalars(t, t->stream))) return rc;
+  if (n_classes) *n_classes = (int64_t)t->h[EQC_SC_CLASSES];
+  if (n_tids) *n_tids = (int64_t)t->h[EQC_SC_POOL];             // (exact: a fold that ran out of pool rebuilt the table)
+  if (total_count) *total_count = t->h[EQC_SC_SUM];
+  return QM_OK;
+}
+
+int qm_eqc_fetch(qm_eqc* t, int64_t* label_offsets, uint32_t* tids, uint64_t* counts) {
+  if (!t || !label_offsets) return fail(QM_E_ARG, "qm_eqc_fetch: bad argument");
+  HIPCHK(hipSetDevice(t->device));
+  int rc;
+  if ((rc = eqc_read_scalars(t, t->stream))) return rc;
+  const size_t cap = (size_t)(t->T.mask + 1), used = (size_t)t->h[EQC_SC_POOL];
+  std::vector<u64> key(cap), cnt(cap); std::vector<long long> loff(cap); std::vector<u32> llen(cap), pool(used + 1);
+  HIPCHK(hipMemcpyAsync(key.data(), t->T.key, cap * 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(cnt.data(), t->T.count, cap * 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(loff.data(), t->T.loff, cap * 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(llen.data(), t->T.llen, cap * 4, hipMemcpyDeviceToHost, t->stream));
+  if (used) HIPCHK(hipMemcpyAsync(pool.data(), t->T.pool, used * 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  std::vector<size_t> order;
+  for (size_t s = 0; s < cap; ++s) if (key[s]) order.push_back(s);
+  if (order.size() != (size_t)t->h[EQC_SC_CLASSES]) return fail(QM_E_STATE, "equivalence-class table: %zu published slots, %llu counted", order.size(), (unsigned long long)t->h[EQC_SC_CLASSES]);
+  // canonical order: labels ascending, compared as sequences of unsigned 32-bit numbers (a proper prefix comes first)
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return std::lexicographical_compare(pool.begin() + loff[a], pool.begin() + loff[a] + llen[a], pool.begin() + loff[b], pool.begin() + loff[b] + llen[b]);
+  });
+  int64_t o = 0;
+  for (size_t i = 0; i < order.size(); ++i) {
+    const size_t s = order[i];
+    label_offsets[i] = o;
+    if (tids) memcpy(tids + o, pool.data() + loff[s], (size_t)llen[s] * 4);
+    if (counts) counts[i] = cnt[s];
+    o += llen[s];
+  }
+  label_offsets[order.size()] = o;
+  return QM_OK;
+}
+
+int qm_eqc_stat(const qm_eqc* t, int which, int64_t* value) {
+  if (!t || !value) return fail(QM_E_ARG, "qm_eqc_stat: bad argument");
+  switch (which) {
+    case QM_EQC_STAT_GROWTHS: *value = t->growths; break;
+    case QM_EQC_STAT_COLLISION_PROBES: *value = (int64_t)t->h[EQC_SC_PROBES]; break;
+    case QM_EQC_STAT_LONG_UNITS: *value = t->longUnits; break;
+    case QM_EQC_STAT_ROUNDS: *value = t->rounds; break;
+    case QM_EQC_STAT_LAST_FOLD_US: *value = t->lastFoldUs; break;
+    default: return fail(QM_E_ARG, "qm_eqc_stat: unknown statistic %d", which);
+  }
+  return QM_OK;
+}
+
+}  // extern "C"

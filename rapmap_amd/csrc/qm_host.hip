@@ -2029,3 +2029,6 @@ int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
 }
 
 }  // extern "C"
+
+// the equivalence-class table (qm_eqc_*): its host driver reads the context's last result
+#include "qm_eqc_host.inl"

@@ -106,6 +106,10 @@ struct qm_stream {
   int64_t nPacked = 0;                     // batches that did
   qm_ingest* g = nullptr;
   std::vector<qm_ctx*> ctx; std::vector<int> ctxDev;
+  std::vector<qm_eqc*> eqc;                // QM_STREAM_EQ_CLASSES: one table per context, merged into eqc[0] by qm_stream_eqc_finish
+  bool eqClasses = false, noHits = false, eqcMerged = false, ended = false;
+  std::vector<int64_t> eqcFolds;           // batches every context folded
+  double tFold = 0;                        // seconds in qm_eqc_add (summed over the contexts)
   std::vector<OutSlot> slots;
   std::mutex mu; std::condition_variable cv;
   int64_t nextOut = 0;
@@ -148,7 +152,14 @@ static void map_loop(qm_stream* s, int which) {
     else if (s->paired) rc = qm_map_pairs(c, &s->opts, n, in->seq[0], in->off[0], in->seq[1], in->off[1], &S.nHits, &S.ctr);
     else rc = qm_map_reads(c, &s->opts, n, in->seq[0], in->off[0], &S.nHits, &S.ctr);
     t1 = now_s();
-    if (!rc) {
+    double tf = 0;
+    if (!rc && s->eqClasses) { rc = qm_eqc_add(s->eqc[(size_t)which], c); tf = now_s() - t1; t1 += tf; }   // folded where it lies, before the next call overwrites it
+    if (!rc && s->noHits) {
+      t2 = now_s();
+      double a = 0, b = 0;
+      if (qm_last_kernel_ms(c, &a, &b) == QM_OK) S.gpuMs = b;
+    }
+    else if (!rc) {
       if (S.capHitOff < (size_t)n + 1) { pin_free(S.hitOff); S.capHitOff = (size_t)n + 1 + (size_t)n / 4; S.hitOff = (int64_t*)pin_alloc(S.capHitOff * 8); }
       if (S.capHits < (size_t)S.nHits + 1) { pin_free(S.hits); S.capHits = (size_t)S.nHits + 1 + (size_t)S.nHits / 4; S.hits = (qm_hit*)pin_alloc(S.capHits * sizeof(qm_hit)); }
       ta = now_s() - t1;
@@ -161,7 +172,7 @@ static void map_loop(qm_stream* s, int which) {
     std::unique_lock<std::mutex> lk(s->mu);
     if (rc) { if (!s->failed) { s->failed = rc; snprintf(s->err, sizeof(s->err), "%s", rc == QM_E_NOMEM ? "out of pinned memory" : qm_last_error()); } break; }
     S.state = 2;
-    s->tMap += t1 - t0; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
+    s->tMap += t1 - t0 - tf; s->tFold += tf; if (s->eqClasses) s->eqcFolds[(size_t)which]++; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
     s->cv.notify_all();
   }
   std::unique_lock<std::mutex> lk(s->mu);
@@ -176,9 +187,11 @@ const char* qm_stream_last_error(void) { return g_serr; }
 int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devices, uint32_t ctx_flags, const qm_opts* opts, const char* path1,
                       const char* path2, int64_t batch_units, int32_t reader_threads, uint32_t stream_flags, qm_stream** out) {
   if (!ix || !opts || !path1 || !out || batch_units <= 0 || !devices || n_devices <= 0) return sfail(QM_E_ARG, "qm_stream_open: bad argument");
+  if ((stream_flags & QM_STREAM_NO_HITS) && !(stream_flags & QM_STREAM_EQ_CLASSES)) return sfail(QM_E_ARG, "qm_stream_open: QM_STREAM_NO_HITS needs QM_STREAM_EQ_CLASSES");
   qm_stream* s = new qm_stream();
   s->t0 = now_s();
   s->ix = ix; s->opts = *opts; s->paired = path2 != nullptr;
+  s->eqClasses = (stream_flags & QM_STREAM_EQ_CLASSES) != 0; s->noHits = (stream_flags & QM_STREAM_NO_HITS) != 0;
   { const char* np = getenv("QM_STREAM_NO_PACK"); s->packed = !(np && atoi(np) != 0); }
   const char* cpd = getenv("QM_STREAM_CTX_PER_DEVICE");
   // contexts (map threads) per device: each uploads, maps and downloads its batch in turn, so several of them keep the link and
@@ -216,6 +229,17 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
       for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
       qm_ingest_close(s->g); delete s; return rc;
     }
+  if (s->eqClasses) {
+    s->eqc.assign((size_t)nctx, nullptr); s->eqcFolds.assign((size_t)nctx, 0);
+    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_eqc_create(s->ctx[(size_t)i], 1 << 16, 0, &s->eqc[(size_t)i]); }
+    if (rc) {
+      sfail(rc, qm_last_error());
+      qm_ingest_cancel(s->g);
+      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
+      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
+      qm_ingest_close(s->g); delete s; return rc;
+    }
+  }
   for (int i = 0; i < nctx; ++i) s->mapThreads.emplace_back(map_loop, s, i);
   s->tOpen = now_s() - s->t0;
   *out = s;
@@ -276,30 +300,60 @@ int qm_stream_next(qm_stream* s, qm_stream_batch* b) {
   s->tWait += now_s() - tw0;
   if (s->failed) return sfail(s->failed, s->err);
   memset(b, 0, sizeof(*b));
-  if (si < 0) return QM_OK;                                 // n_units == 0: end of input
+  if (si < 0) { s->ended = true; return QM_OK; }            // n_units == 0: end of input
   OutSlot& S = s->slots[(size_t)si];
   S.state = 3; s->held = si; s->nextOut++;
   b->n_units = S.n;
   b->seq1 = S.in->seq[0]; b->off1 = S.in->off[0]; b->names1 = S.in->names[0]; b->name_off1 = S.in->noff[0];
   if (s->paired) { b->seq2 = S.in->seq[1]; b->off2 = S.in->off[1]; b->names2 = S.in->names[1]; b->name_off2 = S.in->noff[1]; }
-  b->hit_offsets = S.hitOff; b->hits = S.hits; b->n_hits = S.nHits; b->counters = S.ctr; b->gpu_ms = S.gpuMs; b->device = S.device;
+  b->hit_offsets = s->noHits ? nullptr : S.hitOff; b->hits = s->noHits ? nullptr : S.hits; b->n_hits = S.nHits; b->counters = S.ctr; b->gpu_ms = S.gpuMs; b->device = S.device;
   return QM_OK;
+}
+
+/* The contexts' tables into the first one: each is fetched to the host and folded in with its counts as weights (the tables of
+ * other devices travel the same way). */
+int qm_stream_eqc_finish(qm_stream* s, int64_t* n_classes, int64_t* n_tids) {
+  if (!s) return sfail(QM_E_ARG, "qm_stream_eqc_finish: null stream");
+  if (!s->eqClasses) return sfail(QM_E_STATE, "qm_stream_eqc_finish: the stream was opened without QM_STREAM_EQ_CLASSES");
+  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_eqc_finish: the input has not ended"); }
+  int rc = QM_OK;
+  if (!s->eqcMerged) {
+    std::vector<int64_t> off; std::vector<uint32_t> tids; std::vector<uint64_t> cnt;
+    for (size_t i = 1; i < s->eqc.size() && !rc; ++i) {
+      int64_t nc = 0, nt = 0;
+      if ((rc = qm_eqc_size(s->eqc[i], &nc, &nt, nullptr))) break;
+      off.assign((size_t)nc + 1, 0); tids.resize((size_t)nt + 1); cnt.resize((size_t)nc + 1);
+      if ((rc = qm_eqc_fetch(s->eqc[i], off.data(), tids.data(), cnt.data()))) break;
+      rc = qm_eqc_add_labels(s->eqc[0], nc, off.data(), tids.data(), cnt.data());
+    }
+    if (rc) return sfail(rc, qm_last_error());
+    s->eqcMerged = true;
+  }
+  if ((rc = qm_eqc_size(s->eqc[0], n_classes, n_tids, nullptr))) return sfail(rc, qm_last_error());
+  return QM_OK;
+}
+int qm_stream_eqc_fetch(qm_stream* s, int64_t* label_offsets, uint32_t* tids, uint64_t* counts) {
+  if (!s || !s->eqClasses || !s->eqcMerged) return sfail(QM_E_STATE, "qm_stream_eqc_fetch: call qm_stream_eqc_finish first");
+  const int rc = qm_eqc_fetch(s->eqc[0], label_offsets, tids, counts);
+  return rc ? sfail(rc, qm_last_error()) : QM_OK;
 }
 
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
  * buffers; qm_stream_stats_ex adds [6] open to the first batch packed, [7] parse tasks (summed over the workers), [8] copy tasks
  * (summed), [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that
- * went to the device 2-bit packed */
+ * went to the device 2-bit packed, [13] qm_eqc_add of the batches (QM_STREAM_EQ_CLASSES; not part of [1] or [2]), [14] contexts that
+ * folded at least one batch */
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n) {
   if (!s || !out || n < 0) return sfail(QM_E_ARG, "qm_stream_stats: bad argument");
-  double v[13] = {0}; double ing[8] = {0};
+  double v[15] = {0}; double ing[8] = {0};
   qm_ingest_stats(s->g, ing);
   std::unique_lock<std::mutex> lk(s->mu);
   v[0] = ing[6]; v[1] = s->tMap; v[2] = s->tFetch; v[3] = s->tWait; v[4] = s->tOpen; v[5] = s->tAlloc;
   v[6] = ing[0]; v[7] = ing[1]; v[8] = ing[2]; v[9] = ing[3]; v[10] = ing[4]; v[11] = s->tLastMapped;
   v[12] = (double)__atomic_load_n(&s->nPacked, __ATOMIC_RELAXED);
-  for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
+  v[13] = s->tFold; for (int64_t f : s->eqcFolds) v[14] += f > 0 ? 1 : 0;
+  for (int i = 0; i < n && i < 15; ++i) out[i] = v[i];
   return QM_OK;
 }
 int qm_stream_stats(qm_stream* s, double* out6) { return qm_stream_stats_ex(s, out6, 6); }
@@ -310,6 +364,7 @@ void qm_stream_close(qm_stream* s) {
   qm_ingest_cancel(s->g);                                   // wakes map threads that wait for a batch
   for (auto& t : s->mapThreads) if (t.joinable()) t.join();
   for (OutSlot& S : s->slots) { pin_free(S.hitOff); pin_free(S.hits); }
+  for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
   for (qm_ctx* c : s->ctx) if (c) qm_ctx_destroy(c);
   qm_ingest_close(s->g);
   delete s;

@@ -22,3 +22,23 @@ def all_reduce_counters(counters, device):
     t = torch.tensor([int(counters[k]) for k in COUNTER_KEYS], dtype=torch.int64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.SUM)                # (also with ONE rank under torchrun: the collective library runs, the sum is the input)
     return dict(zip(COUNTER_KEYS, (int(x) for x in t.cpu())))
+
+
+def merge_eq_classes(table, mapper=None):
+    """Every rank's equivalence classes into every rank's table: the fetched tables are all-gathered and each rank folds the
+    others' in through EqClasses.add_labels, counts as weights (the table's one merge primitive).  Without a process group the
+    table is returned unchanged, as all_reduce_counters does for counters.  mapper: the rank's QuasiMapper (its device carries
+    the collective's tensors under the nccl backend)."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return table
+    off, tids, cnt = table.fetch()
+    mine = {"off": off, "tids": tids, "cnt": cnt}
+    parts = [None] * dist.get_world_size()
+    if mapper is not None and dist.get_backend() == "nccl":
+        torch.cuda.set_device(mapper.device)                # all_gather_object moves its pickles through the current device
+    dist.all_gather_object(parts, mine)
+    me = dist.get_rank()
+    for r, p in enumerate(parts):
+        if r != me and len(p["cnt"]):
+            table.add_labels(p["off"], p["tids"], p["cnt"])
+    return table
