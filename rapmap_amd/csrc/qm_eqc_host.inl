@@ -10,12 +10,11 @@
 
 struct qm_eqc {
   int device = 0; hipStream_t stream = nullptr; u64 keyMask = ~0ULL; int aggregate = 1;
-  EqcTable T{}; u64* d_scal = nullptr; u64 h[EQC_SC_WORDS] = {0};
+  EqcTable T{}; DevBuf<u64> d_scal; u64 h[EQC_SC_WORDS] = {0};
   // a fold's scratch
-  u32* d_lab = nullptr; u32* d_len = nullptr; u64* d_key = nullptr; u64* d_q[2] = {nullptr, nullptr}; long long* d_longq = nullptr;
-  int64_t capLab = 0, capLen = 0, capKey = 0, capQ[2] = {0, 0}, capLongq = 0;
-  u64* d_gq[2] = {nullptr, nullptr}; int64_t capGq[2] = {0, 0};       // the queues of a rebuild
-  long long* d_inOff = nullptr; u32* d_inTids = nullptr; u64* d_inW = nullptr; int64_t capInOff = 0, capInTids = 0, capInW = 0;   // qm_eqc_add_labels
+  DevBuf<u32> d_lab, d_len; DevBuf<u64> d_key, d_q[2]; DevBuf<long long> d_longq;
+  DevBuf<u64> d_gq[2];                                                // the queues of a rebuild
+  DevBuf<long long> d_inOff; DevBuf<u32> d_inTids; DevBuf<u64> d_inW; // qm_eqc_add_labels
   int64_t growths = 0, longUnits = 0, rounds = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr; int64_t lastFoldUs = 0;   // around the last fold on its stream (QM_EQC_STAT_LAST_FOLD_US)
 };
@@ -56,9 +55,10 @@ static int eqc_grow(qm_eqc* t, hipStream_t st) {
   if ((rc = eqc_alloc_table(t, cap, poolCap, st, T))) return rc;
   HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_FULL, 0, 6 * sizeof(u64), st));     // FULL, TICKETS, POOL, CLASSES and the two overflow counts
   t->T = T;
-  if ((rc = ensure(t->d_gq[0], t->capGq[0], (int64_t)oldCap)) || (rc = ensure(t->d_gq[1], t->capGq[1], (int64_t)oldCap))) { eqc_free_table(old); return rc; }
+  if ((rc = t->d_gq[0].ensure((int64_t)oldCap)) || (rc = t->d_gq[1].ensure((int64_t)oldCap))) { eqc_free_table(old); return rc; }
   const EqcSet R{old.pool, old.loff, old.llen, old.key, old.count, (long long)oldCap};     // empty slots have length 0: skipped like units without hits
-  rc = eqc_insert(t, R, st, t->d_gq, false);
+  u64* gq[2] = {t->d_gq[0], t->d_gq[1]};
+  rc = eqc_insert(t, R, st, gq, false);
   eqc_free_table(old);
   t->growths++;
   return rc;
@@ -90,25 +90,26 @@ static int eqc_fold(qm_eqc* t, EqcSrc S, int64_t nTids, const u64* d_w, hipStrea
   if (S.n <= 0 || nTids <= 0) return QM_OK;
   if (S.n >= (1LL << 32)) return fail(QM_E_ARG, "more than 2^32 - 1 units in one fold");
   int rc;
-  if ((rc = ensure(t->d_lab, t->capLab, nTids)) || (rc = ensure(t->d_len, t->capLen, S.n)) || (rc = ensure(t->d_key, t->capKey, S.n)) ||
-      (rc = ensure(t->d_q[0], t->capQ[0], S.n)) || (rc = ensure(t->d_q[1], t->capQ[1], S.n)) || (rc = ensure(t->d_longq, t->capLongq, std::max<int64_t>(1024, S.n / 16)))) return rc;
+  if ((rc = t->d_lab.ensure(nTids)) || (rc = t->d_len.ensure(S.n)) || (rc = t->d_key.ensure(S.n)) ||
+      (rc = t->d_q[0].ensure(S.n)) || (rc = t->d_q[1].ensure(S.n)) || (rc = t->d_longq.ensure(std::max<int64_t>(1024, S.n / 16)))) return rc;
   S.lab = t->d_lab; S.len = t->d_len; S.key = t->d_key; S.scal = t->d_scal; S.keyMask = t->keyMask;
   HIPCHK(hipEventRecord(t->ev0, st));
   int64_t nl = 0;
   for (int pass = 0;; ++pass) {
-    S.longq = t->d_longq; S.longCap = (u64)t->capLongq;
+    S.longq = t->d_longq; S.longCap = (u64)t->d_longq.cap;
     HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_LONGQ, 0, sizeof(u64), st));
     HIPCHK(qmk_eqc_label(&S, st));
     if ((rc = eqc_read_scalars(t, st))) return rc;
     nl = (int64_t)t->h[EQC_SC_LONGQ];
-    if (nl <= t->capLongq) break;
+    if (nl <= t->d_longq.cap) break;
     if (pass) return fail(QM_E_STATE, "long-unit queue overflowed twice");
-    if ((rc = ensure(t->d_longq, t->capLongq, nl))) return rc;       // counted, not written: a larger queue and the launch again
+    if ((rc = t->d_longq.ensure(nl))) return rc;       // counted, not written: a larger queue and the launch again
   }
   HIPCHK(qmk_eqc_label_queued(&S, nl, st));
   t->longUnits += nl;
   const EqcSet set{S.lab, S.off, S.len, S.key, d_w, S.n};
-  if ((rc = eqc_insert(t, set, st, t->d_q, true))) return rc;
+  u64* q[2] = {t->d_q[0], t->d_q[1]};
+  if ((rc = eqc_insert(t, set, st, q, true))) return rc;
   HIPCHK(hipEventRecord(t->ev1, st));
   HIPCHK(hipEventSynchronize(t->ev1));                           // (the stream is idle: the insert ended with a read-back)
   float ms = 0;
@@ -128,7 +129,7 @@ int qm_eqc_create(qm_ctx* c, int64_t expected_classes, uint32_t flags, qm_eqc** 
   { const char* e = getenv("QM_EQC_NO_AGGREGATE"); t->aggregate = !(e && atoi(e) != 0); }   // (A/B timing of the per-wavefront aggregation: INTEGRATION.md, environment)
   u64 cap = 16; while (cap < 2 * (u64)expected_classes && cap < (1ULL << 31)) cap <<= 1;
   int rc = QM_OK;
-  if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&t->d_scal, sizeof(t->h)) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: stream / scalars");
+  if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess || t->d_scal.ensure(EQC_SC_WORDS) != QM_OK) rc = fail(QM_E_NOGPU, "qm_eqc_create: stream / scalars");
   if (!rc && (hipEventCreate(&t->ev0) != hipSuccess || hipEventCreate(&t->ev1) != hipSuccess)) rc = fail(QM_E_NOGPU, "qm_eqc_create: events");
   if (!rc && hipMemsetAsync(t->d_scal, 0, sizeof(t->h), t->stream) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: memset");
   if (!rc) rc = eqc_alloc_table(t, cap, std::max<u64>(64, 8 * (u64)expected_classes), t->stream, t->T);
@@ -143,12 +144,10 @@ int qm_eqc_destroy(qm_eqc* t) {
   hipSetDevice(t->device);
   if (t->stream) hipStreamSynchronize(t->stream);
   eqc_free_table(t->T);
-  void* p[] = {t->d_scal, t->d_lab, t->d_len, t->d_key, t->d_q[0], t->d_q[1], t->d_longq, t->d_gq[0], t->d_gq[1], t->d_inOff, t->d_inTids, t->d_inW};
-  for (void* q : p) if (q) hipFree(q);
   if (t->ev0) hipEventDestroy(t->ev0);
   if (t->ev1) hipEventDestroy(t->ev1);
   if (t->stream) hipStreamDestroy(t->stream);
-  delete t;
+  delete t;                    // (the scratch buffers free themselves)
   return QM_OK;
 }
 
@@ -169,12 +168,12 @@ int qm_eqc_clear(qm_eqc* t) {
 
 int qm_eqc_add(qm_eqc* t, qm_ctx* c) {
   if (!t || !c) return fail(QM_E_ARG, "qm_eqc_add: null argument");
-  if (c->lastUnits < 0) return fail(QM_E_STATE, "no mapping result to fold");
+  if (c->last.units < 0) return fail(QM_E_STATE, "no mapping result to fold");
   if (c->device != t->device) return fail(QM_E_ARG, "table on device %d, context on device %d", t->device, c->device);
   HIPCHK(hipSetDevice(t->device));
   EqcSrc S{};
-  S.tids = (const unsigned char*)c->d_hits; S.stride = (int)sizeof(qm_hit); S.off = c->d_offs; S.n = c->lastUnits;
-  return eqc_fold(t, S, c->lastHits, nullptr, c->stream);
+  S.tids = (const unsigned char*)c->d_hits.p; S.stride = (int)sizeof(qm_hit); S.off = c->d_offs; S.n = c->last.units;
+  return eqc_fold(t, S, c->last.hits, nullptr, c->stream);
 }
 
 int qm_eqc_add_labels(qm_eqc* t, int64_t n, const int64_t* offsets, const uint32_t* tids, const uint64_t* weights) {
@@ -191,13 +190,13 @@ int qm_eqc_add_labels(qm_eqc* t, int64_t n, const int64_t* offsets, const uint32
     const int64_t nu = u1 - u0, nt = offsets[u1] - offsets[u0];
     off.resize((size_t)nu + 1);
     for (int64_t i = 0; i <= nu; ++i) off[(size_t)i] = offsets[u0 + i] - offsets[u0];
-    if ((rc = ensure(t->d_inOff, t->capInOff, nu + 1)) || (rc = ensure(t->d_inTids, t->capInTids, std::max<int64_t>(nt, 1))) || (weights && (rc = ensure(t->d_inW, t->capInW, nu)))) return rc;
+    if ((rc = t->d_inOff.ensure(nu + 1)) || (rc = t->d_inTids.ensure(std::max<int64_t>(nt, 1))) || (weights && (rc = t->d_inW.ensure(nu)))) return rc;
     HIPCHK(hipMemcpyAsync(t->d_inOff, off.data(), (size_t)(nu + 1) * 8, hipMemcpyHostToDevice, t->stream));
     if (nt > 0) HIPCHK(hipMemcpyAsync(t->d_inTids, tids + offsets[u0], (size_t)nt * 4, hipMemcpyHostToDevice, t->stream));
     if (weights) HIPCHK(hipMemcpyAsync(t->d_inW, weights + u0, (size_t)nu * 8, hipMemcpyHostToDevice, t->stream));
     HIPCHK(hipStreamSynchronize(t->stream));                    // (the host vector is reused)
     EqcSrc S{};
-    S.tids = (const unsigned char*)t->d_inTids; S.stride = 4; S.off = t->d_inOff; S.n = nu;
+    S.tids = (const unsigned char*)t->d_inTids.p; S.stride = 4; S.off = t->d_inOff; S.n = nu;
     if ((rc = eqc_fold(t, S, nt, weights ? t->d_inW : nullptr, t->stream))) return rc;
     u0 = u1;
   }

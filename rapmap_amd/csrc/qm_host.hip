@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <string>
 #include <vector>
 #include <thread>
@@ -82,88 +83,148 @@ struct qm_index {
   std::vector<std::pair<uint32_t, uint32_t>> phOverflow;
 };
 
-// The index replica of one device: built by the first context on (index, device), shared read-only by every later one
-// (one context per host thread is the intended use: a Salmon-style caller has many), freed with the last of them.
+// A device array that owns its memory: the pointer, the capacity in elements, freed with its owner.  Every device buffer of the
+// replica, the context and the equivalence-class table is one of these (arrays of other types' records: bytes, cast where read).
+template <typename T>
+struct DevBuf {
+  T* p = nullptr; int64_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  operator T*() const { return p; }
+  void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+  // room for `want` elements (contents are not kept)
+  int ensure(int64_t want, int64_t minGrow = 0) {
+    if (want <= cap && p) return QM_OK;
+    if (p) hipFree(p);
+    p = nullptr;
+    int64_t nc = want + minGrow;
+    if (cap > 0 && nc < cap + cap / 2) nc = cap + cap / 2;     // a buffer that grows again grows by half: callers whose batches vary in size (the
+                                                               // compat header's batching service) stop paying a round of hipFree / hipMalloc per new maximum
+    if (nc > want + minGrow && hipMalloc((void**)&p, (size_t)nc * sizeof(T)) != hipSuccess) { p = nullptr; (void)hipGetLastError(); nc = want + minGrow; }   // no room for the slack: the exact size
+    if (!p && hipMalloc((void**)&p, (size_t)nc * sizeof(T)) != hipSuccess) { cap = 0; return fail(QM_E_NOMEM, "hipMalloc of %lld bytes failed", (long long)(nc * sizeof(T))); }
+    cap = nc;
+    return QM_OK;
+  }
+};
+// ... and its sibling in pinned host memory, of a fixed size: allocated at first use
+template <typename T>
+struct PinBuf {
+  T* p = nullptr;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { if (p) hipHostFree(p); }
+  operator T*() const { return p; }
+  int ensure(size_t n) {
+    if (!p) HIPCHK(hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault));
+    return QM_OK;
+  }
+};
+
+// The index replica of one device: built by the first context on (index, device) (build_replica), shared read-only by every later
+// one (one context per host thread is the intended use: a Salmon-style caller has many), freed with the last of them.
 struct Replica {
   int device = 0;
-  uint8_t* d_text = nullptr; uint32_t* d_SA = nullptr; void* d_sainfo = nullptr; void* d_slots = nullptr; uint64_t cap = 0;
-  void* d_ph = nullptr; PhIndex hPh; std::vector<void*> phAllocs; uint32_t* d_txpOff = nullptr; int32_t* d_txpLen = nullptr; int64_t devBytes = 0;
-  std::mutex sanextMu; unsigned int* d_sanext = nullptr;   // -s: built by the first -s call of any context of this replica
-  void* d_saext = nullptr;                                  // the packed characters behind every suffix's k-mer (SaExt), or null
-  void* d_saext2 = nullptr; bool saext2Tried = false;       // ... the wide edition (SaExt2), built when reads of 129 .. 256 characters first ask (sanextMu)
-  ~Replica() {
-    hipSetDevice(device);
-    void* ptrs[] = {d_text, d_SA, d_sainfo, d_slots, d_txpOff, d_txpLen, d_sanext, d_saext, d_saext2};
-    for (void* p : ptrs) if (p) hipFree(p);
-    for (void* p : phAllocs) if (p) hipFree(p);
-  }
+  DevBuf<uint8_t> text; DevBuf<uint32_t> SA; DevBuf<unsigned char> sainfo, slots; uint64_t cap = 0;   // (SaInfo / Bucket records; cap: buckets)
+  const PhIndex* ph = nullptr; PhIndex hPh; std::deque<DevBuf<unsigned char>> phAllocs;   // the compact -p image: PhIndex on the device (in phAllocs, like its arrays), its host copy
+  DevBuf<uint32_t> txpOff; DevBuf<int32_t> txpLen; int64_t devBytes = 0;
+  std::mutex sanextMu; DevBuf<unsigned int> sanext;        // -s: built by the first -s call of any context of this replica
+  DevBuf<unsigned char> saext;                              // the packed characters behind every suffix's k-mer (SaExt), or empty
+  DevBuf<unsigned char> saext2; bool saext2Tried = false;   // ... the wide edition (SaExt2), built when reads of 129 .. 256 characters first ask (sanextMu)
+  ~Replica() { hipSetDevice(device); }                      // (then the members free themselves)
 };
 static std::mutex g_repMu;
 static std::map<std::pair<const qm_index*, int>, std::weak_ptr<Replica>> g_reps;   // key: index, device * 2 + (compact perfect hash)
 static std::map<std::pair<const qm_index*, int>, std::shared_ptr<std::mutex>> g_repBuild;   // one builder per key at a time
+
+// What the last call on a context reported about itself: everything qm_ctx_stat and qm_fetch_skipped read.  The default state is a
+// call that used none of the kernels; the stages fill in what they run.
+struct CallStats {
+  int64_t relaunches = 0, slowReads = 0;
+  int64_t leanReads = -1, leanDeferred = 0;       // leanReads: reads the lean kernel was launched over (-1: not used)
+  int64_t selQuestions = 0, kswTasks = 0, stripTasks = 0;   // -s: alignment questions beyond PERFECT chains, ksw2 / strip alignments run for them
+  int64_t defer[4] = {0, 0, 0, 0};                // QM_STAT_DEFER_*
+  int64_t nPass = 0;                              // QM_STAT_N_PASS_READS: reads the N-aware pass of stage A mapped
+  int64_t duoPairs = -1, duoMerged = 0;           // pairs the pair kernel was launched over (-1: not used), pairs it merged itself
+  int64_t skipped = 0; std::vector<uint64_t> skipList;   // reads skipped, not mapped (ReadBatch::skiplist): how many, the first QM_SKIP_CAP of them
+  // A call mapped in parts (map_device_split) reports its parts' sums.  The kernels' own figures count only where a part ran that
+  // kernel: the lean reads stay -1 until a part ran a lean kernel, the merged pairs are those of the parts that ran the pair kernel,
+  // and the pair kernel's pair count stays -1 (an unsplit call only: qmap_mi355.h).  firstRead: the part's read 0 in the whole batch.
+  void add_part(const CallStats& p, int64_t firstRead) {
+    relaunches += p.relaunches; slowReads += p.slowReads; nPass += p.nPass;
+    selQuestions += p.selQuestions; kswTasks += p.kswTasks; stripTasks += p.stripTasks;
+    for (int t = 0; t < 4; ++t) defer[t] += p.defer[t];
+    if (p.leanReads >= 0) { leanReads = (leanReads < 0 ? 0 : leanReads) + p.leanReads; leanDeferred += p.leanDeferred; }
+    if (p.duoPairs >= 0) duoMerged += p.duoMerged;
+    skipped += p.skipped;
+    const uint64_t idx = (1ULL << 56) - 1;        // (an entry: the read below, the reason above)
+    for (uint64_t e : p.skipList)
+      if (skipList.size() < QM_SKIP_CAP) skipList.push_back(((e & idx) + (uint64_t)firstRead) | (e & ~idx));
+  }
+};
+// ... and what it left to fetch: the result's size and times, and which per-read outputs the buffers hold (-1: none)
+struct LastResult {
+  int64_t units = -1, hits = 0; bool paired = false;
+  double mapMs = 0, totalMs = 0;
+  int64_t ivReads = -1, ivTotal = 0, foundReads = -1, listReads = -1, listWords = 0, tooManyUnits = -1;
+  int64_t stReads = -1, stUnits = -1;             // qm_fetch_stages
+  void invalidate() { *this = LastResult(); }
+};
+static qm_counters counters_from(const u64* hscal) { return qm_counters{hscal[1], hscal[2], hscal[3], hscal[4], hscal[5], hscal[6]}; }
+static qm_counters& operator+=(qm_counters& a, const qm_counters& b) {
+  a.pe_hits += b.pe_hits; a.se_hits += b.se_hits; a.tot_hits += b.tot_hits; a.num_reads += b.num_reads; a.too_many_hits += b.too_many_hits; a.mapped += b.mapped;
+  return a;
+}
 
 struct qm_ctx {
   const qm_index* ix = nullptr;
   std::shared_ptr<Replica> rep;
   int device = 0, numCU = 256;
   hipStream_t stream = nullptr, copyStream = nullptr;      // kernels / host-buffer uploads (overlapped chunk by chunk)
-  unsigned int* d_sanext = nullptr;                         // -s: text characters behind every suffix's k-mer (the replica's, built at its first -s call)
-  void* d_saext = nullptr;                                  // the replica's SaExt table
-  void* d_saext2 = nullptr;                                 // ... and its wide edition, once built
+  // the replica's two tables that are built lazily and its size, as this context last saw them under the replica's sanextMu
+  // (ensure_sanext, ensure_saext2): another context's first -s call may be writing the replica's own fields
+  unsigned int* d_sanext = nullptr;                         // -s: text characters behind every suffix's k-mer
+  void* d_saext2 = nullptr;                                 // the wide edition of the replica's SaExt table, once built
+  int64_t devBytes = 0;
   hipStream_t planStream = nullptr;                         // -s: the plan kernels of the later chunks, under the ksw2 kernel of the earlier ones
   hipEvent_t evPlan[QM_SEL_CHUNKS_B + 1] = {};              // ... [i]: chunk i planned; [last]: the plan stream may start
-  u64* d_ntk = nullptr;                                     // ... per chunk: a task counter, then (at QM_SEL_CHUNKS_B + i) a counter of alignment questions
+  DevBuf<u64> d_ntk;                                        // ... per chunk: a task counter, then (at QM_SEL_CHUNKS_B + i) a counter of alignment questions
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evA = nullptr, evB = nullptr, evCopy = nullptr, evStage[2] = {nullptr, nullptr};
   hipEvent_t evP0 = nullptr, evP1 = nullptr;                // around the second launches of stage A (the N-aware pass, the general kernel over what is left): evA / evB time the whole call
-  unsigned char* h_stage = nullptr;                        // pinned, 2 x 32 MB: result download (qm_fetch_hits)
-  // index replica
-  uint8_t* d_text = nullptr; uint32_t* d_SA = nullptr; void* d_sainfo = nullptr; void* d_slots = nullptr;
-  uint64_t cap = 0;
-  void* d_ph = nullptr; std::vector<void*> phAllocs;       // perfect-hash flavour: PhIndex struct + its arrays
-  PhIndex hPh;                                              // host copy (passed to the kernels by value inside DevIndex)
-  int64_t devBytes = 0;
+  PinBuf<unsigned char> h_stage;                            // pinned, 2 x 32 MB: result download (qm_fetch_hits)
   // work buffers
-  int64_t capCnt = 0, capOffs = 0, capLcnt = 0, capLoff = 0, capLists = 0, capHits = 0, capSeq1 = 0, capSeq2 = 0, capOff1 = 0, capOff2 = 0, capGrid = 0;
-  uint32_t* d_cnt = nullptr; long long* d_offs = nullptr;      // per unit: hits, exclusive scan
-  uint32_t* d_lcnt = nullptr; long long* d_loff = nullptr;     // per read: list length / offset
-  u64* d_lists = nullptr;                                      // bump-allocated per-read hit lists
-  qm_hit* d_hits = nullptr;
-  u64* d_scal = nullptr; /* cursor, counters[6], status */ u64* d_gscr = nullptr; unsigned* d_gslots = nullptr;   // (scratch slots' flags: gscr_for)
-  u64* d_skip = nullptr; std::vector<uint64_t> skipList; int64_t lastSkipped = 0;   // reads the last call skipped (ReadBatch::skiplist)
-  void* d_scanTmp = nullptr; size_t scanTmpBytes = 0;
-  uint8_t* d_seq1 = nullptr; uint8_t* d_seq2 = nullptr; long long* d_off1 = nullptr; long long* d_off2 = nullptr;
+  DevBuf<uint32_t> d_cnt; DevBuf<long long> d_offs;         // per unit: hits, exclusive scan
+  DevBuf<uint32_t> d_lcnt; DevBuf<long long> d_loff;        // per read: list length / offset
+  DevBuf<u64> d_lists;                                      // bump-allocated per-read hit lists
+  DevBuf<qm_hit> d_hits;
+  DevBuf<u64> d_scal; /* cursor, counters[6], status */ DevBuf<u64> d_gscr; DevBuf<unsigned> d_gslots;   // (scratch slots' flags: gscr_for)
+  DevBuf<u64> d_skip;                                       // reads the last call skipped (ReadBatch::skiplist)
+  DevBuf<unsigned char> d_scanTmp;                          // (bytes)
+  DevBuf<uint8_t> d_seq1, d_seq2; DevBuf<long long> d_off1, d_off2;
   // SA-interval hits as an output (qm_fetch_intervals), foundHit flags, tooMany flags of a merge-only call
-  qm_sa_interval_hit* d_iv = nullptr; uint32_t* d_ivcnt = nullptr; long long* d_ivoff = nullptr; int64_t capIv = 0, capIvCnt = 0, capIvOff = 0; int debug = 0;
-  unsigned char* d_found = nullptr; int64_t capFound = 0; unsigned char* d_tooMany = nullptr; int64_t capTooMany = 0;
+  DevBuf<qm_sa_interval_hit> d_iv; DevBuf<uint32_t> d_ivcnt; DevBuf<long long> d_ivoff; int debug = 0;
+  DevBuf<unsigned char> d_found, d_tooMany;
   // inputs of the stage entries
-  qm_sa_interval_hit* d_ivIn = nullptr; int64_t capIvIn = 0; long long* d_ivInOff = nullptr; int64_t capIvInOff = 0;
-  int* d_lenIn = nullptr; int64_t capLenIn = 0; unsigned char* d_foundIn = nullptr; int64_t capFoundIn = 0;
-  int64_t lastIvTotal = 0, lastIvReads = -1, lastFoundReads = -1, lastListReads = -1, lastListWords = 0, lastTooManyUnits = -1;
+  DevBuf<qm_sa_interval_hit> d_ivIn; DevBuf<long long> d_ivInOff; DevBuf<int> d_lenIn;
   // -s (selective alignment) work areas
-  uint32_t* d_txpOff = nullptr; int32_t* d_txpLen = nullptr;
-  unsigned char* d_selscr = nullptr; int64_t capSelScr = 0;
-  uint8_t* d_pk1 = nullptr; uint8_t* d_pk2 = nullptr; int64_t capPk1 = 0, capPk2 = 0;          // 2-bit packed reads as uploaded (qm_map_*_packed)
-  qm_pack_exc* d_exc1 = nullptr; qm_pack_exc* d_exc2 = nullptr; int64_t capExc1 = 0, capExc2 = 0;
-  unsigned char* d_kswRows = nullptr; int64_t capKswRows = 0;   // -s: alignment blocks of the device-memory edition (long reads, band beyond 97)
-  long long* d_todoq = nullptr; int64_t capTodoq = 0; long long* d_todoq2 = nullptr; int64_t capTodoq2 = 0;          // -s: reads the packed list kernel left for the one-read-per-wavefront kernel
-  long long* d_slowq = nullptr; int64_t capSlowq = 0;          // -s slow pass: queue, per-wave scratch descriptors and their memory
-  unsigned char* d_dyn = nullptr; int64_t capDyn = 0; unsigned char* d_dynmem = nullptr; int64_t capDynMem = 0;
-  long long* d_toff = nullptr; int64_t capToff = 0;
-  qm_hit* d_tmp = nullptr; int64_t capTmp = 0; unsigned char* d_sides = nullptr; int64_t capSides = 0; int* d_tsc = nullptr; int64_t capTsc = 0;
-  int* d_tref = nullptr; int64_t capTref = 0; u64* d_torder = nullptr; int64_t capTorder = 0; unsigned char* d_tasks = nullptr; int64_t capTasks = 0;
+  DevBuf<unsigned char> d_selscr;
+  DevBuf<uint8_t> d_pk1, d_pk2;                             // 2-bit packed reads as uploaded (qm_map_*_packed)
+  DevBuf<qm_pack_exc> d_exc1, d_exc2;
+  DevBuf<unsigned char> d_kswRows;                          // -s: alignment blocks of the device-memory edition (long reads, band beyond 97)
+  DevBuf<long long> d_todoq, d_todoq2;                      // -s: reads the packed list kernel left for the one-read-per-wavefront kernel
+  DevBuf<long long> d_slowq;                                // -s slow pass: queue, per-wave scratch descriptors and their memory
+  DevBuf<unsigned char> d_dyn, d_dynmem;
+  DevBuf<long long> d_toff;
+  DevBuf<qm_hit> d_tmp; DevBuf<unsigned char> d_sides; DevBuf<int> d_tsc;
+  DevBuf<int> d_tref; DevBuf<u64> d_torder; DevBuf<unsigned char> d_tasks;
   // qm_fetch_stages: CSR offsets of the per-read interval records / list words (scans queued behind stage A), their totals
   // (pinned: they arrive with stage B's synchronisation), the compacted copies
-  long long* d_ivcsr = nullptr; int64_t capIvcsr = 0; long long* d_lcsr = nullptr; int64_t capLcsr = 0;
-  qm_sa_interval_hit* d_ivC = nullptr; int64_t capIvC = 0; u64* d_wordsC = nullptr; int64_t capWordsC = 0;
-  long long* h_tot = nullptr; int64_t stReads = -1, stUnits = -1;
-  // last result
-  int64_t lastUnits = -1, lastHits = 0; bool lastPaired = false;
-  double lastMapMs = 0, lastTotalMs = 0;
-  int64_t lastSelQuestions = 0, lastKswTasks = 0, lastStripTasks = 0;             // -s: alignment questions beyond PERFECT chains of the last call, ksw2 alignments run for them
-  int64_t lastDefer[4] = {0, 0, 0, 0};            // QM_STAT_DEFER_*
-  int64_t lastNPass = 0;                          // QM_STAT_N_PASS_READS: reads the N-aware pass of stage A mapped
-  int64_t lastDuoPairs = -1, lastDuoMerged = 0;   // pairs the pair kernel was launched over (-1: not used), pairs it merged itself
-  int64_t lastRelaunches = 0, lastSlowReads = 0, lastLeanReads = -1, lastLeanDeferred = 0;   // lastLeanReads: reads the lean kernel was launched over (-1: not used)
+  DevBuf<long long> d_ivcsr, d_lcsr;
+  DevBuf<qm_sa_interval_hit> d_ivC; DevBuf<u64> d_wordsC;
+  PinBuf<long long> h_tot;
+  LastResult last; CallStats stats;                         // what the last call left (begin_call)
   // qm_map_device on a large batch: its parts on helper contexts of the same replica, in flight together (map_device_split)
   uint32_t flags = 0; bool isHelper = false;
   std::vector<qm_ctx*> helpers; struct SplitPool* pool = nullptr;
@@ -211,19 +272,8 @@ struct SplitJoin {
   void pass_turn(int part) { if (!stagger) return; std::lock_guard<std::mutex> lk(mu); if (turn < part + 1) turn = part + 1; cv.notify_all(); }
 };
 
-template <typename T>
-static int ensure(T*& p, int64_t& cap, int64_t want, int64_t minGrow = 0) {
-  if (want <= cap && p) return QM_OK;
-  if (p) hipFree(p);
-  p = nullptr;
-  int64_t nc = want + minGrow;
-  if (cap > 0 && nc < cap + cap / 2) nc = cap + cap / 2;     // a buffer that grows again grows by half: callers whose batches vary in size (the
-                                                             // compat header's batching service) stop paying a round of hipFree / hipMalloc per new maximum
-  if (nc > want + minGrow && hipMalloc((void**)&p, (size_t)nc * sizeof(T)) != hipSuccess) { p = nullptr; (void)hipGetLastError(); nc = want + minGrow; }   // no room for the slack: the exact size
-  if (!p && hipMalloc((void**)&p, (size_t)nc * sizeof(T)) != hipSuccess) { cap = 0; return fail(QM_E_NOMEM, "hipMalloc of %lld bytes failed", (long long)(nc * sizeof(T))); }
-  cap = nc;
-  return QM_OK;
-}
+// every public entry that maps starts from a clean record
+static void begin_call(qm_ctx* c) { c->last.invalidate(); c->stats = CallStats(); }
 
 extern "C" {
 
@@ -503,48 +553,25 @@ int qm_ctx_destroy(qm_ctx* c) {
   delete c->pool; c->pool = nullptr;
   for (qm_ctx* h : c->helpers) qm_ctx_destroy(h);
   c->helpers.clear();
-  if (!c->rep) {               // creation failed half-way: the index arrays are still this context's own
-    void* own[] = {c->d_text, c->d_SA, c->d_sainfo, c->d_slots, c->d_txpOff, c->d_txpLen, c->d_saext};
-    for (void* p : own) if (p) hipFree(p);
-    for (void* p : c->phAllocs) if (p) hipFree(p);
-  }
-  void* ptrs[] = {c->d_cnt, c->d_lcnt, c->d_loff, c->d_lists, c->d_hits, c->d_offs,
-                  c->d_scal, c->d_skip, c->d_gscr, c->d_scanTmp, c->d_seq1, c->d_seq2, c->d_off1, c->d_off2, c->d_iv, c->d_ivcnt, c->d_ivoff, c->d_found, c->d_tooMany, c->d_ivIn, c->d_ivInOff, c->d_lenIn, c->d_foundIn,
-                  c->d_selscr, c->d_kswRows, c->d_pk1, c->d_pk2, c->d_exc1, c->d_exc2, c->d_slowq, c->d_todoq, c->d_todoq2, c->d_dyn, c->d_dynmem, c->d_toff, c->d_tmp, c->d_sides, c->d_tsc, c->d_tref, c->d_torder, c->d_tasks};
-  for (void* p : ptrs) if (p) hipFree(p);
-  if (c->ev0) hipEventDestroy(c->ev0);
-  if (c->ev1) hipEventDestroy(c->ev1);
-  if (c->evA) hipEventDestroy(c->evA);
-  if (c->evB) hipEventDestroy(c->evB);
   if (c->stream) hipStreamDestroy(c->stream);
   if (c->copyStream) hipStreamDestroy(c->copyStream);
   if (c->planStream) hipStreamDestroy(c->planStream);
+  hipEvent_t evs[] = {c->ev0, c->ev1, c->evA, c->evB, c->evCopy, c->evP0, c->evP1, c->evStage[0], c->evStage[1]};
+  for (hipEvent_t e : evs) if (e) hipEventDestroy(e);
   for (hipEvent_t e : c->evPlan) if (e) hipEventDestroy(e);
-  if (c->d_ntk) hipFree(c->d_ntk);
-  if (c->d_gslots) hipFree(c->d_gslots);
-  if (c->d_ivcsr) hipFree(c->d_ivcsr);
-  if (c->d_lcsr) hipFree(c->d_lcsr);
-  if (c->d_ivC) hipFree(c->d_ivC);
-  if (c->d_wordsC) hipFree(c->d_wordsC);
-  if (c->h_tot) hipHostFree(c->h_tot);
-  if (c->evCopy) hipEventDestroy(c->evCopy);
-  if (c->evP0) hipEventDestroy(c->evP0);
-  if (c->evP1) hipEventDestroy(c->evP1);
-  if (c->evStage[0]) hipEventDestroy(c->evStage[0]);
-  if (c->evStage[1]) hipEventDestroy(c->evStage[1]);
-  if (c->h_stage) hipHostFree(c->h_stage);
   {   // the last context on (index, device) frees the replica
     std::lock_guard<std::mutex> lk(g_repMu);
     c->rep.reset();
     for (auto it = g_reps.begin(); it != g_reps.end();) { if (it->second.expired()) it = g_reps.erase(it); else ++it; }
   }
-  delete c;
+  delete c;                    // (the work buffers free themselves)
   return QM_OK;
 }
 
 int qm_ctx_create(const qm_index* ix, int device_id, qm_ctx** out) { return qm_ctx_create_ex(ix, device_id, 0, out); }
 
 static bool ensure_saext2(qm_ctx* c);
+static int build_replica(const qm_index* ix, int device, bool phCompact, hipStream_t stream, Replica& R);
 int qm_ctx_create_ex(const qm_index* ix, int device_id, uint32_t flags, qm_ctx** out) {
   if (!ix || !out) return fail(QM_E_ARG, "null argument");
   const bool phCompact = ix->perfect && (flags & QM_CTX_PH_COMPACT);
@@ -557,17 +584,17 @@ int qm_ctx_create_ex(const qm_index* ix, int device_id, uint32_t flags, qm_ctx**
   c->ix = ix; c->device = device_id; c->flags = flags;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) c->numCU = prop.multiProcessorCount;
-#define CK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { int rc = fail(QM_E_NOGPU, "%s: %s", #x, hipGetErrorString(_e)); qm_ctx_destroy(c); return rc; } } while (0)
+  int rc;
+#define CK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rc = fail(QM_E_NOGPU, "%s: %s", #x, hipGetErrorString(_e)); qm_ctx_destroy(c); return rc; } } while (0)
   CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   CK(hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
   CK(hipStreamCreateWithFlags(&c->planStream, hipStreamNonBlocking));
   for (hipEvent_t& e : c->evPlan) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  CK(hipMalloc((void**)&c->d_ntk, 3 * QM_SEL_CHUNKS_B * sizeof(u64)));
   CK(hipEventCreateWithFlags(&c->evCopy, hipEventDisableTiming));
   CK(hipEventCreate(&c->ev0)); CK(hipEventCreate(&c->ev1)); CK(hipEventCreate(&c->evA)); CK(hipEventCreate(&c->evB));
   CK(hipEventCreate(&c->evP0)); CK(hipEventCreate(&c->evP1));
-  CK(hipMalloc((void**)&c->d_scal, QM_SC_WORDS * sizeof(u64)));
-  CK(hipMalloc((void**)&c->d_skip, QM_SKIP_CAP * sizeof(u64)));
+#undef CK
+  if ((rc = c->d_ntk.ensure(3 * QM_SEL_CHUNKS_B)) || (rc = c->d_scal.ensure(QM_SC_WORDS)) || (rc = c->d_skip.ensure(QM_SKIP_CAP))) { qm_ctx_destroy(c); return rc; }
   // one builder per (index, device image) at a time: a second thread that asks for the same replica while the first one is
   // still uploading waits here and then shares it
   std::shared_ptr<std::mutex> buildMu;
@@ -582,45 +609,52 @@ int qm_ctx_create_ex(const qm_index* ix, int device_id, uint32_t flags, qm_ctx**
     std::lock_guard<std::mutex> lk(g_repMu);
     auto it = g_reps.find(std::make_pair(ix, repKey));
     if (it != g_reps.end()) c->rep = it->second.lock();
-    if (c->rep) {
-      Replica& R = *c->rep;
-      c->d_text = R.d_text; c->d_SA = R.d_SA; c->d_sainfo = R.d_sainfo; c->d_slots = R.d_slots; c->cap = R.cap; c->d_ph = R.d_ph; c->hPh = R.hPh;
-      c->d_txpOff = R.d_txpOff; c->d_txpLen = R.d_txpLen; c->devBytes = R.devBytes;
-      { std::lock_guard<std::mutex> l2(R.sanextMu); c->d_sanext = R.d_sanext; }
-      c->d_saext = R.d_saext;
-    }
   }
-  if (c->rep) {
-    if (flags & QM_CTX_WIDE_READS) (void)ensure_saext2(c);   // (a replica without room for it goes on with the general kernels)
-    *out = c;
-    return QM_OK;
+  if (!c->rep) {
+    auto R = std::make_shared<Replica>();
+    if ((rc = build_replica(ix, device_id, phCompact, c->stream, *R))) { R.reset(); qm_ctx_destroy(c); return rc; }
+    std::lock_guard<std::mutex> lk(g_repMu);
+    c->rep = R;
+    g_reps[std::make_pair(ix, repKey)] = R;
   }
+  { std::lock_guard<std::mutex> lk(c->rep->sanextMu); c->d_sanext = c->rep->sanext; c->devBytes = c->rep->devBytes; }
+  // the wide extension table with the replica when the caller knows reads of 129 .. 256 characters are coming: otherwise the first call
+  // that has such reads builds it (0.2 s for config 2) inside that call (a replica without room for it goes on with the general kernels)
+  if (flags & QM_CTX_WIDE_READS) (void)ensure_saext2(c);
+  *out = c;
+  return QM_OK;
+}
+
+// The device image of an index, built into R on `stream`.  On an error R is left as far as it got: it frees what it holds.
+static int build_replica(const qm_index* ix, int device, bool phCompact, hipStream_t stream, Replica& R) {
+  int rc;
+  R.device = device;
   const size_t pad = 256;
-  CK(hipMalloc((void**)&c->d_text, (size_t)ix->n + pad));
-  CK(hipMemsetAsync(c->d_text + ix->n, 0, pad, c->stream));
-  CK(hipMemcpyAsync(c->d_text, ix->text, (size_t)ix->n, hipMemcpyHostToDevice, c->stream));
-  CK(hipMalloc((void**)&c->d_SA, (size_t)ix->nSA * 4));
-  CK(hipMemcpyAsync(c->d_SA, ix->SA, (size_t)ix->nSA * 4, hipMemcpyHostToDevice, c->stream));
-  CK(hipMalloc(&c->d_sainfo, (size_t)ix->nSA * sizeof(SaInfo)));
-  uint32_t* d_offsets = nullptr; void* d_recs = nullptr;
-  CK(hipMalloc((void**)&d_offsets, (size_t)ix->nTxp * 4));
-  CK(hipMemcpyAsync(d_offsets, ix->offsets, (size_t)ix->nTxp * 4, hipMemcpyHostToDevice, c->stream));
-  CK(qmk_build_sainfo(c->d_SA, ix->nSA, d_offsets, ix->nTxp, c->d_sainfo, c->stream));
+  if ((rc = R.text.ensure(ix->n + (int64_t)pad))) return rc;
+  HIPCHK(hipMemsetAsync(R.text + ix->n, 0, pad, stream));
+  HIPCHK(hipMemcpyAsync(R.text, ix->text, (size_t)ix->n, hipMemcpyHostToDevice, stream));
+  if ((rc = R.SA.ensure(ix->nSA))) return rc;
+  HIPCHK(hipMemcpyAsync(R.SA, ix->SA, (size_t)ix->nSA * 4, hipMemcpyHostToDevice, stream));
+  if ((rc = R.sainfo.ensure(ix->nSA * (int64_t)sizeof(SaInfo)))) return rc;
+  if ((rc = R.txpOff.ensure(ix->nTxp))) return rc;      // kept: -s reads transcript sequences by (offset, length)
+  HIPCHK(hipMemcpyAsync(R.txpOff, ix->offsets, (size_t)ix->nTxp * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(qmk_build_sainfo(R.SA, ix->nSA, R.txpOff, ix->nTxp, R.sainfo, stream));
   if (!getenv("QM_NO_SAEXT") && ix->nSA > 0 && ix->nTxp < (1LL << QM_EXT_TID_BITS)) {
     // the packed characters behind every suffix's k-mer: an MMP extension becomes one trip instead of two (saext_entry);
     // 32 bytes per suffix-array entry.  QM_NO_SAEXT (profiling): without the table, extensions read suffix array and text.
-    if (hipMalloc(&c->d_saext, (size_t)ix->nSA * sizeof(SaExt)) != hipSuccess) { c->d_saext = nullptr; (void)hipGetLastError(); }   // no room: the text path
-    else { CK(qmk_build_saext(c->d_text, ix->n, c->d_SA, ix->nSA, ix->k, c->d_sainfo, c->d_saext, c->stream)); }
+    if (R.saext.ensure(ix->nSA * (int64_t)sizeof(SaExt))) (void)hipGetLastError();   // no room: the text path
+    else HIPCHK(qmk_build_saext(R.text, ix->n, R.SA, ix->nSA, ix->k, R.sainfo, R.saext, stream));
   }
+  DevBuf<unsigned char> recs;                              // staging: the hash records as the file has them
   if (!ix->perfect) {
-    c->cap = bucket_count(ix->nKeys);                  // 64-byte buckets of two canonical entries, at least two buckets per key
-    CK(hipMalloc(&c->d_slots, c->cap * sizeof(Bucket)));
-    CK(hipMalloc(&d_recs, (size_t)(ix->nKeys > 0 ? ix->nKeys : 1) * 16));
-    if (ix->nKeys > 0) CK(hipMemcpyAsync(d_recs, ix->hashRecs, (size_t)ix->nKeys * 16, hipMemcpyHostToDevice, c->stream));
-    CK(qmk_build_slots(d_recs, ix->nKeys, c->d_slots, c->cap, ix->k, c->stream));
+    R.cap = bucket_count(ix->nKeys);                  // 64-byte buckets of two canonical entries, at least two buckets per key
+    if ((rc = R.slots.ensure((int64_t)(R.cap * sizeof(Bucket))))) return rc;
+    if ((rc = recs.ensure((ix->nKeys > 0 ? ix->nKeys : 1) * 16))) return rc;
+    if (ix->nKeys > 0) HIPCHK(hipMemcpyAsync(recs, ix->hashRecs, (size_t)ix->nKeys * 16, hipMemcpyHostToDevice, stream));
+    HIPCHK(qmk_build_slots(recs, ix->nKeys, R.slots, R.cap, ix->k, stream));
   } else {
     // flatten BooPHF + FrugalBooMap: all levels' words / rank samples concatenated, small maps re-hashed
-    c->cap = 1;
+    R.cap = 1;
     PhIndex P; memset(&P, 0, sizeof(P));
     const int nl = (int)ix->phLevels.size();
     std::vector<PhLevelIn> lin((size_t)nl);
@@ -629,23 +663,22 @@ int qm_ctx_create_ex(const qm_index* ix, int device_id, uint32_t flags, qm_ctx**
       lin[i].ranks = (const uint64_t*)ix->phLevels[i].ranks; lin[i].nranks = ix->phLevels[i].nranks;
     }
     std::vector<uint64_t> blocks, tab;
-    if (!ph_flatten_blocks(lin, blocks, tab)) { int rc = fail(QM_E_IO, "hash_info.bph: rank samples do not match the bit arrays"); qm_ctx_destroy(c); return rc; }
-    auto dalloc = [&](size_t bytes) -> void* { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr; c->phAllocs.push_back(q); c->devBytes += (int64_t)bytes; return q; };
+    if (!ph_flatten_blocks(lin, blocks, tab)) return fail(QM_E_IO, "hash_info.bph: rank samples do not match the bit arrays");
+    auto dalloc = [&](size_t bytes) -> void* { DevBuf<unsigned char>& q = R.phAllocs.emplace_back(); if (q.ensure((int64_t)(bytes ? bytes : 16))) return nullptr; R.devBytes += (int64_t)bytes; return q.p; };
     u64* dW = (u64*)dalloc(blocks.size() * 8); u64* dT = (u64*)dalloc(tab.size() * 8);
     PhRec* dRec = (PhRec*)dalloc((size_t)ix->phNelem * sizeof(PhRec));
-    unsigned int* dD = nullptr; unsigned char* dL = nullptr; // staging for the record builder
-    if (hipMalloc((void**)&dD, (size_t)(ix->phNelem ? ix->phNelem : 1) * 4) != hipSuccess || hipMalloc((void**)&dL, (size_t)(ix->phNelem ? ix->phNelem : 1)) != hipSuccess) dD = nullptr;
-    if (!dW || !dT || !dRec || !dD || !dL) { int rc = fail(QM_E_NOMEM, "hipMalloc (perfect hash) failed"); qm_ctx_destroy(c); return rc; }
-    CK(hipMemcpyAsync(dW, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice, c->stream));
-    CK(hipMemcpyAsync(dT, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-    CK(hipMemcpyAsync(dD, ix->phData, (size_t)ix->phNelem * 4, hipMemcpyHostToDevice, c->stream));
-    CK(hipMemcpyAsync(dL, ix->phLens, (size_t)ix->phNelem, hipMemcpyHostToDevice, c->stream));
+    DevBuf<unsigned int> dD; DevBuf<unsigned char> dL;       // staging for the record builder
+    if (dD.ensure((int64_t)(ix->phNelem ? ix->phNelem : 1)) || dL.ensure((int64_t)(ix->phNelem ? ix->phNelem : 1)) || !dW || !dT || !dRec) return fail(QM_E_NOMEM, "hipMalloc (perfect hash) failed");
+    HIPCHK(hipMemcpyAsync(dW, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dT, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dD, ix->phData, (size_t)ix->phNelem * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dL, ix->phLens, (size_t)ix->phNelem, hipMemcpyHostToDevice, stream));
     {
       DevIndex dix; memset(&dix, 0, sizeof(dix));
-      dix.text = c->d_text; dix.n = ix->n; dix.SA = c->d_SA; dix.nSA = ix->nSA; dix.k = ix->k;
-      CK(qmk_build_phrecs(dD, dL, ix->phNelem, &dix, dRec, c->stream));
-      CK(hipStreamSynchronize(c->stream));
-      hipFree(dD); hipFree(dL);
+      dix.text = R.text; dix.n = ix->n; dix.SA = R.SA; dix.nSA = ix->nSA; dix.k = ix->k;
+      HIPCHK(qmk_build_phrecs(dD, dL, ix->phNelem, &dix, dRec, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      dD.release(); dL.release();
     }
     auto mix = [](u64 x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33; return x; };
     std::vector<OvfSlot> ov; std::vector<Slot> fin;
@@ -662,9 +695,9 @@ int qm_ctx_create_ex(const qm_index* ix, int device_id, uint32_t flags, qm_ctx**
     }
     OvfSlot* dO = (OvfSlot*)dalloc(ov.size() * sizeof(OvfSlot)); Slot* dF = (Slot*)dalloc(fin.size() * sizeof(Slot));
     void* dP = dalloc(sizeof(PhIndex));
-    if (!dO || !dF || !dP) { int rc = fail(QM_E_NOMEM, "hipMalloc (perfect hash) failed"); qm_ctx_destroy(c); return rc; }
-    CK(hipMemcpyAsync(dO, ov.data(), ov.size() * sizeof(OvfSlot), hipMemcpyHostToDevice, c->stream));
-    CK(hipMemcpyAsync(dF, fin.data(), fin.size() * sizeof(Slot), hipMemcpyHostToDevice, c->stream));
+    if (!dO || !dF || !dP) return fail(QM_E_NOMEM, "hipMalloc (perfect hash) failed");
+    HIPCHK(hipMemcpyAsync(dO, ov.data(), ov.size() * sizeof(OvfSlot), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dF, fin.data(), fin.size() * sizeof(Slot), hipMemcpyHostToDevice, stream));
     P.blocks = dW; P.levelTab = dT; P.recs = dRec; P.ovf = dO; P.fin = dF;
     P.lastbitsetrank = ix->phLastRank; P.nelem = ix->phNelem; P.nb_levels = nl;
     if (phCompact && !getenv("QM_PH_NO_FILTER")) {
@@ -672,58 +705,39 @@ int qm_ctx_create_ex(const qm_index* ix, int device_id, uint32_t flags, qm_ctx**
       // one sector instead of a walk through the levels.  QM_PH_NO_FILTER (profiling): the bare reference structure.
       const u64 fw = ph_filter_words(ix->phNelem);
       u64* dFil = (u64*)dalloc(fw * 8);
-      if (!dFil) { int rc = fail(QM_E_NOMEM, "hipMalloc (perfect hash filter) failed"); qm_ctx_destroy(c); return rc; }
-      CK(hipMemsetAsync(dFil, 0, fw * 8, c->stream));
-      CK(qmk_build_phfilter(dRec, (long long)ix->phNelem, dFil, fw - 1, ix->k, c->stream));
+      if (!dFil) return fail(QM_E_NOMEM, "hipMalloc (perfect hash filter) failed");
+      HIPCHK(hipMemsetAsync(dFil, 0, fw * 8, stream));
+      HIPCHK(qmk_build_phfilter(dRec, (long long)ix->phNelem, dFil, fw - 1, ix->k, stream));
       P.filter = dFil; P.filterMask = fw - 1;
     }
-    CK(hipMemcpyAsync(dP, &P, sizeof(P), hipMemcpyHostToDevice, c->stream));
-    CK(hipStreamSynchronize(c->stream));    // P, tab, ov, fin are locals
-    c->d_ph = dP; c->hPh = P;
+    HIPCHK(hipMemcpyAsync(dP, &P, sizeof(P), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));    // P, tab, ov, fin are locals
+    R.ph = (const PhIndex*)dP; R.hPh = P;
     if (!phCompact) {
       // Default device image of a -p index: the same one-sector bucket table a dense index gets, filled from the MPHF's own
       // records after each was looked up through the BooPHF walk (so the table is known to answer like FrugalBooMap::find on
       // this file).  288 GB of HBM make the frugal structure unnecessary on this device; QM_CTX_PH_COMPACT keeps it.
-      c->cap = bucket_count((long long)ix->phNelem);
-      unsigned long long* dBad = nullptr; unsigned long long hBad = 0;
-      CK(hipMalloc(&c->d_slots, c->cap * sizeof(Bucket)));
-      CK(hipMalloc((void**)&dBad, sizeof(unsigned long long)));
+      R.cap = bucket_count((long long)ix->phNelem);
+      DevBuf<unsigned long long> dBad; unsigned long long hBad = 0;
+      if ((rc = R.slots.ensure((int64_t)(R.cap * sizeof(Bucket)))) || (rc = dBad.ensure(1))) return rc;
       DevIndex dix; memset(&dix, 0, sizeof(dix));
-      dix.text = c->d_text; dix.n = ix->n; dix.SA = c->d_SA; dix.nSA = ix->nSA; dix.k = ix->k; dix.ph = (const PhIndex*)dP; dix.phv = P;
-      CK(qmk_build_slots_from_ph(&dix, (long long)ix->phNelem, c->d_slots, c->cap, dBad, c->stream));
-      CK(hipMemcpyAsync(&hBad, dBad, sizeof(hBad), hipMemcpyDeviceToHost, c->stream));
-      CK(hipStreamSynchronize(c->stream));
-      hipFree(dBad);
-      if (hBad) { int rc = fail(QM_E_IO, "hash_info.bph / hash_info.val: %llu k-mers are not found by the perfect hash they were stored with", hBad); qm_ctx_destroy(c); return rc; }
-      for (void* q : c->phAllocs) if (q) hipFree(q);
-      c->phAllocs.clear(); c->d_ph = nullptr; c->devBytes = (int64_t)(c->cap * sizeof(Bucket));
+      dix.text = R.text; dix.n = ix->n; dix.SA = R.SA; dix.nSA = ix->nSA; dix.k = ix->k; dix.ph = R.ph; dix.phv = P;
+      HIPCHK(qmk_build_slots_from_ph(&dix, (long long)ix->phNelem, R.slots, R.cap, dBad, stream));
+      HIPCHK(hipMemcpyAsync(&hBad, dBad, sizeof(hBad), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      if (hBad) return fail(QM_E_IO, "hash_info.bph / hash_info.val: %llu k-mers are not found by the perfect hash they were stored with", hBad);
+      R.phAllocs.clear(); R.ph = nullptr; R.devBytes = (int64_t)(R.cap * sizeof(Bucket));
     }
   }
-  CK(hipStreamSynchronize(c->stream));
-  c->d_txpOff = d_offsets;                               // kept: -s reads transcript sequences by (offset, length)
+  HIPCHK(hipStreamSynchronize(stream));
   {
     std::vector<int32_t> l32((size_t)ix->nTxp);
     for (int64_t t = 0; t < ix->nTxp; ++t) l32[(size_t)t] = (int32_t)ix->lens[(size_t)t];
-    CK(hipMalloc((void**)&c->d_txpLen, (size_t)(ix->nTxp ? ix->nTxp : 1) * 4));
-    CK(hipMemcpy(c->d_txpLen, l32.data(), (size_t)ix->nTxp * 4, hipMemcpyHostToDevice));
+    if ((rc = R.txpLen.ensure(ix->nTxp ? ix->nTxp : 1))) return rc;
+    HIPCHK(hipMemcpy(R.txpLen, l32.data(), (size_t)ix->nTxp * 4, hipMemcpyHostToDevice));
   }
-  if (d_recs) hipFree(d_recs);
-  c->devBytes += ix->n + pad + ix->nSA * 4 + ix->nSA * (int64_t)sizeof(SaInfo) + (int64_t)(ix->perfect ? 0 : c->cap * sizeof(Bucket))
-                 + (c->d_saext ? ix->nSA * (int64_t)sizeof(SaExt) : 0);
-#undef CK
-  {
-    auto R = std::make_shared<Replica>();
-    R->device = device_id; R->d_text = c->d_text; R->d_SA = c->d_SA; R->d_sainfo = c->d_sainfo; R->d_slots = c->d_slots; R->cap = c->cap;
-    R->d_ph = c->d_ph; R->hPh = c->hPh; R->phAllocs.swap(c->phAllocs); R->d_txpOff = c->d_txpOff; R->d_txpLen = c->d_txpLen; R->devBytes = c->devBytes;
-    R->d_saext = c->d_saext;
-    std::lock_guard<std::mutex> lk(g_repMu);
-    c->rep = R;
-    g_reps[std::make_pair(ix, repKey)] = R;
-  }
-  // the wide extension table with the replica when the caller knows reads of 129 .. 256 characters are coming: otherwise the first call
-  // that has such reads builds it (0.2 s for config 2) inside that call
-  if (flags & QM_CTX_WIDE_READS) (void)ensure_saext2(c);
-  *out = c;
+  R.devBytes += ix->n + pad + ix->nSA * 4 + ix->nSA * (int64_t)sizeof(SaInfo) + (int64_t)(ix->perfect ? 0 : R.cap * sizeof(Bucket))
+                + (R.saext ? ix->nSA * (int64_t)sizeof(SaExt) : 0);
   return QM_OK;
 }
 
@@ -763,10 +777,11 @@ struct RunReq {
 };
 
 static DevIndex dev_index(const qm_ctx* c) {
-  DevIndex ix; ix.text = c->d_text; ix.n = c->ix->n; ix.SA = c->d_SA; ix.nSA = c->ix->nSA;
-  ix.sainfo = (const SaInfo*)c->d_sainfo; ix.slots = (const Bucket*)c->d_slots; ix.hmask = c->cap - 1; ix.ph = (const PhIndex*)c->d_ph; ix.k = c->ix->k;
-  memset(&ix.phv, 0, sizeof(ix.phv)); if (c->d_ph) ix.phv = c->hPh;
-  ix.sanext = c->d_sanext; ix.saext = (const SaExt*)c->d_saext; ix.saext2 = (const SaExt2*)c->d_saext2;
+  const Replica& R = *c->rep;
+  DevIndex ix; ix.text = R.text; ix.n = c->ix->n; ix.SA = R.SA; ix.nSA = c->ix->nSA;
+  ix.sainfo = (const SaInfo*)R.sainfo.p; ix.slots = (const Bucket*)R.slots.p; ix.hmask = R.cap - 1; ix.ph = R.ph; ix.k = c->ix->k;
+  memset(&ix.phv, 0, sizeof(ix.phv)); if (R.ph) ix.phv = R.hPh;
+  ix.sanext = c->d_sanext; ix.saext = (const SaExt*)R.saext.p; ix.saext2 = (const SaExt2*)c->d_saext2;
   return ix;
 }
 
@@ -780,42 +795,40 @@ static DevIndex dev_index(const qm_ctx* c) {
 // that has no room for it (or no SaExt) goes on with the general kernels.
 static bool ensure_saext2(qm_ctx* c) {
   if (c->d_saext2) return true;
-  if (!c->rep || !c->d_saext || c->ix->nSA <= 0) return false;
   Replica& R = *c->rep;
+  if (!R.saext || c->ix->nSA <= 0) return false;
   std::lock_guard<std::mutex> lk(R.sanextMu);
-  if (!R.d_saext2 && !R.saext2Tried) {
+  if (!R.saext2 && !R.saext2Tried) {
     R.saext2Tried = true;
-    void* p = nullptr;
     // room for the table AND a margin for the work buffers of the replica's contexts (lists, hits, scratch: they grow with the batches);
     // a replica that cannot spare it stays with the general kernels for such reads
     size_t freeB = 0, totalB = 0;
     const size_t need = (size_t)c->ix->nSA * qmk_saext2_bytes(), margin = (size_t)8 << 30;
     if (hipMemGetInfo(&freeB, &totalB) != hipSuccess || freeB < need + margin) { (void)hipGetLastError(); return false; }
-    if (hipMalloc(&p, need) != hipSuccess) { (void)hipGetLastError(); return false; }
-    hipError_t e = qmk_build_saext2(c->d_text, c->ix->n, c->d_SA, c->ix->nSA, c->ix->k, c->d_sainfo, p, c->stream);
+    if (R.saext2.ensure((int64_t)need)) { (void)hipGetLastError(); return false; }
+    hipError_t e = qmk_build_saext2(R.text, c->ix->n, R.SA, c->ix->nSA, c->ix->k, R.sainfo, R.saext2, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { hipFree(p); (void)hipGetLastError(); return false; }
-    R.d_saext2 = p; R.devBytes += c->ix->nSA * (int64_t)qmk_saext2_bytes();
+    if (e != hipSuccess) { R.saext2.release(); (void)hipGetLastError(); return false; }
+    R.devBytes += c->ix->nSA * (int64_t)qmk_saext2_bytes();
   }
-  c->d_saext2 = R.d_saext2; c->devBytes = R.devBytes;
+  c->d_saext2 = R.saext2; c->devBytes = R.devBytes;
   return c->d_saext2 != nullptr;
 }
 
 // The -s extension table (sanext_entry: a capped MMP extension becomes one trip; 4 bytes per suffix-array entry, built from text and SA as
 // they sit in HBM): built by the first -s call on a replica, shared by every context of the replica.
 static int ensure_sanext(qm_ctx* c) {
-  if (c->d_sanext || c->ix->nSA <= 0 || !c->rep) return QM_OK;
+  if (c->d_sanext || c->ix->nSA <= 0) return QM_OK;
   Replica& R = *c->rep;
   std::lock_guard<std::mutex> lk(R.sanextMu);
-  if (!R.d_sanext) {
-    unsigned int* p = nullptr;
-    HIPCHK(hipMalloc((void**)&p, (size_t)c->ix->nSA * sizeof(unsigned int)));
-    hipError_t e = qmk_build_sanext(c->d_text, c->ix->n, c->d_SA, c->ix->nSA, c->ix->k, p, c->stream);
+  if (!R.sanext) {
+    if (int rc = R.sanext.ensure(c->ix->nSA)) return rc;
+    hipError_t e = qmk_build_sanext(R.text, c->ix->n, R.SA, c->ix->nSA, c->ix->k, R.sanext, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { hipFree(p); return fail(QM_E_NOGPU, "building the -s extension table: %s", hipGetErrorString(e)); }
-    R.d_sanext = p; R.devBytes += c->ix->nSA * 4;
+    if (e != hipSuccess) { R.sanext.release(); return fail(QM_E_NOGPU, "building the -s extension table: %s", hipGetErrorString(e)); }
+    R.devBytes += c->ix->nSA * 4;
   }
-  c->d_sanext = R.d_sanext; c->devBytes = R.devBytes;
+  c->d_sanext = R.sanext; c->devBytes = R.devBytes;
   return QM_OK;
 }
 
@@ -830,9 +843,9 @@ static int gscr_for(qm_ctx* c, int grid, unsigned*& slots, int& nslots) {
   slots = nullptr; nslots = 0;
   const char* fe = getenv("QM_GSCR_SLOTS");                  // (tests: slots for launches that would not need them)
   const bool force = fe && atoi(fe) != 0;
-  int rc = ensure(c->d_gscr, c->capGrid, (waves > cap || force ? cap : waves) * QM_GSCR_U64);
+  int rc = c->d_gscr.ensure((waves > cap || force ? cap : waves) * QM_GSCR_U64);
   if (rc || (waves <= cap && !force)) return rc;
-  if (!c->d_gslots && hipMalloc((void**)&c->d_gslots, (size_t)cap * sizeof(unsigned)) != hipSuccess) { c->d_gslots = nullptr; return fail(QM_E_NOMEM, "hipMalloc of the scratch slots' flags failed"); }
+  if ((rc = c->d_gslots.ensure(cap))) return rc;
   HIPCHK(hipMemsetAsync(c->d_gslots, 0, (size_t)cap * sizeof(unsigned), c->stream));
   slots = c->d_gslots; nslots = (int)cap;
   return QM_OK;
@@ -852,7 +865,7 @@ static bool lean_first(const StagePlan& p) { return p.first == SK_LEAN || p.firs
 
 static int plan_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, bool paired, int64_t n, int ns, StagePlan& p) {
   p.paired = paired; p.n = n; p.nreads = paired ? 2 * n : n; p.ns = ns;
-  p.phc = c->d_ph ? 1 : 0;                                // (the compact -p image: its kernels take a larger grid)
+  p.phc = c->rep->ph ? 1 : 0;                                // (the compact -p image: its kernels take a larger grid)
   p.grid = qmk_map_grid_ex(p.nreads, c->numCU, p.phc); p.gslots = nullptr; p.ngslots = 0;
   // The lean kernel (qm_lean.inl: two reads per wavefront and iteration, reads of up to 128 clean characters) takes the fused default
   // call on a dense table; the reads it marks instead of mapping go through the general kernel in a second, small launch (pass_lean_leftovers).
@@ -861,7 +874,7 @@ static int plan_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, bool pair
   // Reads of 129 .. 256 characters (slot classes 3 and 4) take its wide edition -- one read per wavefront -- once the replica holds the
   // wide extension table.
   static const bool wideOff = [] { const char* e = getenv("QM_NO_LEAN_WIDE"); return e && atoi(e) != 0; }();
-  const bool leanBase = !leanOff && rq.mode == QM_RUN_FUSED && o->sensitive && (c->d_slots || c->d_ph) && c->d_saext && c->ix->k <= 31;
+  const bool leanBase = !leanOff && rq.mode == QM_RUN_FUSED && o->sensitive && (c->rep->slots || c->rep->ph) && c->rep->saext && c->ix->k <= 31;
   // (a call that keeps the SA-interval records takes the general kernel: the lean kernels do not write them; foundHit they do -- stage views without intervals)
   p.leanWide = leanBase && !wideOff && (ns == 3 || ns == 4) && (o->sel_aln || !rq.keepIntervals) && ensure_saext2(c);
   const bool useLean = leanBase && !o->sel_aln && (ns == 2 || p.leanWide) && !rq.keepIntervals;
@@ -871,7 +884,7 @@ static int plan_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, bool pair
   // (dense table only: on the compact -p image a position's two orientations are two walks of the BooPHF levels, and a lane per position
   // serialises them -- 301 M pairs/s against qm_lean_kernel's 323, profiles/r06/exp_mix.txt)
   static const bool duoPh = [] { const char* e = getenv("QM_DUO_PH"); return e && atoi(e) != 0; }();
-  const bool useDuo = useLean && !duoOff && !rq.noDuo && !(c->flags & QM_CTX_NO_PAIR_KERNEL) && paired && ns == 2 && (!c->d_ph || duoPh);
+  const bool useDuo = useLean && !duoOff && !rq.noDuo && !(c->flags & QM_CTX_NO_PAIR_KERNEL) && paired && ns == 2 && (!c->rep->ph || duoPh);
   // (qm_lean_kernel holds both mates of a pair in one wavefront too, but merging there was measured and dropped: that kernel is bound by the CU's scalar unit and
   // the merge's bookkeeping cost it 1.3 ms per 10 M pairs -- 62 instead of 28 spilled scalar registers -- where stage B saved 0.5: profiles/r06/exp_mix.txt)
   p.duoMerge = useDuo && !rq.mergeOnly && !rq.stageView;
@@ -891,9 +904,9 @@ static int plan_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, bool pair
 // The work buffers of a call, sized from the plan.
 static int reserve_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, StagePlan& p) {
   int rc;
-  if ((rc = ensure(c->d_lcnt, c->capLcnt, p.nreads + 1))) return rc;
-  if ((rc = ensure(c->d_loff, c->capLoff, p.nreads + 1))) return rc;
-  if (p.duoMerge && (rc = ensure(c->d_cnt, c->capCnt, p.n + 1))) return rc;
+  if ((rc = c->d_lcnt.ensure(p.nreads + 1))) return rc;
+  if ((rc = c->d_loff.ensure(p.nreads + 1))) return rc;
+  if (p.duoMerge && (rc = c->d_cnt.ensure(p.n + 1))) return rc;
   if (!lean_first(p)) {
     // the general kernels' scratch (gscr_for); when even that does not fit next to the index, the launch falls back to the resident grid
     rc = gscr_for(c, p.grid, p.gslots, p.ngslots);
@@ -901,15 +914,15 @@ static int reserve_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, StageP
     if (rc) return rc;
   }
   // lists and interval records come from chunked bump allocators: up to one open chunk per wave
-  if (rq.mode != QM_RUN_COLLECT && (rc = ensure(c->d_lists, c->capLists, p.nreads * 4 + (int64_t)p.grid * 4 * QM_CHUNK * 2))) return rc;
+  if (rq.mode != QM_RUN_COLLECT && (rc = c->d_lists.ensure(p.nreads * 4 + (int64_t)p.grid * 4 * QM_CHUNK * 2))) return rc;
   if (p.wantIv) {
-    if ((rc = ensure(c->d_ivcnt, c->capIvCnt, p.nreads + 1))) return rc;
-    if ((rc = ensure(c->d_ivoff, c->capIvOff, p.nreads + 1))) return rc;
-    if ((rc = ensure(c->d_iv, c->capIv, p.nreads * (o->sel_aln ? 16 : 4) + (int64_t)p.grid * 4 * QM_IVCHUNK * 2))) return rc;
+    if ((rc = c->d_ivcnt.ensure(p.nreads + 1))) return rc;
+    if ((rc = c->d_ivoff.ensure(p.nreads + 1))) return rc;
+    if ((rc = c->d_iv.ensure(p.nreads * (o->sel_aln ? 16 : 4) + (int64_t)p.grid * 4 * QM_IVCHUNK * 2))) return rc;
   }
-  if (p.wantFound && (rc = ensure(c->d_found, c->capFound, p.nreads + 1))) return rc;
+  if (p.wantFound && (rc = c->d_found.ensure(p.nreads + 1))) return rc;
   // -s: per-wave scratch for chaining (qm_sel.inl; the list kernels' grids stay within residency)
-  if (o->sel_aln && (rc = ensure(c->d_selscr, c->capSelScr, (int64_t)qmk_resident_grid(p.nreads, c->numCU) * 4 * (int64_t)qmk_sel_scratch_bytes()))) return rc;
+  if (o->sel_aln && (rc = c->d_selscr.ensure((int64_t)qmk_resident_grid(p.nreads, c->numCU) * 4 * (int64_t)qmk_sel_scratch_bytes()))) return rc;
   return QM_OK;
 }
 
@@ -919,17 +932,17 @@ static void fill_batch(const qm_ctx* c, const qm_opts* o, const RunReq& rq, cons
   memset(&B, 0, sizeof(B));
   B.seq1 = (const unsigned char*)d_seq1; B.off1 = (const long long*)d_off1;
   B.seq2 = (const unsigned char*)d_seq2; B.off2 = (const long long*)d_off2; B.nreads = p.nreads;
-  B.lcnt = c->d_lcnt; B.loff = c->d_loff; B.lists = c->d_lists; B.cursor = c->d_scal; B.lists_cap = c->capLists;
+  B.lcnt = c->d_lcnt; B.loff = c->d_loff; B.lists = c->d_lists; B.cursor = c->d_scal; B.lists_cap = c->d_lists.cap;
   B.status = (int*)(c->d_scal + QM_SC_STATUS); B.gscratch = c->d_gscr; B.gslots = p.gslots; B.ngslots = p.ngslots; B.gxcd = xcds_of(c); B.skiplist = c->d_skip;
   B.lean_wide = p.leanWide ? 1 : 0;
   if (p.duoMerge) { B.pair_cnt = c->d_cnt; B.max_num_hits = o->max_num_hits; B.no_orphans = o->no_orphans; B.no_dovetail = o->no_dovetail; }
-  if (p.wantIv) { B.iv_out = c->d_iv; B.iv_cnt = c->d_ivcnt; B.iv_off = c->d_ivoff; B.iv_cap = c->capIv; }
+  if (p.wantIv) { B.iv_out = c->d_iv; B.iv_cnt = c->d_ivcnt; B.iv_off = c->d_ivoff; B.iv_cap = c->d_iv.cap; }
   if (p.wantFound) B.found_out = c->d_found;
   B.iv_in = rq.ivIn; B.iv_in_off = rq.ivInOff; B.len_in = rq.lenIn; B.found_in = rq.foundIn;
   B.strict_check = o->strict_check; B.max_interval = o->max_interval; B.quasi_cov = o->quasi_cov; B.sensitive = o->sensitive; B.fuzzy = p.paired ? o->fuzzy : 0;
   if (rq.mode == QM_RUN_FROM_INTERVALS) B.fuzzy = o->fuzzy;   // the caller says what kind of list it wants (both orientations kept or not)
   if (o->sel_aln) {                                   // -s: chain scoring + per-wave scratch for chaining (qm_sel.inl)
-    B.selscr = (SelScratch*)c->d_selscr;
+    B.selscr = (SelScratch*)c->d_selscr.p;
     B.max_mmp_ext = o->max_mmp_extension > 0 ? o->max_mmp_extension : 7;
     const float cs = (float)o->consensus_slack;        // MappingOpts::consensusSlack is a float (RapMapSAMapper.cpp:138,184-185)
     B.consensus_fraction = cs < 0 ? -cs : ((cs == 0.0) ? 1.0 : (1.0 - cs));   // negative: MappingConfig::consensusFraction itself (qmap_mi355.h)
@@ -983,7 +996,7 @@ static int read_scalars(qm_ctx* c, u64* hscal, float* timedMs = nullptr) {
 // such reads (a scalar slot): the queue is sized for it and the gather writes no more, whatever lcnt holds.  QM_SC_SLOWQ is the gather's cursor; nothing else reads it.
 static int gather_queue(qm_ctx* c, unsigned mark, int64_t nq, const ReadBatch& B, ReadBatch& Q) {
   int rc;
-  if ((rc = ensure(c->d_slowq, c->capSlowq, nq))) return rc;
+  if ((rc = c->d_slowq.ensure(nq))) return rc;
   HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_SLOWQ, 0, sizeof(u64), c->stream));
   HIPCHK(qmk_collect_marked(c->d_lcnt, B.nreads, mark, c->d_slowq, nq, (unsigned long long*)(c->d_scal + QM_SC_SLOWQ), c->stream));
   Q = B; Q.slowq = c->d_slowq; Q.nreads = nq;
@@ -1014,7 +1027,7 @@ static int pass_n_aware(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const
   HIPCHK(qmk_launch_lean_nq(&ix, &Q, c->numCU, c->stream));
   HIPCHK(hipEventRecord(c->evP1, c->stream));
   if ((rc = read_scalars(c, hscal, &extraMs))) return rc;
-  c->lastNPass = nq - (int64_t)hscal[QM_SC_LEANQ];
+  c->stats.nPass = nq - (int64_t)hscal[QM_SC_LEANQ];
   return QM_OK;
 }
 
@@ -1023,14 +1036,14 @@ static int pass_n_aware(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const
 // writes goes where the first launch would have put it, and the reads it sets aside in turn (beyond its slot class) take the long-read pass.
 static int pass_lean_leftovers(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const ReadBatch& B, u64* hscal, float& extraMs) {
 #ifndef QM_TIMING
-  for (int i = 0; i < 4; ++i) c->lastDefer[i] = (int64_t)hscal[QM_SC_DEFER0 + i];   // why they were left, as the N-aware pass has it now
+  for (int i = 0; i < 4; ++i) c->stats.defer[i] = (int64_t)hscal[QM_SC_DEFER0 + i];   // why they were left, as the N-aware pass has it now
 #endif
-  if (p.duoMerge) c->lastDuoMerged = (int64_t)hscal[4];        // (numReads so far: the pairs the pair kernel merged; stage B's count pass adds the others)
+  if (p.duoMerge) c->stats.duoMerged = (int64_t)hscal[4];        // (numReads so far: the pairs the pair kernel merged; stage B's count pass adds the others)
   const int64_t nq = (int64_t)hscal[QM_SC_LEANQ];
   if (nq <= 0 || !stage_ok(hscal)) return QM_OK;
   int rc; ReadBatch Q;
   if ((rc = gather_queue(c, QM_LCNT_LEAN, nq, B, Q))) return rc;
-  c->lastLeanDeferred = nq;
+  c->stats.leanDeferred = nq;
   if (p.first == SK_LEAN_SEL) {
     // -s: the general chain-scoring collector, before the list kernels go over all reads and inside the call's ev0 .. ev1; its scalars come
     // down with theirs.  It borrows the scratch reserved for the first launch (p.grid blocks), so it stays within that grid.
@@ -1057,7 +1070,7 @@ static int pass_long_reads(qm_ctx* c, const StagePlan& p, const DevIndex& ix, co
   if (nl <= 0 || !stage_ok(hscal)) return QM_OK;
   int rc; ReadBatch Q;
   if ((rc = gather_queue(c, QM_LCNT_SLOW, nl, B, Q))) return rc;
-  c->lastSlowReads = nl;
+  c->stats.slowReads = nl;
   // the launch uses the scratch of the first one, so it stays within its grid; after a lean kernel, which has none, the scratch is reserved here
   const int g2 = qmk_map_grid_ex(nl, c->numCU, p.phc), g = g2 < p.grid ? g2 : p.grid;
   if (lean_first(p)) { if ((rc = gscr_for(c, g, Q.gslots, Q.ngslots))) return rc; Q.gscratch = c->d_gscr; }
@@ -1077,10 +1090,10 @@ static int run_list_kernels(qm_ctx* c, const StagePlan& p, const RunReq& rq, con
   int rc;
   // several reads per wavefront first (qm_selpack.inl); what that kernel cannot take -- hits on both strands, more than 64
   // intervals or suffixes -- it queues, and the one-read-per-wavefront kernel runs over the queue (its length stays on the device)
-  if ((rc = ensure(c->d_todoq, c->capTodoq, p.nreads))) return rc;
+  if ((rc = c->d_todoq.ensure(p.nreads))) return rc;
   // ... then the wide edition (256 lanes' worth per batch: reads of 150 bp and more) over that queue, which leaves one of its own.
   // A batch of reads beyond 192 characters goes to the wide edition directly: hardly any of them fits the narrow one's 64 lanes
-  if ((rc = ensure(c->d_todoq2, c->capTodoq2, p.nreads))) return rc;
+  if ((rc = c->d_todoq2.ensure(p.nreads))) return rc;
   static const int wideFrom = [] { const char* e = getenv("QM_SEL_WIDE_FROM"); return e ? atoi(e) : 192; }();   // (tuning knob)
   if (rq.shortLen > wideFrom) HIPCHK(qmk_h2m_packw(&ix, &H, nullptr, nullptr, c->d_todoq2, p.grid, c->numCU, c->stream));
   else {
@@ -1105,16 +1118,16 @@ static int pass_sel_slow(qm_ctx* c, const qm_opts* o, const RunReq& rq, const De
   int64_t waves = ns_ < 256 ? ns_ : 256;
   while (waves > 4 && (unsigned long long)waves * per > (8ULL << 30)) waves /= 2;      // at most 8 GB of scratch
   const int sgrid = (int)((waves + 3) / 4);
-  if ((rc = ensure(c->d_dynmem, c->capDynMem, (int64_t)((unsigned long long)sgrid * 4 * per)))) return rc;
+  if ((rc = c->d_dynmem.ensure((int64_t)((unsigned long long)sgrid * 4 * per)))) return rc;
   const size_t sb = qmk_sel_dyn_struct_bytes();
   std::vector<unsigned char> hd((size_t)sgrid * 4 * sb);
   for (int w = 0; w < sgrid * 4; ++w) qmk_sel_dyn_bind(hd.data() + (size_t)w * sb, c->d_dynmem + (unsigned long long)w * per, need);
-  if ((rc = ensure(c->d_dyn, c->capDyn, (int64_t)hd.size()))) return rc;
+  if ((rc = c->d_dyn.ensure((int64_t)hd.size()))) return rc;
   HIPCHK(hipMemcpyAsync(c->d_dyn, hd.data(), hd.size(), hipMemcpyHostToDevice, c->stream));
-  Q.dyn = (SelScratchDyn*)c->d_dyn; Q.iv_out = nullptr; Q.found_out = nullptr;   // (intervals and foundHit: already written by the first pass)
+  Q.dyn = (SelScratchDyn*)c->d_dyn.p; Q.iv_out = nullptr; Q.found_out = nullptr;   // (intervals and foundHit: already written by the first pass)
   HIPCHK(qmk_h2m(&ix, &Q, sgrid, c->numCU, c->stream));
   if ((rc = read_scalars(c, hscal))) return rc;           // (hd is a local: the copy above is done)
-  c->lastSlowReads = ns_;
+  c->stats.slowReads = ns_;
   return QM_OK;
 }
 
@@ -1129,15 +1142,15 @@ static int stage_verdict(qm_ctx* c, const StagePlan& p, const u64* hscal) {
   if (!(status & 17)) return QM_OK;
   if (status & 1) {
     int64_t want = (int64_t)hscal[0] + p.nreads + (int64_t)p.grid * 4 * QM_CHUNK;
-    if (want < c->capLists * 2) want = c->capLists * 2;
-    if ((rc = ensure(c->d_lists, c->capLists, want))) return rc;
+    if (want < c->d_lists.cap * 2) want = c->d_lists.cap * 2;
+    if ((rc = c->d_lists.ensure(want))) return rc;
   }
   if (status & 16) {
     int64_t want = (int64_t)hscal[QM_SC_IVCUR] + p.nreads + (int64_t)p.grid * 4 * QM_IVCHUNK;
-    if (want < c->capIv * 2) want = c->capIv * 2;
-    if ((rc = ensure(c->d_iv, c->capIv, want))) return rc;
+    if (want < c->d_iv.cap * 2) want = c->d_iv.cap * 2;
+    if ((rc = c->d_iv.ensure(want))) return rc;
   }
-  c->lastRelaunches += 1;
+  c->stats.relaunches += 1;
   return QM_STAGE_RETRY;
 }
 
@@ -1148,10 +1161,8 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   if ((rc = reserve_stage_a(c, o, rq, p))) return rc;
   const DevIndex ix = dev_index(c);
   const int64_t nreads = p.nreads;
-  c->lastRelaunches = 0; c->lastSlowReads = 0; c->lastIvTotal = 0; c->lastLeanReads = lean_first(p) ? nreads : -1; c->lastLeanDeferred = 0;
-  c->lastDuoPairs = p.first == SK_DUO ? n : -1; c->lastDuoMerged = 0;
-  for (int i = 0; i < 4; ++i) c->lastDefer[i] = 0;
-  c->lastNPass = 0;
+  if (lean_first(p)) c->stats.leanReads = nreads;
+  if (p.first == SK_DUO) c->stats.duoPairs = n;
   float extraMs = 0;                                     // the passes timed by themselves (read_scalars' timedMs), over all retries
   while (true) {
     ReadBatch B;
@@ -1166,7 +1177,7 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
     feeder = nullptr;                                     // a retry finds everything resident
     if (p.first == SK_LEAN_SEL && nreads > 0) {          // -s: what the lean collector left reaches the general one before the list kernels run
       if ((rc = read_scalars(c, hscal)) || (rc = pass_n_aware(c, p, ix, B, hscal, extraMs)) || (rc = pass_lean_leftovers(c, p, ix, B, hscal, extraMs))) return rc;
-      c->lastLeanReads = nreads;
+      c->stats.leanReads = nreads;
     }
     // fused -s with reads beyond QM_MAX_READ_LEN in the batch: the counts come down once more, so that the 32-slot collector has their intervals ready for the list kernels
     if (p.twoPass && rq.longReads && nreads > 0 && ((rc = read_scalars(c, hscal)) || (rc = pass_long_reads(c, p, ix, B, hscal, -32)))) return rc;
@@ -1194,37 +1205,31 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
     break;
   }
   // reads that were skipped, not mapped (beyond QM_MAX_LONG_READ_LEN characters; interval lists beyond the scratch): their list
-  c->lastSkipped = (int64_t)hscal[QM_SC_SKIPCNT]; c->skipList.clear();
-  if (c->lastSkipped > 0) {
-    c->skipList.resize((size_t)(c->lastSkipped < QM_SKIP_CAP ? c->lastSkipped : QM_SKIP_CAP));
-    HIPCHK(hipMemcpy(c->skipList.data(), c->d_skip, c->skipList.size() * sizeof(u64), hipMemcpyDeviceToHost));
+  c->stats.skipped = (int64_t)hscal[QM_SC_SKIPCNT];
+  if (c->stats.skipped > 0) {
+    c->stats.skipList.resize((size_t)(c->stats.skipped < QM_SKIP_CAP ? c->stats.skipped : QM_SKIP_CAP));
+    HIPCHK(hipMemcpy(c->stats.skipList.data(), c->d_skip, c->stats.skipList.size() * sizeof(u64), hipMemcpyDeviceToHost));
   }
-  c->lastIvTotal = p.wantIv ? (int64_t)hscal[QM_SC_IVCUR] : 0;
-  c->lastIvReads = p.wantIv ? nreads : -1;
-  c->lastFoundReads = p.wantFound ? nreads : -1;
-  c->lastListReads = (rq.mode != QM_RUN_COLLECT && !p.duoMerge) ? nreads : -1;   // (pairs the pair kernel merged have no per-read lists)
-  c->lastListWords = (int64_t)hscal[0];
-  float ms = 0; hipEventElapsedTime(&ms, c->ev0, c->ev1); c->lastMapMs = ms + extraMs;
+  if (p.wantIv) { c->last.ivTotal = (int64_t)hscal[QM_SC_IVCUR]; c->last.ivReads = nreads; }
+  if (p.wantFound) c->last.foundReads = nreads;
+  if (rq.mode != QM_RUN_COLLECT && !p.duoMerge) c->last.listReads = nreads;   // (pairs the pair kernel merged have no per-read lists)
+  c->last.listWords = (int64_t)hscal[0];
+  float ms = 0; hipEventElapsedTime(&ms, c->ev0, c->ev1); c->last.mapMs = ms + extraMs;
   return QM_OK;
 }
 
 // the temporary storage of the device scans (qmk_scan_counts) over `items` counts
 static int ensure_scan_tmp(qm_ctx* c, int64_t items) {
   const size_t stb = qmk_scan_temp_bytes(items);
-  if (stb <= c->scanTmpBytes && c->d_scanTmp) return QM_OK;
-  if (c->d_scanTmp) hipFree(c->d_scanTmp);
-  c->d_scanTmp = nullptr; c->scanTmpBytes = 0;
-  HIPCHK(hipMalloc(&c->d_scanTmp, stb ? stb : 16));
-  c->scanTmpBytes = stb;
-  return QM_OK;
+  return c->d_scanTmp.ensure((int64_t)(stb ? stb : 16));
 }
 
 // ---- stage B (+ C with -s): the per-read lists in d_lists -> the units' hits in CSR order.  One thread per unit: count -> scan -> write.
 static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n, bool paired, const void* d_seq1, const void* d_off1,
                        const void* d_seq2, const void* d_off2, u64* hscal, long long& total) {
   int rc;
-  if ((rc = ensure(c->d_cnt, c->capCnt, n + 1))) return rc;
-  if ((rc = ensure(c->d_offs, c->capOffs, n + 1))) return rc;
+  if ((rc = c->d_cnt.ensure(n + 1))) return rc;
+  if ((rc = c->d_offs.ensure(n + 1))) return rc;
   if ((rc = ensure_scan_tmp(c, n + 1))) return rc;
   PairBatch P; memset(&P, 0, sizeof(P));
   P.n = n; P.paired = paired ? 1 : 0; P.off1 = (const long long*)d_off1; P.off2 = (const long long*)d_off2;
@@ -1232,17 +1237,17 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   P.counters = c->d_scal + 1; P.max_num_hits = o->max_num_hits; P.no_orphans = rq.mergeOnly ? 0 : o->no_orphans;
   P.no_dovetail = rq.mergeOnly ? 0 : o->no_dovetail; P.fuzzy = o->fuzzy; P.merge_only = rq.mergeOnly ? 1 : 0;
   if (rq.mergeOnly) {
-    if ((rc = ensure(c->d_tooMany, c->capTooMany, n + 1))) return rc;
+    if ((rc = c->d_tooMany.ensure(n + 1))) return rc;
     HIPCHK(hipMemsetAsync(c->d_tooMany, 0, (size_t)(n + 1), c->stream));
     P.too_many = c->d_tooMany;
   }
-  c->lastTooManyUnits = rq.mergeOnly ? n : -1;
+  if (rq.mergeOnly) c->last.tooManyUnits = n;
   HIPCHK(hipMemsetAsync(c->d_cnt + n, 0, sizeof(uint32_t), c->stream));
   if (o->sel_aln) {
     // -s: merge + selective alignment + filter per unit into temp slots, then compaction (qm_sel.inl)
     HIPCHK(qmk_sel_slots(&P, c->stream));
-    HIPCHK(qmk_scan_counts(c->d_scanTmp, c->scanTmpBytes, c->d_cnt, c->d_offs, n + 1, c->stream));
-    if ((rc = ensure(c->d_toff, c->capToff, n + 1))) return rc;
+    HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_cnt, c->d_offs, n + 1, c->stream));
+    if ((rc = c->d_toff.ensure(n + 1))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_toff, c->d_offs, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, c->stream));
     long long slots = 0;
     HIPCHK(hipMemcpyAsync(&slots, c->d_offs + n, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
@@ -1255,16 +1260,16 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
     for (int i = 1; i < K; ++i) HIPCHK(hipMemcpyAsync(&cslot[i], c->d_offs + cu[i], sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     cslot[K] = slots;
-    if ((rc = ensure(c->d_tmp, c->capTmp, slots + 1))) return rc;
-    if ((rc = ensure(c->d_tsc, c->capTsc, 2 * slots + 2))) return rc;
+    if ((rc = c->d_tmp.ensure(slots + 1))) return rc;
+    if ((rc = c->d_tsc.ensure(2 * slots + 2))) return rc;
     SelBatch A; memset(&A, 0, sizeof(A));
-    A.seq1 = (const unsigned char*)d_seq1; A.seq2 = (const unsigned char*)d_seq2; A.text = c->d_text;
-    A.txp_off = c->d_txpOff; A.txp_len = c->d_txpLen; A.tmp = c->d_tmp; A.toff = c->d_toff; A.tsc = c->d_tsc;
+    A.seq1 = (const unsigned char*)d_seq1; A.seq2 = (const unsigned char*)d_seq2; A.text = c->rep->text;
+    A.txp_off = c->rep->txpOff; A.txp_len = c->rep->txpLen; A.tmp = c->d_tmp; A.toff = c->d_toff; A.tsc = c->d_tsc;
     A.match = o->match_score; A.mismatch = o->mismatch_penalty; A.gap_open = o->gap_open; A.gap_extend = o->gap_extend;
     A.long_reads = rq.longReads ? 1 : 0;
     if (rq.longReads && !rq.mergeOnly && sel_ksw_ring_slots(o->dp_bandwidth) > 128) {
       // reads beyond QM_MAX_READ_LEN under a band beyond 97: the alignment blocks of that (slow, rare) edition live in device memory
-      if ((rc = ensure(c->d_kswRows, c->capKswRows, (int64_t)qmk_sel_gmem_rows_bytes(c->numCU)))) return rc;
+      if ((rc = c->d_kswRows.ensure((int64_t)qmk_sel_gmem_rows_bytes(c->numCU)))) return rc;
       A.ksw_rows = c->d_kswRows;
     }
     A.short_len = rq.shortLen;
@@ -1275,10 +1280,10 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
       HIPCHK(qmk_sel_merge(&P, &A, c->stream));            // the merge alone: no alignment, chain statuses stay in aln_score
     } else {
       // plan (per unit) -> ksw2 extension alignments, four per wavefront, any band -> finish (per unit)
-      if ((rc = ensure(c->d_tref, c->capTref, 2 * slots + 2))) return rc;
-      if ((rc = ensure(c->d_tasks, c->capTasks, (2 * slots + 2 * K + 2) * (int64_t)qmk_sel_task_bytes()))) return rc;
-      if ((rc = ensure(c->d_sides, c->capSides, (2 * slots + 2 * K + 2) * (int64_t)qmk_sel_side_bytes()))) return rc;
-      if ((rc = ensure(c->d_torder, c->capTorder, 2 * (2 * slots + 2 * K + 2)))) return rc;      // (two order lists per chunk: ksw2, strip)
+      if ((rc = c->d_tref.ensure(2 * slots + 2))) return rc;
+      if ((rc = c->d_tasks.ensure((2 * slots + 2 * K + 2) * (int64_t)qmk_sel_task_bytes()))) return rc;
+      if ((rc = c->d_sides.ensure((2 * slots + 2 * K + 2) * (int64_t)qmk_sel_side_bytes()))) return rc;
+      if ((rc = c->d_torder.ensure(2 * (2 * slots + 2 * K + 2)))) return rc;      // (two order lists per chunk: ksw2, strip)
       static const bool noStrip = [] { const char* e = getenv("QM_SEL_NO_STRIP"); return e && atoi(e) != 0; }();
       A.tref = c->d_tref;
       HIPCHK(hipMemsetAsync(c->d_ntk, 0, 3 * QM_SEL_CHUNKS_B * sizeof(u64), c->stream));
@@ -1309,7 +1314,7 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   } else {
     HIPCHK(qmk_pair_count(&P, c->stream));
   }
-  HIPCHK(qmk_scan_counts(c->d_scanTmp, c->scanTmpBytes, c->d_cnt, c->d_offs, n + 1, c->stream));
+  HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_cnt, c->d_offs, n + 1, c->stream));
   total = 0;
   HIPCHK(hipMemcpyAsync(&total, c->d_offs + n, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -1317,19 +1322,17 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   const bool selStats = o->sel_aln && !rq.mergeOnly;
   if (selStats) HIPCHK(hipMemcpyAsync(h, c->d_ntk, sizeof(h), hipMemcpyDeviceToHost, c->stream));   // (with the synchronisation that follows anyway)
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->lastSelQuestions = 0; c->lastKswTasks = 0;
   if (selStats) {
-    c->lastStripTasks = 0;
-    for (int i = 0; i < QM_SEL_CHUNKS_B; ++i) { c->lastKswTasks += (int64_t)h[i]; c->lastSelQuestions += (int64_t)h[QM_SEL_CHUNKS_B + i]; c->lastStripTasks += (int64_t)h[2 * QM_SEL_CHUNKS_B + i]; }
+    for (int i = 0; i < QM_SEL_CHUNKS_B; ++i) { c->stats.kswTasks += (int64_t)h[i]; c->stats.selQuestions += (int64_t)h[QM_SEL_CHUNKS_B + i]; c->stats.stripTasks += (int64_t)h[2 * QM_SEL_CHUNKS_B + i]; }
     static const bool dbg = [] { const char* e = getenv("QM_SEL_DEBUG"); return e && atoi(e) != 0; }();
-    if (dbg) fprintf(stderr, "[qm -s] %lld units: %lld alignment questions beyond PERFECT chains, %lld ksw2 alignments, %lld strip alignments\n", (long long)n, (long long)c->lastSelQuestions, (long long)c->lastKswTasks, (long long)c->lastStripTasks);
+    if (dbg) fprintf(stderr, "[qm -s] %lld units: %lld alignment questions beyond PERFECT chains, %lld ksw2 alignments, %lld strip alignments\n", (long long)n, (long long)c->stats.selQuestions, (long long)c->stats.kswTasks, (long long)c->stats.stripTasks);
   }
   if (rq.join) {
     long long b = 0; qm_hit* dst = nullptr;
     if ((rc = rq.join->arrive(rq.part, total, b, dst))) return rc;
     P.hits = dst + b;
   } else {
-    if ((rc = ensure(c->d_hits, c->capHits, (int64_t)total + 1, total / 8))) return rc;
+    if ((rc = c->d_hits.ensure((int64_t)total + 1, total / 8))) return rc;
     P.hits = c->d_hits;
   }
   if (o->sel_aln) HIPCHK(qmk_sel_compact(&P, c->d_tmp, c->d_toff, c->stream));
@@ -1353,7 +1356,7 @@ static int map_device_impl(qm_ctx* c, const qm_opts* o, int64_t n, const void* d
   const int ns = pick <= 128 ? 2 : (pick <= 192 ? 3 : (pick <= 256 ? 4 : 8));
   const bool paired = d_seq2 != nullptr;
   u64 hscal[QM_SC_WORDS];
-  c->lastUnits = -1;
+  begin_call(c);
   HIPCHK(hipEventRecord(c->evA, c->stream));
   RunReq r2 = rq;
   r2.keepIntervals = rq.keepIntervals || c->debug != 0;
@@ -1363,43 +1366,39 @@ static int map_device_impl(qm_ctx* c, const qm_opts* o, int64_t n, const void* d
   rc = run_stage_a(c, o, r2, n, d_seq1, d_off1, d_seq2, d_off2, ns, feeder, hscal);
   if (rq.join) rq.join->pass_turn(rq.part);
   if (rc) return rc;
-  c->stReads = -1; c->stUnits = -1;
   if (r2.stageView) {
     // where every read's interval records and list words will sit in CSR order: two scans behind stage A; their totals come
     // down with the synchronisation stage B needs anyway
     const int64_t nreads = paired ? 2 * n : n;
-    if ((rc = ensure(c->d_ivcsr, c->capIvcsr, nreads + 1))) return rc;
-    if ((rc = ensure(c->d_lcsr, c->capLcsr, nreads + 1))) return rc;
-    if (!c->h_tot) HIPCHK(hipHostMalloc((void**)&c->h_tot, 2 * sizeof(long long), hipHostMallocDefault));
+    if ((rc = c->d_ivcsr.ensure(nreads + 1))) return rc;
+    if ((rc = c->d_lcsr.ensure(nreads + 1))) return rc;
+    if ((rc = c->h_tot.ensure(2))) return rc;
     if ((rc = ensure_scan_tmp(c, nreads + 1))) return rc;
     if (!r2.keepIntervals) {
       // a stage view without the SA-interval records (QM_STAGES_NO_INTERVALS): every read's count is zero
-      if ((rc = ensure(c->d_ivcnt, c->capIvCnt, nreads + 1))) return rc;
-      if ((rc = ensure(c->d_ivoff, c->capIvOff, nreads + 1))) return rc;
-      if ((rc = ensure(c->d_iv, c->capIv, 1))) return rc;
+      if ((rc = c->d_ivcnt.ensure(nreads + 1))) return rc;
+      if ((rc = c->d_ivoff.ensure(nreads + 1))) return rc;
+      if ((rc = c->d_iv.ensure(1))) return rc;
       HIPCHK(hipMemsetAsync(c->d_ivcnt, 0, (size_t)(nreads + 1) * sizeof(uint32_t), c->stream));
       HIPCHK(hipMemsetAsync(c->d_ivoff, 0, (size_t)(nreads + 1) * sizeof(long long), c->stream));
     }
     HIPCHK(hipMemsetAsync(c->d_ivcnt + nreads, 0, sizeof(uint32_t), c->stream));
     HIPCHK(hipMemsetAsync(c->d_lcnt + nreads, 0, sizeof(uint32_t), c->stream));
-    HIPCHK(qmk_scan_counts(c->d_scanTmp, c->scanTmpBytes, c->d_ivcnt, c->d_ivcsr, nreads + 1, c->stream));
-    HIPCHK(qmk_scan_counts_masked(c->d_scanTmp, c->scanTmpBytes, c->d_lcnt, c->d_lcsr, nreads + 1, c->stream));
+    HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_ivcnt, c->d_ivcsr, nreads + 1, c->stream));
+    HIPCHK(qmk_scan_counts_masked(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_lcnt, c->d_lcsr, nreads + 1, c->stream));
     HIPCHK(hipMemcpyAsync(&c->h_tot[0], c->d_ivcsr + nreads, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(&c->h_tot[1], c->d_lcsr + nreads, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    c->stReads = nreads;
+    c->last.stReads = nreads;
   }
   long long total = 0;
   if ((rc = run_stage_b(c, o, r2, n, paired, d_seq1, d_off1, d_seq2, d_off2, hscal, total))) return rc;
   HIPCHK(hipEventRecord(c->evB, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms = 0; hipEventElapsedTime(&ms, c->evA, c->evB); c->lastTotalMs = ms;
-  c->lastUnits = n; c->lastHits = total; c->lastPaired = paired;
-  if (r2.stageView) c->stUnits = n;
+  float ms = 0; hipEventElapsedTime(&ms, c->evA, c->evB); c->last.totalMs = ms;
+  c->last.units = n; c->last.hits = total; c->last.paired = paired;
+  if (r2.stageView) c->last.stUnits = n;
   if (n_hits) *n_hits = total;
-  if (counters) {
-    counters->pe_hits = hscal[1]; counters->se_hits = hscal[2]; counters->tot_hits = hscal[3];
-    counters->num_reads = hscal[4]; counters->too_many_hits = hscal[5]; counters->mapped = hscal[6];
-  }
+  if (counters) *counters = counters_from(hscal);
   return QM_OK;
 }
 
@@ -1408,7 +1407,7 @@ int SplitJoin::arrive(int part, long long tot, long long& b, qm_hit*& dst) {
   total[part] = tot;
   if (++arrived == K && !failed) {
     for (int i = 0; i < K; ++i) base[i + 1] = base[i] + total[i];
-    const int rc = ensure(owner->d_hits, owner->capHits, (int64_t)base[K] + 1, base[K] / 8);
+    const int rc = owner->d_hits.ensure((int64_t)base[K] + 1, base[K] / 8);
     if (rc) failed = rc; else ready = true;
     cv.notify_all();
   }
@@ -1433,7 +1432,7 @@ static int map_device_split(qm_ctx* c, const qm_opts* o, int K, int64_t n, const
     h->isHelper = true; c->helpers.push_back(h);
   }
   if (!c->pool || (int)c->pool->th.size() < K) { delete c->pool; c->pool = new SplitPool(K); }
-  if ((rc = ensure(c->d_offs, c->capOffs, n + 1))) return rc;
+  if ((rc = c->d_offs.ensure(n + 1))) return rc;
   SplitJoin J; J.owner = c; J.K = K;
   { const char* sg = getenv("QM_SPLIT_STAGGER"); J.stagger = sg ? atoi(sg) != 0 : false; }   // (measured: 73.6-75.4 against 76.4 M pairs/s with all parts started at once -- the kernels are all bound by instruction issue, whichever unit)
   int64_t nh[8] = {0}; qm_counters ctr[8]; int rcs[8] = {0}; char errs[8][256];
@@ -1445,7 +1444,7 @@ static int map_device_split(qm_ctx* c, const qm_opts* o, int K, int64_t n, const
   // of each kind in flight the two kinds of wavefront share every CU and each loads the unit the other leaves idle -- 492 M pairs/s
   // against 447 (all parts the pair kernel) and 473 (all parts qm_lean_kernel), profiles/r06/exp_mix.txt
   static const int duoParts = [] { const char* e = getenv("QM_DUO_PARTS"); return e ? atoi(e) : 0x55; }();   // default: every other part
-  c->lastUnits = -1;
+  begin_call(c);
   HIPCHK(hipEventRecord(c->evA, c->stream));
   c->pool->run(K, [&](int i) {
     qm_ctx* h = c->helpers[(size_t)i];
@@ -1475,31 +1474,16 @@ static int map_device_split(qm_ctx* c, const qm_opts* o, int K, int64_t n, const
     if (hipEventElapsedTime(&t, c->evA, h->ev0) == hipSuccess && t < first) first = t;
     if (hipEventElapsedTime(&t, c->evA, h->ev1) == hipSuccess && t > last) last = t;
   }
-  c->lastMapMs = last > first ? last - first : 0;
-  float ms = 0; hipEventElapsedTime(&ms, c->evA, c->evB); c->lastTotalMs = ms;
-  c->lastRelaunches = 0; c->lastSlowReads = 0; c->lastSkipped = 0; c->skipList.clear(); c->lastSelQuestions = 0; c->lastKswTasks = 0; c->lastStripTasks = 0;
-  c->lastDuoPairs = -1; c->lastDuoMerged = 0; c->lastLeanReads = -1; c->lastLeanDeferred = 0;
-  for (int i = 0; i < 4; ++i) c->lastDefer[i] = 0;
-  c->lastNPass = 0;
+  c->last.mapMs = last > first ? last - first : 0;
+  float ms = 0; hipEventElapsedTime(&ms, c->evA, c->evB); c->last.totalMs = ms;
   qm_counters sum; memset(&sum, 0, sizeof(sum));
   for (int i = 0; i < K; ++i) {
-    sum.pe_hits += ctr[i].pe_hits; sum.se_hits += ctr[i].se_hits; sum.tot_hits += ctr[i].tot_hits; sum.num_reads += ctr[i].num_reads;
-    sum.too_many_hits += ctr[i].too_many_hits; sum.mapped += ctr[i].mapped;
-    qm_ctx* h = c->helpers[(size_t)i];
-    if (h->lastLeanReads >= 0) { c->lastLeanReads = (c->lastLeanReads < 0 ? 0 : c->lastLeanReads) + h->lastLeanReads; c->lastLeanDeferred += h->lastLeanDeferred; }
-    if (h->lastDuoPairs >= 0) { c->lastDuoMerged += h->lastDuoMerged; }
-    for (int t = 0; t < 4; ++t) c->lastDefer[t] += h->lastDefer[t];
-    c->lastNPass += h->lastNPass;
-    c->lastRelaunches += h->lastRelaunches; c->lastSlowReads += h->lastSlowReads; c->lastSelQuestions += h->lastSelQuestions; c->lastKswTasks += h->lastKswTasks; c->lastStripTasks += h->lastStripTasks;
-    // the part's skipped reads, as reads of the whole batch
+    sum += ctr[i];
     int64_t u0 = n * i / K;
     if (K == 2 && firstPct > 0) u0 = i == 0 ? 0 : n * firstPct / 100;
-    c->lastSkipped += h->lastSkipped;
-    for (uint64_t e : h->skipList)
-      if (c->skipList.size() < QM_SKIP_CAP) c->skipList.push_back(((e & ((1ULL << 56) - 1)) + (uint64_t)(paired ? 2 * u0 : u0)) | (e & ~((1ULL << 56) - 1)));
+    c->stats.add_part(c->helpers[(size_t)i]->stats, paired ? 2 * u0 : u0);
   }
-  c->lastUnits = n; c->lastHits = J.base[K]; c->lastPaired = paired;
-  c->lastIvReads = -1; c->lastFoundReads = -1; c->lastListReads = -1; c->lastTooManyUnits = -1; c->stReads = -1; c->stUnits = -1;
+  c->last.units = n; c->last.hits = J.base[K]; c->last.paired = paired;
   if (n_hits) *n_hits = J.base[K];
   if (counters) *counters = sum;
   return QM_OK;
@@ -1524,8 +1508,8 @@ int qm_map_device(qm_ctx* c, const qm_opts* o, int64_t n, const void* d_seq1, co
 }
 
 // offsets of one mate: monotone, longest read; device copies of the offsets (copy stream) and room for the characters
-static int stage_offsets(qm_ctx* c, int64_t n, const int64_t* off, uint8_t*& d_seq, int64_t& capSeq, long long*& d_off, int64_t& capOff,
-                         int32_t& maxLen, int32_t& maxShort) {
+static int stage_offsets(qm_ctx* c, int64_t n, const int64_t* off, DevBuf<uint8_t>& d_seq, DevBuf<long long>& d_off, int32_t& maxLen,
+                         int32_t& maxShort) {
   for (int64_t i = 0; i < n; ++i) {
     int64_t l = off[i + 1] - off[i];
     if (l < 0) return fail(QM_E_ARG, "offsets not monotone");
@@ -1533,8 +1517,8 @@ static int stage_offsets(qm_ctx* c, int64_t n, const int64_t* off, uint8_t*& d_s
     if (l <= QM_MAX_READ_LEN && l > maxShort) maxShort = (int32_t)l;
   }
   int rc;
-  if ((rc = ensure(d_seq, capSeq, off[n] + 64))) return rc;
-  if ((rc = ensure(d_off, capOff, n + 1))) return rc;
+  if ((rc = d_seq.ensure(off[n] + 64))) return rc;
+  if ((rc = d_off.ensure(n + 1))) return rc;
   HIPCHK(hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->copyStream));
   return QM_OK;
 }
@@ -1561,8 +1545,8 @@ static int map_host(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq1, co
   static const int64_t zero = 0;
   if (n == 0) { off1 = &zero; if (seq2) off2 = &zero; }
   if ((rc = check_opts(o))) return rc;
-  if ((rc = stage_offsets(c, n, off1, c->d_seq1, c->capSeq1, c->d_off1, c->capOff1, maxLen, maxShort))) return rc;
-  if (seq2 && (rc = stage_offsets(c, n, off2, c->d_seq2, c->capSeq2, c->d_off2, c->capOff2, maxLen, maxShort))) return rc;
+  if ((rc = stage_offsets(c, n, off1, c->d_seq1, c->d_off1, maxLen, maxShort))) return rc;
+  if (seq2 && (rc = stage_offsets(c, n, off2, c->d_seq2, c->d_off2, maxLen, maxShort))) return rc;
   // the characters follow chunk by chunk, each chunk's kernel behind its own copy (ChunkFeeder); QM_HOST_CHUNK = units per chunk
   HostFeed hf = {c, seq1, off1, seq2, off2};
   const char* ce = getenv("QM_HOST_CHUNK");
@@ -1584,8 +1568,8 @@ int qm_map_reads(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq, const 
 }
 
 // 2-bit packed reads in, the ASCII image the kernels read built on the device (include/qmap_mi355.h)
-static int unpack_mate(qm_ctx* c, int64_t n, const uint8_t* pk, const int64_t* off, const qm_pack_exc* exc, int64_t nexc, uint8_t*& d_seq, int64_t& capSeq,
-                       long long*& d_off, int64_t& capOff, uint8_t*& d_pk, int64_t& capPk, qm_pack_exc*& d_exc, int64_t& capExc, int32_t& maxLen, int32_t& maxShort) {
+static int unpack_mate(qm_ctx* c, int64_t n, const uint8_t* pk, const int64_t* off, const qm_pack_exc* exc, int64_t nexc, DevBuf<uint8_t>& d_seq,
+                       DevBuf<long long>& d_off, DevBuf<uint8_t>& d_pk, DevBuf<qm_pack_exc>& d_exc, int32_t& maxLen, int32_t& maxShort) {
   int32_t mateMax = 0;
   for (int64_t i = 0; i < n; ++i) {
     const int64_t l = off[i + 1] - off[i];
@@ -1597,10 +1581,10 @@ static int unpack_mate(qm_ctx* c, int64_t n, const uint8_t* pk, const int64_t* o
   if (off[n] > 0xffffffffLL) return fail(QM_E_ARG, "more than 2^32 characters in one packed batch");
   int rc;
   const int64_t pkBytes = qm_packed_bytes(off, n);
-  if ((rc = ensure(d_seq, capSeq, off[n] + 64))) return rc;
-  if ((rc = ensure(d_off, capOff, n + 1))) return rc;
-  if ((rc = ensure(d_pk, capPk, pkBytes))) return rc;
-  if ((rc = ensure(d_exc, capExc, nexc + 1))) return rc;
+  if ((rc = d_seq.ensure(off[n] + 64))) return rc;
+  if ((rc = d_off.ensure(n + 1))) return rc;
+  if ((rc = d_pk.ensure(pkBytes))) return rc;
+  if ((rc = d_exc.ensure(nexc + 1))) return rc;
   HIPCHK(hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_pk, pk, (size_t)pkBytes - 8, hipMemcpyHostToDevice, c->stream));
   if (nexc > 0) HIPCHK(hipMemcpyAsync(d_exc, exc, (size_t)nexc * sizeof(qm_pack_exc), hipMemcpyHostToDevice, c->stream));
@@ -1619,8 +1603,8 @@ static int map_packed(qm_ctx* c, const qm_opts* o, int64_t n, const uint8_t* pk1
   static const uint8_t none[8] = {0};
   if (n == 0) { off1 = zero; pk1 = none; if (pk2) { off2 = zero; pk2 = none; } }
   int32_t maxLen = 0, maxShort = 0;
-  if ((rc = unpack_mate(c, n, pk1, off1, exc1, nexc1, c->d_seq1, c->capSeq1, c->d_off1, c->capOff1, c->d_pk1, c->capPk1, c->d_exc1, c->capExc1, maxLen, maxShort))) return rc;
-  if (pk2 && (rc = unpack_mate(c, n, pk2, off2, exc2, nexc2, c->d_seq2, c->capSeq2, c->d_off2, c->capOff2, c->d_pk2, c->capPk2, c->d_exc2, c->capExc2, maxLen, maxShort))) return rc;
+  if ((rc = unpack_mate(c, n, pk1, off1, exc1, nexc1, c->d_seq1, c->d_off1, c->d_pk1, c->d_exc1, maxLen, maxShort))) return rc;
+  if (pk2 && (rc = unpack_mate(c, n, pk2, off2, exc2, nexc2, c->d_seq2, c->d_off2, c->d_pk2, c->d_exc2, maxLen, maxShort))) return rc;
   rc = map_device_impl(c, o, n, c->d_seq1, c->d_off1, pk2 ? c->d_seq2 : nullptr, pk2 ? c->d_off2 : nullptr, maxLen, n_hits, counters, nullptr, rq, maxShort > 0 ? maxShort : 1);
   hipStreamSynchronize(c->stream);                         // nothing of the caller's buffers is in flight after return (error paths too)
   return rc;
@@ -1652,7 +1636,7 @@ static int staged_download(qm_ctx* c, void* dstv, const void* d_src, size_t byte
       // plain pageable hipMemcpy runs at ~9 GB/s.  Instead: DMA into two pinned staging buffers in turn at PCIe rate while
       // host threads copy the previous chunk into the caller's array, so the page faults are spread over several cores.
       const size_t CH = (size_t)32 << 20;
-      if (!c->h_stage) HIPCHK(hipHostMalloc((void**)&c->h_stage, 2 * CH, hipHostMallocDefault));
+      if (int rc = c->h_stage.ensure(2 * CH)) return rc;
       if (!c->evStage[0]) { HIPCHK(hipEventCreateWithFlags(&c->evStage[0], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->evStage[1], hipEventDisableTiming)); }
       const size_t nch = (bytes + CH - 1) / CH;
       auto drain = [&](size_t i) -> hipError_t {             // chunk i: staging -> caller's array, 8 threads
@@ -1682,37 +1666,37 @@ static int staged_download(qm_ctx* c, void* dstv, const void* d_src, size_t byte
 }
 
 int qm_fetch_hits(qm_ctx* c, int64_t* hit_offsets, qm_hit* hits) {
-  if (!c || c->lastUnits < 0) return fail(QM_E_STATE, "no mapping result to fetch");
+  if (!c || c->last.units < 0) return fail(QM_E_STATE, "no mapping result to fetch");
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  if (hit_offsets && (rc = staged_download(c, hit_offsets, c->d_offs, (size_t)(c->lastUnits + 1) * 8))) return rc;
-  if (hits && c->lastHits > 0 && (rc = staged_download(c, hits, c->d_hits, (size_t)c->lastHits * sizeof(qm_hit)))) return rc;
+  if (hit_offsets && (rc = staged_download(c, hit_offsets, c->d_offs, (size_t)(c->last.units + 1) * 8))) return rc;
+  if (hits && c->last.hits > 0 && (rc = staged_download(c, hits, c->d_hits, (size_t)c->last.hits * sizeof(qm_hit)))) return rc;
   return QM_OK;
 }
 
 int qm_fetch_hits_pinned(qm_ctx* c, int64_t* hit_offsets, qm_hit* hits) {
-  if (!c || c->lastUnits < 0) return fail(QM_E_STATE, "no mapping result to fetch");
+  if (!c || c->last.units < 0) return fail(QM_E_STATE, "no mapping result to fetch");
   HIPCHK(hipSetDevice(c->device));
-  if (hit_offsets) HIPCHK(hipMemcpyAsync(hit_offsets, c->d_offs, (size_t)(c->lastUnits + 1) * 8, hipMemcpyDeviceToHost, c->copyStream));
-  if (hits && c->lastHits > 0) HIPCHK(hipMemcpyAsync(hits, c->d_hits, (size_t)c->lastHits * sizeof(qm_hit), hipMemcpyDeviceToHost, c->copyStream));
+  if (hit_offsets) HIPCHK(hipMemcpyAsync(hit_offsets, c->d_offs, (size_t)(c->last.units + 1) * 8, hipMemcpyDeviceToHost, c->copyStream));
+  if (hits && c->last.hits > 0) HIPCHK(hipMemcpyAsync(hits, c->d_hits, (size_t)c->last.hits * sizeof(qm_hit), hipMemcpyDeviceToHost, c->copyStream));
   HIPCHK(hipStreamSynchronize(c->copyStream));
   return QM_OK;
 }
 
 int qm_result_device(qm_ctx* c, const void** d_hit_offsets, const void** d_hits) {
-  if (!c || c->lastUnits < 0) return fail(QM_E_STATE, "no mapping result");
+  if (!c || c->last.units < 0) return fail(QM_E_STATE, "no mapping result");
   if (d_hit_offsets) *d_hit_offsets = c->d_offs;
   if (d_hits) *d_hits = c->d_hits;
   return QM_OK;
 }
 
 int qm_fetch_intervals(qm_ctx* c, int64_t* int_offsets, qm_sa_interval_hit* ints, int64_t cap) {
-  if (!c || c->lastIvReads < 0) return fail(QM_E_STATE, "no SA-interval hits kept (qm_ctx_set_debug / qm_collect_reads / qm_map_pairs_stages before mapping)");
+  if (!c || c->last.ivReads < 0) return fail(QM_E_STATE, "no SA-interval hits kept (qm_ctx_set_debug / qm_collect_reads / qm_map_pairs_stages before mapping)");
   if (!int_offsets) return fail(QM_E_ARG, "null int_offsets");
   HIPCHK(hipSetDevice(c->device));
   // per unit: a pair's four lists (left fwd, left rc, right fwd, right rc) follow each other; a single read's two
-  const int64_t nreads = c->lastIvReads;
-  const int mates = (c->lastUnits >= 0 && c->lastPaired && c->lastIvReads == 2 * c->lastUnits) ? 2 : 1;
+  const int64_t nreads = c->last.ivReads;
+  const int mates = (c->last.units >= 0 && c->last.paired && c->last.ivReads == 2 * c->last.units) ? 2 : 1;
   const int64_t n = nreads / mates;
   std::vector<uint32_t> cnt((size_t)nreads + 1); std::vector<long long> off((size_t)nreads + 1);
   if (nreads) {
@@ -1729,7 +1713,7 @@ int qm_fetch_intervals(qm_ctx* c, int64_t* int_offsets, qm_sa_interval_hit* ints
   if (cap < int_offsets[n]) return fail(QM_E_ARG, "interval buffer too small");
   // the cursor of the chunked allocator may stand up to one chunk behind the buffer's end (a chunk is reserved whole, the
   // overflow check is per read): only what lies inside the allocation is copied -- every recorded interval does
-  const int64_t used = c->lastIvTotal < c->capIv ? c->lastIvTotal : c->capIv;
+  const int64_t used = c->last.ivTotal < c->d_iv.cap ? c->last.ivTotal : c->d_iv.cap;
   std::vector<qm_sa_interval_hit> all((size_t)used + 1);
   if (used) HIPCHK(hipMemcpy(all.data(), c->d_iv, (size_t)used * sizeof(qm_sa_interval_hit), hipMemcpyDeviceToHost));
   int64_t w = 0;
@@ -1758,13 +1742,13 @@ int qm_collect_reads(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq, co
   int32_t maxLen = 0;
   for (int64_t i = 0; i < n; ++i) { const int64_t l = off[i + 1] - off[i]; if (l < 0) return fail(QM_E_ARG, "offsets not monotone"); if (l > maxLen) maxLen = (int32_t)(l > 0x7fffffff ? 0x7fffffff : l); }
   if (maxLen > QM_MAX_LONG_READ_LEN) return fail(QM_E_TOOLONG, "read length %d > %d", maxLen, QM_MAX_LONG_READ_LEN);
-  if ((rc = ensure(c->d_seq1, c->capSeq1, off[n] + 64))) return rc;
-  if ((rc = ensure(c->d_off1, c->capOff1, n + 1))) return rc;
+  if ((rc = c->d_seq1.ensure(off[n] + 64))) return rc;
+  if ((rc = c->d_off1.ensure(n + 1))) return rc;
   if ((rc = upload(c, c->d_off1, off, (size_t)(n + 1) * 8))) return rc;
   if ((rc = upload(c, c->d_seq1, seq, (size_t)off[n]))) return rc;
   RunReq rq; rq.mode = QM_RUN_COLLECT;
   u64 hscal[QM_SC_WORDS];
-  c->lastUnits = -1;
+  begin_call(c);
   if ((rc = run_stage_a(c, o, rq, n, c->d_seq1, c->d_off1, nullptr, nullptr, 8, nullptr, hscal))) return rc;
   if (n_intervals) {
     std::vector<uint32_t> cnt((size_t)n + 1);
@@ -1776,10 +1760,10 @@ int qm_collect_reads(qm_ctx* c, const qm_opts* o, int64_t n, const char* seq, co
 }
 
 int qm_fetch_found(qm_ctx* c, uint8_t* found) {
-  if (!c || c->lastFoundReads < 0) return fail(QM_E_STATE, "no foundHit flags kept by the last call");
+  if (!c || c->last.foundReads < 0) return fail(QM_E_STATE, "no foundHit flags kept by the last call");
   if (!found) return fail(QM_E_ARG, "null buffer");
   HIPCHK(hipSetDevice(c->device));
-  if (c->lastFoundReads) HIPCHK(hipMemcpy(found, c->d_found, (size_t)c->lastFoundReads, hipMemcpyDeviceToHost));
+  if (c->last.foundReads) HIPCHK(hipMemcpy(found, c->d_found, (size_t)c->last.foundReads, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 
@@ -1803,15 +1787,15 @@ int qm_hits_to_mappings(qm_ctx* c, const qm_opts* o, int64_t n, const int32_t* r
     }
     if (nf > QM_ICAP + QM_IOVF || nr > QM_ICAP + QM_IOVF) return fail(QM_E_ARG, "read %lld: more than %d intervals on one strand", (long long)i, QM_ICAP + QM_IOVF);
   }
-  if ((rc = ensure(c->d_ivIn, c->capIvIn, ni + 1))) return rc;
-  if ((rc = ensure(c->d_ivInOff, c->capIvInOff, n + 1))) return rc;
-  if ((rc = ensure(c->d_lenIn, c->capLenIn, n + 1))) return rc;
+  if ((rc = c->d_ivIn.ensure(ni + 1))) return rc;
+  if ((rc = c->d_ivInOff.ensure(n + 1))) return rc;
+  if ((rc = c->d_lenIn.ensure(n + 1))) return rc;
   if ((rc = upload(c, c->d_ivIn, ints, (size_t)ni * sizeof(qm_sa_interval_hit)))) return rc;
   if ((rc = upload(c, c->d_ivInOff, int_offsets, (size_t)(n + 1) * 8))) return rc;
   if ((rc = upload(c, c->d_lenIn, read_len, (size_t)n * 4))) return rc;
   RunReq rq; rq.mode = QM_RUN_FROM_INTERVALS; rq.ivIn = c->d_ivIn; rq.ivInOff = c->d_ivInOff; rq.lenIn = c->d_lenIn;
   u64 hscal[QM_SC_WORDS];
-  c->lastUnits = -1;
+  begin_call(c);
   // the kernel walks the reads of one "mate"; seq/off are not touched in this mode (a non-null seq1 keeps the argument checks simple)
   if ((rc = run_stage_a(c, o, rq, n, c->d_lenIn, c->d_ivInOff, nullptr, nullptr, 4, nullptr, hscal))) return rc;
   if (n_words) {
@@ -1824,10 +1808,10 @@ int qm_hits_to_mappings(qm_ctx* c, const qm_opts* o, int64_t n, const int32_t* r
 }
 
 int qm_fetch_read_lists(qm_ctx* c, int64_t* list_offsets, uint64_t* words, int64_t cap) {
-  if (!c || c->lastListReads < 0) return fail(QM_E_STATE, "no per-read hit lists kept by the last call");
+  if (!c || c->last.listReads < 0) return fail(QM_E_STATE, "no per-read hit lists kept by the last call");
   if (!list_offsets) return fail(QM_E_ARG, "null list_offsets");
   HIPCHK(hipSetDevice(c->device));
-  const int64_t nreads = c->lastListReads;
+  const int64_t nreads = c->last.listReads;
   std::vector<uint32_t> cnt((size_t)nreads + 1); std::vector<long long> off((size_t)nreads + 1);
   if (nreads) {
     HIPCHK(hipMemcpy(cnt.data(), c->d_lcnt, (size_t)nreads * 4, hipMemcpyDeviceToHost));
@@ -1838,7 +1822,7 @@ int qm_fetch_read_lists(qm_ctx* c, int64_t* list_offsets, uint64_t* words, int64
   if (!words) return QM_OK;
   if (cap < list_offsets[nreads]) return fail(QM_E_ARG, "list buffer too small");
   // the lists sit in bump-allocated chunks: bring the used part of the buffer down once, gather on the host
-  const int64_t used = c->lastListWords < c->capLists ? c->lastListWords : c->capLists;
+  const int64_t used = c->last.listWords < c->d_lists.cap ? c->last.listWords : c->d_lists.cap;
   std::vector<uint64_t> all((size_t)used + 1);
   if (used) HIPCHK(hipMemcpy(all.data(), c->d_lists, (size_t)used * 8, hipMemcpyDeviceToHost));
   for (int64_t r = 0; r < nreads; ++r) {
@@ -1872,11 +1856,11 @@ int qm_merge_lists(qm_ctx* c, const qm_opts* o, int64_t n, const int64_t* loff_l
     off[(size_t)(2 * u)] = loff_left[u]; off[(size_t)(2 * u + 1)] = wl + loff_right[u];
     o1[(size_t)u + 1] = o1[(size_t)u] + len_left[u]; o2[(size_t)u + 1] = o2[(size_t)u] + len_right[u];
   }
-  if ((rc = ensure(c->d_lcnt, c->capLcnt, 2 * n + 1))) return rc;
-  if ((rc = ensure(c->d_loff, c->capLoff, 2 * n + 1))) return rc;
-  if (c->capLists < wl + wr + 1) { if ((rc = ensure(c->d_lists, c->capLists, wl + wr + 1))) return rc; }
-  if ((rc = ensure(c->d_off1, c->capOff1, n + 1))) return rc;
-  if ((rc = ensure(c->d_off2, c->capOff2, n + 1))) return rc;
+  if ((rc = c->d_lcnt.ensure(2 * n + 1))) return rc;
+  if ((rc = c->d_loff.ensure(2 * n + 1))) return rc;
+  if (c->d_lists.cap < wl + wr + 1) { if ((rc = c->d_lists.ensure(wl + wr + 1))) return rc; }
+  if ((rc = c->d_off1.ensure(n + 1))) return rc;
+  if ((rc = c->d_off2.ensure(n + 1))) return rc;
   if ((rc = upload(c, c->d_lcnt, cnt.data(), (size_t)(2 * n) * 4))) return rc;
   if ((rc = upload(c, c->d_loff, off.data(), (size_t)(2 * n) * 8))) return rc;
   if ((rc = upload(c, c->d_lists, words_left, (size_t)wl * 8))) return rc;
@@ -1886,23 +1870,20 @@ int qm_merge_lists(qm_ctx* c, const qm_opts* o, int64_t n, const int64_t* loff_l
   HIPCHK(hipMemsetAsync(c->d_scal, 0, QM_SC_WORDS * sizeof(u64), c->stream));
   RunReq rq; rq.mergeOnly = true;
   u64 hscal[QM_SC_WORDS]; long long total = 0;
-  c->lastUnits = -1; c->lastListReads = -1; c->lastIvReads = -1; c->lastFoundReads = -1;
+  begin_call(c);
   if ((rc = run_stage_b(c, o, rq, n, true, nullptr, c->d_off1, nullptr, c->d_off2, hscal, total))) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->lastUnits = n; c->lastHits = total; c->lastPaired = true; c->lastMapMs = 0; c->lastTotalMs = 0;
+  c->last.units = n; c->last.hits = total; c->last.paired = true;
   if (n_hits) *n_hits = total;
-  if (counters) {
-    counters->pe_hits = hscal[1]; counters->se_hits = hscal[2]; counters->tot_hits = hscal[3];
-    counters->num_reads = hscal[4]; counters->too_many_hits = hscal[5]; counters->mapped = hscal[6];
-  }
+  if (counters) *counters = counters_from(hscal);
   return QM_OK;
 }
 
 int qm_fetch_too_many(qm_ctx* c, uint8_t* too_many) {
-  if (!c || c->lastTooManyUnits < 0) return fail(QM_E_STATE, "no tooManyHits flags kept by the last call");
+  if (!c || c->last.tooManyUnits < 0) return fail(QM_E_STATE, "no tooManyHits flags kept by the last call");
   if (!too_many) return fail(QM_E_ARG, "null buffer");
   HIPCHK(hipSetDevice(c->device));
-  if (c->lastTooManyUnits) HIPCHK(hipMemcpy(too_many, c->d_tooMany, (size_t)c->lastTooManyUnits, hipMemcpyDeviceToHost));
+  if (c->last.tooManyUnits) HIPCHK(hipMemcpy(too_many, c->d_tooMany, (size_t)c->last.tooManyUnits, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 
@@ -1944,21 +1925,21 @@ StageLayout stage_layout(int64_t nreads, int64_t n, int64_t nIv, int64_t nWords,
 
 int qm_stage_bytes(qm_ctx* c, int64_t* bytes) {
   if (!c || !bytes) return fail(QM_E_ARG, "null argument");
-  if (c->stUnits < 0 || c->stReads < 0 || c->lastUnits != c->stUnits) return fail(QM_E_STATE, "qm_stage_bytes: the last call on this context was not qm_map_pairs_stages");
-  *bytes = (int64_t)stage_layout(c->stReads, c->stUnits, c->h_tot[0], c->h_tot[1], c->lastHits).total;
+  if (c->last.stUnits < 0 || c->last.stReads < 0 || c->last.units != c->last.stUnits) return fail(QM_E_STATE, "qm_stage_bytes: the last call on this context was not qm_map_pairs_stages");
+  *bytes = (int64_t)stage_layout(c->last.stReads, c->last.stUnits, c->h_tot[0], c->h_tot[1], c->last.hits).total;
   return QM_OK;
 }
 
 int qm_fetch_stages(qm_ctx* c, void* arena, int64_t arena_bytes, qm_stage_view* v) {
   if (!c || !arena || !v) return fail(QM_E_ARG, "null argument");
-  if (c->stUnits < 0 || c->stReads < 0 || c->lastUnits != c->stUnits) return fail(QM_E_STATE, "qm_fetch_stages: the last call on this context was not qm_map_pairs_stages");
+  if (c->last.stUnits < 0 || c->last.stReads < 0 || c->last.units != c->last.stUnits) return fail(QM_E_STATE, "qm_fetch_stages: the last call on this context was not qm_map_pairs_stages");
   HIPCHK(hipSetDevice(c->device));
-  const int64_t nreads = c->stReads, n = c->stUnits, nIv = c->h_tot[0], nWords = c->h_tot[1], nHits = c->lastHits;
+  const int64_t nreads = c->last.stReads, n = c->last.stUnits, nIv = c->h_tot[0], nWords = c->h_tot[1], nHits = c->last.hits;
   const StageLayout L = stage_layout(nreads, n, nIv, nWords, nHits);
   if ((int64_t)L.total > arena_bytes) return fail(QM_E_ARG, "qm_fetch_stages: arena of %lld bytes, %lld needed (qm_stage_bytes)", (long long)arena_bytes, (long long)L.total);
   int rc;
-  if ((rc = ensure(c->d_ivC, c->capIvC, nIv + 1, nIv / 4))) return rc;
-  if ((rc = ensure(c->d_wordsC, c->capWordsC, nWords + 1, nWords / 4))) return rc;
+  if ((rc = c->d_ivC.ensure(nIv + 1, nIv / 4))) return rc;
+  if ((rc = c->d_wordsC.ensure(nWords + 1, nWords / 4))) return rc;
   HIPCHK(qmk_stage_gather(nreads, c->d_ivcnt, c->d_ivoff, c->d_iv, c->d_ivcsr, c->d_ivC, c->d_lcnt, c->d_loff, (const unsigned long long*)c->d_lists, c->d_lcsr,
                           (unsigned long long*)c->d_wordsC, c->stream));
   unsigned char* A = (unsigned char*)arena;
@@ -1991,20 +1972,21 @@ void qm_pinned_free(void* p) { if (p) hipHostFree(p); }
 
 int qm_ctx_stat(const qm_ctx* c, int which, int64_t* value) {
   if (!c || !value) return fail(QM_E_ARG, "null argument");
+  const CallStats& s = c->stats;
   switch (which) {
-    case QM_STAT_RELAUNCHES: *value = c->lastRelaunches; break;
-    case QM_STAT_LIST_WORDS: *value = c->capLists; break;
-    case QM_STAT_SLOW_READS: *value = c->lastSlowReads; break;
-    case QM_STAT_LEAN_READS: *value = c->lastLeanReads; break;
-    case QM_STAT_LEAN_DEFERRED: *value = c->lastLeanDeferred; break;
-    case QM_STAT_SKIPPED_READS: *value = c->lastSkipped; break;
-    case QM_STAT_SEL_QUESTIONS: *value = c->lastSelQuestions; break;
-    case QM_STAT_KSW2_ALIGNMENTS: *value = c->lastKswTasks; break;
-    case QM_STAT_STRIP_ALIGNMENTS: *value = c->lastStripTasks; break;
-    case QM_STAT_PAIR_KERNEL_PAIRS: *value = c->lastDuoPairs; break;
-    case QM_STAT_PAIRS_MERGED: *value = c->lastDuoMerged; break;
-    case QM_STAT_N_PASS_READS: *value = c->lastNPass; break;
-    case QM_STAT_DEFER_DIRTY: case QM_STAT_DEFER_HOMOPOLYMER: case QM_STAT_DEFER_WIDE: case QM_STAT_DEFER_BOTH_STRANDS: *value = c->lastDefer[which - QM_STAT_DEFER_DIRTY]; break;
+    case QM_STAT_RELAUNCHES: *value = s.relaunches; break;
+    case QM_STAT_LIST_WORDS: *value = c->d_lists.cap; break;
+    case QM_STAT_SLOW_READS: *value = s.slowReads; break;
+    case QM_STAT_LEAN_READS: *value = s.leanReads; break;
+    case QM_STAT_LEAN_DEFERRED: *value = s.leanDeferred; break;
+    case QM_STAT_SKIPPED_READS: *value = s.skipped; break;
+    case QM_STAT_SEL_QUESTIONS: *value = s.selQuestions; break;
+    case QM_STAT_KSW2_ALIGNMENTS: *value = s.kswTasks; break;
+    case QM_STAT_STRIP_ALIGNMENTS: *value = s.stripTasks; break;
+    case QM_STAT_PAIR_KERNEL_PAIRS: *value = s.duoPairs; break;
+    case QM_STAT_PAIRS_MERGED: *value = s.duoMerged; break;
+    case QM_STAT_N_PASS_READS: *value = s.nPass; break;
+    case QM_STAT_DEFER_DIRTY: case QM_STAT_DEFER_HOMOPOLYMER: case QM_STAT_DEFER_WIDE: case QM_STAT_DEFER_BOTH_STRANDS: *value = s.defer[which - QM_STAT_DEFER_DIRTY]; break;
     default: return fail(QM_E_ARG, "unknown statistic %d", which);
   }
   return QM_OK;
@@ -2012,19 +1994,19 @@ int qm_ctx_stat(const qm_ctx* c, int which, int64_t* value) {
 
 int qm_fetch_skipped(const qm_ctx* c, int64_t* reads, int32_t* codes, int64_t cap, int64_t* total) {
   if (!c || !total) return fail(QM_E_ARG, "null argument");
-  *total = c->lastSkipped;
-  const int64_t n = (int64_t)c->skipList.size() < cap ? (int64_t)c->skipList.size() : cap;
+  *total = c->stats.skipped;
+  const int64_t n = (int64_t)c->stats.skipList.size() < cap ? (int64_t)c->stats.skipList.size() : cap;
   for (int64_t i = 0; i < n; ++i) {
-    if (reads) reads[i] = (int64_t)(c->skipList[(size_t)i] & ((1ULL << 56) - 1));
-    if (codes) codes[i] = (int32_t)(c->skipList[(size_t)i] >> 56);
+    if (reads) reads[i] = (int64_t)(c->stats.skipList[(size_t)i] & ((1ULL << 56) - 1));
+    if (codes) codes[i] = (int32_t)(c->stats.skipList[(size_t)i] >> 56);
   }
   return QM_OK;
 }
 
 int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
-  if (!c || c->lastUnits < 0) return fail(QM_E_STATE, "no mapping result");
-  if (map_ms) *map_ms = c->lastMapMs;
-  if (total_ms) *total_ms = c->lastTotalMs;
+  if (!c || c->last.units < 0) return fail(QM_E_STATE, "no mapping result");
+  if (map_ms) *map_ms = c->last.mapMs;
+  if (total_ms) *total_ms = c->last.totalMs;
   return QM_OK;
 }
 

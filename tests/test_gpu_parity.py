@@ -466,6 +466,46 @@ def test_device_resident_batch_in_parts(synth_medium, oracle_mod, monkeypatch):
     assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "in parts, single-end")
 
 
+def test_batch_in_parts_bookkeeping(synth_medium, monkeypatch):
+    """What a call mapped in parts reports besides its hits (map_device_split): the skipped reads of every part as reads of the
+    whole batch, the statistics summed over the parts (the pair kernel's pair count stays -1: qmap_mi355.h), with -s the
+    alignment statistics of the unsplit call.  Three reads beyond QM_MAX_LONG_READ_LEN, one in each of three parts, are skipped;
+    with max_read_len bounding them the call takes the general kernels (QM_STAT_LEAN_READS is -1, split or not), so the sum of
+    the parts' lean reads is checked on the same batch without them."""
+    import torch
+    import rapmap_amd as ra
+    ix, _ = load_oracle(synth_medium["idx"])
+    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    n = 3001
+    o = synth_medium["off"]
+    r1 = [synth_medium["seq1"][o[i]: o[i + 1]].tobytes() for i in range(n)]
+    r2 = [synth_medium["seq2"][o[i]: o[i + 1]].tobytes() for i in range(n)]
+    long1 = bytes(np.asarray(ix.text[:2100]).tobytes()).replace(b"$", b"A")      # beyond QM_MAX_LONG_READ_LEN: skipped, code 1
+    l1 = list(r1); l2 = list(r2)
+    l1[7] = long1; l2[1500] = long1; l1[2999] = long1                           # in the first, the middle and the last of three parts
+    pad = np.zeros(8, np.uint8)
+    monkeypatch.setenv("QM_SPLIT_MIN", "1000")
+    for m1, m2, max_len, skipped, lean in ((l1, l2, len(long1), [14, 3001, 5998], -1), (r1, r2, 100, [], 2 * n)):
+        (q1, o1), (q2, o2) = pack(m1), pack(m2)
+        d1 = torch.from_numpy(np.concatenate([q1, pad])).cuda(); d2 = torch.from_numpy(np.concatenate([q2, pad])).cuda()
+        do1 = torch.from_numpy(o1).cuda(); do2 = torch.from_numpy(o2).cuda()
+        torch.cuda.synchronize()
+        for go in ({}, {"sel_aln": 1}):
+            out = {}
+            for parts in ("1", "3"):
+                monkeypatch.setenv("QM_SPLIT", parts)
+                gr = mp.map_device(n, d1.data_ptr(), do1.data_ptr(), d2.data_ptr(), do2.data_ptr(), max_len, opts=ra.default_opts(**go), fetch=True)
+                tot, reads, codes = mp.skipped()
+                out[parts] = (gr, [mp.stat(i) for i in range(16)])
+                print(go, "max_read_len", max_len, "QM_SPLIT", parts, "skipped", tot, reads.tolist(), codes.tolist(), "stat", out[parts][1], gr.counters)
+                assert (tot, sorted(reads.tolist()), set(codes.tolist())) == (len(skipped), skipped, {1} if skipped else set()), (go, parts, tot, reads, codes)
+            (whole, wstat), (gr, stat) = out["1"], out["3"]
+            assert np.array_equal(gr.hit_offsets, whole.hit_offsets) and gr.hits.tobytes() == whole.hits.tobytes() and gr.counters == whole.counters, go
+            assert stat[5] == len(skipped) and stat[9] == -1 and stat[3] == lean, (go, stat)
+            if go:
+                assert stat[6:9] == wstat[6:9], (stat, wstat)
+
+
 def test_repeat_families(repeat_data, oracle_mod):
     """lists beyond a lane's private memory (wave fix-up), beyond LDS (global scratch), tooManyHits, maxInterval"""
     ix, orc = load_oracle(repeat_data["idx"])
