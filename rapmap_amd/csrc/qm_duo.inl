@@ -621,4 +621,31 @@ QM_DEV void duo_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, in
   }
 }
 
+// The wave body of qm_duo_kernel: wave gw of nw maps pairs gw, gw + nw, ... (lean_wave's pipeline, plus duo_prepare one pair ahead) and
+// adds the HitCounters of the pairs it merged to B.cursor[1 .. 6] (stage B's count pass adds the others').
+template <bool PH, bool COV>
+QM_DEV void duo_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, DuoMem& M) {
+  const int nit = (int)(B.nreads >> 1);                     // pairs (reads per launch < 2^31)
+  QM_LANES(l) { if (l < 16) M.pk[l >> 3][(l >> 2) & 1][4 + (l & 3)] = 0; }   // the words behind the images stay zero
+  WaveAlloc wa;
+  DuoCtr ctr = {0, 0, 0, 0, 0, 0};
+  duo_stage_offsets(B, gw, nit, M, 0);
+  lds_dma_wait();
+  duo_stage_chars(B, gw, nit, M, 0);
+  duo_stage_offsets(B, gw + nw, nit, M, 1);
+  lds_dma_wait();
+  int par = 0;
+  DuoNext N;
+  QM_LANES(l) { N.Lv[l] = 0; N.defv[l] = 0; N.ck[l] = 0; N.flg[l] = 0; }
+  duo_prepare<PH>(ix, B, gw, nit, nw, 0, M, N);             // (every later pair is prepared by the iteration before it)
+  for (int it = gw; it < nit; it += nw) {
+    duo_iter<PH, COV>(ix, B, it, nit, nw, par, M, wa, ctr, N);
+    par ^= 1;
+  }
+  QM_LANES(l) {
+    const u32 v = l == 0 ? ctr.pe : (l == 1 ? ctr.se : (l == 2 ? ctr.tot : (l == 3 ? ctr.reads : (l == 4 ? ctr.tooMany : ctr.mapped))));
+    if (l < 6 && v) atomic_add_u64(B.cursor + 1 + l, (u64)v);
+  }
+}
+
 }  // namespace qm

@@ -18,12 +18,8 @@
 
 namespace qm {
 
-template <bool ON> struct SelLds { SelScratchLds s; QM_DEV SelScratchLds* ptr() { return &s; } };
-template <> struct SelLds<false> { QM_DEV SelScratchLds* ptr() { return nullptr; } };
-
-// Stage entry "from intervals" (hit_manager::hitsToMappingsSimple as a call of its own, include/HitManager.hpp:130-135): one
-// wavefront per read, the read's SA-interval hits come from the caller instead of the collector.  F: 0 or QM_F_SEL.
-struct H2mMem { u64 buf[3][QM_CAP]; IntRec ints[2][QM_ICAP]; };        // 2 KB per wave: sort buffers + the first intervals of each strand
+// Stage entry "from intervals": one wavefront per read (h2m_wave, qm_mapper.inl).  F: 0 or QM_F_SEL.
+// QM_TIMING phases of this kernel (-s): 0 interval records in, 1 suffixes gathered, 2 sort, 3 groups + chaining, 4 list assembled, 6 write-out
 #ifndef QM_H2M_WPS
 #define QM_H2M_WPS 4       // waves per SIMD the list kernel is built for (its LDS -- 39 KB per block -- allows no more)
 #endif
@@ -33,105 +29,34 @@ __global__ __launch_bounds__(256, QM_H2M_WPS) void qm_h2m_kernel(DevIndex ix, Re
   __shared__ SelLds<(F & QM_F_SEL) != 0> sels[4];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const long long gw = (long long)blockIdx.x * 4 + wave;
-  const long long nw = (long long)gridDim.x * 4;
-  u64* gscr = B.gscratch + gw * QM_GSCR_U64;
-  WaveAlloc wa; wa.base = -1; wa.used = 0; wa.ivBase = -1; wa.ivUsed = 0;
-#ifdef QM_TIMING       // phases of this kernel (-s): 0 interval records in, 1 suffixes gathered, 2 sort, 3 groups + chaining, 4 list assembled, 6 write-out
-  if ((threadIdx.x & 63) == 0) { for (int i = 0; i < 9; ++i) qm_tim[wave][i] = 0; qm_tim[wave][9] = __builtin_readcyclecounter(); }
-#endif
-  long long nslots = B.nreads;
-  if (B.nreads_dev) { const long long q = (long long)uniform(*B.nreads_dev); nslots = q < nslots ? q : nslots; }
-  for (long long r = gw; r < nslots; r += nw) {
-    const long long read = read_id<F>(B, r);
-    H2mMem& M = mem[wave];
-    IntervalList fi, ri;
-    fi.lds = (QM_LDS(IntRec)*)M.ints[0]; ri.lds = (QM_LDS(IntRec)*)M.ints[1];
-    fi.ovf = (IntRec*)(gscr + 3 * QM_GCAP); ri.ovf = fi.ovf + QM_IOVF;
-    fi.n = 0; ri.n = 0; fi.pf = nullptr; ri.pf = nullptr; fi.pfcap = 0; ri.pfcap = 0;
-    long long i0, i1; int len, mate = 0;
-    if (B.iv_in_cnt) {                                  // second pass of a fused -s call: what the collector pass left for this read
-      i0 = uniform(B.iv_in_off[read]); i1 = i0 + (long long)uniform(B.iv_in_cnt[read]);
-      const unsigned char* src; const long long* off; long long unit;
-      read_src(B, read, src, off, unit);
-      len = (int)(uniform(off[unit + 1]) - uniform(off[unit]));
-      mate = B.seq2 ? (int)(read & 1) : 0;
-    } else {
-      i0 = uniform(B.iv_in_off[read]); i1 = uniform(B.iv_in_off[read + 1]);
-      len = uniform(B.len_in[read]);
-    }
-    // all of the read's records in one round of loads: lane l takes record base + l and files it behind the records of its
-    // strand that precede it (forward-strand records come first)
-    for (long long base = i0; base < i1; base += 64) {
-      LV<bool> isF, isR;
-      qm_sa_interval_hit h; h.begin = 0; h.end = 0; h.len = 0; h.query_pos = 0; h.query_rc = 0;
-      const bool have = base + (long long)(threadIdx.x & 63) < i1;
-      if (have) h = B.iv_in[base + (long long)(threadIdx.x & 63)];
-      isF.v[0] = have && h.query_rc == 0; isR.v[0] = have && h.query_rc != 0;
-      const u64 fm = ballot(isF), rm = ballot(isR);
-      if (have) {
-        const int l = (int)(threadIdx.x & 63);
-        const bool rc = h.query_rc != 0;
-        const int idx = rc ? ri.n + popc64(rm & lanemask_lt(l)) : fi.n + popc64(fm & lanemask_lt(l));
-        IntRec r; r.b = (u32)h.begin; r.e = (u32)h.end; r.len = h.len; r.q = h.query_pos;
-        IntervalList& L = rc ? ri : fi;
-        if (idx < QM_ICAP) { L.lds[idx].b = r.b; L.lds[idx].e = r.e; L.lds[idx].len = r.len; L.lds[idx].q = r.q; }
-        else L.ovf[idx - QM_ICAP] = r;
-      }
-      fi.n += popc64(fm); ri.n += popc64(rm);
-    }
-    wave_fence();
-    QM_T(0);
-    const bool found = B.found_in ? uniform((int)B.found_in[read]) != 0 : false;
-    finish_read<4, F>(ix, B, read, len, mate, found, M.buf, gscr, wa, fi, ri, (F & QM_F_SEL) ? B.selscr + gw : nullptr, sels[wave].ptr(),
-                      ((F & QM_F_SEL) && B.dyn) ? B.dyn + gw : nullptr);
-  }
-#ifdef QM_TIMING
-  if ((threadIdx.x & 63) == 0) for (int i = 0; i < 8; ++i) atomicAdd((unsigned long long*)&B.cursor[32 + i], (unsigned long long)qm_tim[wave][i]);
-#endif
+  qm_tim_begin(wave);
+  h2m_wave<F>(ix, B, gw, (long long)gridDim.x * 4, mem[wave], B.gscratch + gw * QM_GSCR_U64, (F & QM_F_SEL) ? B.selscr + gw : nullptr, sels[wave].ptr(),
+              ((F & QM_F_SEL) && B.dyn) ? B.dyn + gw : nullptr);
+  qm_tim_flush(B.cursor, wave, 32, 8);
 }
 
-// The list kernel of a fused -s call, several reads per wavefront (qm_selpack.inl): every wavefront owns a contiguous range of
+// The list kernel of a fused -s call, several reads per wavefront (pack_wave, qm_selpack.inl): every wavefront owns a contiguous range of
 // the reads and walks it in batches of as many reads as fit its 64 lanes; what it cannot take goes to `todoq` for qm_h2m_kernel.
+// QM_TIMING phases: 0 candidates + intervals, 1 suffix gather + keys, 2 rank sort, 3 heads + interval counting, 4 chaining, 5 words, 6 write-out
 #ifndef QM_PK_WPS
 #define QM_PK_WPS 6
 #endif
 __global__ __launch_bounds__(256, QM_PK_WPS) void qm_h2m_pack_kernel(DevIndex ix, ReadBatch B, long long* todoq) {
   __shared__ PackMem mem[4];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long gw = (long long)blockIdx.x * 4 + wave;
-  const long long nw = (long long)gridDim.x * 4;
-  const long long per = (B.nreads + nw - 1) / nw;
-  long long r = gw * per;
-  const long long rEnd = r + per < B.nreads ? r + per : B.nreads;
-  WaveAlloc wa; wa.base = -1; wa.used = 0; wa.ivBase = -1; wa.ivUsed = 0;
-#ifdef QM_TIMING       // phases: 0 candidates + intervals, 1 suffix gather + keys, 2 rank sort, 3 heads + interval counting, 4 chaining, 5 words, 6 write-out
-  if ((threadIdx.x & 63) == 0) { for (int i = 0; i < 9; ++i) qm_tim[wave][i] = 0; qm_tim[wave][9] = __builtin_readcyclecounter(); }
-#endif
-  while (r < rEnd) r += (long long)sel_pack_batch(ix, B, r, rEnd, mem[wave], wa, todoq);
-#ifdef QM_TIMING
-  if ((threadIdx.x & 63) == 0) for (int i = 0; i < 8; ++i) atomicAdd((unsigned long long*)&B.cursor[40 + i], (unsigned long long)qm_tim[wave][i]);
-#endif
+  qm_tim_begin(wave);
+  pack_wave(ix, B, (long long)blockIdx.x * 4 + wave, (long long)gridDim.x * 4, mem[wave], todoq);
+  qm_tim_flush(B.cursor, wave, 40, 8);
 }
 
 // ... and its wide edition (256 intervals / suffixes per batch) over the queue the narrow one leaves: reads of 150 bp and more
+// (QM_TIMING: the narrow kernel's slots -- [qm timing pack] of a batch of long reads is this kernel)
 __global__ __launch_bounds__(256, 2) void qm_h2m_packw_kernel(DevIndex ix, ReadBatch B, const long long* ids, const u64* nids, long long* todoq) {
   __shared__ PackMemW<4> mem[4];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long gw = (long long)blockIdx.x * 4 + wave;
-  const long long nw = (long long)gridDim.x * 4;
-  long long nq = B.nreads;
-  if (nids) { const long long d = (long long)uniform(*nids); nq = d < nq ? d : nq; }
-  const long long per = (nq + nw - 1) / nw;
-  long long q = gw * per;
-  const long long qEnd = q + per < nq ? q + per : nq;
-  WaveAlloc wa; wa.base = -1; wa.used = 0; wa.ivBase = -1; wa.ivUsed = 0;
-#ifdef QM_TIMING
-  if ((threadIdx.x & 63) == 0) { for (int i = 0; i < 9; ++i) qm_tim[wave][i] = 0; qm_tim[wave][9] = __builtin_readcyclecounter(); }
-#endif
-  while (q < qEnd) q += (long long)sel_pack_batch_wide<4>(ix, B, ids, q, qEnd, mem[wave], wa, todoq);
-#ifdef QM_TIMING       // (the narrow kernel's slots: [qm timing pack] of a batch of long reads is this kernel)
-  if ((threadIdx.x & 63) == 0) for (int i = 0; i < 8; ++i) atomicAdd((unsigned long long*)&B.cursor[40 + i], (unsigned long long)qm_tim[wave][i]);
-#endif
+  qm_tim_begin(wave);
+  packw_wave<4>(ix, B, ids, nids, (long long)blockIdx.x * 4 + wave, (long long)gridDim.x * 4, mem[wave], todoq);
+  qm_tim_flush(B.cursor, wave, 40, 8);
 }
 
 // stage B pass 1: hits per unit + the HitCounters

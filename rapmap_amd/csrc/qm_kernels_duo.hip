@@ -16,38 +16,7 @@ __global__ __launch_bounds__(256, 8) void qm_duo_kernel(DevIndex ix_, ReadBatch 
   const DevIndex& ix = args->ix; const ReadBatch& B = args->B;
   __shared__ __attribute__((aligned(16))) DuoMem mem[4];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int gw = (int)blockIdx.x * 4 + wave;
-  const int nw = (int)gridDim.x * 4;
-  const int nit = (int)(B.nreads >> 1);                     // pairs (reads per launch < 2^31)
-  DuoMem& M = mem[wave];
-  {                                                          // the words behind the images stay zero
-    const int l = (int)(threadIdx.x & 63);
-    if (l < 16) M.pk[l >> 3][(l >> 2) & 1][4 + (l & 3)] = 0;
-  }
-  WaveAlloc wa; wa.base = -1; wa.used = 0; wa.ivBase = -1; wa.ivUsed = 0;
-  DuoCtr ctr = {0, 0, 0, 0, 0, 0};
-  duo_stage_offsets(B, gw, nit, M, 0);
-  lds_dma_wait();
-  duo_stage_chars(B, gw, nit, M, 0);
-  duo_stage_offsets(B, gw + nw, nit, M, 1);
-  lds_dma_wait();
-  int par = 0;
-  DuoNext N;
-  {
-    const int l = (int)(threadIdx.x & 63);
-    N.Lv[l] = 0; N.defv[l] = 0; N.ck[l] = 0; N.flg[l] = 0;
-  }
-  duo_prepare<PH>(ix, B, gw, nit, nw, 0, M, N);             // (every later pair is prepared by the iteration before it)
-  for (int it = gw; it < nit; it += nw) {
-    duo_iter<PH, COV>(ix, B, it, nit, nw, par, M, wa, ctr, N);
-    par ^= 1;
-  }
-  // the HitCounters of the pairs this wave merged (stage B's count pass adds the others')
-  {
-    const int l = (int)(threadIdx.x & 63);
-    const u32 v = l == 0 ? ctr.pe : (l == 1 ? ctr.se : (l == 2 ? ctr.tot : (l == 3 ? ctr.reads : (l == 4 ? ctr.tooMany : ctr.mapped))));
-    if (l < 6 && v) atomicAdd((unsigned long long*)(B.cursor + 1 + l), (unsigned long long)v);
-  }
+  duo_wave<PH, COV>(ix, B, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, mem[wave]);
 }
 
 }  // namespace qm

@@ -988,4 +988,27 @@ QM_DEV void lean_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, i
   }
 }
 
+// The wave body of qm_lean_kernel: wave gw of nw maps iterations gw, gw + nw, ... with the software pipeline of the general kernel
+// (characters of the next iteration and offsets of the one after staged in LDS meanwhile).  The slab holds whatever it held.
+template <bool PAIRED, bool SEL, bool PH, bool WIDE = false, bool NQ = false>
+QM_DEV void lean_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, LeanMem& M) {
+  const int nit = WIDE ? (int)B.nreads : (int)((B.nreads + 1) >> 1);   // iterations: two reads each, one in the wide edition (reads per launch < 2^31)
+  QM_LANES(l) {                                              // the words behind the images stay zero
+    if (WIDE) { if (l < 16) (&M.pk[0][0][0])[16 * (l >> 3) + 8 + (l & 7)] = 0; }
+    else if (l < 16) M.pk[l >> 3][(l >> 2) & 1][4 + (l & 3)] = 0;
+    if (l < 5 * QM_LEAN_NMW) (&M.nm[0][0][0])[l] = 0;        // the N flags (and nmz behind them): lean_iter writes words 0-3 of a read with N's, the rest stays zero
+  }
+  WaveAlloc wa;
+  lean_stage_offsets<PAIRED, WIDE, NQ>(B, gw, nit, M, 0);
+  lds_dma_wait();
+  lean_stage_chars<PAIRED, WIDE, NQ>(B, gw, nit, M, 0);
+  lean_stage_offsets<PAIRED, WIDE, NQ>(B, gw + nw, nit, M, 1);
+  lds_dma_wait();
+  int par = 0;
+  for (int it = gw; it < nit; it += nw) {
+    lean_iter<PAIRED, SEL, PH, WIDE, NQ>(ix, B, it, nit, nw, par, M, wa);
+    par ^= 1;
+  }
+}
+
 }  // namespace qm

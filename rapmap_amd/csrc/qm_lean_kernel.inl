@@ -17,27 +17,7 @@ __global__ __launch_bounds__(256, 8) void qm_lean_kernel(DevIndex ix_, ReadBatch
   const DevIndex& ix = args->ix; const ReadBatch& B = args->B;
   __shared__ __attribute__((aligned(16))) LeanMem mem[4];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int gw = (int)blockIdx.x * 4 + wave;
-  const int nw = (int)gridDim.x * 4;
-  const int nit = WIDE ? (int)B.nreads : (int)((B.nreads + 1) >> 1);   // iterations: two reads each, one in the wide edition (reads per launch < 2^31)
-  LeanMem& M = mem[wave];
-  {                                                          // the words behind the images stay zero
-    const int l = (int)(threadIdx.x & 63);
-    if (WIDE) { if (l < 16) (&M.pk[0][0][0])[16 * (l >> 3) + 8 + (l & 7)] = 0; }
-    else if (l < 16) M.pk[l >> 3][(l >> 2) & 1][4 + (l & 3)] = 0;
-    if (l < 5 * QM_LEAN_NMW) (&M.nm[0][0][0])[l] = 0;        // the N flags (and nmz behind them): lean_iter writes words 0-3 of a read with N's, the rest stays zero
-  }
-  WaveAlloc wa; wa.base = -1; wa.used = 0; wa.ivBase = -1; wa.ivUsed = 0;
-  lean_stage_offsets<PAIRED, WIDE, NQ>(B, gw, nit, M, 0);
-  lds_dma_wait();
-  lean_stage_chars<PAIRED, WIDE, NQ>(B, gw, nit, M, 0);
-  lean_stage_offsets<PAIRED, WIDE, NQ>(B, gw + nw, nit, M, 1);
-  lds_dma_wait();
-  int par = 0;
-  for (int it = gw; it < nit; it += nw) {
-    lean_iter<PAIRED, SEL, PH, WIDE, NQ>(ix, B, it, nit, nw, par, M, wa);
-    par ^= 1;
-  }
+  lean_wave<PAIRED, SEL, PH, WIDE, NQ>(ix, B, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, mem[wave]);
 }
 
 }  // namespace qm

@@ -307,8 +307,17 @@ extern unsigned long long qm_prof[32];
 __shared__ u64 qm_tim[4][10];
 #define QM_T(id) do { u64 t_ = __builtin_readcyclecounter(); int w_ = (int)(threadIdx.x >> 6);                  \
     if ((threadIdx.x & 63) == 0) { qm_tim[w_][id] += t_ - qm_tim[w_][9]; qm_tim[w_][9] = t_; } } while (0)
+// the brackets a kernel puts around its wave body: clear the wave's sums and start its clock / add sums 0 .. n to cursor[first .. first + n)
+__device__ __forceinline__ void qm_tim_begin(int wave) {
+  if ((threadIdx.x & 63) == 0) { for (int i = 0; i < 9; ++i) qm_tim[wave][i] = 0; qm_tim[wave][9] = __builtin_readcyclecounter(); }
+}
+__device__ __forceinline__ void qm_tim_flush(u64* cursor, int wave, int first, int n) {
+  if ((threadIdx.x & 63) == 0) for (int i = 0; i < n; ++i) atomicAdd((unsigned long long*)&cursor[first + i], (unsigned long long)qm_tim[wave][i]);
+}
 #else
 #define QM_T(id) ((void)0)
+QM_DEV void qm_tim_begin(int) {}
+QM_DEV void qm_tim_flush(u64*, int, int, int) {}
 #endif
 #define QM_F_PH 1      // perfect-hash (-p) index
 #define QM_F_NIP 2     // --noSensitive: NIP skipping + k-mer vote
@@ -1805,7 +1814,7 @@ QM_DEV int sel_hits_to_mappings(const DevIndex& ix, const ReadBatch& B, const In
 
 // ------------------------------------------------------------------ stage A driver
 // One read: load -> collect -> hits->mappings -> list to global memory.
-struct WaveAlloc { long long base; int used; long long ivBase; int ivUsed; };   // the wave's current chunks of B.lists / B.iv_out (wave-uniform)
+struct WaveAlloc { long long base = -1; int used = 0; long long ivBase = -1; int ivUsed = 0; };   // the wave's current chunks of B.lists / B.iv_out (wave-uniform): none yet
 
 // Software pipeline of the persistent loop: the offsets of the read after next and the characters of the next read are
 // requested while the current read is processed, so the two dependent round trips that start a read (offsets ->
@@ -1998,6 +2007,90 @@ QM_DEV void map_read(const DevIndex& ix, const ReadBatch& B, long long read, lon
   if (B.found_out) { QM_LANES(l) { if (l == 0) B.found_out[read] = foundHit ? 1 : 0; } }
   if (F & QM_F_COLLECT) return;          // stage entry "collector only" (SACollector::operator() as a call of its own)
   finish_read<NS, F>(ix, B, read, len, mate, foundHit, M.buf, gscr, wa, fi, ri, ss, sl, dyn);
+}
+
+// ------------------------------------------------------------------ wave bodies
+// A wave body is everything one wavefront of a wave-per-read kernel does between "I know my slab and my index" (gw of nw waves) and
+// "I am done": its allocator, the pipeline's prologue, the persistent loop.  The __global__ function is one call of it; so is an
+// emulated wave (tests/emu), which therefore runs the prologues and loops the device runs, on a slab that holds garbage.
+
+// qm_read_kernel<NS, WPS, F>: reads gw, gw + nw, ... of the launch; the characters of the next read and the offsets of the one after
+// are staged in LDS while a read is mapped.  Reads per launch < 2^31: 32-bit slot arithmetic.
+template <int NS, int F>
+QM_DEV void read_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, WaveMem<NS>& M, u64* gscr, SelScratch* ss, struct SelScratchLds* sl,
+                      SelScratchDyn* dyn) {
+  const int nreads = (int)B.nreads;
+  WaveAlloc wa;
+  stage_offsets<NS, F>(B, gw, M, 0);
+  lds_dma_wait();
+  stage_chars<NS, F>(B, gw, M, 0);
+  stage_offsets<NS, F>(B, gw + nw, M, 1);
+  lds_dma_wait();
+  int par = 0;
+  for (int r = gw; r < nreads; r += nw) {
+    map_read<NS, F>(ix, B, read_id<F, NS>(B, r), r, nw, par, M, gscr, wa, ss, sl, dyn);
+    par ^= 1;
+  }
+}
+
+// qm_h2m_kernel<F>, the stage entry "from intervals" (hit_manager::hitsToMappingsSimple as a call of its own, include/HitManager.hpp:130-135):
+// one wavefront per read, the read's SA-interval hits come from the caller (or the collector pass of a fused -s call) instead of the
+// collector.  F: 0 or QM_F_SEL.
+struct H2mMem { u64 buf[3][QM_CAP]; IntRec ints[2][QM_ICAP]; };        // 2 KB per wave: sort buffers + the first intervals of each strand
+template <int F>
+QM_DEV void h2m_wave(const DevIndex& ix, const ReadBatch& B, long long gw, long long nw, H2mMem& M, u64* gscr, SelScratch* ss, struct SelScratchLds* sl,
+                     SelScratchDyn* dyn) {
+  WaveAlloc wa;
+  long long nslots = B.nreads;
+  if (B.nreads_dev) { const long long q = (long long)uniform(*B.nreads_dev); nslots = q < nslots ? q : nslots; }
+  for (long long r = gw; r < nslots; r += nw) {
+    const long long read = read_id<F>(B, r);
+    IntervalList fi, ri;
+    fi.lds = (QM_LDS(IntRec)*)M.ints[0]; ri.lds = (QM_LDS(IntRec)*)M.ints[1];
+    fi.ovf = (IntRec*)(gscr + 3 * QM_GCAP); ri.ovf = fi.ovf + QM_IOVF;
+    fi.n = 0; ri.n = 0; fi.pf = nullptr; ri.pf = nullptr; fi.pfcap = 0; ri.pfcap = 0;
+    long long i0, i1; int len, mate = 0;
+    if (B.iv_in_cnt) {                                  // second pass of a fused -s call: what the collector pass left for this read
+      i0 = uniform(B.iv_in_off[read]); i1 = i0 + (long long)uniform(B.iv_in_cnt[read]);
+      const unsigned char* src; const long long* off; long long unit;
+      read_src(B, read, src, off, unit);
+      len = (int)(uniform(off[unit + 1]) - uniform(off[unit]));
+      mate = B.seq2 ? (int)(read & 1) : 0;
+    } else {
+      i0 = uniform(B.iv_in_off[read]); i1 = uniform(B.iv_in_off[read + 1]);
+      len = uniform(B.len_in[read]);
+    }
+    // all of the read's records in one round of loads: lane l takes record base + l and files it behind the records of its
+    // strand that precede it (forward-strand records come first)
+    for (long long base = i0; base < i1; base += 64) {
+      LV<bool> isF, isR;
+      LV<qm_sa_interval_hit> hv;
+      QM_LANES(l) {
+        qm_sa_interval_hit h; h.begin = 0; h.end = 0; h.len = 0; h.query_pos = 0; h.query_rc = 0;
+        const bool have = base + (long long)l < i1;
+        if (have) h = B.iv_in[base + (long long)l];
+        isF[l] = have && h.query_rc == 0; isR[l] = have && h.query_rc != 0;
+        hv[l] = h;
+      }
+      const u64 fm = ballot(isF), rm = ballot(isR);
+      QM_LANES(l) {
+        if (base + (long long)l < i1) {
+          const qm_sa_interval_hit h = hv[l];
+          const bool rc = h.query_rc != 0;
+          const int idx = rc ? ri.n + popc64(rm & lanemask_lt(l)) : fi.n + popc64(fm & lanemask_lt(l));
+          IntRec rec; rec.b = (u32)h.begin; rec.e = (u32)h.end; rec.len = h.len; rec.q = h.query_pos;
+          IntervalList& L = rc ? ri : fi;
+          if (idx < QM_ICAP) { L.lds[idx].b = rec.b; L.lds[idx].e = rec.e; L.lds[idx].len = rec.len; L.lds[idx].q = rec.q; }
+          else L.ovf[idx - QM_ICAP] = rec;
+        }
+      }
+      fi.n += popc64(fm); ri.n += popc64(rm);
+    }
+    wave_fence();
+    QM_T(0);
+    const bool found = B.found_in ? uniform((int)B.found_in[read]) != 0 : false;
+    finish_read<4, F>(ix, B, read, len, mate, found, M.buf, gscr, wa, fi, ri, ss, sl, dyn);
+  }
 }
 
 // ------------------------------------------------------------------ stage B: one thread per unit

@@ -9,9 +9,6 @@
 
 namespace qm {
 
-template <bool ON> struct SelLds { SelScratchLds s; QM_DEV SelScratchLds* ptr() { return &s; } };
-template <> struct SelLds<false> { QM_DEV SelScratchLds* ptr() { return nullptr; } };
-
 // stage A: one wavefront per read.  WPS = minimum waves per SIMD the register allocator must leave room for.
 // F: compile-time feature flags (QM_F_PH, QM_F_NIP) -- the default kernel carries no optional code.
 // Waves per workgroup: four, except in the long-read kernels, whose per-wave LDS slab (41 KB at NS = 32) allows two.
@@ -38,7 +35,6 @@ __global__ __launch_bounds__(64 * WavesPerBlock<NS>::value, WPS) void qm_read_ke
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int gw = (int)blockIdx.x * WB + wave;            // reads per launch < 2^31: 32-bit slot arithmetic
   const int nw = (int)gridDim.x * WB;
-  const int nreads = (int)B.nreads;
   // the wave's 112 KB of device-memory scratch: its own by launch index, or -- a grid several times the resident one -- a slot taken
   // from the flags of the XCD the wave runs on (linear probing from a hashed start inside that eighth of the flags: at least twice as
   // many slots as an XCD's resident waves, so one is always free).  A slot only ever passes between waves of one XCD -- one L2 --, so
@@ -61,30 +57,14 @@ __global__ __launch_bounds__(64 * WavesPerBlock<NS>::value, WPS) void qm_read_ke
     if (gslot < 0) return;                                   // no slot: this wave maps nothing rather than write into scratch another wave holds
   }
   u64* gscr = B.gscratch + (long long)gslot * QM_GSCR_U64;
-  WaveAlloc wa; wa.base = -1; wa.used = 0; wa.ivBase = -1; wa.ivUsed = 0;
-#ifdef QM_TIMING
-  if ((threadIdx.x & 63) == 0) { for (int i = 0; i < 9; ++i) qm_tim[wave][i] = 0; qm_tim[wave][9] = __builtin_readcyclecounter(); }
-#endif
-  // reads gw, gw + nw, ...: characters of the next read and offsets of the one after are staged in LDS while a read is mapped
-  WaveMem<NS>& M = *reinterpret_cast<WaveMem<NS>*>(memraw + (unsigned)wave * STRIDE);
-  stage_offsets<NS, F>(B, gw, M, 0);
-  lds_dma_wait();
-  stage_chars<NS, F>(B, gw, M, 0);
-  stage_offsets<NS, F>(B, gw + nw, M, 1);
-  lds_dma_wait();
-  int par = 0;
-  for (int r = gw; r < nreads; r += nw) {
-    map_read<NS, F>(ix, B, read_id<F, NS>(B, r), r, nw, par, M, gscr, wa, (F & QM_F_SEL) ? B.selscr + gw : nullptr, sels[wave].ptr(),
-                    ((F & QM_F_SEL) && B.dyn) ? B.dyn + gw : nullptr);
-    par ^= 1;
-  }
+  qm_tim_begin(wave);
+  read_wave<NS, F>(ix, B, gw, nw, *reinterpret_cast<WaveMem<NS>*>(memraw + (unsigned)wave * STRIDE), gscr, (F & QM_F_SEL) ? B.selscr + gw : nullptr,
+                   sels[wave].ptr(), ((F & QM_F_SEL) && B.dyn) ? B.dyn + gw : nullptr);
   if (B.gslots) {
     __builtin_amdgcn_s_waitcnt(0);                           // (this wave's stores to the slot have reached the L2 before the next holder's can)
     if ((threadIdx.x & 63) == 0) __hip_atomic_store(&B.gslots[gslot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-#ifdef QM_TIMING
-  if ((threadIdx.x & 63) == 0) for (int i = 0; i < 7; ++i) atomicAdd((unsigned long long*)&B.cursor[20 + i], (unsigned long long)qm_tim[wave][i]);
-#endif
+  qm_tim_flush(B.cursor, wave, 20, 7);
 }
 
 

@@ -83,6 +83,9 @@ struct SelScratchLds {
   QM_LDS(u64)* out;                 // (typed: a plain pointer read back from this struct would be generic, its stores FLAT)
   QM_DEV SelGroup* grpp(int s) { return s == 0 ? grp0 : grp1; }
 };
+// a kernel's per-wave LDS edition of the scratch, or (ON false: the collector-only kernels, the plain list kernel) none
+template <bool ON> struct SelLds { SelScratchLds s; QM_DEV SelScratchLds* ptr() { return &s; } };
+template <> struct SelLds<false> { QM_DEV SelScratchLds* ptr() { return nullptr; } };
 QM_DEV const u64* sel_out(const SelScratch& S) { return S.out; }
 
 QM_DEV u64 sel_header(u32 tid, bool primaryRC, int cs, int nP) {

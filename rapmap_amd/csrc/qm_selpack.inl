@@ -525,6 +525,15 @@ QM_DEV int sel_chain_diag_mem(const SelRec* H, int hn, int maxDist, int* f, int*
   return nStarts;
 }
 
+// The wave body of qm_h2m_pack_kernel: wave gw of nw owns a contiguous nw-th of the reads and walks it in batches.
+QM_DEV void pack_wave(const DevIndex& ix, const ReadBatch& B, long long gw, long long nw, PackMem& M, long long* todoq) {
+  const long long per = (B.nreads + nw - 1) / nw;
+  long long r = gw * per;
+  const long long rEnd = r + per < B.nreads ? r + per : B.nreads;
+  WaveAlloc wa;
+  while (r < rEnd) r += (long long)sel_pack_batch(ix, B, r, rEnd, M, wa, todoq);
+}
+
 // ------------------------------------------------------------------ the wide edition: 64 * C intervals / suffixes per batch
 // Reads of 150 and 250 bp bring 45 .. 90 suffixes per strand (an interval every maxMMPExtension + 1 positions, a suffix per isoform in
 // each): they do not fit the 64 lanes above and went to the one-read kernel's device-memory scratch -- 725 ms per 4 M reads of 250 bp.
@@ -1003,4 +1012,18 @@ QM_DEV int sel_pack_batch_wide(const DevIndex& ix, const ReadBatch& B, const lon
   wave_fence();
   QM_T(6);
   return R;
+}
+
+// The wave body of qm_h2m_packw_kernel: wave gw of nw owns a contiguous nw-th of the queue ids[0 .. min(*nids, B.nreads)) -- the count stays
+// on the device; nids null: all B.nreads slots.
+template <int C>
+QM_DEV void packw_wave(const DevIndex& ix, const ReadBatch& B, const long long* ids, const u64* nids, long long gw, long long nw, PackMemW<C>& M,
+                       long long* todoq) {
+  long long nq = B.nreads;
+  if (nids) { const long long d = (long long)uniform(*nids); nq = d < nq ? d : nq; }
+  const long long per = (nq + nw - 1) / nw;
+  long long q = gw * per;
+  const long long qEnd = q + per < nq ? q + per : nq;
+  WaveAlloc wa;
+  while (q < qEnd) q += (long long)sel_pack_batch_wide<C>(ix, B, ids, q, qEnd, M, wa, todoq);
 }

@@ -14,7 +14,8 @@ _SRC = [os.path.join(_HERE, "qm_emu.cpp"),
         os.path.join(_HERE, "../../rapmap_amd/csrc/qm_wave.h"),
         os.path.join(_HERE, "../../rapmap_amd/csrc/qm_phflat.h"),
         os.path.join(_HERE, "../../rapmap_amd/csrc/qm_sel.inl"),
-        os.path.join(_HERE, "../../rapmap_amd/csrc/qm_selpack.inl")]
+        os.path.join(_HERE, "../../rapmap_amd/csrc/qm_selpack.inl"),
+        os.path.join(_HERE, "../../include/qmap_mi355.h")]
 
 HIT_DTYPE = np.dtype([
     ("tid", "<u4"), ("pos", "<i4"), ("mate_pos", "<i4"), ("frag_len", "<u4"),
@@ -108,10 +109,11 @@ class Emu:
         opts = opts or default_opts()
         nunits = len(off1) - 1
         pad = np.zeros(8, dtype=np.uint8)                        # reads are fetched four characters at a time
-        seq1 = np.concatenate([np.asarray(seq1, dtype=np.uint8), pad]); off1 = np.ascontiguousarray(off1, dtype=np.int64)
+        # (an offset more than the batch has: the empty "read" behind the last one, which the queue checks of qe_map name -- see its canary)
+        seq1 = np.concatenate([np.asarray(seq1, dtype=np.uint8), pad]); off1 = np.append(np.asarray(off1, dtype=np.int64), off1[-1])
         paired = seq2 is not None
         if paired:
-            seq2 = np.concatenate([np.asarray(seq2, dtype=np.uint8), pad]); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+            seq2 = np.concatenate([np.asarray(seq2, dtype=np.uint8), pad]); off2 = np.append(np.asarray(off2, dtype=np.int64), off2[-1])
         ho = np.zeros(nunits + 1, dtype=np.int64); io = np.zeros(nunits + 1, dtype=np.int64)
         ctr = np.zeros(6, dtype=np.uint64)
         hp = C.c_void_p(); ip = C.c_void_p(); st = C.c_int(0)

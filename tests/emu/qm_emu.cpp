@@ -3,6 +3,8 @@
 // 64-entry array and every QM_LANES block a loop: the kernel's source runs on the
 // CPU one wavefront at a time.  Used by tests/ (not gpu-marked) to check the wave
 // algorithm against the oracle without a GPU.  Never part of libqmap_mi355.so.
+// Every pass here is a loop over a kernel's wave body (read_wave, lean_wave, duo_wave, h2m_wave, pack_wave, packw_wave: what the
+// __global__ function calls once) with gw = 0 .. NW - 1 of NW waves, each on a slab filled with 0xA5.
 #define QM_EMU 1
 #ifdef QM_PROFILE
 namespace qm { unsigned long long qm_prof[32]; }
@@ -18,29 +20,57 @@ namespace qm { unsigned long long qm_prof[32]; }
 
 using namespace qm;
 
-// the N-aware pass of stage A (lean_iter<..., NQ>, qm_host.hip run_stage_a): the lean kernel once more over the queue of the reads its first pass
-// marked; what it maps is compared like everything else the lean kernel maps, what it marks again stays marked
-template <bool PAIRED, bool SEL>
-static void emu_n_pass(const qm::DevIndex& ix, qm::ReadBatch Lb, std::vector<long long>& q, u64* scal) {
-  using namespace qm;
-  if (q.empty()) return;
-  scal[QM_SC_LEANQ] = 0;
-  for (int i = 0; i < 4; ++i) scal[QM_SC_DEFER0 + i] = 0;
-  Lb.slowq = q.data(); Lb.nreads = (long long)q.size();
-  const long long nit = (Lb.nreads + 1) >> 1, NW = 3;
-  static LeanMem Ms[3];
-  for (long long w = 0; w < NW; ++w) {
-    LeanMem& M = Ms[w]; memset(&M, 0, sizeof(M));
-    WaveAlloc wl; wl.base = -1; wl.used = 0; wl.ivBase = -1; wl.ivUsed = 0;
-    lean_stage_offsets<PAIRED, false, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<PAIRED, false, true>(Lb, (int)w, (int)nit, M, 0);
-    lean_stage_offsets<PAIRED, false, true>(Lb, (int)(w + NW), (int)nit, M, 1);
-    int par = 0;
-    for (long long it = w; it < nit; it += NW) {
-      if (ix.ph) lean_iter<PAIRED, SEL, true, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl);
-      else lean_iter<PAIRED, SEL, false, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl);
-      par ^= 1;
-    }
+// A wave's LDS slab as a kernel finds it: whatever the LDS held before.  (One slab per type: the emulated waves run one after the other.)
+template <class T> static T& garbage_slab() { static T m; memset((void*)&m, 0xA5, sizeof(T)); return m; }
+
+// qm_read_kernel<NS, ., F> as NW = 3 waves.  slAlt: only every other wave gets the LDS edition of the -s scratch, so that both sizes are exercised
+struct ReadPass { const DevIndex& ix; const ReadBatch& B; u64* gscr; SelScratch* ss; SelScratchLds* sl; bool slAlt; SelScratchDyn* dyn; };
+template <int NS, int F> static void emu_read_waves(const ReadPass& p) {
+  const int NW = 3;
+  for (int w = 0; w < NW; ++w) read_wave<NS, F>(p.ix, p.B, w, NW, garbage_slab<WaveMem<NS>>(), p.gscr, p.ss, (p.slAlt && !(w & 1)) ? nullptr : p.sl, p.dyn);
+}
+template <int NS> static void emu_read_f(int F, const ReadPass& p) {
+  switch (F) {
+    case 0: emu_read_waves<NS, 0>(p); break; case 1: emu_read_waves<NS, 1>(p); break; case 2: emu_read_waves<NS, 2>(p); break; case 3: emu_read_waves<NS, 3>(p); break;
+    case 4: emu_read_waves<NS, 4>(p); break; case 5: emu_read_waves<NS, 5>(p); break; case 6: emu_read_waves<NS, 6>(p); break; default: emu_read_waves<NS, 7>(p); break;
   }
+}
+// the runtime (slot class, feature flags) of a launch -> its instantiation, as launch_reads_ns picks it (a slot class the library does not build: four)
+static void emu_read(int ns, int F, const ReadPass& p) {
+  switch (ns) {
+    case 2: emu_read_f<2>(F, p); break; case 3: emu_read_f<3>(F, p); break; case 8: emu_read_f<8>(F, p); break; case 32: emu_read_f<32>(F, p); break;
+    default: emu_read_f<4>(F, p); break;
+  }
+}
+
+// qm_lean_kernel<PAIRED, SEL, PH, WIDE, NQ> as three waves; the runtime flags -> the instantiation, as qmk_launch_lean picks it
+template <bool PAIRED, bool SEL, bool PH, bool WIDE, bool NQ> static void emu_lean_waves(const DevIndex& ix, const ReadBatch& B) {
+  const int NW = 3;
+  for (int w = 0; w < NW; ++w) lean_wave<PAIRED, SEL, PH, WIDE, NQ>(ix, B, w, NW, garbage_slab<LeanMem>());
+}
+template <bool WIDE, bool NQ> static void emu_lean(bool paired, bool sel, const DevIndex& ix, const ReadBatch& B) {
+  switch ((paired ? 4 : 0) | (sel ? 2 : 0) | (ix.ph ? 1 : 0)) {
+    case 0: emu_lean_waves<false, false, false, WIDE, NQ>(ix, B); break; case 1: emu_lean_waves<false, false, true, WIDE, NQ>(ix, B); break;
+    case 2: emu_lean_waves<false, true, false, WIDE, NQ>(ix, B); break;  case 3: emu_lean_waves<false, true, true, WIDE, NQ>(ix, B); break;
+    case 4: emu_lean_waves<true, false, false, WIDE, NQ>(ix, B); break;  case 5: emu_lean_waves<true, false, true, WIDE, NQ>(ix, B); break;
+    case 6: emu_lean_waves<true, true, false, WIDE, NQ>(ix, B); break;   default: emu_lean_waves<true, true, true, WIDE, NQ>(ix, B); break;
+  }
+}
+// the lean kernel over a batch and (the narrow edition) its N-aware pass over the queue of the reads the first pass marked (qm_host.hip, run_stage_a):
+// what that pass maps is compared like everything else the lean kernel maps, what it marks again stays marked
+static void emu_lean_passes(bool paired, bool sel, bool wide, const DevIndex& ix, ReadBatch Lb, const std::vector<u32>& lcnt2, u64* scal, const char* what) {
+  if (wide) { emu_lean<true, false>(paired, sel, ix, Lb); return; }
+  emu_lean<false, false>(paired, sel, ix, Lb);
+  if (getenv("QM_EMU_NO_NPASS")) return;
+  std::vector<long long> q;
+  for (long long r = 0; r < Lb.nreads; ++r) if (lcnt2[r] == QM_LCNT_LEAN) q.push_back(r);
+  if (!q.empty()) {
+    scal[QM_SC_LEANQ] = 0;
+    for (int i = 0; i < 4; ++i) scal[QM_SC_DEFER0 + i] = 0;
+    Lb.slowq = q.data(); Lb.nreads = (long long)q.size();
+    emu_lean<false, true>(paired, sel, ix, Lb);
+  }
+  if (getenv("QM_EMU_LEAN_STATS")) fprintf(stderr, "[qm emu] N-aware pass%s over %zu reads, %llu marked again\n", what, q.size(), (unsigned long long)scal[QM_SC_LEANQ]);
 }
 
 extern "C" {
@@ -112,117 +142,56 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
   while (true) {
     lists.assign((size_t)cap, 0);
     B.lists = lists.data(); B.lists_cap = cap; memset(scal, 0, sizeof(scal)); status = 0;
-    // emulate 7 interleaved "waves", each with its own chunk allocator
-    WaveAlloc wa[7];
-    for (auto& w : wa) { w.base = -1; w.used = 0; w.ivBase = -1; w.ivUsed = 0; }
-    {
-      // the persistent loop of qm_read_kernel with three "waves": wave w maps slots w, w + 3, ... with the kernel's own software
-      // pipeline (characters of the next read and offsets of the one after staged while a read is mapped), so that what rides on
-      // it -- the first-probe prefetch for the wave's next read -- runs here as it does on the device
-      const int F = (ix.ph ? QM_F_PH : 0) | (B.sensitive ? 0 : QM_F_NIP) | (o->sel_aln ? QM_F_SEL : 0);
-#define QE_CALL(NS_, F_) { const long long NW = 3; static WaveMem<NS_> Ms[3];                                                  \
-        for (long long w = 0; w < NW; ++w) { WaveMem<NS_>& M = Ms[w];                                              \
-          stage_offsets<NS_, F_>(B, w, M, 0); stage_chars<NS_, F_>(B, w, M, 0); stage_offsets<NS_, F_>(B, w + NW, M, 1);          \
-          int par = 0;                                                                                                             \
-          for (long long r = w; r < nreads; r += NW) {                                                                             \
-            map_read<NS_, F_>(ix, B, r, r, NW, par, M, gs.data(), wa[r % 7], selscr, (r & 2) ? &sellds : nullptr); par ^= 1; } } }
-      if (ns == 2) { switch (F) { case 0: QE_CALL(2, 0) break; case 1: QE_CALL(2, 1) break; case 2: QE_CALL(2, 2) break; case 3: QE_CALL(2, 3) break;
-                                  case 4: QE_CALL(2, 4) break; case 5: QE_CALL(2, 5) break; case 6: QE_CALL(2, 6) break; default: QE_CALL(2, 7) break; } }
-      else if (ns == 3) { switch (F) { case 0: QE_CALL(3, 0) break; case 1: QE_CALL(3, 1) break; case 2: QE_CALL(3, 2) break; case 3: QE_CALL(3, 3) break;
-                                       case 4: QE_CALL(3, 4) break; case 5: QE_CALL(3, 5) break; case 6: QE_CALL(3, 6) break; default: QE_CALL(3, 7) break; } }
-      else if (ns == 8) { switch (F) { case 0: QE_CALL(8, 0) break; case 1: QE_CALL(8, 1) break; case 2: QE_CALL(8, 2) break; case 3: QE_CALL(8, 3) break;
-                                       case 4: QE_CALL(8, 4) break; case 5: QE_CALL(8, 5) break; case 6: QE_CALL(8, 6) break; default: QE_CALL(8, 7) break; } }
-      else { switch (F) { case 0: QE_CALL(4, 0) break; case 1: QE_CALL(4, 1) break; case 2: QE_CALL(4, 2) break; case 3: QE_CALL(4, 3) break;
-                          case 4: QE_CALL(4, 4) break; case 5: QE_CALL(4, 5) break; case 6: QE_CALL(4, 6) break; default: QE_CALL(4, 7) break; } }
-#undef QE_CALL
-    }
-    if (!o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & 1)) {
-      // the long-read pass (pass_long_reads in qm_host.hip): reads beyond the slot count of the first pass again, on the 32-slot kernels
-      std::vector<long long> q;
-      for (long long r = 0; r < nreads; ++r) if (lcnt[r] == QM_LCNT_SLOW) q.push_back(r);
-      ReadBatch S2 = B; S2.slowq = q.data(); S2.nreads = (long long)q.size();
-      {                                                   // (a read beyond QM_MAX_LONG_READ_LEN is skipped by that pass: empty result, scalar slot QM_SC_SKIPCNT)
-        const int F = (ix.ph ? QM_F_PH : 0) | (B.sensitive ? 0 : QM_F_NIP);
-        for (long long r = 0; r < (long long)q.size(); ++r) {
-#define QE_LONG(F_) { static WaveMem<32> M; stage_offsets<32, F_>(S2, r, M, 0); stage_chars<32, F_>(S2, r, M, 0); \
-                      map_read<32, F_>(ix, S2, read_id<F_, 32>(S2, r), r, S2.nreads, 0, M, gs.data(), wa[r % 7]); }
-          switch (F) { case 0: QE_LONG(0) break; case 1: QE_LONG(1) break; case 2: QE_LONG(2) break; default: QE_LONG(3) break; }
-#undef QE_LONG
-        }
-      }
-    }
+    const int F0 = (ix.ph ? QM_F_PH : 0) | (B.sensitive ? 0 : QM_F_NIP);
+    // qm_read_kernel (-s: the fused edition, collector and list kernel in one) over the batch
+    emu_read(ns, F0 | (o->sel_aln ? QM_F_SEL : 0), ReadPass{ix, B, gs.data(), selscr, &sellds, true, nullptr});
     auto rawLen = [&](long long r) -> long long {
       const unsigned char* src; const long long* off; long long unit; read_src(B, r, src, off, unit);
       return off[unit + 1] - off[unit];
     };
-    if (o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & 1)) {
-      // -s, reads beyond the slot class (the device, pass_long_reads before the list kernels: the 32-slot chain-scoring collector, then the list kernel; here the fused
-      // 32-slot kernel).  A read whose intervals overflow the scratch is queued again, for the slow pass below.
+    // a pass over a queue of the reads that carry `mark` (gather_queue in qm_host.hip); longOnes: only those beyond / within the slot class
+    auto queue_pass = [&](int nsq, int F, int longOnes, SelScratchLds* sl, SelScratchDyn* dyn, bool ivOut) {
       std::vector<long long> q;
-      for (long long r = 0; r < nreads; ++r) if (lcnt[r] == QM_LCNT_SLOW && rawLen(r) > 64 * ns) q.push_back(r);
-      if (!q.empty()) {
-        ReadBatch S2 = B; S2.slowq = q.data(); S2.nreads = (long long)q.size();
-        const int F = (ix.ph ? QM_F_PH : 0) | (B.sensitive ? 0 : QM_F_NIP) | QM_F_SEL;
-        for (long long r = 0; r < (long long)q.size(); ++r) {
-#define QE_LONGS(F_) { static WaveMem<32> M; stage_offsets<32, F_>(S2, r, M, 0); stage_chars<32, F_>(S2, r, M, 0); \
-                       map_read<32, F_>(ix, S2, read_id<F_, 32>(S2, r), r, S2.nreads, 0, M, gs.data(), wa[r % 7], selscr, nullptr); }
-          switch (F) { case 4: QE_LONGS(4) break; case 5: QE_LONGS(5) break; case 6: QE_LONGS(6) break; default: QE_LONGS(7) break; }
-#undef QE_LONGS
-        }
-      }
-    }
+      for (long long r = 0; r < nreads; ++r) if (lcnt[r] == QM_LCNT_SLOW && (longOnes < 0 || (rawLen(r) > 64 * ns) == (longOnes != 0))) q.push_back(r);
+      if (q.empty()) return;
+      ReadBatch S2 = B; S2.slowq = q.data(); S2.nreads = (long long)q.size(); S2.dyn = dyn;
+      if (!ivOut) S2.iv_out = nullptr;
+      emu_read(nsq, F, ReadPass{ix, S2, gs.data(), selscr, sl, false, dyn});
+    };
+    // the long-read pass (pass_long_reads in qm_host.hip): reads beyond the slot count of the first pass again, on the 32-slot kernels
+    // (a read beyond QM_MAX_LONG_READ_LEN is skipped by that pass: empty result, scalar slot QM_SC_SKIPCNT)
+    if (!o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & 1)) queue_pass(32, F0, -1, nullptr, nullptr, true);
+    // -s, reads beyond the slot class (the device, pass_long_reads before the list kernels: the 32-slot chain-scoring collector, then the list kernel; here the fused
+    // 32-slot kernel).  A read whose intervals overflow the scratch is queued again, for the slow pass below.
+    if (o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & 1)) queue_pass(32, F0 | QM_F_SEL, 1, nullptr, nullptr, true);
     if (o->sel_aln && scal[QM_SC_SLOWCNT] > 0 && !(status & (1 | 4))) {
       // the slow pass of -s (pass_sel_slow in qm_host.hip): the queued reads again, on scratch sized for the largest of them
       const long long need = (((long long)scal[QM_SC_SLOWMAX] + 63) / 64) * 64 + 64;
       std::vector<unsigned char> dmem((size_t)SelScratchDyn::bytes_for(need));
       SelScratchDyn dyn; dyn.bind(dmem.data(), need);
-      std::vector<long long> q;
-      for (long long r = 0; r < nreads; ++r) if (lcnt[r] == QM_LCNT_SLOW) q.push_back(r);
-      ReadBatch S2 = B; S2.slowq = q.data(); S2.dyn = &dyn; S2.nreads = (long long)q.size(); S2.iv_out = nullptr;
-      const int F = (ix.ph ? QM_F_PH : 0) | (B.sensitive ? 0 : QM_F_NIP) | QM_F_SEL;
-      for (long long r = 0; r < (long long)q.size(); ++r) {
-#define QE_SLOW(NS_, F_) { static WaveMem<NS_> M; stage_offsets<NS_, F_>(S2, r, M, 0); stage_chars<NS_, F_>(S2, r, M, 0); \
-                           map_read<NS_, F_>(ix, S2, read_id<F_>(S2, r), r, S2.nreads, 0, M, gs.data(), wa[r % 7], selscr, &sellds, &dyn); }
-#define QE_SLOWL(F_) { static WaveMem<32> M; stage_offsets<32, F_>(S2, r, M, 0); stage_chars<32, F_>(S2, r, M, 0); \
-                       map_read<32, F_>(ix, S2, read_id<F_, 32>(S2, r), r, S2.nreads, 0, M, gs.data(), wa[r % 7], selscr, &sellds, &dyn); }
-        if (rawLen(q[(size_t)r]) > 64 * ns) { switch (F) { case 4: QE_SLOWL(4) break; case 5: QE_SLOWL(5) break; case 6: QE_SLOWL(6) break; default: QE_SLOWL(7) break; } }
-        else
-        if (ns == 2) { switch (F) { case 4: QE_SLOW(2, 4) break; case 5: QE_SLOW(2, 5) break; case 6: QE_SLOW(2, 6) break; default: QE_SLOW(2, 7) break; } }
-        else if (ns == 3) { switch (F) { case 4: QE_SLOW(3, 4) break; case 5: QE_SLOW(3, 5) break; case 6: QE_SLOW(3, 6) break; default: QE_SLOW(3, 7) break; } }
-        else if (ns == 8) { switch (F) { case 4: QE_SLOW(8, 4) break; case 5: QE_SLOW(8, 5) break; case 6: QE_SLOW(8, 6) break; default: QE_SLOW(8, 7) break; } }
-        else { switch (F) { case 4: QE_SLOW(4, 4) break; case 5: QE_SLOW(4, 5) break; case 6: QE_SLOW(4, 6) break; default: QE_SLOW(4, 7) break; } }
-#undef QE_SLOW
-#undef QE_SLOWL
-      }
+      queue_pass(32, F0 | QM_F_SEL, 1, &sellds, &dyn, false);
+      queue_pass(ns, F0 | QM_F_SEL, 0, &sellds, &dyn, false);
     }
     if (o->sel_aln && !(status & (1 | 4)) && !getenv("QM_EMU_NO_PACK")) {
       // the packed list kernel (qm_selpack.inl: several reads per wavefront) over the intervals the passes above left behind, three
       // "waves" with a contiguous range of the reads each; every list it writes must be the one the fused path wrote for that read
       // word for word, and the reads it leaves for the one-read kernel must be exactly those on its queue
+      // (what lies behind a queue's count names slot `nreads`, which belongs to no read: a kernel that walks past the count writes there)
+      const u32 canary = 0xdeadbeefu;
       std::vector<u32> lcnt2(nreads + 1, 0); std::vector<long long> loff2(nreads + 1, 0); std::vector<unsigned char> fnd(nreads + 1, 0);
-      std::vector<long long> todo((size_t)nreads + 1, -1);
+      std::vector<long long> todo((size_t)nreads + 1, nreads);
+      lcnt2[nreads] = canary;
       for (long long r = 0; r < nreads; ++r) fnd[r] = (lcnt[r] >> 31) & 1;
       ReadBatch H = B; H.iv_in = dints.data(); H.iv_in_off = doff.data(); H.iv_in_cnt = dcnt.data(); H.found_in = fnd.data();
       H.iv_out = nullptr; H.lcnt = lcnt2.data(); H.loff = loff2.data();
       scal[QM_SC_TODO] = 0;
-      static PackMem pm[3];
-      const long long NW = 3, per = (nreads + NW - 1) / NW;
-      for (long long w = 0; w < NW; ++w) {
-        WaveAlloc pw; pw.base = -1; pw.used = 0; pw.ivBase = -1; pw.ivUsed = 0;
-        long long r = w * per; const long long rEnd = r + per < nreads ? r + per : nreads;
-        while (r < rEnd) r += sel_pack_batch(ix, H, r, rEnd, pm[w], pw, todo.data());
-      }
+      for (long long w = 0; w < 3; ++w) pack_wave(ix, H, w, 3, garbage_slab<PackMem>(), todo.data());
       // the wide edition (256 intervals / suffixes per batch) over the queue the narrow one left, two "waves"
-      std::vector<long long> todo2((size_t)nreads + 1, -1);
+      std::vector<long long> todo2((size_t)nreads + 1, nreads);
       scal[QM_SC_TODO2] = 0;
       if (!getenv("QM_EMU_NO_PACKW")) {
-        static PackMemW<4> pw4[2];
-        const long long nq = (long long)scal[QM_SC_TODO], NQW = 2, perq = (nq + NQW - 1) / NQW;
-        for (long long w = 0; w < NQW; ++w) {
-          WaveAlloc pw; pw.base = -1; pw.used = 0; pw.ivBase = -1; pw.ivUsed = 0;
-          long long q = w * perq; const long long qEnd = q + perq < nq ? q + perq : nq;
-          while (q < qEnd) q += sel_pack_batch_wide<4>(ix, H, todo.data(), q, qEnd, pw4[w], pw, todo2.data());
-        }
+        const long long nq = (long long)scal[QM_SC_TODO];
+        for (long long w = 0; w < 2; ++w) packw_wave<4>(ix, H, todo.data(), &scal[QM_SC_TODO], w, 2, garbage_slab<PackMemW<4>>(), todo2.data());
         if (getenv("QM_EMU_PACK_STATS")) fprintf(stderr, "[qm emu] wide packed list kernel took %lld of %lld queued reads\n", nq - (long long)scal[QM_SC_TODO2], nq);
         todo.swap(todo2); scal[QM_SC_TODO] = scal[QM_SC_TODO2];
       }
@@ -240,7 +209,39 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
           else { loff[r] = loff2[r]; }        // downstream reads the packed kernel's copy
         }
         if (getenv("QM_EMU_PACK_STATS")) fprintf(stderr, "[qm emu] packed list kernel took %lld of %lld reads\n", npk, nreads);
+        if (lcnt2[nreads] != canary) { fprintf(stderr, "[qm emu] packed list kernel: walked past its queue's count\n"); ++bad; }
         if (bad) status |= 64;
+      }
+      if (!(status & 1)) {
+        // the one-read list kernel (qm_h2m_kernel<QM_F_SEL>, the instantiation the library runs whatever the index and the options) over the
+        // queue the packed kernels left, three "waves" -- and, as pass_sel_slow does, once more with scratch sized for them over the reads it
+        // queues itself: every list must be the one the fused path wrote for that read word for word
+        std::vector<u32> lcnt3(nreads + 1, 0); std::vector<long long> loff3(nreads + 1, 0);
+        lcnt3[nreads] = canary;
+        const u64 slowCnt = scal[QM_SC_SLOWCNT], slowMax = scal[QM_SC_SLOWMAX];
+        scal[QM_SC_SLOWCNT] = 0; scal[QM_SC_SLOWMAX] = 0;
+        ReadBatch T = H; T.lcnt = lcnt3.data(); T.loff = loff3.data(); T.slowq = todo.data(); T.nreads_dev = &scal[QM_SC_TODO];
+        for (long long w = 0; w < 3; ++w) h2m_wave<QM_F_SEL>(ix, T, w, 3, garbage_slab<H2mMem>(), gs.data(), selscr, (w & 1) ? &sellds : nullptr, nullptr);
+        if (scal[QM_SC_SLOWCNT] > 0) {
+          const long long need = (((long long)scal[QM_SC_SLOWMAX] + 63) / 64) * 64 + 64;
+          std::vector<unsigned char> dmem((size_t)SelScratchDyn::bytes_for(need));
+          SelScratchDyn dyn; dyn.bind(dmem.data(), need);
+          std::vector<long long> q;
+          for (long long r = 0; r < nreads; ++r) if (lcnt3[r] == QM_LCNT_SLOW) q.push_back(r);
+          ReadBatch Q = T; Q.slowq = q.data(); Q.nreads = (long long)q.size(); Q.nreads_dev = nullptr; Q.dyn = &dyn;
+          for (long long w = 0; w < 3; ++w) h2m_wave<QM_F_SEL>(ix, Q, w, 3, garbage_slab<H2mMem>(), gs.data(), selscr, &sellds, &dyn);
+        }
+        scal[QM_SC_SLOWCNT] = slowCnt; scal[QM_SC_SLOWMAX] = slowMax;
+        long long bad = 0;
+        for (long long q = 0; q < (long long)scal[QM_SC_TODO] && !(status & 1); ++q) {
+          const long long r = todo[q];
+          bool same = lcnt3[r] == lcnt[r];
+          const long long nwd = lcnt[r] & 0x7fffffffu;
+          for (long long t = 0; same && t < nwd; ++t) same = lists[loff3[r] + t] == lists[loff[r] + t];
+          if (!same) { if (bad < 5) fprintf(stderr, "[qm emu] one-read list kernel: read %lld differs (words %u vs %u)\n", r, lcnt3[r] & 0x7fffffffu, lcnt[r] & 0x7fffffffu); ++bad; }
+        }
+        if (lcnt3[nreads] != canary) { fprintf(stderr, "[qm emu] one-read list kernel: walked past its queue's count\n"); ++bad; }
+        if (bad && !(status & 1)) status |= 2;
       }
     }
     if (!(status & 1)) break;
@@ -260,36 +261,7 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
     const unsigned long long prof1 = qm::qm_prof[1], prof3 = qm::qm_prof[3];
     struct ProfOut { unsigned long long a, b; long long n; ~ProfOut() { fprintf(stderr, "[qm emu prof] lean kernel: %.2f bucket loads, %.2f probe rounds per read\n", (double)(qm::qm_prof[1] - a) / n, (double)(qm::qm_prof[3] - b) / n); } } profOut{prof1, prof3, nreads};
 #endif
-    const long long nit = leanWide ? nreads : (nreads + 1) >> 1, NW = 3;
-    static LeanMem Ms[3];
-    for (long long w = 0; w < NW; ++w) {
-      LeanMem& M = Ms[w]; memset(&M, 0, sizeof(M));
-      WaveAlloc wl; wl.base = -1; wl.used = 0; wl.ivBase = -1; wl.ivUsed = 0;
-      if (leanWide && paired) {
-        lean_stage_offsets<true, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<true, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<true, true>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<true, false, true, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<true, false, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      } else if (leanWide) {
-        lean_stage_offsets<false, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<false, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<false, true>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<false, false, true, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<false, false, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      } else if (paired) {
-        lean_stage_offsets<true>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<true>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<true>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<true, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<true, false, false>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      } else {
-        lean_stage_offsets<false>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<false>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<false>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<false, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<false, false, false>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      }
-    }
-    if (!leanWide && !getenv("QM_EMU_NO_NPASS")) {
-      std::vector<long long> q;
-      for (long long r = 0; r < nreads; ++r) if (lcnt2[r] == QM_LCNT_LEAN) q.push_back(r);
-      const size_t before = q.size();
-      if (paired) emu_n_pass<true, false>(ix, Lb, q, scal2); else emu_n_pass<false, false>(ix, Lb, q, scal2);
-      if (getenv("QM_EMU_LEAN_STATS")) fprintf(stderr, "[qm emu] N-aware pass over %zu reads, %llu marked again\n", before, (unsigned long long)scal2[QM_SC_LEANQ]);
-    }
+    emu_lean_passes(paired, false, leanWide, ix, Lb, lcnt2, scal2, "");
     long long bad = 0, deferred = 0;
     for (long long r = 0; r < nreads; ++r) {
       if (lcnt2[r] == QM_LCNT_LEAN) { ++deferred; continue; }
@@ -311,36 +283,7 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
     u64 scal2[QM_SC_WORDS]; memset(scal2, 0, sizeof(scal2)); int status2 = 0;
     ReadBatch Lb = B; Lb.lcnt = lcnt2.data(); Lb.loff = loff2.data(); Lb.cursor = scal2; Lb.status = &status2;
     Lb.iv_out = di2.data(); Lb.iv_cnt = dc2.data(); Lb.iv_off = do2.data(); Lb.iv_cap = (long long)di2.size(); Lb.found_out = fo2.data();
-    const long long nit = leanWide ? nreads : (nreads + 1) >> 1, NW = 3;
-    static LeanMem Ms[3];
-    for (long long w = 0; w < NW; ++w) {
-      LeanMem& M = Ms[w]; memset(&M, 0, sizeof(M));
-      WaveAlloc wl; wl.base = -1; wl.used = 0; wl.ivBase = -1; wl.ivUsed = 0;
-      if (leanWide && paired) {
-        lean_stage_offsets<true, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<true, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<true, true>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<true, true, true, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<true, true, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      } else if (leanWide) {
-        lean_stage_offsets<false, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<false, true>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<false, true>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<false, true, true, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<false, true, false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      } else if (paired) {
-        lean_stage_offsets<true>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<true>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<true>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<true, true, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<true, true, false>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      } else {
-        lean_stage_offsets<false>(Lb, (int)w, (int)nit, M, 0); lean_stage_chars<false>(Lb, (int)w, (int)nit, M, 0); lean_stage_offsets<false>(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        for (long long it = w; it < nit; it += NW) { if (ix.ph) lean_iter<false, true, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); else lean_iter<false, true, false>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl); par ^= 1; }
-      }
-    }
-    if (!leanWide && !getenv("QM_EMU_NO_NPASS")) {
-      std::vector<long long> q;
-      for (long long r = 0; r < nreads; ++r) if (lcnt2[r] == QM_LCNT_LEAN) q.push_back(r);
-      const size_t before = q.size();
-      if (paired) emu_n_pass<true, true>(ix, Lb, q, scal2); else emu_n_pass<false, true>(ix, Lb, q, scal2);
-      if (getenv("QM_EMU_LEAN_STATS")) fprintf(stderr, "[qm emu] N-aware pass (-s collector) over %zu reads, %llu marked again\n", before, (unsigned long long)scal2[QM_SC_LEANQ]);
-    }
+    emu_lean_passes(paired, true, leanWide, ix, Lb, lcnt2, scal2, " (-s collector)");
     long long bad = 0, deferred = 0;
     for (long long r = 0; r < nreads; ++r) {
       if (lcnt2[r] == QM_LCNT_LEAN) { ++deferred; continue; }
@@ -373,23 +316,10 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
       const unsigned long long prof1 = qm::qm_prof[1], prof3 = qm::qm_prof[3];
       struct ProfOut { unsigned long long a, b; long long n; ~ProfOut() { fprintf(stderr, "[qm emu prof] pair kernel: %.2f bucket loads, %.2f probe rounds per read\n", (double)(qm::qm_prof[1] - a) / n, (double)(qm::qm_prof[3] - b) / n); } } profOut{prof1, prof3, nreads};
 #endif
-      const long long nit = nunits, NW = 3;
-      static DuoMem Ms[3];
-      DuoCtr dc[3];
-      for (long long w = 0; w < NW; ++w) {
-        DuoMem& M = Ms[w]; memset(&M, 0xA5, sizeof(M));
-        for (int a = 0; a < 2; ++a) for (int b = 0; b < 2; ++b) for (int c = 4; c < 8; ++c) M.pk[a][b][c] = 0;      // (the kernel's own initialisation)
-        WaveAlloc wl; wl.base = -1; wl.used = 0; wl.ivBase = -1; wl.ivUsed = 0;
-        dc[w] = DuoCtr{0, 0, 0, 0, 0, 0};
-        duo_stage_offsets(Lb, (int)w, (int)nit, M, 0); duo_stage_chars(Lb, (int)w, (int)nit, M, 0); duo_stage_offsets(Lb, (int)(w + NW), (int)nit, M, 1);
-        int par = 0;
-        static DuoNext Nx; memset(&Nx, 0, sizeof(Nx));
-        if (ix.ph) duo_prepare<true>(ix, Lb, (int)w, (int)nit, (int)NW, 0, M, Nx); else duo_prepare<false>(ix, Lb, (int)w, (int)nit, (int)NW, 0, M, Nx);
-        for (long long it = w; it < nit; it += NW) {
-          if (B.quasi_cov > 0.0) { if (ix.ph) duo_iter<true, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl, dc[w], Nx); else duo_iter<false, true>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl, dc[w], Nx); }
-          else { if (ix.ph) duo_iter<true, false>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl, dc[w], Nx); else duo_iter<false, false>(ix, Lb, (int)it, (int)nit, (int)NW, par, M, wl, dc[w], Nx); }
-          par ^= 1;
-        }
+      for (int w = 0; w < 3; ++w) {
+        DuoMem& M = garbage_slab<DuoMem>();
+        if (B.quasi_cov > 0.0) { if (ix.ph) duo_wave<true, true>(ix, Lb, w, 3, M); else duo_wave<false, true>(ix, Lb, w, 3, M); }
+        else { if (ix.ph) duo_wave<true, false>(ix, Lb, w, 3, M); else duo_wave<false, false>(ix, Lb, w, 3, M); }
       }
       PairBatch Pg; memset(&Pg, 0, sizeof(Pg));           // the general kernel's lists through stage B: what a merged pair must equal
       std::vector<u32> hcg(nunits + 1, 0);
@@ -423,8 +353,8 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
           if (!same) { if (bad < 5) fprintf(stderr, "[qm emu] %s: read %lld differs (words %u vs %u)\n", kname, r, lcnt2[r], lcnt[r]); ++bad; }
         }
       }
-      DuoCtr got = {0, 0, 0, 0, 0, 0};
-      for (long long w = 0; w < NW; ++w) { got.pe += dc[w].pe; got.se += dc[w].se; got.tot += dc[w].tot; got.reads += dc[w].reads; got.tooMany += dc[w].tooMany; got.mapped += dc[w].mapped; }
+      // the merged pairs' counters, from where the kernel's waves added them (B.cursor[1 .. 6])
+      const DuoCtr got = {(u32)scal2[1], (u32)scal2[2], (u32)scal2[3], (u32)scal2[4], (u32)scal2[5], (u32)scal2[6]};
       if (got.pe != want.pe || got.se != want.se || got.tot != want.tot || got.reads != want.reads || got.tooMany != want.tooMany || got.mapped != want.mapped) {
         fprintf(stderr, "[qm emu] %s: counters of the merged pairs %u %u %u %u %u %u, stage B says %llu %llu %llu %llu %llu %llu\n", kname, got.pe, got.se, got.tot, got.reads, got.tooMany, got.mapped,
                 (unsigned long long)want.pe, (unsigned long long)want.se, (unsigned long long)want.tot, (unsigned long long)want.reads, (unsigned long long)want.tooMany, (unsigned long long)want.mapped);
