@@ -362,6 +362,44 @@ int qm_eqc_fetch(qm_eqc* t, int64_t* label_offsets /*[n_classes+1]*/, uint32_t* 
 enum { QM_EQC_STAT_GROWTHS = 0, QM_EQC_STAT_COLLISION_PROBES = 1, QM_EQC_STAT_LONG_UNITS = 2, QM_EQC_STAT_ROUNDS = 3, QM_EQC_STAT_LAST_FOLD_US = 4 };
 int qm_eqc_stat(const qm_eqc* t, int which, int64_t* value);
 
+/* ---- abundance estimation on the device: the EM over an equivalence-class table --------------------------------------------
+ * (No counterpart in the reference; consumer of qm_eqc.  The step every consumer of eq_classes.txt performs next.)  With classes c
+ * of label L_c and count n_c, a positive effective length e_t per transcript and alpha_t the fragments assigned to t, one
+ * iteration is, all in float64:
+ *     w_t = alpha_t / e_t     d_c = sum of w_t over t in L_c     r_c = n_c / d_c (0 when d_c < DBL_MIN: the class is skipped)
+ *     alpha'_t = w_t * (sum of r_c over the classes that contain t)
+ * A class of one tid has d_c = w_t, so its term is n_c: it is added as it is (nothing when w_t < DBL_MIN) instead of being rounded
+ * twice; a transcript that occurs in single-tid classes only holds exactly its count.
+ * Two launches per iteration and no floating-point atomic: every sum is taken by one wavefront in an order that the table alone
+ * fixes (class index = ascending slot index; a transcript's classes ascending), so a run is reproducible bit for bit.  No bias
+ * models, no variational Bayes, no online phase, no truncation of small values at the end.  Not thread-safe (one per host thread). */
+typedef struct qm_quant qm_quant;   /* the bipartite graph of a table and the current alpha, in the device memory of the table's GPU */
+/* no counterpart in the reference; consumer of qm_eqc.  A SNAPSHOT of t: later folds into t (or its destruction) do not alter the
+ * quant object, which runs on a stream of its own.  n_txps: transcripts (alpha has that many entries); a label that names a tid
+ * >= n_txps fails the create with QM_E_ARG.  eff_len: n_txps positive finite numbers, NULL = 1.0 each (QM_E_ARG otherwise).  An
+ * empty table is valid.  The start is the uniform default of qm_quant_set_start. */
+int qm_quant_create(qm_eqc* t, int64_t n_txps, const double* eff_len, qm_quant** out);
+/* no counterpart in the reference; consumer of qm_eqc.  alpha0: n_txps non-negative finite numbers (QM_E_ARG otherwise); NULL = the
+ * uniform default: total / M for the M transcripts that occur in at least one label, 0 for all others (they stay 0). */
+int qm_quant_set_start(qm_quant* q, const double* alpha0);
+/* no counterpart in the reference; consumer of qm_eqc.  Up to max_iter iterations from the current alpha (a later call goes on
+ * where the last one stopped).  Every check_every-th iteration (>= 1) the host reads one word: the largest |alpha'_t - alpha_t| /
+ * alpha'_t over the transcripts with alpha'_t > min_alpha (>= 0); below rel_tol the run stops.  rel_tol = 0: exactly max_iter
+ * iterations and no read-back at all.  Salmon's offline EM: max_iter 10000, check_every 10, rel_tol 1e-2, min_alpha 1e-8.
+ * iterations: the iterations of this call; last_rel_change: the last value read, -1 when none was.  Either may be NULL. */
+int qm_quant_run(qm_quant* q, int32_t max_iter, int32_t check_every, double rel_tol, double min_alpha, int32_t* iterations, double* last_rel_change);
+/* no counterpart in the reference; consumer of qm_eqc.  The current alpha: n_txps doubles, all that crosses PCIe. */
+int qm_quant_fetch(qm_quant* q, double* alpha /*[n_txps]*/);
+/* no counterpart in the reference; consumer of qm_eqc.  Classes and label entries of the snapshot, transcripts that occur in a
+ * label (M), the longest label and the longest transcript list, labels / transcript lists of more than 8 entries (handled one
+ * per wavefront), the last qm_quant_run from its first launch to its last, and the structure build inside qm_quant_create (its
+ * read-backs included), both in microseconds, by HIP events on its stream */
+enum { QM_QUANT_STAT_CLASSES = 0, QM_QUANT_STAT_ENTRIES = 1, QM_QUANT_STAT_PRESENT = 2, QM_QUANT_STAT_LONGEST_LABEL = 3, QM_QUANT_STAT_LONGEST_LIST = 4,
+       QM_QUANT_STAT_QUEUED_LABELS = 5, QM_QUANT_STAT_QUEUED_TXPS = 6, QM_QUANT_STAT_LAST_RUN_US = 7, QM_QUANT_STAT_BUILD_US = 8 };
+int qm_quant_stat(const qm_quant* q, int which, int64_t* value);
+/* no counterpart in the reference; consumer of qm_eqc */
+int qm_quant_destroy(qm_quant* q);
+
 /* ---- host-side callers of the path -------------------------------------------
  * Read ingest: replaces fastx_parser::FastxParser<ReadPair|ReadSeq> (include/FastxParser.hpp:62-66,
  * src/FastxParser.cpp:229-328: one kseq producer thread, per-record std::strings).  FASTA/FASTQ, plain or

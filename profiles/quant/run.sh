@@ -1,0 +1,21 @@
+#!/bin/bash
+# Measurements (a)-(d) of the EM over the equivalence-class table.  PARENT: a checkout of the parent commit with its library built
+# (only (d) needs it); OUT: where the lines go.  Every GPU step has a time limit of its own and the steps are chained: the first that
+# fails ends the script.
+#   bash profiles/quant/run.sh PARENT OUT [abc|d ...]
+set -o pipefail
+PARENT=${1:?parent tree}; OUT=${2:?output directory}; shift 2
+WHAT=${*:-abc d}
+HERE=$(cd "$(dirname "$0")/../.." && pwd)
+mkdir -p "$OUT"
+for w in $WHAT; do
+  case $w in
+  abc)  # structure build, time per iteration beside the byte floor and the numpy restatement, convergence at the defaults
+    timeout -k 10 500 python "$HERE/profiles/quant/measure_quant.py" | tail -1 | tee "$OUT/abc_quant.json" || exit 1 ;;
+  d)    # the default path is untouched: plain bench.py, parent and branch in turn
+    for i in 1 2 3; do
+      (cd "$PARENT" && timeout -k 10 400 python bench.py --gpus 1 --steps 8 --warmup 2 | tail -1 | tee -a "$OUT/d_bench_parent.jsonl") &&
+      (cd "$HERE" && timeout -k 10 400 python bench.py --gpus 1 --steps 8 --warmup 2 | tail -1 | tee -a "$OUT/d_bench_branch.jsonl") || exit 1
+    done ;;
+  esac
+done

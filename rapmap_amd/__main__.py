@@ -74,6 +74,13 @@ def _quasimap(argv):
     ap.add_argument("--eqClasses", default="", metavar="FILE", help="write the equivalence classes of the run (the sets of transcripts the "
                     "fragments map to, with their counts) to FILE in the format of Salmon's eq_classes.txt; they are built on the GPU, "
                     "and with -n no hit leaves the device")
+    ap.add_argument("--quant", default="", metavar="FILE", help="estimate transcript abundances on the GPU (the EM over the run's equivalence "
+                    "classes, which are built on the device whether or not --eqClasses is given) and write them to FILE in the format of "
+                    "Salmon's quant.sf; with -n no hit leaves the device")
+    ap.add_argument("--quantMaxIter", type=int, default=10000, help="[only with quant]: iterations of the EM at the most")
+    ap.add_argument("--quantRelTol", type=float, default=1e-2, help="[only with quant]: stop when no abundance changes by more than this fraction")
+    ap.add_argument("--quantFragLenMean", type=float, default=0.0, metavar="F", help="[only with quant]: effective length = max(1, Length - F + 1); "
+                    "the default 0 takes the transcript length itself.  The fragment-length distribution is NOT estimated from the mapped pairs")
     ap.add_argument("--chunk", type=int, default=1 << 18, help="read pairs per GPU batch")
     a = ap.parse_args(argv)
 
@@ -174,7 +181,7 @@ def _quasimap(argv):
     # (a stream's own contexts share it)
     keep = [ra.QuasiMapper(qi, d) for d in sorted(set(devices))]
     # --eqClasses: every stream folds its batches on the devices; the streams' merged tables (one per file) meet in this one
-    classes = ra.EqClasses(keep[0]) if a.eqClasses else None
+    classes = ra.EqClasses(keep[0]) if a.eqClasses or a.quant else None
     for f1, f2 in pairs:
         os.environ.setdefault("QM_INGEST_PIN", "1")   # a whole-machine job with one ingest engine: its workers on the NUMA node that holds the files' pages
         st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None,
@@ -196,8 +203,19 @@ def _quasimap(argv):
         log("stream: " + ", ".join("%s %.3f" % kv for kv in st.stats().items()))
         st.close()
     if classes is not None:
-        classes.write(a.eqClasses, qi.txp_names)
-        log("wrote %d equivalence classes (%d fragments) to %s" % (classes.n_classes, classes.total, a.eqClasses))
+        if a.eqClasses:
+            classes.write(a.eqClasses, qi.txp_names)
+            log("wrote %d equivalence classes (%d fragments) to %s" % (classes.n_classes, classes.total, a.eqClasses))
+        if a.quant:
+            # --quant: the EM over the merged table where it lies; n_txps doubles come back
+            lens = np.asarray(qi.txp_lens, dtype=np.int64)
+            eff = np.maximum(1.0, lens.astype(np.float64) - a.quantFragLenMean + 1.0) if a.quantFragLenMean else np.maximum(1.0, lens.astype(np.float64))
+            qn = ra.Quant(classes, qi.n_txps, eff)
+            iters, rel = qn.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
+            ra.write_quant(a.quant, qi.txp_names, lens, eff, qn.fetch())
+            log("wrote abundances of %d transcripts to %s (%d EM iterations, %.3f ms on the GPU, last relative change %g)" % (
+                qi.n_txps, a.quant, iters, qn.stat()["last_run_us"] / 1e3, rel))
+            qn.close()
         classes.close()
     for k_ in keep:
         k_.close()

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "qm_reader_open", "qm_reader_next", "qm_reader_close", "qm_io_last_error", "qm_sam_header", "qm_sam_records",
     "qm_eqc_create", "qm_eqc_destroy", "qm_eqc_clear", "qm_eqc_add", "qm_eqc_add_labels", "qm_eqc_size", "qm_eqc_fetch", "qm_eqc_stat",
     "qm_stream_eqc_finish", "qm_stream_eqc_fetch",
+    "qm_quant_create", "qm_quant_set_start", "qm_quant_run", "qm_quant_fetch", "qm_quant_stat", "qm_quant_destroy",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
 ]
 
@@ -186,6 +187,12 @@ def lib():
     L.qm_eqc_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
     L.qm_stream_eqc_finish.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.qm_stream_eqc_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_quant_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.qm_quant_set_start.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_quant_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.qm_quant_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_quant_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_quant_destroy.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -633,6 +640,15 @@ class EqClasses:
         off, tids, cnt = self.fetch()
         write_eq_classes(path, txp_names, off, tids, cnt)
 
+    def quantify(self, n_txps, eff_lens=None, **run_kw):
+        """the one-call form of Quant: alpha float64[n_txps] after a run from the uniform start (run_kw: Quant.run's)"""
+        q = Quant(self, n_txps, eff_lens)
+        try:
+            q.run(**run_kw)
+            return q.fetch()
+        finally:
+            q.close()
+
     def close(self):
         if self._h:
             lib().qm_eqc_destroy(self._h)
@@ -643,6 +659,102 @@ class EqClasses:
             self.close()
         except Exception:
             pass
+
+
+class Quant:
+    """qm_quant_*: abundance estimation on the device, the EM over a snapshot of an EqClasses table (later folds into the table do
+    not alter it).  One iteration, all in float64: w = alpha / eff; d_c = sum of w over the class's label; r_c = n_c / d_c;
+    alpha'_t = w_t * sum of r_c over the classes that contain t.  eff_lens: n_txps positive numbers (None: 1.0 each).  The start is
+    total / M for the M transcripts that occur in a label and 0 for the others, unless set_start gives another one."""
+
+    STATS = ("classes", "entries", "present", "longest_label", "longest_list", "queued_labels", "queued_txps", "last_run_us", "build_us")
+    DEFAULTS = dict(max_iter=10000, check_every=10, rel_tol=1e-2, min_alpha=1e-8)     # Salmon's offline EM
+
+    def __init__(self, eq_classes, n_txps, eff_lens=None):
+        self._h = C.c_void_p()
+        self.n_txps = int(n_txps)
+        if eff_lens is not None:
+            eff_lens = np.ascontiguousarray(eff_lens, dtype=np.float64)
+            if eff_lens.size != self.n_txps:
+                raise ValueError("one effective length per transcript")
+        _check(lib().qm_quant_create(eq_classes._h, self.n_txps, eff_lens.ctypes.data if eff_lens is not None and eff_lens.size else None,
+                                     C.byref(self._h)))
+        self.device = eq_classes.device
+
+    def set_start(self, alpha0=None):
+        """alpha0: n_txps non-negative numbers; None: the uniform default"""
+        if alpha0 is not None:
+            alpha0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+            if alpha0.size != self.n_txps:
+                raise ValueError("one start value per transcript")
+        _check(lib().qm_quant_set_start(self._h, alpha0.ctypes.data if alpha0 is not None and alpha0.size else None))
+
+    def run(self, max_iter=DEFAULTS["max_iter"], check_every=DEFAULTS["check_every"], rel_tol=DEFAULTS["rel_tol"], min_alpha=DEFAULTS["min_alpha"]):
+        """up to max_iter iterations from the current alpha -> (iterations, last_rel_change); the relative change is looked at every
+        check_every-th iteration only (rel_tol=0: never, exactly max_iter iterations, last_rel_change -1)"""
+        it, rel = C.c_int32(), C.c_double()
+        _check(lib().qm_quant_run(self._h, int(max_iter), int(check_every), float(rel_tol), float(min_alpha), C.byref(it), C.byref(rel)))
+        return it.value, rel.value
+
+    def fetch(self):
+        """the current alpha: float64[n_txps]"""
+        a = np.zeros(self.n_txps, dtype=np.float64)
+        _check(lib().qm_quant_fetch(self._h, a.ctypes.data if a.size else None))
+        return a
+
+    def stat(self):
+        """qm_quant_stat: a dictionary of STATS (last_run_us, build_us: the last run / the structure build by HIP events on its stream)"""
+        d = {}
+        for i, k in enumerate(self.STATS):
+            v = C.c_int64()
+            _check(lib().qm_quant_stat(self._h, i, C.byref(v)))
+            d[k] = v.value
+        return d
+
+    def close(self):
+        if self._h:
+            lib().qm_quant_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+QUANT_HEADER = "Name\tLength\tEffectiveLength\tTPM\tNumReads"
+
+
+def write_quant(path, names, lens, eff_lens, alpha):
+    """Salmon's quant.sf: Name, Length, EffectiveLength, TPM, NumReads, tab-separated under that header.  TPM is (alpha / eff) over
+    its sum, times 1e6.  Floats are written with repr: read_quant gives NumReads back bit for bit."""
+    alpha = np.asarray(alpha, dtype=np.float64); eff = np.asarray(eff_lens, dtype=np.float64)
+    if not (len(names) == len(lens) == eff.size == alpha.size):
+        raise ValueError("names, lens, eff_lens and alpha differ in length")
+    rate = alpha / eff
+    tot = float(rate.sum())
+    tpm = rate / tot * 1e6 if tot > 0 else np.zeros_like(rate)
+    with open(path, "w") as f:
+        f.write(QUANT_HEADER + "\n")
+        for i, nm in enumerate(names):
+            f.write("%s\t%d\t%s\t%s\t%s\n" % (nm, int(lens[i]), repr(float(eff[i])), repr(float(tpm[i])), repr(float(alpha[i]))))
+
+
+def read_quant(path):
+    """the inverse of write_quant: (names, lens int64[], eff_lens float64[], tpm float64[], num_reads float64[])"""
+    names, cols = [], ([], [], [], [])
+    with open(path) as f:
+        if f.readline().rstrip("\n") != QUANT_HEADER:
+            raise ValueError("%s: not a quant file (header)" % path)
+        for ln, line in enumerate(f, 2):
+            w = line.rstrip("\n").split("\t")
+            if len(w) != 5:
+                raise ValueError("%s:%d: %d fields, 5 expected" % (path, ln, len(w)))
+            names.append(w[0]); cols[0].append(int(w[1]))
+            for j in (1, 2, 3):
+                cols[j].append(float(w[j + 1]))
+    return names, np.array(cols[0], dtype=np.int64), np.array(cols[1], dtype=np.float64), np.array(cols[2], dtype=np.float64), np.array(cols[3], dtype=np.float64)
 
 
 PACK_EXC_DTYPE = np.dtype([("pos", "<u4"), ("ch", "<u4")])

@@ -84,4 +84,19 @@ hipError_t qmk_eqc_probe(const void* table, const void* set, const unsigned long
 hipError_t qmk_eqc_publish(const void* table, const void* set, const unsigned long long* q, long long nq, hipStream_t st);
 hipError_t qmk_eqc_reset_probes(unsigned long long* q, long long n, hipStream_t st);
 hipError_t qmk_eqc_sum(const unsigned long long* count, const unsigned long long* key, long long cap, unsigned long long* out, hipStream_t st);
+// the EM over the equivalence-class table (qm_quant.inl; build / state: QuantBuild, QuantState by address)
+hipError_t qmk_quant_mark(const void* build, hipStream_t st);
+hipError_t qmk_quant_compact(const void* build, hipStream_t st);
+hipError_t qmk_quant_bounds(const unsigned int* sorted_tid, long long n, long long n_txps, long long* bound, hipStream_t st);
+hipError_t qmk_quant_rowstat(const long long* off, long long n, unsigned int* flag, unsigned long long* scal, int max_word, int present, hipStream_t st);
+hipError_t qmk_quant_queue(const unsigned int* flag, const long long* pos, long long n, long long* queue, hipStream_t st);
+hipError_t qmk_quant_start(const long long* toff, long long n_txps, double value, double* alpha, hipStream_t st);
+hipError_t qmk_quant_weights(const double* alpha, const double* eff, long long n_txps, double* w, hipStream_t st);
+hipError_t qmk_quant_class(const void* state, hipStream_t st);
+hipError_t qmk_quant_txp(const void* state, hipStream_t st);
+size_t qmk_quant_scan_temp_bytes(long long n);
+hipError_t qmk_quant_scan(void* temp, size_t temp_bytes, const unsigned int* in, long long* out, long long n, hipStream_t st);
+size_t qmk_quant_sort_temp_bytes(long long n);
+hipError_t qmk_quant_sort(void* temp, size_t temp_bytes, const unsigned int* tid_in, unsigned int* tid_out, const unsigned int* cls_in, unsigned int* cls_out,
+                          long long n, hipStream_t st);
 }

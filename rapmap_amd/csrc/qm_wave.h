@@ -179,6 +179,20 @@ QM_DEV void half_max(LV<int>& x) {
   for (int b = 0; b < 64; b += 32) { int m = x.v[b]; for (int l = b + 1; l < b + 32; ++l) m = x.v[l] > m ? x.v[l] : m; for (int l = b; l < b + 32; ++l) x.v[l] = m; }
 }
 QM_DEV void load_48(const void* p, U4& a, U4& b, U4& c) { a = load_16(p); b = load_16((const unsigned char*)p + 16); c = load_16((const unsigned char*)p + 32); }
+// ---- double-typed cross-lane sums (qm_quant.inl).  The order of the additions is FIXED: a butterfly over lanes ^1, ^2, then the
+// mirror image within 8 (^7) and within 16 (^15) -- the two operands of every step are the same pair of numbers in both lanes,
+// and a + b == b + a in IEEE arithmetic, so every lane of a group ends with the same bits:
+// ((x0 + x1) + (x2 + x3)) + ((x4 + x5) + (x6 + x7)), and for 16 that plus the same over x8..x15.  G: 8 or 16, wave-uniform.
+QM_DEV void group_sum_f64(LV<double>& x, int G) {
+  static const int pair[4] = {1, 2, 7, 15};
+  for (int s = 0; s < (G > 8 ? 4 : 3); ++s) { LV<double> t; for (int l = 0; l < 64; ++l) t.v[l] = x.v[l] + x.v[l ^ pair[s]]; x = t; }
+}
+// the sum over the whole wavefront: the four rows' sums of group_sum_f64(x, 16), then (R0 + R1) + (R2 + R3)
+QM_DEV double wave_sum_f64(const LV<double>& x) {
+  LV<double> t = x;
+  group_sum_f64(t, 16);
+  return (t.v[0] + t.v[16]) + (t.v[32] + t.v[48]);
+}
 #else
 // DPP reductions (profiles/microbench/dpp_check.hip: row_shr:n gives lane i the value of lane i - n of its row of 16;
 // a lane without a source keeps `old`).  A step is one VALU instruction and no trip through the LDS crossbar --
@@ -359,6 +373,32 @@ QM_DEV void load_48(const void* p, U4& a, U4& b, U4& c) {
   v4u x = ((const v4u*)p)[0], y = ((const v4u*)p)[1], z = ((const v4u*)p)[2];
   asm volatile("" : "+v"(x), "+v"(y), "+v"(z));
   a.x = x.x; a.y = x.y; a.z = x.z; a.w = x.w; b.x = y.x; b.y = y.y; b.z = y.z; b.w = y.w; c.x = z.x; c.y = z.y; c.z = z.z; c.w = z.w;
+}
+// ---- double-typed cross-lane sums (qm_quant.inl): a double travels as its two dwords, one DPP move each (every lane has a source
+// in all four pairings, so there is no old value to keep); all 64 lanes must be active.  The order of the additions is fixed, and
+// both lanes of a pairing add the same two numbers: every lane of a group ends with the same bits (see the emulation above).
+template <int CTRL> QM_DEV double dpp_get_f64(double v) {
+  const u64 b = __builtin_bit_cast(u64, v);
+  const u32 lo = (u32)dpp_get<CTRL, 0xf>((int)(u32)b), hi = (u32)dpp_get<CTRL, 0xf>((int)(u32)(b >> 32));
+  return __builtin_bit_cast(double, ((u64)hi << 32) | lo);
+}
+QM_DEV void group_sum_f64(LV<double>& x, int G) {
+  double v = x.v[0];
+  v += dpp_get_f64<0xB1>(v);                                 // quad_perm:[1,0,3,2]
+  v += dpp_get_f64<0x4E>(v);                                 // quad_perm:[2,3,0,1]
+  v += dpp_get_f64<0x141>(v);                                // row_half_mirror
+  if (G > 8) v += dpp_get_f64<0x140>(v);                     // row_mirror
+  x.v[0] = v;
+}
+QM_DEV double read_lane(const LV<double>& x, int lane) {
+  const u64 b = __builtin_bit_cast(u64, x.v[0]);
+  const int lo = __builtin_amdgcn_readlane((int)(u32)b, lane), hi = __builtin_amdgcn_readlane((int)(u32)(b >> 32), lane);
+  return __builtin_bit_cast(double, ((u64)(u32)hi << 32) | (u32)lo);
+}
+QM_DEV double wave_sum_f64(const LV<double>& x) {
+  LV<double> t = x;
+  group_sum_f64(t, 16);
+  return (read_lane(t, 0) + read_lane(t, 16)) + (read_lane(t, 32) + read_lane(t, 48));
 }
 #endif
 
