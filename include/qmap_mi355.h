@@ -400,6 +400,54 @@ int qm_quant_stat(const qm_quant* q, int which, int64_t* value);
 /* no counterpart in the reference; consumer of qm_eqc */
 int qm_quant_destroy(qm_quant* q);
 
+/* ---- bootstrap replicates of the abundance estimate (Salmon's --numBootstraps) -------------------------
+ * A replicate resamples the snapshot's class counts -- a multinomial over the classes, N = their sum draws -- and runs the EM of
+ * qm_quant on the resampled counts; B replicates are iterated at once, every per-replicate array replicate-innermost, so that one
+ * gathered item is a run of contiguous doubles.  The draw is defined exactly (n_c: the snapshot's counts in the order of
+ * qm_quant_fetch_classes, cum their exclusive prefix sum; seed, R, k unsigned 64-bit): draw j (0 <= j < N) of replicate number R is
+ *   k = j >> 1;  (x0, x1, x2, x3) = Philox4x32-10(counter = (lo k, hi k, lo R, hi R), key = (lo seed, hi seed));
+ *   u = (j & 1) ? (x2 | x3 << 32) : (x0 | x1 << 32);  p = the high 64 bits of u * N;  the class c with cum[c] <= p < cum[c + 1]
+ * so a replicate's counts depend on (snapshot, seed, R) alone, and its alpha on those and the run's arguments: not on n_reps, not
+ * on its slot.  A resample costs N draws per replicate, whatever the number of classes.  Not thread-safe (one per host thread,
+ * and not concurrently with its qm_quant: they share a stream). */
+typedef struct qm_boot qm_boot;     /* the counts, weights and alphas of n_reps replicates over the graph of a qm_quant */
+/* no counterpart in the reference; consumer of qm_quant.  The snapshot's class side in the snapshot's own order (ascending slot
+ * index of the table it was taken from; NOT the sorted order of qm_eqc_fetch): offsets[classes + 1], tids[entries],
+ * counts[classes] (QM_QUANT_STAT_CLASSES, _ENTRIES).  QM_E_UNSUPPORTED when the counts add up to 2^53 or more. */
+int qm_quant_fetch_classes(qm_quant* q, int64_t* offsets /*[classes+1]*/, uint32_t* tids, uint64_t* counts);
+/* no counterpart in the reference; consumer of qm_quant.  Borrows q's graph, effective lengths and stream: qm_quant_destroy(q)
+ * returns QM_E_STATE and destroys nothing while a qm_boot of it lives.  n_reps < 1: QM_E_ARG; more than 65535: QM_E_UNSUPPORTED
+ * (run batches: first_rep); no memory: QM_E_NOMEM with everything freed.  An empty table is valid. */
+int qm_boot_create(qm_quant* q, int32_t n_reps, qm_boot** out);
+/* no counterpart in the reference; consumer of qm_quant.  Slot i (0 <= i < n_reps) receives the counts of replicate number
+ * first_rep + i under `seed`, its uniform start (N / M for the M transcripts that occur in a label) and starts anew: iteration
+ * count, done flag. */
+int qm_boot_resample(qm_boot* b, uint64_t seed, int64_t first_rep);
+/* no counterpart in the reference; consumer of qm_quant.  One slot's counts as given (a resampling scheme of the caller's own),
+ * in the order of qm_quant_fetch_classes; the slot starts anew from (their sum) / M.  rep outside [0, n_reps): QM_E_ARG. */
+int qm_boot_set_counts(qm_boot* b, int32_t rep, const uint64_t* counts /*[classes]*/);
+/* no counterpart in the reference; consumer of qm_quant.  One slot's counts. */
+int qm_boot_fetch_counts(qm_boot* b, int32_t rep, uint64_t* counts /*[classes]*/);
+/* no counterpart in the reference; consumer of qm_quant.  qm_quant_run's arguments and stopping rule, PER REPLICATE: on a checking
+ * iteration every replicate's largest relative change is held against rel_tol; a replicate below it is done and frozen -- nothing
+ * of it is written again, by this or a later call -- while the others go on; the host reads one word per check (how many are
+ * done).  rel_tol = 0: exactly max_iter iterations, no read-back.  A later call goes on with the replicates that are not done.
+ * iterations[i]: the iterations slot i made in this call; last_rel_change[i]: the last value held against rel_tol (-1: none yet;
+ * a replicate done before this call keeps the value it stopped at).  Either may be NULL.  Before any qm_boot_resample or
+ * qm_boot_set_counts: QM_E_STATE. */
+int qm_boot_run(qm_boot* b, int32_t max_iter, int32_t check_every, double rel_tol, double min_alpha,
+                int32_t* iterations /*[n_reps]*/, double* last_rel_change /*[n_reps]*/);
+/* no counterpart in the reference; consumer of qm_quant.  The current alphas, transposed on the device and copied once. */
+int qm_boot_fetch(qm_boot* b, double* alpha /*[n_reps][n_txps], row-major*/);
+/* no counterpart in the reference; consumer of qm_quant.  Replicates; draws per replicate of the last resample (N); the last
+ * resample and the last run in microseconds, by HIP events on the stream; kernel launches of the last run; labels / transcript
+ * lists of more than 32 entries (one wavefront per row and tile of 16 replicates) */
+enum { QM_BOOT_STAT_REPLICATES = 0, QM_BOOT_STAT_DRAWS = 1, QM_BOOT_STAT_LAST_RESAMPLE_US = 2, QM_BOOT_STAT_LAST_RUN_US = 3, QM_BOOT_STAT_LAUNCHES = 4,
+       QM_BOOT_STAT_QUEUED_LABELS = 5, QM_BOOT_STAT_QUEUED_TXPS = 6 };
+int qm_boot_stat(const qm_boot* b, int which, int64_t* value);
+/* no counterpart in the reference; consumer of qm_quant */
+int qm_boot_destroy(qm_boot* b);
+
 /* ---- host-side callers of the path -------------------------------------------
  * Read ingest: replaces fastx_parser::FastxParser<ReadPair|ReadSeq> (include/FastxParser.hpp:62-66,
  * src/FastxParser.cpp:229-328: one kseq producer thread, per-record std::strings).  FASTA/FASTQ, plain or

@@ -5,4 +5,4 @@ of the reference's call surface), synth.py (synthetic transcriptome / reads)."""
 from .api import (QuasiIndex, QuasiMapper, QmError, QmOpts, default_opts, build_index, pack_reads,  # noqa: F401
                   FastxReader, ReadBatch, MappedStream, reserve_stream_memory, SamWriter, sam_header_text, sam_records_text,
                   HIT_DTYPE, INTERVAL_DTYPE, LIB_PATH, ABI_SYMBOLS, EqClasses, write_eq_classes, read_eq_classes,
-                  Quant, write_quant, read_quant)
+                  Quant, write_quant, read_quant, Bootstrap, write_bootstraps, read_bootstraps)

@@ -81,8 +81,16 @@ def _quasimap(argv):
     ap.add_argument("--quantRelTol", type=float, default=1e-2, help="[only with quant]: stop when no abundance changes by more than this fraction")
     ap.add_argument("--quantFragLenMean", type=float, default=0.0, metavar="F", help="[only with quant]: effective length = max(1, Length - F + 1); "
                     "the default 0 takes the transcript length itself.  The fragment-length distribution is NOT estimated from the mapped pairs")
+    ap.add_argument("--numBootstraps", type=int, default=0, metavar="B", help="[only with quant]: B bootstrap replicates of the estimate on the GPU (the "
+                    "class counts resampled, the EM run again per replicate, 64 replicates at a time), written to FILE.bootstraps.gz in the "
+                    "layout of Salmon's bootstraps.gz: B x transcripts little-endian float64")
+    ap.add_argument("--bootstrapSeed", type=int, default=0, metavar="S", help="[only with numBootstraps]: seed of the resampling")
     ap.add_argument("--chunk", type=int, default=1 << 18, help="read pairs per GPU batch")
     a = ap.parse_args(argv)
+    if a.numBootstraps and not a.quant:
+        ap.error("--numBootstraps needs --quant")
+    if a.numBootstraps < 0:
+        ap.error("--numBootstraps must not be negative")
 
     paired = bool(a.leftMates and a.rightMates)
     single = bool(a.unmatedReads)
@@ -215,6 +223,19 @@ def _quasimap(argv):
             ra.write_quant(a.quant, qi.txp_names, lens, eff, qn.fetch())
             log("wrote abundances of %d transcripts to %s (%d EM iterations, %.3f ms on the GPU, last relative change %g)" % (
                 qi.n_txps, a.quant, iters, qn.stat()["last_run_us"] / 1e3, rel))
+            if a.numBootstraps:
+                # --numBootstraps: batches of at most 64 replicates through first_rep, so that memory stays bounded
+                import gzip
+                us = 0
+                with gzip.open(a.quant + ".bootstraps.gz", "wb") as f:
+                    for first in range(0, a.numBootstraps, 64):
+                        bs = ra.Bootstrap(qn, min(64, a.numBootstraps - first))
+                        bs.resample(seed=a.bootstrapSeed, first_rep=first)
+                        bs.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
+                        f.write(np.ascontiguousarray(bs.fetch(), dtype="<f8").tobytes())
+                        st = bs.stat(); us += st["last_resample_us"] + st["last_run_us"]
+                        bs.close()
+                log("wrote %d bootstrap replicates to %s.bootstraps.gz (seed %d, %.3f ms on the GPU)" % (a.numBootstraps, a.quant, a.bootstrapSeed, us / 1e3))
             qn.close()
         classes.close()
     for k_ in keep:

@@ -40,6 +40,8 @@ ABI_SYMBOLS = [
     "qm_eqc_create", "qm_eqc_destroy", "qm_eqc_clear", "qm_eqc_add", "qm_eqc_add_labels", "qm_eqc_size", "qm_eqc_fetch", "qm_eqc_stat",
     "qm_stream_eqc_finish", "qm_stream_eqc_fetch",
     "qm_quant_create", "qm_quant_set_start", "qm_quant_run", "qm_quant_fetch", "qm_quant_stat", "qm_quant_destroy",
+    "qm_quant_fetch_classes", "qm_boot_create", "qm_boot_resample", "qm_boot_set_counts", "qm_boot_fetch_counts", "qm_boot_run", "qm_boot_fetch",
+    "qm_boot_stat", "qm_boot_destroy",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
 ]
 
@@ -193,6 +195,15 @@ def lib():
     L.qm_quant_fetch.argtypes = [C.c_void_p, C.c_void_p]
     L.qm_quant_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
     L.qm_quant_destroy.argtypes = [C.c_void_p]
+    L.qm_quant_fetch_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_boot_create.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    L.qm_boot_resample.argtypes = [C.c_void_p, C.c_uint64, C.c_int64]
+    L.qm_boot_set_counts.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.qm_boot_fetch_counts.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.qm_boot_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    L.qm_boot_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_boot_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_boot_destroy.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -711,9 +722,29 @@ class Quant:
             d[k] = v.value
         return d
 
+    def classes(self):
+        """qm_quant_fetch_classes: the snapshot's class side in the snapshot's own order, which is what a bootstrap draw is defined
+        against (NOT the sorted order of EqClasses.fetch): (label_offsets int64[classes + 1], tids uint32[], counts uint64[classes])"""
+        st = self.stat()
+        nc, ne = st["classes"], st["entries"]
+        off = np.zeros(nc + 1, dtype=np.int64); tids = np.zeros(ne + 1, dtype=np.uint32); cnt = np.zeros(nc + 1, dtype=np.uint64)
+        _check(lib().qm_quant_fetch_classes(self._h, off.ctypes.data, tids.ctypes.data, cnt.ctypes.data))
+        return off, tids[:ne], cnt[:nc]
+
+    def bootstrap(self, n_reps, seed=0, **run_kw):
+        """the one-call form of Bootstrap: float64[n_reps, n_txps], replicate numbers 0 .. n_reps - 1 under `seed` (run_kw: Bootstrap.run's)"""
+        b = Bootstrap(self, n_reps)
+        try:
+            b.resample(seed=seed)
+            b.run(**run_kw)
+            return b.fetch()
+        finally:
+            b.close()
+
     def close(self):
+        """qm_quant_destroy; raises while a Bootstrap of this object lives (nothing is destroyed then)"""
         if self._h:
-            lib().qm_quant_destroy(self._h)
+            _check(lib().qm_quant_destroy(self._h))
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -721,6 +752,95 @@ class Quant:
             self.close()
         except Exception:
             pass
+
+
+class Bootstrap:
+    """qm_boot_*: bootstrap replicates of a Quant's estimate on the device (Salmon's --numBootstraps).  A replicate resamples the
+    snapshot's class counts -- N draws, a multinomial over the classes -- and runs Quant's EM on them; n_reps replicates are iterated
+    at once and each stops by itself.  Slot i holds replicate number first_rep + i; a replicate's counts depend on (snapshot, seed,
+    replicate number) alone and its alpha on those and run's arguments, not on n_reps or its slot.  Borrows the Quant's graph and
+    stream: close this before the Quant."""
+
+    STATS = ("replicates", "draws", "last_resample_us", "last_run_us", "launches", "queued_labels", "queued_txps")
+
+    def __init__(self, quant, n_reps):
+        self._h = C.c_void_p()
+        self.n_reps = int(n_reps); self.n_txps = quant.n_txps
+        self._quant = quant                                           # (kept alive: the ABI object borrows it)
+        _check(lib().qm_boot_create(quant._h, self.n_reps, C.byref(self._h)))
+        self.n_classes = quant.stat()["classes"]
+
+    def resample(self, seed=0, first_rep=0):
+        """every slot anew: the counts of replicate numbers first_rep .. first_rep + n_reps - 1 under `seed`, the uniform start"""
+        _check(lib().qm_boot_resample(self._h, int(seed) & (2 ** 64 - 1), int(first_rep)))
+
+    def set_counts(self, rep, counts):
+        """one slot's counts as given, in the order of Quant.classes(); the slot starts anew"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if counts.size != self.n_classes:
+            raise ValueError("one count per class")
+        _check(lib().qm_boot_set_counts(self._h, int(rep), counts.ctypes.data if counts.size else None))
+
+    def counts(self, rep):
+        """one slot's counts: uint64[classes], in the order of Quant.classes()"""
+        c = np.zeros(self.n_classes, dtype=np.uint64)
+        _check(lib().qm_boot_fetch_counts(self._h, int(rep), c.ctypes.data if c.size else None))
+        return c
+
+    def run(self, max_iter=Quant.DEFAULTS["max_iter"], check_every=Quant.DEFAULTS["check_every"], rel_tol=Quant.DEFAULTS["rel_tol"],
+            min_alpha=Quant.DEFAULTS["min_alpha"]):
+        """Quant.run per replicate -> (iterations int32[n_reps] of this call, last relative change float64[n_reps]); a replicate that
+        stopped is frozen, a later run goes on with the others"""
+        it = np.zeros(self.n_reps, dtype=np.int32); rel = np.zeros(self.n_reps, dtype=np.float64)
+        _check(lib().qm_boot_run(self._h, int(max_iter), int(check_every), float(rel_tol), float(min_alpha), it.ctypes.data, rel.ctypes.data))
+        return it, rel
+
+    def fetch(self):
+        """the current alphas: float64[n_reps, n_txps]"""
+        a = np.zeros((self.n_reps, self.n_txps), dtype=np.float64)
+        _check(lib().qm_boot_fetch(self._h, a.ctypes.data if a.size else None))
+        return a
+
+    def stat(self):
+        """qm_boot_stat: a dictionary of STATS (last_resample_us, last_run_us: by HIP events on the stream)"""
+        d = {}
+        for i, k in enumerate(self.STATS):
+            v = C.c_int64()
+            _check(lib().qm_boot_stat(self._h, i, C.byref(v)))
+            d[k] = v.value
+        return d
+
+    def close(self):
+        if self._h:
+            lib().qm_boot_destroy(self._h)
+            self._h = C.c_void_p()
+            self._quant = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_bootstraps(path, alphas):
+    """Salmon's bootstraps.gz: gzip of B x n_txps little-endian float64, row-major, transcripts in quant.sf order"""
+    import gzip
+    a = np.ascontiguousarray(alphas, dtype="<f8")
+    if a.ndim != 2:
+        raise ValueError("alphas: [replicates, transcripts]")
+    with gzip.open(path, "wb") as f:
+        f.write(a.tobytes())
+
+
+def read_bootstraps(path, n_txps):
+    """the inverse of write_bootstraps: float64[B, n_txps]"""
+    import gzip
+    with gzip.open(path, "rb") as f:
+        raw = f.read()
+    if n_txps <= 0 or len(raw) % (8 * n_txps):
+        raise ValueError("%s: %d bytes are no whole number of rows of %d float64" % (path, len(raw), n_txps))
+    return np.frombuffer(raw, dtype="<f8").astype(np.float64).reshape(-1, n_txps)
 
 
 QUANT_HEADER = "Name\tLength\tEffectiveLength\tTPM\tNumReads"

@@ -99,4 +99,21 @@ hipError_t qmk_quant_scan(void* temp, size_t temp_bytes, const unsigned int* in,
 size_t qmk_quant_sort_temp_bytes(long long n);
 hipError_t qmk_quant_sort(void* temp, size_t temp_bytes, const unsigned int* tid_in, unsigned int* tid_out, const unsigned int* cls_in, unsigned int* cls_out,
                           long long n, hipStream_t st);
+// bootstrap replicates of the EM (qm_boot.inl; draw / book / state: BootDraw, BootBook, BootState by address)
+hipError_t qmk_boot_counts(const double* dcnt, long long nc, unsigned long long* out, hipStream_t st);
+hipError_t qmk_boot_rowflag(const long long* off, long long n, unsigned int* flag, hipStream_t st);
+hipError_t qmk_boot_resample(const void* draw, long long n_slots, int aggregate, hipStream_t st);
+hipError_t qmk_boot_single(const long long* coff, const unsigned int* clab, long long nc, const unsigned long long* cnt, double* single, long long bp, hipStream_t st);
+hipError_t qmk_boot_column(const long long* coff, const unsigned int* clab, long long nc, unsigned long long* cnt, double* single, long long bp, long long slot,
+                           unsigned long long* col, int put, hipStream_t st);
+hipError_t qmk_boot_start(const long long* toff, const double* eff, long long n_txps, double value, double* alpha, double* w, long long bp, long long s0, long long ns, hipStream_t st);
+hipError_t qmk_boot_reset(const void* book, long long s0, long long ns, hipStream_t st);
+hipError_t qmk_boot_begin(const void* book, long long n_reps, hipStream_t st);
+hipError_t qmk_boot_mark(const void* book, long long n_reps, int it, double rel_tol, hipStream_t st);
+hipError_t qmk_boot_end(const void* book, long long n_reps, int it, hipStream_t st);
+hipError_t qmk_boot_transpose(const double* alpha, long long n_txps, long long bp, long long n_reps, double* out, hipStream_t st);
+hipError_t qmk_boot_class(const void* state, hipStream_t st);
+hipError_t qmk_boot_txp(const void* state, hipStream_t st);
+size_t qmk_boot_scan_temp_bytes(long long n);
+hipError_t qmk_boot_scan(void* temp, size_t temp_bytes, const unsigned long long* in, unsigned long long* out, long long n, hipStream_t st);
 }

@@ -2015,3 +2015,4 @@ int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
 // the equivalence-class table (qm_eqc_*): its host driver reads the context's last result
 #include "qm_eqc_host.inl"
 #include "qm_quant_host.inl"
+#include "qm_boot_host.inl"

@@ -17,6 +17,7 @@ struct qm_quant {
   DevBuf<double> d_cnt, d_eff, d_single, d_w, d_r, d_alpha[2]; int cur = 0;     // alpha: two buffers, d_alpha[cur] holds the current one
   DevBuf<u64> d_scal; u64 h[QNT_SC_WORDS] = {0}; PinBuf<u64> h_rel;
   DevBuf<unsigned char> d_tmp;                                        // rocPRIM's scratch (structure build)
+  int boots = 0;                                                      // live qm_boot objects that borrow the graph and the stream (qm_boot_host.inl)
   hipEvent_t ev0 = nullptr, ev1 = nullptr; int64_t lastRunUs = 0, buildUs = 0;   // around the last run / the structure build on its stream (QM_QUANT_STAT_LAST_RUN_US, _BUILD_US)
 };
 
@@ -124,6 +125,7 @@ int qm_quant_create(qm_eqc* t, int64_t n_txps, const double* eff_len, qm_quant**
 
 int qm_quant_destroy(qm_quant* q) {
   if (!q) return QM_OK;
+  if (q->boots > 0) return fail(QM_E_STATE, "qm_quant_destroy: %d bootstrap object(s) still borrow this quant object", q->boots);
   hipSetDevice(q->device);
   if (q->stream) hipStreamSynchronize(q->stream);
   if (q->ev0) hipEventDestroy(q->ev0);

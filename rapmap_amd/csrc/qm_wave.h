@@ -193,6 +193,11 @@ QM_DEV double wave_sum_f64(const LV<double>& x) {
   group_sum_f64(t, 16);
   return (t.v[0] + t.v[16]) + (t.v[32] + t.v[48]);
 }
+// the four quarters of the wavefront (lanes 0-15, 16-31, 32-47, 48-63) added lane for lane (qm_boot.inl): every lane ends with
+// (q0 + q1) + (q2 + q3) of its column l % 16 -- the lanes of quarters 1 and 3 add the same pairs the other way round, the same bits
+QM_DEV void quarters_sum_f64(LV<double>& x) {
+  for (int s = 16; s <= 32; s <<= 1) { LV<double> t; for (int l = 0; l < 64; ++l) t.v[l] = x.v[l] + x.v[l ^ s]; x = t; }
+}
 #else
 // DPP reductions (profiles/microbench/dpp_check.hip: row_shr:n gives lane i the value of lane i - n of its row of 16;
 // a lane without a source keeps `old`).  A step is one VALU instruction and no trip through the LDS crossbar --
@@ -399,6 +404,19 @@ QM_DEV double wave_sum_f64(const LV<double>& x) {
   LV<double> t = x;
   group_sum_f64(t, 16);
   return (read_lane(t, 0) + read_lane(t, 16)) + (read_lane(t, 32) + read_lane(t, 48));
+}
+// the four quarters of the wavefront added lane for lane (see the emulation above): across rows of 16 there is no DPP pairing, so
+// the two steps go through the LDS crossbar (ds_bpermute), a double as its two dwords; all 64 lanes must be active
+QM_DEV double shfl_xor_f64(double v, int mask) {
+  const u64 b = __builtin_bit_cast(u64, v);
+  const u32 lo = (u32)__shfl_xor((int)(u32)b, mask, 64), hi = (u32)__shfl_xor((int)(u32)(b >> 32), mask, 64);
+  return __builtin_bit_cast(double, ((u64)hi << 32) | lo);
+}
+QM_DEV void quarters_sum_f64(LV<double>& x) {
+  double v = x.v[0];
+  v += shfl_xor_f64(v, 16);
+  v += shfl_xor_f64(v, 32);
+  x.v[0] = v;
 }
 #endif
 
