@@ -448,6 +448,60 @@ int qm_boot_stat(const qm_boot* b, int which, int64_t* value);
 /* no counterpart in the reference; consumer of qm_quant */
 int qm_boot_destroy(qm_boot* b);
 
+/* ---- fragment-length distribution and effective lengths from the mapped pairs ---------------------------------------------
+ * (No counterpart in the reference; consumer of the hit records.)  A qm_fld is a histogram fragment length -> number of fragments
+ * in the device memory of a context's GPU: count[l], 0 <= l <= max_len, unsigned 64-bit; bin 0 exists and is never used.  A batch
+ * is folded where it lies.  Every unit u of a batch falls into exactly one of six categories -- the first condition that holds --,
+ * each with a 64-bit counter; the six always add up to the units folded:
+ *     unmapped      hit_offsets[u + 1] - hit_offsets[u] == 0
+ *     multi         ... >= 2
+ *     not_paired    the one hit has mate_status != 3 (PE_PAIRED)
+ *     same_strand   fwd == mate_is_fwd (where fragLengthPedantic answers 0)
+ *     out_of_range  frag_len == 0 or frag_len > max_len, compared as unsigned 32-bit numbers (a wrapped negative lands here)
+ *     used          otherwise: count[frag_len] += 1
+ * The length is the record's frag_len as it stands (what pair_merge / unit_merge / sel_unit_merge set, as mergeLeftRightHits does,
+ * include/RapMapUtils.hpp:1185-1264); it is NOT clipped to the transcript's end.  A single-end batch is valid: every mapped unit
+ * is not_paired.  Integer adds only: a histogram does not depend on the grid or on the order the wavefronts arrive in.
+ * Effective lengths, a defined model of this project (no prior, no smoothing; not Salmon's, and not held against it): with
+ * P[m] = sum of count[l] and Q[m] = sum of l * count[l] over 1 <= l <= m, both 64-bit integers, a transcript of length L has,
+ * with m = min(L, max_len),
+ *     e = (double)L                                          when P[m] == 0
+ *     e = (double)(L + 1) - (double)Q[m] / (double)P[m]      otherwise (one division, one subtraction, nothing fused)
+ * -- the length minus the mean of the fragment lengths that fit, plus one; e >= 1 without a clamp.  A caller who wants a prior
+ * adds pseudo-counts (qm_fld_add_counts).  Not thread-safe (one per context / host thread; merge with qm_fld_add_counts). */
+typedef struct qm_fld qm_fld;
+#define QM_FLD_DEFAULT_MAX_LEN 1000
+/* no counterpart in the reference; consumer of the hit records.  1 <= max_len <= 1023 (max_len + 1 bins of 4 bytes are one 4 KB
+ * slab per wavefront): 0 or negative is QM_E_ARG, above 1023 QM_E_UNSUPPORTED.  flags & 0xffff: at most that many workgroups per
+ * fold (0 = as many as are resident; tests, tuning); other bits must be 0. */
+int qm_fld_create(qm_ctx* ctx, int32_t max_len, uint32_t flags, qm_fld** out);
+/* no counterpart in the reference; consumer of the hit records */
+int qm_fld_destroy(qm_fld* f);
+/* no counterpart in the reference; consumer of the hit records.  Bins and counters back to zero. */
+int qm_fld_clear(qm_fld* f);
+/* no counterpart in the reference; consumer of the hit records.  Folds the result of ctx's last map call (what qm_result_device
+ * names) where it lies, on ctx's stream, before anything can overwrite it.  QM_E_STATE without a result, QM_E_ARG when histogram
+ * and context are on different devices. */
+int qm_fld_add(qm_fld* f, qm_ctx* ctx);
+/* no counterpart in the reference; consumer of the hit records.  The same kernel over arrays in HOST memory, uploaded in parts.
+ * hits may be NULL when no unit has a hit. */
+int qm_fld_add_hits(qm_fld* f, int64_t n_units, const int64_t* hit_offsets, const qm_hit* hits);
+/* no counterpart in the reference; consumer of the hit records.  count[l] += counts[l]: the merge primitive (contexts, devices,
+ * ranks) and the way to a prior.  Their sum is added to `used` and to the units.  counts[0] != 0: QM_E_ARG. */
+int qm_fld_add_counts(qm_fld* f, const uint64_t* counts /*[max_len+1]*/);
+/* no counterpart in the reference; consumer of the hit records */
+int qm_fld_fetch(qm_fld* f, uint64_t* counts /*[max_len+1]*/);
+/* no counterpart in the reference; consumer of the hit records.  Since creation / the last clear: the units folded, the six
+ * categories, max_len, the folds, and the last fold's kernel in microseconds, by HIP events on the fold's stream */
+enum { QM_FLD_STAT_UNITS = 0, QM_FLD_STAT_USED = 1, QM_FLD_STAT_UNMAPPED = 2, QM_FLD_STAT_MULTI = 3, QM_FLD_STAT_NOT_PAIRED = 4, QM_FLD_STAT_SAME_STRAND = 5,
+       QM_FLD_STAT_OUT_OF_RANGE = 6, QM_FLD_STAT_MAX_LEN = 7, QM_FLD_STAT_FOLDS = 8, QM_FLD_STAT_LAST_FOLD_US = 9 };
+int qm_fld_stat(const qm_fld* f, int which, int64_t* value);
+/* no counterpart in the reference; consumer of the hit records.  The arithmetic above as a pure host function: no device, no
+ * context.  lens[i] == 0, counts[0] != 0, max_len < 1: QM_E_ARG; max_len > 1023, or Q[max_len] reaching 2^53: QM_E_UNSUPPORTED. */
+int qm_fld_eff_lens_from_counts(int32_t max_len, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, const uint32_t* lens, double* eff /*[n_txps]*/);
+/* no counterpart in the reference; consumer of the hit records.  qm_fld_fetch + qm_fld_eff_lens_from_counts. */
+int qm_fld_eff_lens(qm_fld* f, int64_t n_txps, const uint32_t* lens, double* eff /*[n_txps]*/);
+
 /* ---- host-side callers of the path -------------------------------------------
  * Read ingest: replaces fastx_parser::FastxParser<ReadPair|ReadSeq> (include/FastxParser.hpp:62-66,
  * src/FastxParser.cpp:229-328: one kseq producer thread, per-record std::strings).  FASTA/FASTQ, plain or
@@ -493,6 +547,10 @@ int qm_stream_open(const qm_index* ix, int device_id, uint32_t ctx_flags, const 
  * hits of a batch are NULL; n_hits, counters, gpu_ms and device stay as they are. */
 #define QM_STREAM_EQ_CLASSES 2u
 #define QM_STREAM_NO_HITS 4u
+/* QM_STREAM_FLD -- every map context owns a qm_fld of QM_FLD_DEFAULT_MAX_LEN and folds each batch into it after mapping, on the
+ * context's stream, before the batch's buffers are reused; with or without QM_STREAM_EQ_CLASSES (QM_STREAM_NO_HITS keeps its rule:
+ * only together with QM_STREAM_EQ_CLASSES).  qm_stream_fld_fetch sums the contexts' histograms. */
+#define QM_STREAM_FLD 8u
 int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devices, uint32_t ctx_flags, const qm_opts* opts,
                       const char* path1, const char* path2, int64_t batch_units, int32_t reader_threads, uint32_t stream_flags,
                       qm_stream** out);
@@ -507,12 +565,17 @@ int qm_stream_next(qm_stream* s, qm_stream_batch* batch);
  * qm_eqc_add_labels) and reports its size; qm_stream_eqc_fetch then hands it out as qm_eqc_fetch does. */
 int qm_stream_eqc_finish(qm_stream* s, int64_t* n_classes, int64_t* n_tids);
 int qm_stream_eqc_fetch(qm_stream* s, int64_t* label_offsets, uint32_t* tids, uint64_t* counts);
+/* No counterpart in the reference; consumer of the hit records.  Once qm_stream_next has returned the end of the input (where
+ * qm_stream_eqc_finish is valid; QM_E_STATE otherwise, and for a stream opened without QM_STREAM_FLD): the contexts' histograms and
+ * counters summed, across devices.  stats7: the units, then used, unmapped, multi, not_paired, same_strand, out_of_range. */
+int qm_stream_fld_fetch(qm_stream* s, uint64_t* counts /*[QM_FLD_DEFAULT_MAX_LEN+1]*/, int64_t* stats7);
 void qm_stream_close(qm_stream* s);
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
- * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 15) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
+ * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 16) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
  * [8] copy tasks, [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that went
- * to the device 2-bit packed, [13] qm_eqc_add of the batches (summed over the contexts), [14] contexts that folded at least one batch */
+ * to the device 2-bit packed, [13] qm_eqc_add of the batches (summed over the contexts), [14] contexts that folded at least one batch,
+ * [15] qm_fld_add of the batches of a QM_STREAM_FLD stream (seconds, summed over the contexts; not part of [1], [2] or [13]) */
 int qm_stream_stats(qm_stream* s, double* out6);
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n);
 const char* qm_stream_last_error(void);

@@ -81,6 +81,9 @@ def _quasimap(argv):
     ap.add_argument("--quantRelTol", type=float, default=1e-2, help="[only with quant]: stop when no abundance changes by more than this fraction")
     ap.add_argument("--quantFragLenMean", type=float, default=0.0, metavar="F", help="[only with quant]: effective length = max(1, Length - F + 1); "
                     "the default 0 takes the transcript length itself.  The fragment-length distribution is NOT estimated from the mapped pairs")
+    ap.add_argument("--quantFLD", action="store_true", help="[only with quant, paired-end reads]: learn the fragment-length distribution from the "
+                    "run's uniquely and properly paired fragments on the GPU; effective length = Length + 1 - (mean of the fragment lengths "
+                    "that fit the transcript); the distribution is written to FILE.flenDist.txt.  Not together with --quantFragLenMean")
     ap.add_argument("--numBootstraps", type=int, default=0, metavar="B", help="[only with quant]: B bootstrap replicates of the estimate on the GPU (the "
                     "class counts resampled, the EM run again per replicate, 64 replicates at a time), written to FILE.bootstraps.gz in the "
                     "layout of Salmon's bootstraps.gz: B x transcripts little-endian float64")
@@ -91,6 +94,12 @@ def _quasimap(argv):
         ap.error("--numBootstraps needs --quant")
     if a.numBootstraps < 0:
         ap.error("--numBootstraps must not be negative")
+    if a.quantFLD and not a.quant:
+        ap.error("--quantFLD needs --quant")
+    if a.quantFLD and a.quantFragLenMean:
+        ap.error("--quantFLD learns the fragment lengths from the run: not together with --quantFragLenMean")
+    if a.quantFLD and not (a.leftMates and a.rightMates):
+        ap.error("--quantFLD needs paired-end reads (-1 and -2)")
 
     paired = bool(a.leftMates and a.rightMates)
     single = bool(a.unmatedReads)
@@ -190,10 +199,13 @@ def _quasimap(argv):
     keep = [ra.QuasiMapper(qi, d) for d in sorted(set(devices))]
     # --eqClasses: every stream folds its batches on the devices; the streams' merged tables (one per file) meet in this one
     classes = ra.EqClasses(keep[0]) if a.eqClasses or a.quant else None
+    # --quantFLD: every stream folds its batches into fragment-length histograms as well; their sums (one per file) meet here
+    fld_counts = np.zeros(ra.FLD_DEFAULT_MAX_LEN + 1, dtype=np.uint64) if a.quantFLD else None
+    fld_stats = dict.fromkeys(ra.FLD_STATS, 0); fld_s = 0.0
     for f1, f2 in pairs:
         os.environ.setdefault("QM_INGEST_PIN", "1")   # a whole-machine job with one ingest engine: its workers on the NUMA node that holds the files' pages
         st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None,
-                             eq_classes=classes is not None, hits=out is not None or classes is None)
+                             eq_classes=classes is not None, hits=out is not None or classes is None, frag_len_dist=a.quantFLD)
         for b in st:
             gpu_ms += b.gpu_ms
             for kk in tot:
@@ -208,6 +220,11 @@ def _quasimap(argv):
                     tot["numReads"], tot["peHits"] / max(1, tot["numReads"]), tot["seHits"] / max(1, tot["numReads"])))
         if classes is not None:
             classes.add_labels(*st.eq_classes())
+        if a.quantFLD:
+            c_, s_ = st.frag_len_dist()
+            fld_counts += c_; fld_s += st.stats()["fld_fold_s"]
+            for kk in fld_stats:
+                fld_stats[kk] += s_[kk]
         log("stream: " + ", ".join("%s %.3f" % kv for kv in st.stats().items()))
         st.close()
     if classes is not None:
@@ -217,7 +234,15 @@ def _quasimap(argv):
         if a.quant:
             # --quant: the EM over the merged table where it lies; n_txps doubles come back
             lens = np.asarray(qi.txp_lens, dtype=np.int64)
-            eff = np.maximum(1.0, lens.astype(np.float64) - a.quantFragLenMean + 1.0) if a.quantFragLenMean else np.maximum(1.0, lens.astype(np.float64))
+            if a.quantFLD:
+                eff = ra.eff_lens_from_counts(fld_counts, lens)
+                ra.write_flen_dist(a.quant + ".flenDist.txt", fld_counts)
+                log("fragment lengths: mean %g, %s, folded in %.3f ms; wrote %s.flenDist.txt" % (
+                    ra.frag_len_mean(fld_counts), ", ".join("%s %d" % (kk, fld_stats[kk]) for kk in ra.FLD_STATS), fld_s * 1e3, a.quant))
+                if not fld_stats["used"]:
+                    log("no usable fragment (uniquely mapped, properly paired, 1 .. %d bases): effective length = length" % ra.FLD_DEFAULT_MAX_LEN)
+            else:
+                eff = np.maximum(1.0, lens.astype(np.float64) - a.quantFragLenMean + 1.0) if a.quantFragLenMean else np.maximum(1.0, lens.astype(np.float64))
             qn = ra.Quant(classes, qi.n_txps, eff)
             iters, rel = qn.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
             ra.write_quant(a.quant, qi.txp_names, lens, eff, qn.fetch())

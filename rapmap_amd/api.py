@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "qm_quant_create", "qm_quant_set_start", "qm_quant_run", "qm_quant_fetch", "qm_quant_stat", "qm_quant_destroy",
     "qm_quant_fetch_classes", "qm_boot_create", "qm_boot_resample", "qm_boot_set_counts", "qm_boot_fetch_counts", "qm_boot_run", "qm_boot_fetch",
     "qm_boot_stat", "qm_boot_destroy",
+    "qm_fld_create", "qm_fld_destroy", "qm_fld_clear", "qm_fld_add", "qm_fld_add_hits", "qm_fld_add_counts", "qm_fld_fetch", "qm_fld_stat",
+    "qm_fld_eff_lens_from_counts", "qm_fld_eff_lens", "qm_stream_fld_fetch",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
 ]
 
@@ -204,6 +206,17 @@ def lib():
     L.qm_boot_fetch.argtypes = [C.c_void_p, C.c_void_p]
     L.qm_boot_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
     L.qm_boot_destroy.argtypes = [C.c_void_p]
+    L.qm_fld_create.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.qm_fld_destroy.argtypes = [C.c_void_p]
+    L.qm_fld_clear.argtypes = [C.c_void_p]
+    L.qm_fld_add.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_fld_add_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_fld_add_counts.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_fld_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_fld_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_fld_eff_lens_from_counts.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_fld_eff_lens.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_stream_fld_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -877,6 +890,125 @@ def read_quant(path):
     return names, np.array(cols[0], dtype=np.int64), np.array(cols[1], dtype=np.float64), np.array(cols[2], dtype=np.float64), np.array(cols[3], dtype=np.float64)
 
 
+FLD_DEFAULT_MAX_LEN = 1000                                            # QM_FLD_DEFAULT_MAX_LEN
+FLD_STATS = ("units", "used", "unmapped", "multi", "not_paired", "same_strand", "out_of_range")
+
+
+def _fld_lens(lens):
+    a = np.asarray(lens)
+    if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+        raise ValueError("transcript lengths must fit 32 unsigned bits")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def eff_lens_from_counts(counts, lens):
+    """qm_fld_eff_lens_from_counts, a pure host function: effective lengths float64[len(lens)] from a fragment-length histogram
+    counts uint64[max_len + 1] -- e = L + 1 - (mean of the fragment lengths up to min(L, max_len)), e = L where there are none"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64); lens = _fld_lens(lens)
+    eff = np.zeros(lens.size, dtype=np.float64)
+    _check(lib().qm_fld_eff_lens_from_counts(int(counts.size) - 1, counts.ctypes.data if counts.size else None, int(lens.size),
+                                             lens.ctypes.data if lens.size else None, eff.ctypes.data if lens.size else None))
+    return eff
+
+
+def frag_len_mean(counts):
+    """Q / P over all bins of a histogram: the mean fragment length, nan when it is empty"""
+    c = [int(x) for x in np.asarray(counts, dtype=np.uint64)]
+    p = sum(c[1:]); q = sum(l * c[l] for l in range(1, len(c)))
+    return q / p if p else float("nan")
+
+
+def write_flen_dist(path, counts):
+    """one line of max_len + 1 tab-separated values count[l] / used, %.17g (every value 0 when nothing was used)"""
+    c = np.asarray(counts, dtype=np.uint64)
+    used = int(c.sum())
+    with open(path, "w") as f:
+        f.write("\t".join("%.17g" % (int(x) / used if used else 0.0) for x in c) + "\n")
+
+
+def read_flen_dist(path):
+    """the inverse of write_flen_dist: float64[max_len + 1]"""
+    with open(path) as f:
+        return np.array([float(x) for x in f.readline().rstrip("\n").split("\t")], dtype=np.float64)
+
+
+class FragLenDist:
+    """qm_fld_*: a histogram fragment length -> fragments in the device memory of a mapper's GPU.  add(mapper) folds the mapper's
+    last result where it lies; add_hits folds arrays held on the host through the same kernel; add_counts adds another histogram's
+    counts (the merge primitive, and the way to a prior).  Only a unit with exactly one hit that is properly paired, on opposite
+    strands and of 1 .. max_len bases counts; stat() tells where the others went.  max_blocks: at most that many workgroups per
+    fold (0: as many as are resident)."""
+
+    STATS = FLD_STATS + ("max_len", "folds", "last_fold_us")
+
+    def __init__(self, mapper, max_len=FLD_DEFAULT_MAX_LEN, max_blocks=0):
+        self._h = C.c_void_p()
+        if not 0 <= int(max_blocks) <= 0xffff:
+            raise ValueError("max_blocks must be 0 .. 65535")
+        _check(lib().qm_fld_create(mapper._h, int(max_len), int(max_blocks), C.byref(self._h)))
+        self.device = mapper.device
+        self.max_len = int(max_len)
+
+    def add(self, mapper):
+        """fold the result of the mapper's last map call"""
+        _check(lib().qm_fld_add(self._h, mapper._h))
+
+    def add_hits(self, hit_offsets, hits):
+        hit_offsets = np.ascontiguousarray(hit_offsets, dtype=np.int64)
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE) if hits is not None else np.zeros(0, dtype=HIT_DTYPE)
+        n = len(hit_offsets) - 1
+        if n < 0:
+            raise ValueError("hit_offsets needs n + 1 entries")
+        if n and int(hit_offsets[-1]) > hits.size:
+            raise ValueError("hit_offsets point beyond hits")
+        _check(lib().qm_fld_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
+
+    def add_counts(self, counts):
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if counts.size != self.max_len + 1:
+            raise ValueError("max_len + 1 counts")
+        _check(lib().qm_fld_add_counts(self._h, counts.ctypes.data))
+
+    def counts(self):
+        """uint64[max_len + 1]; bin 0 is never used"""
+        c = np.zeros(self.max_len + 1, dtype=np.uint64)
+        _check(lib().qm_fld_fetch(self._h, c.ctypes.data))
+        return c
+
+    def stat(self):
+        """qm_fld_stat: a dictionary of STATS (the six categories add up to units; last_fold_us: the last fold's kernel by HIP events)"""
+        d = {}
+        for i, k in enumerate(self.STATS):
+            v = C.c_int64()
+            _check(lib().qm_fld_stat(self._h, i, C.byref(v)))
+            d[k] = v.value
+        return d
+
+    def eff_lens(self, lens):
+        """qm_fld_eff_lens: effective lengths float64[len(lens)] from the histogram as it stands"""
+        lens = _fld_lens(lens)
+        eff = np.zeros(lens.size, dtype=np.float64)
+        _check(lib().qm_fld_eff_lens(self._h, int(lens.size), lens.ctypes.data if lens.size else None, eff.ctypes.data if lens.size else None))
+        return eff
+
+    def mean(self):
+        return frag_len_mean(self.counts())
+
+    def clear(self):
+        _check(lib().qm_fld_clear(self._h))
+
+    def close(self):
+        if self._h:
+            lib().qm_fld_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 PACK_EXC_DTYPE = np.dtype([("pos", "<u4"), ("ch", "<u4")])
 
 
@@ -1002,10 +1134,11 @@ class MappedStream:
     objects that also carry hit_offsets / hits / counters / device; every array is a zero-copy view that stays valid until
     the next batch is taken.  names=False: read names are not kept (hits-only callers).  eq_classes=True: every batch is folded
     into equivalence classes on its device (eq_classes() after the last batch); with hits=False on top the hits stay on the
-    device -- hit_offsets / hits of a batch are None, n_hits and counters as ever."""
+    device -- hit_offsets / hits of a batch are None, n_hits and counters as ever.  frag_len_dist=True: every batch is folded into a
+    fragment-length histogram on its device as well (frag_len_dist() after the last batch)."""
 
     def __init__(self, index: QuasiIndex, path1, path2=None, opts=None, device=0, batch_units=1 << 20, threads=None, ph_compact=False,
-                 names=True, eq_classes=False, hits=True):
+                 names=True, eq_classes=False, hits=True, frag_len_dist=False):
         self._h = C.c_void_p()
         self.paired = path2 is not None
         self.names = bool(names)
@@ -1020,7 +1153,7 @@ class MappedStream:
         rc = lib().qm_stream_open_ex(index._h, darr, len(devs), 1 if ph_compact else 0, C.byref(opts), os.fsencode(path1),
                                      os.fsencode(path2) if path2 else None, int(batch_units),
                                      int(threads or min(32, os.cpu_count() or 1)),
-                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4), C.byref(self._h))
+                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0), C.byref(self._h))
         if rc != 0:
             raise QmError("qm_stream_open failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
         self._index = index
@@ -1068,13 +1201,22 @@ class MappedStream:
             raise QmError("qm_stream_eqc_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
         return off, tids[:nt.value], cnt[:nc.value]
 
+    def frag_len_dist(self):
+        """after the last batch of a stream opened with frag_len_dist=True: (counts uint64[1001], stats) summed over the stream's
+        contexts and devices -- stats: a dictionary of units and the six categories (FLD_STATS)"""
+        c = np.zeros(FLD_DEFAULT_MAX_LEN + 1, dtype=np.uint64); st = np.zeros(7, dtype=np.int64)
+        rc = lib().qm_stream_fld_fetch(self._h, c.ctypes.data, st.ctypes.data)
+        if rc != 0:
+            raise QmError("qm_stream_fld_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        return c, dict(zip(FLD_STATS, (int(x) for x in st)))
+
     def stats(self):
         """seconds: read_s = open to the last batch packed (wall), map_s / fetch_s = upload + kernels / download summed over the
         contexts, parse_cpu_s / copy_cpu_s = the ingest workers' task time summed over the workers"""
-        a = (C.c_double * 15)()
-        _check(lib().qm_stream_stats_ex(self._h, a, 15))
+        a = (C.c_double * 16)()
+        _check(lib().qm_stream_stats_ex(self._h, a, 16))
         return dict(zip(("read_s", "map_s", "fetch_s", "caller_wait_s", "open_s", "alloc_s", "first_batch_s", "parse_cpu_s", "copy_cpu_s",
-                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts"), [float(x) for x in a]))
+                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts", "fld_fold_s"), [float(x) for x in a]))
 
     def close(self):
         if self._h:

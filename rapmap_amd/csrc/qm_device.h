@@ -116,4 +116,8 @@ hipError_t qmk_boot_class(const void* state, hipStream_t st);
 hipError_t qmk_boot_txp(const void* state, hipStream_t st);
 size_t qmk_boot_scan_temp_bytes(long long n);
 hipError_t qmk_boot_scan(void* temp, size_t temp_bytes, const unsigned long long* in, unsigned long long* out, long long n, hipStream_t st);
+// the fragment-length histogram (qm_fld.inl; src / acc: FldSrc, FldAcc by address).  blocks: workgroups of the persistent grid
+// (qmk_fld_grid: as many as are resident on num_cu compute units and have work, at most max_blocks when that is not 0)
+int qmk_fld_grid(long long n_units, int num_cu, int max_blocks);
+hipError_t qmk_fld_fold(const void* src, const void* acc, int blocks, hipStream_t st);
 }

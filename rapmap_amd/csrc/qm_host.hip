@@ -2016,3 +2016,4 @@ int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
 #include "qm_eqc_host.inl"
 #include "qm_quant_host.inl"
 #include "qm_boot_host.inl"
+#include "qm_fld_host.inl"

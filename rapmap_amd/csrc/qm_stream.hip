@@ -110,6 +110,9 @@ struct qm_stream {
   bool eqClasses = false, noHits = false, eqcMerged = false, ended = false;
   std::vector<int64_t> eqcFolds;           // batches every context folded
   double tFold = 0;                        // seconds in qm_eqc_add (summed over the contexts)
+  std::vector<qm_fld*> fld;                // QM_STREAM_FLD: one fragment-length histogram per context, summed by qm_stream_fld_fetch
+  bool fldOn = false;
+  double tFld = 0;                         // seconds in qm_fld_add (summed over the contexts)
   std::vector<OutSlot> slots;
   std::mutex mu; std::condition_variable cv;
   int64_t nextOut = 0;
@@ -154,6 +157,8 @@ static void map_loop(qm_stream* s, int which) {
     t1 = now_s();
     double tf = 0;
     if (!rc && s->eqClasses) { rc = qm_eqc_add(s->eqc[(size_t)which], c); tf = now_s() - t1; t1 += tf; }   // folded where it lies, before the next call overwrites it
+    double tl = 0;
+    if (!rc && s->fldOn) { rc = qm_fld_add(s->fld[(size_t)which], c); tl = now_s() - t1; t1 += tl; }          // ... and so is the histogram
     if (!rc && s->noHits) {
       t2 = now_s();
       double a = 0, b = 0;
@@ -172,7 +177,7 @@ static void map_loop(qm_stream* s, int which) {
     std::unique_lock<std::mutex> lk(s->mu);
     if (rc) { if (!s->failed) { s->failed = rc; snprintf(s->err, sizeof(s->err), "%s", rc == QM_E_NOMEM ? "out of pinned memory" : qm_last_error()); } break; }
     S.state = 2;
-    s->tMap += t1 - t0 - tf; s->tFold += tf; if (s->eqClasses) s->eqcFolds[(size_t)which]++; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
+    s->tMap += t1 - t0 - tf - tl; s->tFold += tf; s->tFld += tl; if (s->eqClasses) s->eqcFolds[(size_t)which]++; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
     s->cv.notify_all();
   }
   std::unique_lock<std::mutex> lk(s->mu);
@@ -192,6 +197,7 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
   s->t0 = now_s();
   s->ix = ix; s->opts = *opts; s->paired = path2 != nullptr;
   s->eqClasses = (stream_flags & QM_STREAM_EQ_CLASSES) != 0; s->noHits = (stream_flags & QM_STREAM_NO_HITS) != 0;
+  s->fldOn = (stream_flags & QM_STREAM_FLD) != 0;
   { const char* np = getenv("QM_STREAM_NO_PACK"); s->packed = !(np && atoi(np) != 0); }
   const char* cpd = getenv("QM_STREAM_CTX_PER_DEVICE");
   // contexts (map threads) per device: each uploads, maps and downloads its batch in turn, so several of them keep the link and
@@ -235,6 +241,18 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
     if (rc) {
       sfail(rc, qm_last_error());
       qm_ingest_cancel(s->g);
+      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
+      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
+      qm_ingest_close(s->g); delete s; return rc;
+    }
+  }
+  if (s->fldOn) {
+    s->fld.assign((size_t)nctx, nullptr);
+    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_fld_create(s->ctx[(size_t)i], QM_FLD_DEFAULT_MAX_LEN, 0, &s->fld[(size_t)i]); }
+    if (rc) {
+      sfail(rc, qm_last_error());
+      qm_ingest_cancel(s->g);
+      for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
       for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
       for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
       qm_ingest_close(s->g); delete s; return rc;
@@ -338,22 +356,40 @@ int qm_stream_eqc_fetch(qm_stream* s, int64_t* label_offsets, uint32_t* tids, ui
   return rc ? sfail(rc, qm_last_error()) : QM_OK;
 }
 
+/* The contexts' fragment-length histograms and counters summed on the host: 8 KB and seven numbers per context. */
+int qm_stream_fld_fetch(qm_stream* s, uint64_t* counts, int64_t* stats7) {
+  if (!s || !counts || !stats7) return sfail(QM_E_ARG, "qm_stream_fld_fetch: bad argument");
+  if (!s->fldOn) return sfail(QM_E_STATE, "qm_stream_fld_fetch: the stream was opened without QM_STREAM_FLD");
+  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_fld_fetch: the input has not ended"); }
+  std::vector<uint64_t> part((size_t)QM_FLD_DEFAULT_MAX_LEN + 1);
+  for (int l = 0; l <= QM_FLD_DEFAULT_MAX_LEN; ++l) counts[l] = 0;
+  for (int i = 0; i < 7; ++i) stats7[i] = 0;
+  for (qm_fld* f : s->fld) {
+    int rc = qm_fld_fetch(f, part.data());
+    for (int i = 0; i < 7 && !rc; ++i) { int64_t v = 0; rc = qm_fld_stat(f, QM_FLD_STAT_UNITS + i, &v); stats7[i] += v; }
+    if (rc) return sfail(rc, qm_last_error());
+    for (int l = 0; l <= QM_FLD_DEFAULT_MAX_LEN; ++l) counts[l] += part[(size_t)l];
+  }
+  return QM_OK;
+}
+
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
  * buffers; qm_stream_stats_ex adds [6] open to the first batch packed, [7] parse tasks (summed over the workers), [8] copy tasks
  * (summed), [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that
  * went to the device 2-bit packed, [13] qm_eqc_add of the batches (QM_STREAM_EQ_CLASSES; not part of [1] or [2]), [14] contexts that
- * folded at least one batch */
+ * folded at least one batch, [15] qm_fld_add of the batches (QM_STREAM_FLD; not part of [1], [2] or [13]) */
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n) {
   if (!s || !out || n < 0) return sfail(QM_E_ARG, "qm_stream_stats: bad argument");
-  double v[15] = {0}; double ing[8] = {0};
+  double v[16] = {0}; double ing[8] = {0};
   qm_ingest_stats(s->g, ing);
   std::unique_lock<std::mutex> lk(s->mu);
   v[0] = ing[6]; v[1] = s->tMap; v[2] = s->tFetch; v[3] = s->tWait; v[4] = s->tOpen; v[5] = s->tAlloc;
   v[6] = ing[0]; v[7] = ing[1]; v[8] = ing[2]; v[9] = ing[3]; v[10] = ing[4]; v[11] = s->tLastMapped;
   v[12] = (double)__atomic_load_n(&s->nPacked, __ATOMIC_RELAXED);
   v[13] = s->tFold; for (int64_t f : s->eqcFolds) v[14] += f > 0 ? 1 : 0;
-  for (int i = 0; i < n && i < 15; ++i) out[i] = v[i];
+  v[15] = s->tFld;
+  for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
   return QM_OK;
 }
 int qm_stream_stats(qm_stream* s, double* out6) { return qm_stream_stats_ex(s, out6, 6); }
@@ -365,6 +401,7 @@ void qm_stream_close(qm_stream* s) {
   for (auto& t : s->mapThreads) if (t.joinable()) t.join();
   for (OutSlot& S : s->slots) { pin_free(S.hitOff); pin_free(S.hits); }
   for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
+  for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
   for (qm_ctx* c : s->ctx) if (c) qm_ctx_destroy(c);
   qm_ingest_close(s->g);
   delete s;

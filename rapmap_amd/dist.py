@@ -2,6 +2,7 @@
 collective -- the sum of the HitCounters (include/RapMapUtils.hpp:208-216) -- after the last batch
 (SURVEY.md section 8e).  torch.distributed is plumbing here: backend "nccl" is RCCL over xGMI on the
 GPU box, "gloo" in the CPU tests."""
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -22,6 +23,18 @@ def all_reduce_counters(counters, device):
     t = torch.tensor([int(counters[k]) for k in COUNTER_KEYS], dtype=torch.int64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.SUM)                # (also with ONE rank under torchrun: the collective library runs, the sum is the input)
     return dict(zip(COUNTER_KEYS, (int(x) for x in t.cpu())))
+
+
+def all_reduce_frag_len_counts(counts, device):
+    """a fragment-length histogram (FragLenDist.counts, MappedStream.frag_len_dist) -> its sum over all ranks: one int64 all_reduce
+    over the bins (8 KB on the wire).  Without a process group the input comes back unchanged, as all_reduce_counters does for
+    counters.  The sum goes into a histogram through FragLenDist.add_counts."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return counts
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    t = torch.from_numpy(c.view(np.int64).copy()).to(device)    # (counts stay far below 2^63: the bits are the same either way)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().numpy().view(np.uint64)
 
 
 def merge_eq_classes(table, mapper=None):
