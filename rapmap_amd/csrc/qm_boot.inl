@@ -13,7 +13,7 @@
 // BOOT_TILE contiguous doubles: four whole 32-byte sectors.  A wavefront takes BOOT_ROWS rows x BOOT_TILE replicates: lane l has
 // row l / 16 of its four and replicate l % 16 of its tile, and reads the index arrays once for the sixteen replicates.
 // Written against qm_wave.h: the same source runs lane by lane under -DQM_EMU (tests/emu/qm_emu_boot.cpp).  Every function here is
-// the body of ONE wavefront; qm_kernels_boot.hip wraps them into kernels.  No floating-point atomic anywhere.
+// the body of ONE wavefront; qm_boot_host.inl launches them (qm_exec.h).  No floating-point atomic anywhere.
 //
 //   boot_counts_wave      the snapshot's counts (doubles in the quant object) as 64-bit integers: what cum is scanned from
 //   boot_rowflag_wave     per row of a side: more than BOOT_LONG items?  (a scan and quant_queue_wave make the side's queue)

@@ -77,45 +77,10 @@ hipError_t qmk_scan_counts_masked(void* temp, size_t temp_bytes, const unsigned 
 hipError_t qmk_stage_gather(long long nreads, const unsigned int* ivcnt, const long long* ivoff, const void* iv, const long long* ivcsr, void* iv_out,
                             const unsigned int* lcnt, const long long* loff, const unsigned long long* lists, const long long* lcsr,
                             unsigned long long* words_out, hipStream_t st);
-// the equivalence-class table (qm_eqc.inl; src / table / set: EqcSrc, EqcTable, EqcSet by address)
-hipError_t qmk_eqc_label(const void* src, hipStream_t st);
+// the kernels of the equivalence-class table that are no plain wave body (src: EqcSrc by address)
 hipError_t qmk_eqc_label_queued(const void* src, long long nq, hipStream_t st);
-hipError_t qmk_eqc_probe(const void* table, const void* set, const unsigned long long* qin, long long nin, unsigned long long* qout, int aggregate, hipStream_t st);
-hipError_t qmk_eqc_publish(const void* table, const void* set, const unsigned long long* q, long long nq, hipStream_t st);
 hipError_t qmk_eqc_reset_probes(unsigned long long* q, long long n, hipStream_t st);
 hipError_t qmk_eqc_sum(const unsigned long long* count, const unsigned long long* key, long long cap, unsigned long long* out, hipStream_t st);
-// the EM over the equivalence-class table (qm_quant.inl; build / state: QuantBuild, QuantState by address)
-hipError_t qmk_quant_mark(const void* build, hipStream_t st);
-hipError_t qmk_quant_compact(const void* build, hipStream_t st);
-hipError_t qmk_quant_bounds(const unsigned int* sorted_tid, long long n, long long n_txps, long long* bound, hipStream_t st);
-hipError_t qmk_quant_rowstat(const long long* off, long long n, unsigned int* flag, unsigned long long* scal, int max_word, int present, hipStream_t st);
-hipError_t qmk_quant_queue(const unsigned int* flag, const long long* pos, long long n, long long* queue, hipStream_t st);
-hipError_t qmk_quant_start(const long long* toff, long long n_txps, double value, double* alpha, hipStream_t st);
-hipError_t qmk_quant_weights(const double* alpha, const double* eff, long long n_txps, double* w, hipStream_t st);
-hipError_t qmk_quant_class(const void* state, hipStream_t st);
-hipError_t qmk_quant_txp(const void* state, hipStream_t st);
-size_t qmk_quant_scan_temp_bytes(long long n);
-hipError_t qmk_quant_scan(void* temp, size_t temp_bytes, const unsigned int* in, long long* out, long long n, hipStream_t st);
-size_t qmk_quant_sort_temp_bytes(long long n);
-hipError_t qmk_quant_sort(void* temp, size_t temp_bytes, const unsigned int* tid_in, unsigned int* tid_out, const unsigned int* cls_in, unsigned int* cls_out,
-                          long long n, hipStream_t st);
-// bootstrap replicates of the EM (qm_boot.inl; draw / book / state: BootDraw, BootBook, BootState by address)
-hipError_t qmk_boot_counts(const double* dcnt, long long nc, unsigned long long* out, hipStream_t st);
-hipError_t qmk_boot_rowflag(const long long* off, long long n, unsigned int* flag, hipStream_t st);
-hipError_t qmk_boot_resample(const void* draw, long long n_slots, int aggregate, hipStream_t st);
-hipError_t qmk_boot_single(const long long* coff, const unsigned int* clab, long long nc, const unsigned long long* cnt, double* single, long long bp, hipStream_t st);
-hipError_t qmk_boot_column(const long long* coff, const unsigned int* clab, long long nc, unsigned long long* cnt, double* single, long long bp, long long slot,
-                           unsigned long long* col, int put, hipStream_t st);
-hipError_t qmk_boot_start(const long long* toff, const double* eff, long long n_txps, double value, double* alpha, double* w, long long bp, long long s0, long long ns, hipStream_t st);
-hipError_t qmk_boot_reset(const void* book, long long s0, long long ns, hipStream_t st);
-hipError_t qmk_boot_begin(const void* book, long long n_reps, hipStream_t st);
-hipError_t qmk_boot_mark(const void* book, long long n_reps, int it, double rel_tol, hipStream_t st);
-hipError_t qmk_boot_end(const void* book, long long n_reps, int it, hipStream_t st);
-hipError_t qmk_boot_transpose(const double* alpha, long long n_txps, long long bp, long long n_reps, double* out, hipStream_t st);
-hipError_t qmk_boot_class(const void* state, hipStream_t st);
-hipError_t qmk_boot_txp(const void* state, hipStream_t st);
-size_t qmk_boot_scan_temp_bytes(long long n);
-hipError_t qmk_boot_scan(void* temp, size_t temp_bytes, const unsigned long long* in, unsigned long long* out, long long n, hipStream_t st);
 // the fragment-length histogram (qm_fld.inl; src / acc: FldSrc, FldAcc by address).  blocks: workgroups of the persistent grid
 // (qmk_fld_grid: as many as are resident on num_cu compute units and have work, at most max_blocks when that is not 0)
 int qmk_fld_grid(long long n_units, int num_cu, int max_blocks);

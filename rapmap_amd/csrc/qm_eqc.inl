@@ -2,7 +2,7 @@
 //
 // A unit's LABEL is the ascending list of the distinct transcript ids of its hit list; the table counts the units (or sums the
 // weights) that carried each label.  Written against qm_wave.h: the same source runs lane by lane under -DQM_EMU
-// (tests/emu/qm_emu_eqc.cpp).  Every function here is the body of ONE wavefront; qm_kernels_eqc.hip wraps them into kernels.
+// (tests/emu/qm_emu_eqc.cpp).  Every function here is the body of ONE wavefront; qm_eqc_host.inl launches them (qm_exec.h).
 //
 // Label stage (two launches)
 //   eqc_label_groups<8>   eight units per wavefront, eight lanes each: a unit of up to 8 hits is ranked among its group's lanes

@@ -1,5 +1,6 @@
-// qm_eqc_host.inl -- host driver of the equivalence-class table (device code: qm_eqc.inl, kernels: qm_kernels_eqc.hip).
-// Included at the end of qm_host.hip: qm_eqc_add reads the context's last result where it lies in device memory.
+// qm_eqc_host.inl -- host driver of the equivalence-class table (device code: qm_eqc.inl; the kernels that are no plain wave body:
+// qm_kernels_eqc.hip).  Included at the end of qm_host.hip: qm_eqc_add reads the context's last result where it lies in device memory.
+// Everything above the extern "C" block is written against qm_exec.h and compiled twice: here, and with -DQM_EMU by tests/emu.
 //
 // A fold = label launch (+ queue launch for the units of more than EQC_GROUP hits), then rounds of probe / publish until the
 // pending queue is empty; the host reads the scalar block once per round.  When slots or pool run out (counted by the kernels,
@@ -7,70 +8,100 @@
 // launches as units whose weights are their counts -- and the pending units start over.
 #include <algorithm>
 #include "qm_eqc.inl"
+#include "qm_exec.h"
 
+struct EqcStore {              // the six arrays of a table; EqcTable is a view of them
+  DevBuf<u64> key, claim, count; DevBuf<long long> loff; DevBuf<u32> llen, pool;
+  void swap(EqcStore& o) { key.swap(o.key); claim.swap(o.claim); count.swap(o.count); loff.swap(o.loff); llen.swap(o.llen); pool.swap(o.pool); }
+};
 struct qm_eqc {
-  int device = 0; hipStream_t stream = nullptr; u64 keyMask = ~0ULL; int aggregate = 1;
-  EqcTable T{}; DevBuf<u64> d_scal; u64 h[EQC_SC_WORDS] = {0};
+  int device = 0; qx::Stream stream{}; u64 keyMask = ~0ULL; int aggregate = 1;
+  EqcStore store; EqcTable T{}; DevBuf<u64> d_scal; u64 h[EQC_SC_WORDS] = {0};
   // a fold's scratch
   DevBuf<u32> d_lab, d_len; DevBuf<u64> d_key, d_q[2]; DevBuf<long long> d_longq;
+  int64_t longMin = 1024;                                             // the long-unit queue's least capacity (the emulation starts smaller: the regrow is tested)
   DevBuf<u64> d_gq[2];                                                // the queues of a rebuild
   DevBuf<long long> d_inOff; DevBuf<u32> d_inTids; DevBuf<u64> d_inW; // qm_eqc_add_labels
   int64_t growths = 0, longUnits = 0, rounds = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr; int64_t lastFoldUs = 0;   // around the last fold on its stream (QM_EQC_STAT_LAST_FOLD_US)
+  qx::Event ev0{}, ev1{}; int64_t lastFoldUs = 0;                    // around the last fold on its stream (QM_EQC_STAT_LAST_FOLD_US)
 };
 
-static void eqc_free_table(EqcTable& T) {
-  void* p[] = {T.key, T.claim, T.loff, T.llen, T.count, T.pool};
-  for (void* q : p) if (q) hipFree(q);
-  T.key = T.claim = T.count = nullptr; T.loff = nullptr; T.llen = nullptr; T.pool = nullptr;
+// the kernels that are no plain wave body (qm_kernels_eqc.hip, declared in qm_device.h), as the emulation runs them
+#ifdef QM_EMU
+static int qmk_eqc_label_queued(const void* src, long long nq, qx::Stream) {
+  std::vector<u32> slab(EQC_SLAB);
+  for (long long w = 0; w < nq; ++w) eqc_label_queued(*(const EqcSrc*)src, w, slab.data());
+  return 0;
 }
-static int eqc_alloc_table(qm_eqc* t, u64 cap, u64 poolCap, hipStream_t st, EqcTable& T) {
-  T = EqcTable{};
-  const bool ok = hipMalloc((void**)&T.key, cap * 8) == hipSuccess && hipMalloc((void**)&T.claim, cap * 8) == hipSuccess && hipMalloc((void**)&T.loff, cap * 8) == hipSuccess &&
-                  hipMalloc((void**)&T.llen, cap * 4) == hipSuccess && hipMalloc((void**)&T.count, cap * 8) == hipSuccess && hipMalloc((void**)&T.pool, poolCap * 4) == hipSuccess;
-  if (!ok) { (void)hipGetLastError(); eqc_free_table(T); return fail(QM_E_NOMEM, "no device memory for an equivalence-class table of %llu slots", (unsigned long long)cap); }
-  T.mask = cap - 1; T.maxClasses = cap / 2; T.poolCap = poolCap; T.scal = t->d_scal;
-  HIPCHK(hipMemsetAsync(T.key, 0, cap * 8, st));
-  HIPCHK(hipMemsetAsync(T.llen, 0, cap * 4, st));
-  HIPCHK(hipMemsetAsync(T.count, 0, cap * 8, st));
-  HIPCHK(hipMemsetAsync(T.claim, 0xff, cap * 8, st));
-  return QM_OK;
+static int qmk_eqc_reset_probes(u64* q, long long n, qx::Stream) {
+  for (long long i = 0; i < n; ++i) q[i] &= 0xffffffffULL;
+  return 0;
 }
-static int eqc_read_scalars(qm_eqc* t, hipStream_t st) {
-  HIPCHK(hipMemcpyAsync(t->h, t->d_scal, sizeof(t->h), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return QM_OK;
+static int qmk_eqc_sum(const u64* count, const u64* key, long long cap, u64* out, qx::Stream) {
+  for (long long i = 0; i < cap; ++i) if (key[i]) *out += count[i];
+  return 0;
+}
+#endif
+// (the probe body takes the wavefront's index before its last argument)
+QM_DEV void eqc_probe_body(const EqcTable& T, const EqcSet& S, const u64* qin, long long nin, u64* qout, int aggregate, long long wave) {
+  eqc_probe_wave(T, S, qin, nin, qout, wave, aggregate);
 }
 
-static int eqc_insert(qm_eqc* t, const EqcSet& S, hipStream_t st, u64** q, bool mayGrow);
-static int eqc_grow(qm_eqc* t, hipStream_t st) {
-  EqcTable old = t->T;
+static int eqc_clear_table(const EqcTable& T, qx::Stream st) {
+  const u64 cap = T.mask + 1;
+  QXCHK(qx::fill(st, T.key, 0, cap * 8)); QXCHK(qx::fill(st, T.llen, 0, cap * 4)); QXCHK(qx::fill(st, T.count, 0, cap * 8));
+  return qx::fill(st, T.claim, 0xff, cap * 8);
+}
+// a cleared table of cap slots in `s`, and its view
+static int eqc_alloc_table(qm_eqc* t, u64 cap, u64 poolCap, qx::Stream st, EqcStore& s, EqcTable& T) {
+  if (s.key.ensure((int64_t)cap) || s.claim.ensure((int64_t)cap) || s.loff.ensure((int64_t)cap) || s.llen.ensure((int64_t)cap) || s.count.ensure((int64_t)cap) || s.pool.ensure((int64_t)poolCap))
+    return fail(QM_E_NOMEM, "no device memory for an equivalence-class table of %llu slots", (unsigned long long)cap);
+  T = EqcTable{s.key, s.claim, s.loff, s.llen, s.count, s.pool, cap - 1, cap / 2, poolCap, t->d_scal};
+  return eqc_clear_table(T, st);
+}
+// the scalars and the first table of a new object
+static int eqc_open(qm_eqc* t, u64 cap, u64 poolCap) {
+  int rc;
+  if ((rc = t->d_scal.ensure(EQC_SC_WORDS)) || (rc = qx::fill(t->stream, t->d_scal, 0, sizeof(t->h))) || (rc = eqc_alloc_table(t, cap, poolCap, t->stream, t->store, t->T))) return rc;
+  return qx::sync(t->stream);
+}
+static int eqc_clear(qm_eqc* t) {
+  int rc;
+  if ((rc = eqc_clear_table(t->T, t->stream)) || (rc = qx::fill(t->stream, t->d_scal, 0, sizeof(t->h))) || (rc = qx::sync(t->stream))) return rc;
+  memset(t->h, 0, sizeof(t->h));
+  t->growths = t->longUnits = t->rounds = 0;
+  return QM_OK;
+}
+static int eqc_read_scalars(qm_eqc* t, qx::Stream st) { return qx::read(st, t->h, t->d_scal, sizeof(t->h)); }
+
+static int eqc_insert(qm_eqc* t, const EqcSet& S, qx::Stream st, u64** q, bool mayGrow);
+static int eqc_grow(qm_eqc* t, qx::Stream st) {
+  const EqcTable old = t->T;
   const u64 oldCap = old.mask + 1;
   const bool slots = t->h[EQC_SC_SLOT_OVF] || t->h[EQC_SC_FULL];
   // unit and slot indices travel as 32-bit numbers (queue entries, claim words)
   if (slots && oldCap >= (1ULL << 31)) return fail(QM_E_UNSUPPORTED, "equivalence-class table: more than 2^30 classes (a table cannot grow beyond 2^31 slots)");
   const u64 cap = slots ? (oldCap * 4 > (1ULL << 31) ? (1ULL << 31) : oldCap * 4) : oldCap, poolCap = t->h[EQC_SC_POOL_OVF] ? old.poolCap * 4 : old.poolCap;
   int rc;
-  EqcTable T;
-  if ((rc = eqc_alloc_table(t, cap, poolCap, st, T))) return rc;
-  HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_FULL, 0, 6 * sizeof(u64), st));     // FULL, TICKETS, POOL, CLASSES and the two overflow counts
-  t->T = T;
-  if ((rc = t->d_gq[0].ensure((int64_t)oldCap)) || (rc = t->d_gq[1].ensure((int64_t)oldCap))) { eqc_free_table(old); return rc; }
+  EqcStore s; EqcTable T;                                             // the new arrays; after the swap the old ones, freed on the way out
+  if ((rc = eqc_alloc_table(t, cap, poolCap, st, s, T))) return rc;
+  QXCHK(qx::fill(st, t->d_scal + EQC_SC_FULL, 0, 6 * sizeof(u64)));  // FULL, TICKETS, POOL, CLASSES and the two overflow counts
+  t->store.swap(s); t->T = T;
+  if ((rc = t->d_gq[0].ensure((int64_t)oldCap)) || (rc = t->d_gq[1].ensure((int64_t)oldCap))) return rc;
   const EqcSet R{old.pool, old.loff, old.llen, old.key, old.count, (long long)oldCap};     // empty slots have length 0: skipped like units without hits
   u64* gq[2] = {t->d_gq[0], t->d_gq[1]};
   rc = eqc_insert(t, R, st, gq, false);
-  eqc_free_table(old);
   t->growths++;
   return rc;
 }
 
 // every unit of S into the table; q: two queues of S.n entries each
-static int eqc_insert(qm_eqc* t, const EqcSet& S, hipStream_t st, u64** q, bool mayGrow) {
+static int eqc_insert(qm_eqc* t, const EqcSet& S, qx::Stream st, u64** q, bool mayGrow) {
   const u64* qin = nullptr; long long nin = S.n; int cur = 0, rc;
   for (long long guard = 0;; ++guard) {
     if (guard > (1LL << 40)) return fail(QM_E_STATE, "equivalence-class insert does not end");
-    HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_PEND, 0, 2 * sizeof(u64), st));   // PEND, FULL
-    HIPCHK(qmk_eqc_probe(&t->T, &S, (const unsigned long long*)qin, nin, (unsigned long long*)q[cur], t->aggregate, st));
+    QXCHK(qx::fill(st, t->d_scal + EQC_SC_PEND, 0, 2 * sizeof(u64)));   // PEND, FULL
+    HIPCHK(qx::launch<eqc_probe_body>(st, qx::waves_of(nin), t->T, S, qin, nin, q[cur], t->aggregate));
     t->rounds++;
     if ((rc = eqc_read_scalars(t, st))) return rc;
     const long long pend = (long long)t->h[EQC_SC_PEND];
@@ -78,27 +109,27 @@ static int eqc_insert(qm_eqc* t, const EqcSet& S, hipStream_t st, u64** q, bool 
     if (t->h[EQC_SC_SLOT_OVF] || t->h[EQC_SC_POOL_OVF] || t->h[EQC_SC_FULL]) {
       if (!mayGrow) return fail(QM_E_STATE, "equivalence-class table overflowed while it was rebuilt");
       if ((rc = eqc_grow(t, st))) return rc;
-      HIPCHK(qmk_eqc_reset_probes((unsigned long long*)q[cur], pend, st));
+      HIPCHK(qmk_eqc_reset_probes(q[cur], pend, st));
     }
-    else HIPCHK(qmk_eqc_publish(&t->T, &S, (const unsigned long long*)q[cur], pend, st));
+    else HIPCHK(qx::launch<eqc_publish_wave>(st, qx::waves_of(pend), t->T, S, (const u64*)q[cur], pend));
     qin = q[cur]; nin = pend; cur ^= 1;
   }
 }
 
 // S: tids, stride, off, n filled in; nTids = off[n] (off[0] = 0)
-static int eqc_fold(qm_eqc* t, EqcSrc S, int64_t nTids, const u64* d_w, hipStream_t st) {
+static int eqc_fold(qm_eqc* t, EqcSrc S, int64_t nTids, const u64* d_w, qx::Stream st) {
   if (S.n <= 0 || nTids <= 0) return QM_OK;
   if (S.n >= (1LL << 32)) return fail(QM_E_ARG, "more than 2^32 - 1 units in one fold");
   int rc;
   if ((rc = t->d_lab.ensure(nTids)) || (rc = t->d_len.ensure(S.n)) || (rc = t->d_key.ensure(S.n)) ||
-      (rc = t->d_q[0].ensure(S.n)) || (rc = t->d_q[1].ensure(S.n)) || (rc = t->d_longq.ensure(std::max<int64_t>(1024, S.n / 16)))) return rc;
+      (rc = t->d_q[0].ensure(S.n)) || (rc = t->d_q[1].ensure(S.n)) || (rc = t->d_longq.ensure(std::max<int64_t>(t->longMin, S.n / 16)))) return rc;
   S.lab = t->d_lab; S.len = t->d_len; S.key = t->d_key; S.scal = t->d_scal; S.keyMask = t->keyMask;
-  HIPCHK(hipEventRecord(t->ev0, st));
+  if ((rc = qx::tick(t->ev0, st))) return rc;
   int64_t nl = 0;
   for (int pass = 0;; ++pass) {
     S.longq = t->d_longq; S.longCap = (u64)t->d_longq.cap;
-    HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_LONGQ, 0, sizeof(u64), st));
-    HIPCHK(qmk_eqc_label(&S, st));
+    QXCHK(qx::fill(st, t->d_scal + EQC_SC_LONGQ, 0, sizeof(u64)));
+    HIPCHK(qx::launch<eqc_label_wave>(st, (S.n + 64 / EQC_GROUP - 1) / (64 / EQC_GROUP), S));
     if ((rc = eqc_read_scalars(t, st))) return rc;
     nl = (int64_t)t->h[EQC_SC_LONGQ];
     if (nl <= t->d_longq.cap) break;
@@ -110,13 +141,24 @@ static int eqc_fold(qm_eqc* t, EqcSrc S, int64_t nTids, const u64* d_w, hipStrea
   const EqcSet set{S.lab, S.off, S.len, S.key, d_w, S.n};
   u64* q[2] = {t->d_q[0], t->d_q[1]};
   if ((rc = eqc_insert(t, set, st, q, true))) return rc;
-  HIPCHK(hipEventRecord(t->ev1, st));
-  HIPCHK(hipEventSynchronize(t->ev1));                           // (the stream is idle: the insert ended with a read-back)
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, t->ev0, t->ev1) == hipSuccess) t->lastFoldUs = (int64_t)(ms * 1000.0f + 0.5f);
+  return qx::tock(t->ev0, t->ev1, st, &t->lastFoldUs);              // (the stream is idle: the insert ended with a read-back)
+}
+
+// the counters of the table; with total_count the sum of the published slots' counts (one launch more)
+static int eqc_size(qm_eqc* t, int64_t* n_classes, int64_t* n_tids, uint64_t* total_count) {
+  if (total_count) {
+    QXCHK(qx::fill(t->stream, t->d_scal + EQC_SC_SUM, 0, sizeof(u64)));
+    HIPCHK(qmk_eqc_sum(t->T.count, t->T.key, (long long)(t->T.mask + 1), t->d_scal + EQC_SC_SUM, t->stream));
+  }
+  int rc;
+  if ((rc = eqc_read_scalars(t, t->stream))) return rc;
+  if (n_classes) *n_classes = (int64_t)t->h[EQC_SC_CLASSES];
+  if (n_tids) *n_tids = (int64_t)t->h[EQC_SC_POOL];             // (exact: a fold that ran out of pool rebuilt the table)
+  if (total_count) *total_count = t->h[EQC_SC_SUM];
   return QM_OK;
 }
 
+#ifndef QM_EMU
 extern "C" {
 
 int qm_eqc_create(qm_ctx* c, int64_t expected_classes, uint32_t flags, qm_eqc** out) {
@@ -129,11 +171,9 @@ int qm_eqc_create(qm_ctx* c, int64_t expected_classes, uint32_t flags, qm_eqc** 
   { const char* e = getenv("QM_EQC_NO_AGGREGATE"); t->aggregate = !(e && atoi(e) != 0); }   // (A/B timing of the per-wavefront aggregation: INTEGRATION.md, environment)
   u64 cap = 16; while (cap < 2 * (u64)expected_classes && cap < (1ULL << 31)) cap <<= 1;
   int rc = QM_OK;
-  if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess || t->d_scal.ensure(EQC_SC_WORDS) != QM_OK) rc = fail(QM_E_NOGPU, "qm_eqc_create: stream / scalars");
+  if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: stream");
   if (!rc && (hipEventCreate(&t->ev0) != hipSuccess || hipEventCreate(&t->ev1) != hipSuccess)) rc = fail(QM_E_NOGPU, "qm_eqc_create: events");
-  if (!rc && hipMemsetAsync(t->d_scal, 0, sizeof(t->h), t->stream) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: memset");
-  if (!rc) rc = eqc_alloc_table(t, cap, std::max<u64>(64, 8 * (u64)expected_classes), t->stream, t->T);
-  if (!rc && hipStreamSynchronize(t->stream) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: synchronize");
+  if (!rc) rc = eqc_open(t, cap, std::max<u64>(64, 8 * (u64)expected_classes));
   if (rc) { qm_eqc_destroy(t); return rc; }
   *out = t;
   return QM_OK;
@@ -143,27 +183,17 @@ int qm_eqc_destroy(qm_eqc* t) {
   if (!t) return QM_OK;
   hipSetDevice(t->device);
   if (t->stream) hipStreamSynchronize(t->stream);
-  eqc_free_table(t->T);
   if (t->ev0) hipEventDestroy(t->ev0);
   if (t->ev1) hipEventDestroy(t->ev1);
   if (t->stream) hipStreamDestroy(t->stream);
-  delete t;                    // (the scratch buffers free themselves)
+  delete t;                    // (the table and the scratch buffers free themselves)
   return QM_OK;
 }
 
 int qm_eqc_clear(qm_eqc* t) {
   if (!t) return fail(QM_E_ARG, "null table");
   HIPCHK(hipSetDevice(t->device));
-  const u64 cap = t->T.mask + 1;
-  HIPCHK(hipMemsetAsync(t->T.key, 0, cap * 8, t->stream));
-  HIPCHK(hipMemsetAsync(t->T.llen, 0, cap * 4, t->stream));
-  HIPCHK(hipMemsetAsync(t->T.count, 0, cap * 8, t->stream));
-  HIPCHK(hipMemsetAsync(t->T.claim, 0xff, cap * 8, t->stream));
-  HIPCHK(hipMemsetAsync(t->d_scal, 0, sizeof(t->h), t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  memset(t->h, 0, sizeof(t->h));
-  t->growths = t->longUnits = t->rounds = 0;
-  return QM_OK;
+  return eqc_clear(t);
 }
 
 int qm_eqc_add(qm_eqc* t, qm_ctx* c) {
@@ -206,16 +236,7 @@ int qm_eqc_add_labels(qm_eqc* t, int64_t n, const int64_t* offsets, const uint32
 int qm_eqc_size(qm_eqc* t, int64_t* n_classes, int64_t* n_tids, uint64_t* total_count) {
   if (!t) return fail(QM_E_ARG, "null table");
   HIPCHK(hipSetDevice(t->device));
-  if (total_count) {
-    HIPCHK(hipMemsetAsync(t->d_scal + EQC_SC_SUM, 0, sizeof(u64), t->stream));
-    HIPCHK(qmk_eqc_sum((const unsigned long long*)t->T.count, (const unsigned long long*)t->T.key, (long long)(t->T.mask + 1), (unsigned long long*)(t->d_scal + EQC_SC_SUM), t->stream));
-  }
-  int rc;
-  if ((rc = eqc_read_scalars(t, t->stream))) return rc;
-  if (n_classes) *n_classes = (int64_t)t->h[EQC_SC_CLASSES];
-  if (n_tids) *n_tids = (int64_t)t->h[EQC_SC_POOL];             // (exact: a fold that ran out of pool rebuilt the table)
-  if (total_count) *total_count = t->h[EQC_SC_SUM];
-  return QM_OK;
+  return eqc_size(t, n_classes, n_tids, total_count);
 }
 
 int qm_eqc_fetch(qm_eqc* t, int64_t* label_offsets, uint32_t* tids, uint64_t* counts) {
@@ -264,3 +285,4 @@ int qm_eqc_stat(const qm_eqc* t, int which, int64_t* value) {
 }
 
 }  // extern "C"
+#endif

@@ -84,7 +84,7 @@ struct qm_index {
 };
 
 // A device array that owns its memory: the pointer, the capacity in elements, freed with its owner.  Every device buffer of the
-// replica, the context and the equivalence-class table is one of these (arrays of other types' records: bytes, cast where read).
+// replica, the context and the estimation objects (the equivalence-class table's six arrays included) is one of these (arrays of other types' records: bytes, cast where read).
 template <typename T>
 struct DevBuf {
   T* p = nullptr; int64_t cap = 0;
@@ -94,6 +94,7 @@ struct DevBuf {
   ~DevBuf() { release(); }
   operator T*() const { return p; }
   void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
   // room for `want` elements (contents are not kept)
   int ensure(int64_t want, int64_t minGrow = 0) {
     if (want <= cap && p) return QM_OK;

@@ -1,4 +1,6 @@
-// qm_kernels_eqc.hip -- the kernels of the equivalence-class table (qm_eqc.inl) and their launch wrappers
+// qm_kernels_eqc.hip -- the kernels of the equivalence-class table that are no plain wave body (an LDS slab per wavefront, one
+// thread per entry, a grid-stride sum) and their launch wrappers; the wave bodies of qm_eqc.inl are launched by qm_eqc_host.inl
+// through qm_exec.h
 #include "qm_eqc.inl"
 #include "qm_device.h"
 
@@ -8,17 +10,10 @@ using namespace qm;
 static inline unsigned eqc_blocks(long long waves) { return (unsigned)((waves + EQC_BLOCK / 64 - 1) / (EQC_BLOCK / 64)); }
 __device__ __forceinline__ long long eqc_wave_id() { return ((long long)blockIdx.x * EQC_BLOCK + threadIdx.x) >> 6; }
 
-__global__ void __launch_bounds__(EQC_BLOCK) qm_eqc_label_kernel(EqcSrc S) { eqc_label_wave(S, eqc_wave_id()); }
 __global__ void __launch_bounds__(EQC_BLOCK) qm_eqc_label_queued_kernel(EqcSrc S, long long nq) {
   __shared__ u32 slab[EQC_BLOCK / 64][EQC_SLAB];
   const long long w = eqc_wave_id();
   if (w < nq) eqc_label_queued(S, w, (QM_LDS(u32)*)&slab[threadIdx.x >> 6][0]);
-}
-__global__ void __launch_bounds__(EQC_BLOCK) qm_eqc_probe_kernel(EqcTable T, EqcSet S, const u64* qin, long long nin, u64* qout, int aggregate) {
-  eqc_probe_wave(T, S, qin, nin, qout, eqc_wave_id(), aggregate);
-}
-__global__ void __launch_bounds__(EQC_BLOCK) qm_eqc_publish_kernel(EqcTable T, EqcSet S, const u64* q, long long nq) {
-  eqc_publish_wave(T, S, q, nq, eqc_wave_id());
 }
 // after the table has grown every pending unit starts its probe sequence anew
 __global__ void __launch_bounds__(EQC_BLOCK) qm_eqc_reset_probes_kernel(u64* q, long long n) {
@@ -32,28 +27,10 @@ __global__ void __launch_bounds__(EQC_BLOCK) qm_eqc_sum_kernel(const u64* count,
 }
 
 extern "C" {
-hipError_t qmk_eqc_label(const void* src, hipStream_t st) {
-  const EqcSrc& S = *(const EqcSrc*)src;
-  if (S.n <= 0) return hipSuccess;
-  const long long waves = (S.n + 64 / EQC_GROUP - 1) / (64 / EQC_GROUP);
-  hipLaunchKernelGGL(qm_eqc_label_kernel, dim3(eqc_blocks(waves)), dim3(EQC_BLOCK), 0, st, S);
-  return hipGetLastError();
-}
 hipError_t qmk_eqc_label_queued(const void* src, long long nq, hipStream_t st) {
   const EqcSrc& S = *(const EqcSrc*)src;
   if (nq <= 0) return hipSuccess;
   hipLaunchKernelGGL(qm_eqc_label_queued_kernel, dim3(eqc_blocks(nq)), dim3(EQC_BLOCK), 0, st, S, nq);
-  return hipGetLastError();
-}
-hipError_t qmk_eqc_probe(const void* table, const void* set, const unsigned long long* qin, long long nin, unsigned long long* qout, int aggregate, hipStream_t st) {
-  if (nin <= 0) return hipSuccess;
-  hipLaunchKernelGGL(qm_eqc_probe_kernel, dim3(eqc_blocks((nin + 63) / 64)), dim3(EQC_BLOCK), 0, st, *(const EqcTable*)table, *(const EqcSet*)set, (const u64*)qin, nin,
-                     (u64*)qout, aggregate);
-  return hipGetLastError();
-}
-hipError_t qmk_eqc_publish(const void* table, const void* set, const unsigned long long* q, long long nq, hipStream_t st) {
-  if (nq <= 0) return hipSuccess;
-  hipLaunchKernelGGL(qm_eqc_publish_kernel, dim3(eqc_blocks((nq + 63) / 64)), dim3(EQC_BLOCK), 0, st, *(const EqcTable*)table, *(const EqcSet*)set, (const u64*)q, nq);
   return hipGetLastError();
 }
 hipError_t qmk_eqc_reset_probes(unsigned long long* q, long long n, hipStream_t st) {

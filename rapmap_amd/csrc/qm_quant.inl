@@ -8,7 +8,7 @@
 // back -- its count is kept per transcript (`single`) and added as it is (unless w_t < DBL_MIN: the class is skipped, as above), and
 // its r_c is 0.  A transcript that occurs in single-tid classes only then holds exactly its count, whatever the iteration.
 // Written against qm_wave.h: the same source runs lane by lane under -DQM_EMU (tests/emu/qm_emu_quant.cpp).  Every function here
-// is the body of ONE wavefront; qm_kernels_quant.hip wraps them into kernels.  No floating-point atomic anywhere: every sum is
+// is the body of ONE wavefront; qm_quant_host.inl launches them (qm_exec.h).  No floating-point atomic anywhere: every sum is
 // taken by one wavefront, in an order that the structure alone fixes.
 //
 // Structure build (once per quant object)

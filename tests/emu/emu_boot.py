@@ -7,17 +7,13 @@ import subprocess
 
 import numpy as np
 
+import emu_quant
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libqm_emu_boot.so")
-_SRC = [os.path.join(_HERE, "qm_emu_boot.cpp")] + [os.path.join(_HERE, "../../rapmap_amd/csrc", f) for f in ("qm_boot.inl", "qm_quant.inl", "qm_eqc.inl", "qm_wave.h")]
-
-
-class ArgError(RuntimeError):
-    """what the device reports as QM_E_ARG"""
-
-
-class StateError(RuntimeError):
-    """what the device reports as QM_E_STATE"""
+_SRC = [os.path.join(_HERE, "qm_emu_boot.cpp"), os.path.join(_HERE, "qm_emu_quant.cpp")] + [os.path.join(_HERE, "../../rapmap_amd/csrc", f) for f in (
+    "qm_boot_host.inl", "qm_quant_host.inl", "qm_eqc_host.inl", "qm_exec.h", "qm_boot.inl", "qm_quant.inl", "qm_eqc.inl", "qm_wave.h")]
+ArgError, StateError, check = emu_quant.ArgError, emu_quant.StateError, emu_quant.check
 
 
 def build():
@@ -32,10 +28,9 @@ def _lib():
     if _lib_h is None:
         if not os.path.exists(_LIB) or any(os.path.getmtime(_LIB) < os.path.getmtime(s) for s in _SRC):
             build()
-        lib = C.CDLL(_LIB)
+        lib = emu_quant.declare(C.CDLL(_LIB))
         lib.qe_boot_create.restype = C.c_void_p
-        lib.qe_boot_destroy.restype = None
-        for f in (lib.qe_boot_info, lib.qe_boot_classes, lib.qe_boot_resample, lib.qe_boot_fetch, lib.qe_boot_philox):
+        for f in (lib.qe_boot_destroy, lib.qe_boot_info, lib.qe_boot_philox):
             f.restype = None
         _lib_h = lib
     return _lib_h
@@ -52,18 +47,16 @@ def _p(a):
 
 
 class Boot:
-    def __init__(self, off, tids, cnt, n_txps, eff, n_reps, aggregate=0):
-        off = np.ascontiguousarray(off, dtype=np.int64); tids = np.ascontiguousarray(tids, dtype=np.uint32); cnt = np.ascontiguousarray(cnt, dtype=np.uint64)
+    """over a quant object of its own, made from the canonical arrays, or over `quant` (an emu_quant.Quant made with lib=emu_boot._lib())"""
+
+    def __init__(self, off, tids, cnt, n_txps, eff, n_reps, aggregate=0, quant=None):
         self.n_txps = int(n_txps); self.n_reps = int(n_reps); self._h = None
-        if self.n_reps < 1:
-            raise ArgError("n_reps")
-        eff = np.ones(self.n_txps) if eff is None else np.ascontiguousarray(eff, dtype=np.float64)
+        self.quant = quant or emu_quant.Quant(off, tids, cnt, n_txps, eff, lib=_lib()); self._own = quant is None
         err = C.c_int()
-        h = _lib().qe_boot_create(C.c_longlong(len(off) - 1), _p(off), _p(tids), _p(cnt), C.c_longlong(self.n_txps), _p(eff), C.c_int(self.n_reps), C.c_int(aggregate), C.byref(err))
-        if err.value == -1:
-            raise ArgError("a label names a transcript beyond n_txps")
-        if not h:
-            raise RuntimeError("qe_boot_create failed (%d)" % err.value)
+        h = _lib().qe_boot_create(self.quant._h, C.c_int(self.n_reps), C.c_int(aggregate), C.byref(err))
+        if err.value and self._own:
+            self.quant.close()
+        check(err.value, "qe_boot_create")
         self._h = C.c_void_p(h)
         st = np.zeros(6, dtype=np.int64)
         _lib().qe_boot_info(self._h, _p(st))
@@ -72,45 +65,41 @@ class Boot:
 
     def classes(self):
         nc, ne = self.info["classes"], self.info["entries"]
-        off = np.zeros(nc + 1, dtype=np.int64); tids = np.zeros(ne + 1, dtype=np.uint32); cnt = np.zeros(nc + 1, dtype=np.uint64)
-        _lib().qe_boot_classes(self._h, _p(off), _p(tids), _p(cnt))
-        return off, tids[:ne], cnt[:nc]
+        off = np.zeros(nc + 1, dtype=np.int64); tids = np.zeros(ne, dtype=np.uint32); cnt = np.zeros(nc, dtype=np.uint64)
+        check(_lib().qe_boot_classes(self._h, _p(off), _p(tids), _p(cnt)), "qe_boot_classes")
+        return off, tids, cnt
 
     def resample(self, seed=0, first_rep=0):
-        _lib().qe_boot_resample(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_longlong(int(first_rep)))
+        check(_lib().qe_boot_resample(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_longlong(int(first_rep))), "qe_boot_resample")
 
     def set_counts(self, rep, counts):
         counts = np.ascontiguousarray(counts, dtype=np.uint64)
         if counts.size != self.info["classes"]:
             raise ValueError("one count per class")
-        col = np.concatenate([counts, np.zeros(1, dtype=np.uint64)])
-        if _lib().qe_boot_column(self._h, C.c_int(int(rep)), _p(col), C.c_int(1)):
-            raise ArgError("rep")
+        check(_lib().qe_boot_set_counts(self._h, C.c_int(int(rep)), _p(counts)), "qe_boot_set_counts")
 
     def counts(self, rep):
-        col = np.zeros(self.info["classes"] + 1, dtype=np.uint64)
-        if _lib().qe_boot_column(self._h, C.c_int(int(rep)), _p(col), C.c_int(0)):
-            raise ArgError("rep")
-        return col[:-1]
+        col = np.zeros(self.info["classes"], dtype=np.uint64)
+        check(_lib().qe_boot_fetch_counts(self._h, C.c_int(int(rep)), _p(col)), "qe_boot_fetch_counts")
+        return col
 
     def run(self, max_iter=10000, check_every=10, rel_tol=1e-2, min_alpha=1e-8):
         it = np.zeros(self.n_reps, dtype=np.int32); rel = np.zeros(self.n_reps, dtype=np.float64); n = C.c_longlong()
-        rc = _lib().qe_boot_run(self._h, C.c_int(max_iter), C.c_int(check_every), C.c_double(rel_tol), C.c_double(min_alpha), _p(it), _p(rel), C.byref(n))
-        if rc == -7:
-            raise StateError("no counts yet")
+        check(_lib().qe_boot_run(self._h, C.c_int(max_iter), C.c_int(check_every), C.c_double(rel_tol), C.c_double(min_alpha), _p(it), _p(rel), C.byref(n)), "qe_boot_run")
         self.launches = n.value
         return it, rel
 
     def fetch(self):
         out = np.zeros((self.n_reps, self.n_txps), dtype=np.float64)
-        if out.size:
-            _lib().qe_boot_fetch(self._h, _p(out))
+        check(_lib().qe_boot_fetch(self._h, _p(out)), "qe_boot_fetch")
         return out
 
     def close(self):
         if self._h:
             _lib().qe_boot_destroy(self._h)
             self._h = None
+            if self._own:
+                self.quant.close()
 
     def __del__(self):
         self.close()

@@ -8,9 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libqm_emu_eqc.so")
-_SRC = [os.path.join(_HERE, "qm_emu_eqc.cpp"),
-        os.path.join(_HERE, "../../rapmap_amd/csrc/qm_eqc.inl"),
-        os.path.join(_HERE, "../../rapmap_amd/csrc/qm_wave.h")]
+_SRC = [os.path.join(_HERE, "qm_emu_eqc.cpp")] + [os.path.join(_HERE, "../../rapmap_amd/csrc", f) for f in ("qm_eqc_host.inl", "qm_exec.h", "qm_eqc.inl", "qm_wave.h")]
 
 
 def build():

@@ -118,6 +118,33 @@ def test_emulated_errors(env):
     bc.check_errors(env)
 
 
+def test_emulated_lifetime(env):
+    """what test_boot_gpu.py's test_lifetime_and_snapshot asks of the device objects, of the emulated ones: closing a quant object that a
+    boot object borrows is refused and destroys nothing, a run goes on where the last one stopped, the launches are counted"""
+    import emu_boot
+    import emu_quant
+    L, n, nt = bc.mixed_table()
+    off, tids, cnt = qc.table_of(L, n)
+    q = emu_quant.Quant(off, tids, cnt, nt, lib=emu_boot._lib())
+    b = emu_boot.Boot(None, None, None, nt, None, 4, quant=q)
+    with pytest.raises(env.StateError):
+        q.close()
+    b.resample(seed=3)
+    before = [b.counts(r) for r in range(4)]
+    b.run(max_iter=12, rel_tol=0.0)
+    a = b.fetch()
+    assert b.launches == 24 and b.info["draws"] == int(cnt.sum())
+    assert q.run(max_iter=3, rel_tol=0.0) == (3, -1.0)                # the quant object is still whole
+    b.resample(seed=3)
+    assert all(np.array_equal(b.counts(r), before[r]) for r in range(4))
+    b.run(max_iter=5, rel_tol=0.0); b.run(max_iter=7, rel_tol=0.0)     # a run goes on where the last one stopped
+    assert b.fetch().tobytes() == a.tobytes()
+    with pytest.raises(env.StateError):
+        q.close()
+    b.close()
+    q.close()
+
+
 def test_emulated_determinism(env):
     bc.check_determinism(env)
 

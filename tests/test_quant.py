@@ -88,6 +88,26 @@ def test_emulated_determinism_and_continuation(solve, crafted):
     assert a.tobytes() == c.tobytes()
 
 
+def test_emulated_object_runs_again(solve, crafted):
+    """what test_quant_gpu.py asks of one object on the device, of the emulated one: a run from the same start repeats bit for bit, a
+    second object on the same table agrees, a run goes on where the last one stopped, and the statistics stay"""
+    import emu_quant
+    g, eff = crafted
+    q = emu_quant.Quant(g.off, g.tid, g.cnt, g.nt, eff)
+    assert q.run(max_iter=30, rel_tol=0.0) == (30, -1.0)
+    a = q.fetch(); before = q.stat()
+    q.set_start(None)
+    q.run(max_iter=30, rel_tol=0.0)
+    assert q.fetch().tobytes() == a.tobytes()
+    p = emu_quant.Quant(g.off, g.tid, g.cnt, g.nt, eff)
+    p.run(max_iter=12, rel_tol=0.0); p.run(max_iter=18, rel_tol=0.0)
+    assert p.fetch().tobytes() == a.tobytes() and q.stat() == before == p.stat()
+    for kw in (dict(max_iter=-1), dict(check_every=0), dict(rel_tol=-1.0), dict(rel_tol=float("nan")), dict(min_alpha=-1.0)):
+        with pytest.raises(emu_quant.ArgError):
+            q.run(**kw)
+    p.close(); q.close()
+
+
 def test_emulated_errors_and_edges(solve):
     import emu_quant
     qc.check_errors_and_edges(solve, emu_quant.ArgError)
