@@ -372,7 +372,10 @@ int qm_eqc_stat(const qm_eqc* t, int which, int64_t* value);
  * twice; a transcript that occurs in single-tid classes only holds exactly its count.
  * Two launches per iteration and no floating-point atomic: every sum is taken by one wavefront in an order that the table alone
  * fixes (class index = ascending slot index; a transcript's classes ascending), so a run is reproducible bit for bit.  No bias
- * models, no variational Bayes, no online phase, no truncation of small values at the end.  Not thread-safe (one per host thread). */
+ * models, no online phase, no truncation of small values at the end.  Not thread-safe (one per host thread).
+ * The variational Bayes method (qm_quant_set_method) differs in w_t alone: w_t = E(alpha_t + p_t) / e_t with a prior p_t >= 0 per
+ * transcript and E(x) = exp(digamma(x)), 0 for x < 1e-10 -- a function of this library's own (qm_quant_exp_digamma), defined
+ * operation by operation in DESIGN.md section 4.13, so that a variational run is reproducible bit for bit as well. */
 typedef struct qm_quant qm_quant;   /* the bipartite graph of a table and the current alpha, in the device memory of the table's GPU */
 /* no counterpart in the reference; consumer of qm_eqc.  A SNAPSHOT of t: later folds into t (or its destruction) do not alter the
  * quant object, which runs on a stream of its own.  n_txps: transcripts (alpha has that many entries); a label that names a tid
@@ -382,6 +385,16 @@ int qm_quant_create(qm_eqc* t, int64_t n_txps, const double* eff_len, qm_quant**
 /* no counterpart in the reference; consumer of qm_eqc.  alpha0: n_txps non-negative finite numbers (QM_E_ARG otherwise); NULL = the
  * uniform default: total / M for the M transcripts that occur in at least one label, 0 for all others (they stay 0). */
 int qm_quant_set_start(qm_quant* q, const double* alpha0);
+/* no counterpart in the reference; consumer of qm_eqc.  The method of every later qm_quant_run and of every qm_boot made later: the
+ * EM (the default) or the variational Bayes EM with the prior p_t.  alpha stays as it is: a run begins with the weights of the
+ * current alpha under its method, so a caller may run EM iterations and go on in VBEM.  What alpha reports does not change: the
+ * expected fragments, without the prior.  An unknown method, or a prior that is negative or not finite: QM_E_ARG; while a qm_boot
+ * borrows q: QM_E_STATE; nothing is changed then.  (Salmon's per-nucleotide prior is p_t = P * e_t, its per-transcript one
+ * p_t = P; its default P is believed to be 1e-2.  Parity with Salmon is not claimed: none was at hand to compare with.) */
+enum { QM_QUANT_METHOD_EM = 0, QM_QUANT_METHOD_VBEM = 1 };
+int qm_quant_set_method(qm_quant* q, int method, const double* prior /*[n_txps] >= 0 and finite; NULL: 0.0 each; ignored for EM*/);
+/* no counterpart in the reference.  E over an array: out[i] = E(x[i]), one small launch on `device`, for tests and callers */
+int qm_quant_exp_digamma(int device, const double* x, int64_t n, double* out);
 /* no counterpart in the reference; consumer of qm_eqc.  Up to max_iter iterations from the current alpha (a later call goes on
  * where the last one stopped).  Every check_every-th iteration (>= 1) the host reads one word: the largest |alpha'_t - alpha_t| /
  * alpha'_t over the transcripts with alpha'_t > min_alpha (>= 0); below rel_tol the run stops.  rel_tol = 0: exactly max_iter

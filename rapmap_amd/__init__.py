@@ -5,5 +5,5 @@ of the reference's call surface), synth.py (synthetic transcriptome / reads)."""
 from .api import (QuasiIndex, QuasiMapper, QmError, QmOpts, default_opts, build_index, pack_reads,  # noqa: F401
                   FastxReader, ReadBatch, MappedStream, reserve_stream_memory, SamWriter, sam_header_text, sam_records_text,
                   HIT_DTYPE, INTERVAL_DTYPE, LIB_PATH, ABI_SYMBOLS, EqClasses, write_eq_classes, read_eq_classes,
-                  Quant, write_quant, read_quant, Bootstrap, write_bootstraps, read_bootstraps,
+                  Quant, exp_digamma, write_quant, read_quant, Bootstrap, write_bootstraps, read_bootstraps,
                   FragLenDist, eff_lens_from_counts, frag_len_mean, write_flen_dist, read_flen_dist, FLD_DEFAULT_MAX_LEN, FLD_STATS)

@@ -84,6 +84,11 @@ def _quasimap(argv):
     ap.add_argument("--quantFLD", action="store_true", help="[only with quant, paired-end reads]: learn the fragment-length distribution from the "
                     "run's uniquely and properly paired fragments on the GPU; effective length = Length + 1 - (mean of the fragment lengths "
                     "that fit the transcript); the distribution is written to FILE.flenDist.txt.  Not together with --quantFragLenMean")
+    ap.add_argument("--quantVB", action="store_true", help="[only with quant]: the variational Bayes EM in place of the EM: a transcript's weight is "
+                    "exp(digamma(abundance + prior)) / effective length; the bootstrap replicates of --numBootstraps use it as well")
+    ap.add_argument("--quantVBPrior", type=float, default=1e-2, metavar="P", help="[only with quantVB]: the prior, per nucleotide: P x effective length "
+                    "for every transcript")
+    ap.add_argument("--quantPerTranscriptPrior", action="store_true", help="[only with quantVB]: the prior is P for every transcript")
     ap.add_argument("--numBootstraps", type=int, default=0, metavar="B", help="[only with quant]: B bootstrap replicates of the estimate on the GPU (the "
                     "class counts resampled, the EM run again per replicate, 64 replicates at a time), written to FILE.bootstraps.gz in the "
                     "layout of Salmon's bootstraps.gz: B x transcripts little-endian float64")
@@ -96,6 +101,10 @@ def _quasimap(argv):
         ap.error("--numBootstraps must not be negative")
     if a.quantFLD and not a.quant:
         ap.error("--quantFLD needs --quant")
+    if a.quantVB and not a.quant:
+        ap.error("--quantVB needs --quant")
+    if not (a.quantVBPrior >= 0 and a.quantVBPrior < float("inf")):
+        ap.error("--quantVBPrior must be a non-negative number")
     if a.quantFLD and a.quantFragLenMean:
         ap.error("--quantFLD learns the fragment lengths from the run: not together with --quantFragLenMean")
     if a.quantFLD and not (a.leftMates and a.rightMates):
@@ -244,10 +253,14 @@ def _quasimap(argv):
             else:
                 eff = np.maximum(1.0, lens.astype(np.float64) - a.quantFragLenMean + 1.0) if a.quantFragLenMean else np.maximum(1.0, lens.astype(np.float64))
             qn = ra.Quant(classes, qi.n_txps, eff)
+            if a.quantVB:
+                # --quantVB: the prior is built from the effective lengths that Quant was given
+                qn.set_method("vbem", prior=a.quantVBPrior, per_transcript=a.quantPerTranscriptPrior)
             iters, rel = qn.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
             ra.write_quant(a.quant, qi.txp_names, lens, eff, qn.fetch())
-            log("wrote abundances of %d transcripts to %s (%d EM iterations, %.3f ms on the GPU, last relative change %g)" % (
-                qi.n_txps, a.quant, iters, qn.stat()["last_run_us"] / 1e3, rel))
+            what = "VBEM iterations, prior %g per %s" % (a.quantVBPrior, "transcript" if a.quantPerTranscriptPrior else "nucleotide") if a.quantVB else "EM iterations"
+            log("wrote abundances of %d transcripts to %s (%d %s, %.3f ms on the GPU, last relative change %g)" % (
+                qi.n_txps, a.quant, iters, what, qn.stat()["last_run_us"] / 1e3, rel))
             if a.numBootstraps:
                 # --numBootstraps: batches of at most 64 replicates through first_rep, so that memory stays bounded
                 import gzip

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "qm_reader_open", "qm_reader_next", "qm_reader_close", "qm_io_last_error", "qm_sam_header", "qm_sam_records",
     "qm_eqc_create", "qm_eqc_destroy", "qm_eqc_clear", "qm_eqc_add", "qm_eqc_add_labels", "qm_eqc_size", "qm_eqc_fetch", "qm_eqc_stat",
     "qm_stream_eqc_finish", "qm_stream_eqc_fetch",
-    "qm_quant_create", "qm_quant_set_start", "qm_quant_run", "qm_quant_fetch", "qm_quant_stat", "qm_quant_destroy",
+    "qm_quant_create", "qm_quant_set_start", "qm_quant_set_method", "qm_quant_exp_digamma", "qm_quant_run", "qm_quant_fetch", "qm_quant_stat", "qm_quant_destroy",
     "qm_quant_fetch_classes", "qm_boot_create", "qm_boot_resample", "qm_boot_set_counts", "qm_boot_fetch_counts", "qm_boot_run", "qm_boot_fetch",
     "qm_boot_stat", "qm_boot_destroy",
     "qm_fld_create", "qm_fld_destroy", "qm_fld_clear", "qm_fld_add", "qm_fld_add_hits", "qm_fld_add_counts", "qm_fld_fetch", "qm_fld_stat",
@@ -193,6 +193,8 @@ def lib():
     L.qm_stream_eqc_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qm_quant_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]
     L.qm_quant_set_start.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_quant_set_method.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.qm_quant_exp_digamma.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     L.qm_quant_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.qm_quant_fetch.argtypes = [C.c_void_p, C.c_void_p]
     L.qm_quant_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
@@ -664,10 +666,13 @@ class EqClasses:
         off, tids, cnt = self.fetch()
         write_eq_classes(path, txp_names, off, tids, cnt)
 
-    def quantify(self, n_txps, eff_lens=None, **run_kw):
-        """the one-call form of Quant: alpha float64[n_txps] after a run from the uniform start (run_kw: Quant.run's)"""
+    def quantify(self, n_txps, eff_lens=None, method="em", prior=1e-2, per_transcript=False, **run_kw):
+        """the one-call form of Quant: alpha float64[n_txps] after a run from the uniform start (method, prior, per_transcript:
+        Quant.set_method's; run_kw: Quant.run's)"""
         q = Quant(self, n_txps, eff_lens)
         try:
+            if method != "em":
+                q.set_method(method, prior, per_transcript)
             q.run(**run_kw)
             return q.fetch()
         finally:
@@ -689,7 +694,8 @@ class Quant:
     """qm_quant_*: abundance estimation on the device, the EM over a snapshot of an EqClasses table (later folds into the table do
     not alter it).  One iteration, all in float64: w = alpha / eff; d_c = sum of w over the class's label; r_c = n_c / d_c;
     alpha'_t = w_t * sum of r_c over the classes that contain t.  eff_lens: n_txps positive numbers (None: 1.0 each).  The start is
-    total / M for the M transcripts that occur in a label and 0 for the others, unless set_start gives another one."""
+    total / M for the M transcripts that occur in a label and 0 for the others, unless set_start gives another one.  set_method
+    chooses the variational Bayes EM instead, which differs in w alone."""
 
     STATS = ("classes", "entries", "present", "longest_label", "longest_list", "queued_labels", "queued_txps", "last_run_us", "build_us")
     DEFAULTS = dict(max_iter=10000, check_every=10, rel_tol=1e-2, min_alpha=1e-8)     # Salmon's offline EM
@@ -704,6 +710,28 @@ class Quant:
         _check(lib().qm_quant_create(eq_classes._h, self.n_txps, eff_lens.ctypes.data if eff_lens is not None and eff_lens.size else None,
                                      C.byref(self._h)))
         self.device = eq_classes.device
+        self._eff = eff_lens                                          # (what a per-nucleotide prior is built from)
+
+    METHODS = {"em": 0, "vbem": 1}                                    # QM_QUANT_METHOD_*
+
+    def set_method(self, method="em", prior=1e-2, per_transcript=False):
+        """qm_quant_set_method: "em", or "vbem": the variational Bayes EM, whose weight is w = exp(digamma(alpha + p)) / eff with the
+        prior p_t = prior * eff_t (per nucleotide, the default) or p_t = prior (per_transcript=True); prior may also be an array of
+        n_txps numbers, taken as p itself, or None (0.0 each).  Holds for every later run and for Bootstraps made later; alpha stays
+        as it is, and keeps meaning the expected fragments without the prior.  Raises while a Bootstrap of this object lives."""
+        if method not in self.METHODS:
+            raise ValueError("method is 'em' or 'vbem'")
+        p = None
+        if method == "vbem" and prior is not None:
+            if np.ndim(prior) == 0:
+                p = np.full(self.n_txps, float(prior), dtype=np.float64)
+                if not per_transcript and self._eff is not None:
+                    p = float(prior) * self._eff
+            else:
+                p = np.ascontiguousarray(prior, dtype=np.float64)
+                if p.size != self.n_txps:
+                    raise ValueError("one prior per transcript")
+        _check(lib().qm_quant_set_method(self._h, self.METHODS[method], p.ctypes.data if p is not None and p.size else None))
 
     def set_start(self, alpha0=None):
         """alpha0: n_txps non-negative numbers; None: the uniform default"""
@@ -767,9 +795,19 @@ class Quant:
             pass
 
 
+def exp_digamma(x, device=0):
+    """qm_quant_exp_digamma: E(x) = exp(digamma(x)), 0 below 1e-10, as the variational method computes it on the device -> float64
+    array of x's shape"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros(x.shape, dtype=np.float64)
+    _check(lib().qm_quant_exp_digamma(int(device), x.ctypes.data if x.size else None, x.size, out.ctypes.data if x.size else None))
+    return out
+
+
 class Bootstrap:
     """qm_boot_*: bootstrap replicates of a Quant's estimate on the device (Salmon's --numBootstraps).  A replicate resamples the
-    snapshot's class counts -- N draws, a multinomial over the classes -- and runs Quant's EM on them; n_reps replicates are iterated
+    snapshot's class counts -- N draws, a multinomial over the classes -- and runs Quant's method (the EM, or what set_method chose
+    before this object was made) on them; n_reps replicates are iterated
     at once and each stops by itself.  Slot i holds replicate number first_rep + i; a replicate's counts depend on (snapshot, seed,
     replicate number) alone and its alpha on those and run's arguments, not on n_reps or its slot.  Borrows the Quant's graph and
     stream: close this before the Quant."""

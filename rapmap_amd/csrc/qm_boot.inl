@@ -23,6 +23,7 @@
 //   boot_start_wave       start values and weights of a range of replicates; boot_reset_wave: their bookkeeping
 //   boot_class_wave       r from w;  boot_txp_wave: alpha and the next w from r, and on a checking iteration every replicate's
 //                         largest relative change into ITS OWN word (an integer atomic max over the bits)
+//                         (boot_start_vb_wave, boot_txp_vb_wave: the same bodies with the variational weight of qm_quant.inl)
 //   boot_mark_wave        after a checking iteration: replicates whose word is below rel_tol are done (frozen from here on)
 //   boot_begin_wave / boot_end_wave   a run's per-replicate iteration counts
 //   boot_transpose_wave   alpha[t * Bp + rep] -> out[rep * nTxps + t]
@@ -134,14 +135,24 @@ QM_DEV void boot_column_wave(const long long* coff, const u32* clab, long long n
   }
 }
 // slots s0 .. s0 + ns - 1 start anew: `value` for the transcripts that occur in a label, 0 for all others, and the weights of that
-QM_DEV void boot_start_wave(const long long* toff, const double* eff, long long nTxps, double value, double* alpha, double* w, long long Bp, long long s0, long long ns,
-                            long long wave, long long tile) {
+// (VB: quant_weight's method, decided when the kernel is compiled; prior: [transcripts], the same for every replicate)
+template <int VB>
+QM_DEV void boot_start_body(const long long* toff, const double* eff, const double* prior, long long nTxps, double value, double* alpha, double* w, long long Bp,
+                            long long s0, long long ns, long long wave, long long tile) {
   QM_LANES(l) {
     const long long t = wave * BOOT_ROWS + l / BOOT_TILE, b = tile * BOOT_TILE + (l & (BOOT_TILE - 1));
     if (t >= nTxps || b < s0 || b >= s0 + ns) continue;
     const double a = toff[t + 1] > toff[t] ? value : 0.0;
-    alpha[t * Bp + b] = a; w[t * Bp + b] = a / eff[t];
+    alpha[t * Bp + b] = a; w[t * Bp + b] = quant_weight<VB>(a, prior, t, eff[t]);
   }
+}
+QM_DEV void boot_start_wave(const long long* toff, const double* eff, long long nTxps, double value, double* alpha, double* w, long long Bp, long long s0, long long ns,
+                            long long wave, long long tile) {
+  boot_start_body<0>(toff, eff, nullptr, nTxps, value, alpha, w, Bp, s0, ns, wave, tile);
+}
+QM_DEV void boot_start_vb_wave(const long long* toff, const double* eff, const double* prior, long long nTxps, double value, double* alpha, double* w, long long Bp,
+                               long long s0, long long ns, long long wave, long long tile) {
+  boot_start_body<1>(toff, eff, prior, nTxps, value, alpha, w, Bp, s0, ns, wave, tile);
 }
 struct BootBook {             // per replicate slot, [Bp]
   u32* done; u64* rel; int* iters; double* lastRel; u64* scal;
@@ -231,7 +242,8 @@ QM_DEV void boot_class_wave(const BootState& S, long long wave, long long tile) 
   }
 }
 
-QM_DEV void boot_txp_wave(const BootState& S, long long wave, long long tile) {
+template <int VB>
+QM_DEV void boot_txp_body(const BootState& S, const double* prior, long long wave, long long tile) {
   LV<bool> live; LV<long long> row; LV<double> s;
   if (!boot_row_sums(S, S.txp, S.r, wave, tile, live, row, s)) return;
   QM_LANES(l) {
@@ -245,8 +257,10 @@ QM_DEV void boot_txp_wave(const BootState& S, long long wave, long long tile) {
       u64 bits; __builtin_memcpy(&bits, &rel, 8);                // rel >= 0: the bits order as the numbers do
       if (bits > S.rel[b]) atomic_max_u64(&S.rel[b], bits);      // (the word only rises within a launch: a stale read costs an atomic, no more)
     }
-    S.alpha[at] = a1; S.w[at] = a1 / S.eff[t];                   // (alpha and w of (t, replicate) are this lane's alone in this launch)
+    S.alpha[at] = a1; S.w[at] = quant_weight<VB>(a1, prior, t, S.eff[t]);   // (alpha and w of (t, replicate) are this lane's alone in this launch)
   }
 }
+QM_DEV void boot_txp_wave(const BootState& S, long long wave, long long tile) { boot_txp_body<0>(S, nullptr, wave, tile); }
+QM_DEV void boot_txp_vb_wave(const BootState& S, const double* prior, long long wave, long long tile) { boot_txp_body<1>(S, prior, wave, tile); }
 
 }  // namespace qm

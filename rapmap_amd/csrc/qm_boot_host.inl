@@ -104,8 +104,13 @@ static void boot_close(qm_boot* b) { if (b->counted) b->q->boots--; b->counted =
 static int boot_restart(qm_boot* b, int64_t s0, int64_t ns, uint64_t total) {
   qm_quant* q = b->q; qx::Stream st = q->stream;
   const double value = q->present > 0 ? (double)total / (double)q->present : 0.0;
-  HIPCHK(qx::launch2<boot_start_wave>(st, boot_row_waves(q->nTxps), b->Bp / BOOT_TILE, (const long long*)q->d_toff.p, (const double*)q->d_eff.p, (long long)q->nTxps, value,
-                                      b->d_alpha.p, b->d_w.p, (long long)b->Bp, (long long)s0, (long long)ns));
+  // (the method and the prior are the quant object's, and fixed while this object lives: qm_quant_set_method refuses)
+  if (q->method == QM_QUANT_METHOD_VBEM)
+    HIPCHK(qx::launch2<boot_start_vb_wave>(st, boot_row_waves(q->nTxps), b->Bp / BOOT_TILE, (const long long*)q->d_toff.p, (const double*)q->d_eff.p, (const double*)q->d_prior.p,
+                                           (long long)q->nTxps, value, b->d_alpha.p, b->d_w.p, (long long)b->Bp, (long long)s0, (long long)ns));
+  else
+    HIPCHK(qx::launch2<boot_start_wave>(st, boot_row_waves(q->nTxps), b->Bp / BOOT_TILE, (const long long*)q->d_toff.p, (const double*)q->d_eff.p, (long long)q->nTxps, value,
+                                        b->d_alpha.p, b->d_w.p, (long long)b->Bp, (long long)s0, (long long)ns));
   HIPCHK(qx::launch<boot_reset_wave>(st, qx::waves_of(ns), boot_book(b), (long long)s0, (long long)ns));
   return QM_OK;
 }
@@ -175,7 +180,8 @@ static int boot_run(qm_boot* b, int32_t max_iter, int32_t check_every, double re
       const bool check = rel_tol > 0 && (it + 1) % check_every == 0;
       S.check = check ? 1 : 0;
       HIPCHK(qx::launch2<boot_class_wave>(st, boot_side_waves(S.cls), tiles, S));
-      HIPCHK(qx::launch2<boot_txp_wave>(st, boot_side_waves(S.txp), tiles, S));
+      if (q->method == QM_QUANT_METHOD_VBEM) HIPCHK(qx::launch2<boot_txp_vb_wave>(st, boot_side_waves(S.txp), tiles, S, (const double*)q->d_prior.p));
+      else HIPCHK(qx::launch2<boot_txp_wave>(st, boot_side_waves(S.txp), tiles, S));
       ++it; launches += 2;
       if (check) {                                                  // the one word the host reads
         HIPCHK(qx::launch<boot_mark_wave>(st, qx::waves_of(nReps), K, nReps, (int)it, rel_tol)); ++launches;

@@ -24,6 +24,8 @@
 //   quant_class_wave      r_c from w: a launch over the class side
 //   quant_txp_wave        alpha'_t and the next w_t from r: a launch over the transcript side; on a checking iteration the largest
 //                         relative change is folded into one word (an integer atomic max over the bits of a non-negative double)
+//   quant_txp_vb_wave     the same body with the variational weight w_t = E(alpha_t + p_t) / e_t (quant_weight, quant_exp_digamma); the
+//                         method is a template parameter of the body: the EM's kernels are what they were
 //   Both go through quant_row_sums: the first ceil(rows / 8) wavefronts of a launch take eight rows each, eight lanes per row (rows
 //   of up to QNT_GROUP items), the remaining ones one queued row each (a strided loop per lane, then the sum over the wavefront).
 #pragma once
@@ -136,8 +138,75 @@ QM_DEV void quant_queue_wave(const u32* flag, const long long* pos, long long n,
 QM_DEV void quant_start_wave(const long long* toff, long long nTxps, double value, double* alpha, long long wave) {
   QM_LANES(l) { const long long t = wave * 64 + l; if (t < nTxps) alpha[t] = toff[t + 1] > toff[t] ? value : 0.0; }
 }
+// ---- the variational method.  E(x) = exp(digamma(x)) for x >= QNT_VB_X_MIN, 0.0 below it, defined by
+// the operations below and by nothing else: + - * / on doubles, comparisons, one conversion to an integer and the exponent bits
+// of two powers of two, never contracted -- the device, the lane emulation and tests/vb_cases.py give the same 64 bits.
+//   y = x, s = 0; while y < 10: s += 1 / y, y += 1                   (digamma(x) = digamma(y) - s; ten steps at the most)
+//   digamma(y) = log y + t,  t = -1/(2y) - 1/(12 y^2) + 1/(120 y^4) - 1/(252 y^6) + 1/(240 y^8) - 1/(132 y^10) + 691/(32760 y^12)
+//   E(x) = y * exp(t - s): no logarithm is taken.  u = t - s <= 0; below -750 the answer is 0.0 (y * exp(u) is under half the
+//   smallest subnormal); k = the integer nearest u / ln 2, r = u - k ln 2 in two pieces (the high one has 32 bits: k times it is
+//   exact), exp(r) by its Taylor polynomial of degree 14 (|r| <= 0.35: the remainder is below 1e-19), and 2^k in two halves, so
+//   that each is a normal number and the one rounding of a subnormal answer is the last multiplication's.
+#define QNT_VB_X_MIN 1e-10
+QM_DEV double quant_pow2(long long e) {                            // 2^e, -1022 <= e <= 1023, from its exponent bits
+  const u64 bits = (u64)(1023 + e) << 52;
+  double p; __builtin_memcpy(&p, &bits, 8);
+  return p;
+}
+QM_DEV double quant_exp_digamma(double x) {
+#ifndef QM_EMU
+#pragma clang fp contract(off)
+#endif
+  if (!(x >= QNT_VB_X_MIN)) return 0.0;
+  double y = x, s = 0.0;
+  while (y < 10.0) { s += 1.0 / y; y += 1.0; }
+  const double z = 1.0 / y, z2 = z * z;
+  double p = 0.021092796092796094;                                  // 691/32760, then 1/132, 1/240, 1/252, 1/120, 1/12
+  p = 0.007575757575757576 - z2 * p;
+  p = 0.004166666666666667 - z2 * p;
+  p = 0.003968253968253968 - z2 * p;
+  p = 0.008333333333333333 - z2 * p;
+  p = 0.08333333333333333 - z2 * p;
+  const double u = (-0.5 * z - z2 * p) - s;
+  if (!(u >= -750.0)) return 0.0;
+  const long long k = (long long)(u * 1.4426950408889634 - 0.5);    // (u <= 0: the conversion truncates towards zero)
+  const double kf = (double)k;
+  const double r = (u - kf * 0.6931471803691238) - kf * 1.9082149292705877e-10;
+  double q = 1.1470745597729725e-11;                                // 1/14!, then 1/13! .. 1/2!, 1, 1
+  q = 1.6059043836821613e-10 + r * q;
+  q = 2.08767569878681e-09 + r * q;
+  q = 2.505210838544172e-08 + r * q;
+  q = 2.755731922398589e-07 + r * q;
+  q = 2.7557319223985893e-06 + r * q;
+  q = 2.48015873015873e-05 + r * q;
+  q = 0.0001984126984126984 + r * q;
+  q = 0.001388888888888889 + r * q;
+  q = 0.008333333333333333 + r * q;
+  q = 0.041666666666666664 + r * q;
+  q = 0.16666666666666666 + r * q;
+  q = 0.5 + r * q;
+  q = 1.0 + r * q;
+  q = 1.0 + r * q;
+  const long long h = (-k) >> 1;
+  return ((y * q) * quant_pow2(-h)) * quant_pow2(k + h);
+}
+QM_DEV void quant_exp_digamma_wave(const double* x, long long n, double* out, long long wave) {
+  QM_LANES(l) { const long long i = wave * 64 + l; if (i < n) out[i] = quant_exp_digamma(x[i]); }
+}
+
+// w_t of a transcript from its current alpha: VB = 0 the EM's alpha / e, VB = 1 the variational E(alpha + prior) / e (the method
+// is decided when the kernel is compiled: an EM kernel holds nothing of E and reads no prior)
+template <int VB>
+QM_DEV double quant_weight(double alpha, const double* prior, long long t, double eff) {
+  if (VB) return quant_exp_digamma(alpha + prior[t]) / eff;
+  return alpha / eff;
+}
+
 QM_DEV void quant_weights_wave(const double* alpha, const double* eff, long long nTxps, double* w, long long wave) {
   QM_LANES(l) { const long long t = wave * 64 + l; if (t < nTxps) w[t] = alpha[t] / eff[t]; }
+}
+QM_DEV void quant_weights_vb_wave(const double* alpha, const double* eff, const double* prior, long long nTxps, double* w, long long wave) {
+  QM_LANES(l) { const long long t = wave * 64 + l; if (t < nTxps) w[t] = quant_weight<1>(alpha[t], prior, t, eff[t]); }
 }
 
 // ---- iteration.  Wavefront `wave` of a launch over side A: row[l] >= 0 in the ONE lane that finishes a row (the first lane of
@@ -189,7 +258,9 @@ QM_DEV void quant_class_wave(const QuantState& Q, long long wave) {
   }
 }
 
-QM_DEV void quant_txp_wave(const QuantState& Q, long long wave) {
+// (the row logic keeps all 64 lanes; under VB = 1 only the lanes that finish a row evaluate E)
+template <int VB>
+QM_DEV void quant_txp_body(const QuantState& Q, const double* prior, long long wave) {
   LV<long long> row; LV<double> s;
   quant_row_sums(Q.txp, Q.r, wave, row, s);
   QM_LANES(l) {
@@ -197,7 +268,7 @@ QM_DEV void quant_txp_wave(const QuantState& Q, long long wave) {
     if (t < 0) continue;
     const double wt = Q.w[t];
     const double a1 = quant_mul_add(wt, s[l], wt < QNT_DBL_MIN ? 0.0 : Q.single[t]);
-    Q.alphaNew[t] = a1; Q.w[t] = a1 / Q.eff[t];                  // (w_t is read by this lane alone in this launch)
+    Q.alphaNew[t] = a1; Q.w[t] = quant_weight<VB>(a1, prior, t, Q.eff[t]);   // (w_t is read by this lane alone in this launch)
     if (Q.check && a1 > Q.minAlpha) {
       const double rel = __builtin_fabs(a1 - Q.alpha[t]) / a1;
       u64 bits; __builtin_memcpy(&bits, &rel, 8);                // rel >= 0: the bits order as the numbers do
@@ -205,5 +276,7 @@ QM_DEV void quant_txp_wave(const QuantState& Q, long long wave) {
     }
   }
 }
+QM_DEV void quant_txp_wave(const QuantState& Q, long long wave) { quant_txp_body<0>(Q, nullptr, wave); }
+QM_DEV void quant_txp_vb_wave(const QuantState& Q, const double* prior, long long wave) { quant_txp_body<1>(Q, prior, wave); }
 
 }  // namespace qm

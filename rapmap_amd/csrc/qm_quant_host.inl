@@ -7,7 +7,8 @@
 // row statistics, a scan and the queue of the rows of more than QNT_GROUP items.  The quant object owns everything it made and its
 // own stream; the table may be folded into, cleared or destroyed afterwards.
 // run = per iteration a class launch and a transcript launch on that stream; the host reads ONE word on a checking iteration
-// (every check_every-th), nothing otherwise.
+// (every check_every-th), nothing otherwise.  The method (EM or variational Bayes) and the prior are state of the object: a run
+// begins with the weights of the current alpha under its method and launches that method's transcript kernel.
 #include <cmath>
 #include "qm_quant.inl"
 #include "qm_exec.h"
@@ -20,6 +21,7 @@ struct qm_quant {
   DevBuf<double> d_cnt, d_eff, d_single, d_w, d_r, d_alpha[2]; int cur = 0;     // alpha: two buffers, d_alpha[cur] holds the current one
   DevBuf<u64> d_scal; u64 h[QNT_SC_WORDS] = {0}; PinBuf<u64> h_rel;
   DevBuf<unsigned char> d_tmp;                                        // the scans' and the sort's scratch (structure build)
+  int method = QM_QUANT_METHOD_EM; DevBuf<double> d_prior;           // the weight of a transcript (quant_weight); the prior: [n_txps], made by the first set_method
   int boots = 0;                                                      // live qm_boot objects that borrow the graph and the stream (qm_boot_host.inl)
   qx::Event ev0{}, ev1{}; int64_t lastRunUs = 0, buildUs = 0;        // around the last run / the structure build on its stream (QM_QUANT_STAT_LAST_RUN_US, _BUILD_US)
 };
@@ -115,13 +117,44 @@ static int quant_may_close(const qm_quant* q) {
   return q->boots > 0 ? fail(QM_E_STATE, "qm_quant_destroy: %d bootstrap object(s) still borrow this quant object", q->boots) : QM_OK;
 }
 
+// the method of every later run, and of the replicates of a qm_boot made later; alpha stays as it is (a run begins with the weights
+// of the current alpha under its method)
+static int quant_set_method(qm_quant* q, int method, const double* prior) {
+  if (method != QM_QUANT_METHOD_EM && method != QM_QUANT_METHOD_VBEM) return fail(QM_E_ARG, "qm_quant_set_method: unknown method %d", method);
+  if (method == QM_QUANT_METHOD_VBEM && prior) for (int64_t i = 0; i < q->nTxps; ++i) if (!(prior[i] >= 0) || !std::isfinite(prior[i])) return fail(QM_E_ARG, "qm_quant_set_method: prior[%lld] is not a non-negative finite number", (long long)i);
+  if (q->boots > 0) return fail(QM_E_STATE, "qm_quant_set_method: %d bootstrap object(s) borrow this quant object", q->boots);
+  if (method == QM_QUANT_METHOD_VBEM) {
+    const int64_t nT1 = std::max<int64_t>(q->nTxps, 1); int rc;
+    if ((rc = q->d_prior.ensure(nT1))) return rc;
+    if (prior && q->nTxps > 0) QXCHK(qx::upload(q->stream, q->d_prior, prior, (size_t)q->nTxps * 8));
+    else QXCHK(qx::fill(q->stream, q->d_prior, 0, (size_t)nT1 * 8));
+    QXCHK(qx::sync(q->stream));                                     // (the caller's array is free again)
+  }
+  q->method = method;
+  return QM_OK;
+}
+
+// E over an array (qm_quant.inl: quant_exp_digamma): one launch on `st`
+static int quant_exp_digamma_array(qx::Stream st, const double* x, int64_t n, double* out) {
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(QM_E_ARG, "qm_quant_exp_digamma: bad argument");
+  if (n == 0) return QM_OK;
+  DevBuf<double> dx, dy; int rc;
+  if ((rc = dx.ensure(n)) || (rc = dy.ensure(n))) return rc;
+  QXCHK(qx::upload(st, dx, x, (size_t)n * 8));
+  HIPCHK(qx::launch<quant_exp_digamma_wave>(st, qx::waves_of(n), (const double*)dx.p, (long long)n, dy.p));
+  return qx::read(st, out, dy, (size_t)n * 8);
+}
+
 static int quant_run(qm_quant* q, int32_t max_iter, int32_t check_every, double rel_tol, double min_alpha, int32_t* iterations, double* last_rel_change) {
   if (max_iter < 0 || check_every < 1 || !(rel_tol >= 0) || !(min_alpha >= 0)) return fail(QM_E_ARG, "qm_quant_run: bad argument");
   qx::Stream st = q->stream;
+  const bool vb = q->method == QM_QUANT_METHOD_VBEM;
+  const double* prior = q->d_prior.p;
   int32_t it = 0; double rel = -1.0; int rc;
   QXCHK(qx::tick(q->ev0, st));
   if (q->nClasses > 0 && max_iter > 0) {
-    HIPCHK(qx::launch<quant_weights_wave>(st, qx::waves_of(q->nTxps), (const double*)q->d_alpha[q->cur].p, (const double*)q->d_eff.p, (long long)q->nTxps, q->d_w.p));
+    if (vb) HIPCHK(qx::launch<quant_weights_vb_wave>(st, qx::waves_of(q->nTxps), (const double*)q->d_alpha[q->cur].p, (const double*)q->d_eff.p, prior, (long long)q->nTxps, q->d_w.p));
+    else HIPCHK(qx::launch<quant_weights_wave>(st, qx::waves_of(q->nTxps), (const double*)q->d_alpha[q->cur].p, (const double*)q->d_eff.p, (long long)q->nTxps, q->d_w.p));
     QuantState Q{};
     Q.cls = QuantCsr{q->d_coff, q->d_clab, q->nClasses, q->d_qCls, q->nqCls};
     Q.txp = QuantCsr{q->d_toff, q->d_tcls, q->nTxps, q->d_qTxp, q->nqTxp};
@@ -131,7 +164,8 @@ static int quant_run(qm_quant* q, int32_t max_iter, int32_t check_every, double 
       Q.alpha = q->d_alpha[q->cur]; Q.alphaNew = q->d_alpha[q->cur ^ 1]; Q.check = check ? 1 : 0;
       if (check) QXCHK(qx::fill(st, q->d_scal + QNT_SC_REL, 0, sizeof(u64)));
       HIPCHK(qx::launch<quant_class_wave>(st, quant_side_waves(Q.cls), Q));
-      HIPCHK(qx::launch<quant_txp_wave>(st, quant_side_waves(Q.txp), Q));
+      if (vb) HIPCHK(qx::launch<quant_txp_vb_wave>(st, quant_side_waves(Q.txp), Q, prior));
+      else HIPCHK(qx::launch<quant_txp_wave>(st, quant_side_waves(Q.txp), Q));
       q->cur ^= 1; ++it;
       if (check) {                                                  // the one word the host reads
         if ((rc = qx::read(st, q->h_rel.p, q->d_scal + QNT_SC_REL, sizeof(u64)))) return rc;
@@ -184,6 +218,17 @@ int qm_quant_set_start(qm_quant* q, const double* alpha0) {
   if (!q) return fail(QM_E_ARG, "null quant object");
   HIPCHK(hipSetDevice(q->device));
   return quant_set_start(q, alpha0);
+}
+
+int qm_quant_set_method(qm_quant* q, int method, const double* prior) {
+  if (!q) return fail(QM_E_ARG, "null quant object");
+  HIPCHK(hipSetDevice(q->device));
+  return quant_set_method(q, method, prior);
+}
+
+int qm_quant_exp_digamma(int device, const double* x, int64_t n, double* out) {
+  HIPCHK(hipSetDevice(device));
+  return quant_exp_digamma_array(nullptr, x, n, out);              // (the null stream: no object is at hand)
 }
 
 int qm_quant_run(qm_quant* q, int32_t max_iter, int32_t check_every, double rel_tol, double min_alpha, int32_t* iterations, double* last_rel_change) {
