@@ -793,11 +793,13 @@ static DevIndex dev_index(const qm_ctx* c) {
 
 // The wide extension table (SaExt2: 224 characters behind every suffix's k-mer, 64 bytes per suffix-array entry) for the one-read-per-
 // wavefront lean kernel: built by the first call that has reads of 129 .. 256 characters, shared by the replica's contexts; a replica
-// that has no room for it (or no SaExt) goes on with the general kernels.
+// that has no room for it (or no SaExt) goes on with the general kernels.  So does an index of 2^QM_EXT2_TID_BITS transcripts or more:
+// the limit comes from the entry layout (saext2_entry keeps the transcript in that many bits, one fewer than SaExt's), so SaExt being
+// there does not imply it.
 static bool ensure_saext2(qm_ctx* c) {
   if (c->d_saext2) return true;
   Replica& R = *c->rep;
-  if (!R.saext || c->ix->nSA <= 0) return false;
+  if (!R.saext || c->ix->nSA <= 0 || c->ix->nTxp >= (1LL << QM_EXT2_TID_BITS)) return false;
   std::lock_guard<std::mutex> lk(R.sanextMu);
   if (!R.saext2 && !R.saext2Tried) {
     R.saext2Tried = true;
