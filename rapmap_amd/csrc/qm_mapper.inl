@@ -1320,8 +1320,11 @@ QM_DEV void get_sa_hits(const DevIndex& ix, const ReadBatch& B, Strand<NS>& V, c
       if (!(F & QM_F_SEL) && out.n == 0 && ub - lb <= (u32)out.pfcap && !xs.done) {
         // three reads in four end with exactly one interval per strand, whose (tid, pos) entries hits->mappings needs next:
         // ask for them now, straight into LDS, so that the trip to sainfo runs under the rest of the walk
-        QM_LANES(l) {
-          if (l < (int)(ub - lb)) { const u32* g = (const u32*)&ix.sainfo[lb + l]; lds_dma_u32(g, out.pf, l); lds_dma_u32(g + 1, out.pf + out.pfcap, l); }
+        // (pfcap = 64 NS - P may exceed a wavefront's 64 lanes -- a read much shorter than its slot class: one round of 64 records after the other)
+        for (int base = 0; base < (int)(ub - lb); base += 64) {
+          QM_LANES(l) {
+            if (base + l < (int)(ub - lb)) { const u32* g = (const u32*)&ix.sainfo[lb + base + l]; lds_dma_u32(g, out.pf + base, l); lds_dma_u32(g + 1, out.pf + out.pfcap + base, l); }
+          }
         }
       }
       out.push(lb, ub, (u32)mlen, (u32)p);
@@ -1568,10 +1571,13 @@ QM_DEV int single_interval(const DevIndex& ix, const Bufs& bf, int rOff, u32 lb,
   QM_CNT(12, 1); QM_CNT(13, n);
   if (pf && n <= pfcap) {                                // the only interval of the list is the first one recorded: staged by get_sa_hits
     lds_dma_wait();
-    QM_LANES(l) {
-      if (l < n) {
-        const int hitPos = (int)(pf[pfcap + l] - qpos);
-        bf.A[l] = ((u64)pf[l] << 32) | ((u32)hitPos ^ 0x80000000u);
+    for (int base = 0; base < n; base += 64) {           // n > 64 here: every staged record, not the first 64
+      QM_LANES(l) {
+        int i = base + l;
+        if (i < n) {
+          const int hitPos = (int)(pf[pfcap + i] - qpos);
+          bf.A[i] = ((u64)pf[i] << 32) | ((u32)hitPos ^ 0x80000000u);
+        }
       }
     }
   } else

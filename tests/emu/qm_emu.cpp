@@ -56,6 +56,8 @@ template <bool WIDE, bool NQ> static void emu_lean(bool paired, bool sel, const 
     case 6: emu_lean_waves<true, true, false, WIDE, NQ>(ix, B); break;   default: emu_lean_waves<true, true, true, WIDE, NQ>(ix, B); break;
   }
 }
+// QM_EMU_LEAN_STATS=2: besides the counts, the reads each kernel left, by index (one line per kernel and pass)
+static bool lean_stats_list() { const char* e = getenv("QM_EMU_LEAN_STATS"); return e && e[0] == '2'; }
 // the lean kernel over a batch and (the narrow edition) its N-aware pass over the queue of the reads the first pass marked (qm_host.hip, run_stage_a):
 // what that pass maps is compared like everything else the lean kernel maps, what it marks again stays marked
 static void emu_lean_passes(bool paired, bool sel, bool wide, const DevIndex& ix, ReadBatch Lb, const std::vector<u32>& lcnt2, u64* scal, const char* what) {
@@ -272,6 +274,7 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
     }
     if ((long long)scal2[QM_SC_LEANQ] != deferred) { fprintf(stderr, "[qm emu] lean kernel: %lld marks, counter says %llu\n", deferred, (unsigned long long)scal2[QM_SC_LEANQ]); ++bad; }
     if (getenv("QM_EMU_LEAN_STATS")) fprintf(stderr, "[qm emu] lean kernel took %lld of %lld reads\n", nreads - deferred, nreads);
+    if (lean_stats_list()) { fprintf(stderr, "[qm emu] lean kernel left:"); for (long long r = 0; r < nreads; ++r) if (lcnt2[r] == QM_LCNT_LEAN) fprintf(stderr, " %lld", r); fprintf(stderr, "\n"); }
     if (bad || (status2 & ~1)) status |= 128;
   }
   if ((ns == 2 || leanWide) && (ix.slots || ix.ph) && ix.saext && ix.sanext && B.sensitive && o->sel_aln && !(status & 1) && !getenv("QM_EMU_NO_LEAN")) {
@@ -362,6 +365,7 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
       }
       if ((long long)scal2[QM_SC_LEANQ] != deferred) { fprintf(stderr, "[qm emu] %s: %lld marks, counter says %llu\n", kname, deferred, (unsigned long long)scal2[QM_SC_LEANQ]); ++bad; }
       if (getenv("QM_EMU_LEAN_STATS")) fprintf(stderr, "[qm emu] %s (pass %d) took %lld of %lld reads, merged %lld of %lld pairs\n", kname, pass, nreads - deferred, nreads, merged, nunits);
+      if (lean_stats_list()) { fprintf(stderr, "[qm emu] %s (pass %d) left:", kname, pass); for (long long r = 0; r < nreads; ++r) if (lcnt2[r] == QM_LCNT_LEAN) fprintf(stderr, " %lld", r); fprintf(stderr, "\n"); }
       if (bad || (status2 & ~1)) status |= 32;
     }
   }
