@@ -7,3 +7,7 @@ from .api import (QuasiIndex, QuasiMapper, QmError, QmOpts, default_opts, build_
                   HIT_DTYPE, INTERVAL_DTYPE, LIB_PATH, ABI_SYMBOLS, EqClasses, write_eq_classes, read_eq_classes,
                   Quant, exp_digamma, write_quant, read_quant, Bootstrap, write_bootstraps, read_bootstraps,
                   FragLenDist, eff_lens_from_counts, frag_len_mean, write_flen_dist, read_flen_dist, FLD_DEFAULT_MAX_LEN, FLD_STATS)
+from . import api
+
+# QM_STAT_* and QM_EQC_STAT_*: what QuasiMapper.stat and EqClasses.stat are asked for
+globals().update({name: value for name, value in vars(api).items() if name.startswith(("QM_STAT_", "QM_EQC_STAT_"))})

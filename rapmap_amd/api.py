@@ -47,6 +47,12 @@ ABI_SYMBOLS = [
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
 ]
 
+# the `which` of QuasiMapper.stat (qm_ctx_stat) and of EqClasses.stat (qm_eqc_stat): the two enums of include/qmap_mi355.h, which says what each counts
+(QM_STAT_RELAUNCHES, QM_STAT_LIST_WORDS, QM_STAT_SLOW_READS, QM_STAT_LEAN_READS, QM_STAT_LEAN_DEFERRED, QM_STAT_SKIPPED_READS,
+ QM_STAT_SEL_QUESTIONS, QM_STAT_KSW2_ALIGNMENTS, QM_STAT_STRIP_ALIGNMENTS, QM_STAT_PAIR_KERNEL_PAIRS, QM_STAT_PAIRS_MERGED,
+ QM_STAT_DEFER_DIRTY, QM_STAT_DEFER_HOMOPOLYMER, QM_STAT_DEFER_WIDE, QM_STAT_DEFER_BOTH_STRANDS, QM_STAT_N_PASS_READS) = range(16)
+QM_EQC_STAT_GROWTHS, QM_EQC_STAT_COLLISION_PROBES, QM_EQC_STAT_LONG_UNITS, QM_EQC_STAT_ROUNDS, QM_EQC_STAT_LAST_FOLD_US = range(5)
+
 
 class QmError(RuntimeError):
     pass
@@ -406,12 +412,14 @@ class QuasiMapper:
         return tot.value, reads, codes
 
     def stat(self, which):
-        """qm_ctx_stat: 0 stage-A relaunches of the last call, 1 list buffer capacity (words), 2 reads on the -s slow path,
-        3 reads the lean stage-A kernel was launched over (-1: the general kernel ran), 4 reads it left to the general kernel,
-        5 reads that were skipped (qm_fetch_skipped), 6 / 7 / 8 (-s) alignment questions beyond PERFECT chains / ksw2 alignments run for them / alignments the strip DP answered,
-        9 pairs the pair kernel was launched over (-1: not used), 10 pairs it merged itself, 11 .. 14 why the reads of 4 were left: a character that is not
-        A C G T / a window of k equal bases / an interval or a list beyond the kernel's lanes / hits on the other strand as well,
-        15 reads with N's that the N-aware second pass of stage A mapped (not part of 4 or 11)"""
+        """qm_ctx_stat; which is one of this module's QM_STAT_*: RELAUNCHES stage-A relaunches of the last call, LIST_WORDS list buffer capacity
+        (words), SLOW_READS reads on the -s slow path, LEAN_READS reads the lean stage-A kernel was launched over (-1: the general kernel ran),
+        LEAN_DEFERRED reads it left to the general kernel, SKIPPED_READS reads that were skipped (qm_fetch_skipped), SEL_QUESTIONS / KSW2_ALIGNMENTS /
+        STRIP_ALIGNMENTS (-s) alignment questions beyond PERFECT chains / ksw2 alignments run for them / alignments the strip DP answered,
+        PAIR_KERNEL_PAIRS pairs the pair kernel was launched over (-1: not used), PAIRS_MERGED pairs it merged itself, DEFER_DIRTY / DEFER_HOMOPOLYMER /
+        DEFER_WIDE / DEFER_BOTH_STRANDS why the reads of LEAN_DEFERRED were left: a character that is not A C G T / a window of k equal bases / an
+        interval or a list beyond the kernel's lanes / hits on the other strand as well, N_PASS_READS reads with N's that the N-aware second pass of
+        stage A mapped (not part of LEAN_DEFERRED or DEFER_DIRTY)"""
         v = C.c_int64()
         _check(lib().qm_ctx_stat(self._h, int(which), C.byref(v)))
         return v.value
@@ -654,7 +662,8 @@ class EqClasses:
         return off, tids[:nt], cnt[:nc]
 
     def stat(self, which):
-        """qm_eqc_stat: GROWTHS, COLLISION_PROBES, LONG_UNITS, ROUNDS, LAST_FOLD_US (the last fold by HIP events on its stream)"""
+        """qm_eqc_stat; which is one of this module's QM_EQC_STAT_*: GROWTHS, COLLISION_PROBES, LONG_UNITS, ROUNDS, LAST_FOLD_US (the last fold by
+        HIP events on its stream)"""
         v = C.c_int64()
         _check(lib().qm_eqc_stat(self._h, int(which), C.byref(v)))
         return v.value

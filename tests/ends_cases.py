@@ -11,12 +11,10 @@ The seeds: txome(k, seed=TXOME_SEED) -- make_transcriptome(8, seed) for the ordi
 transcripts and the places of the substrings; reads(..., seed=READS_SEED) -- default_rng(seed * 1000 + L * 32 + k) for flanks and
 substitutions.  Nothing else is random.
 
-No test functions here.  Indices and read sets are built once per process (kmer_cases' cache)."""
-import os
-
+No test functions here.  Indices and read sets are built once per process (mapping_harness.once)."""
 import numpy as np
 
-from kmer_cases import _B, _COMP, _build, _dir, _once, check, odd_single  # noqa: F401  (check and odd_single: used by the test modules)
+import mapping_harness as mh
 
 TXOME_SEED = 31
 READS_SEED = 7
@@ -39,7 +37,7 @@ def txome(k, seed=TXOME_SEED):
     def make():
         from rapmap_amd import synth
         rng = np.random.default_rng(seed * 1000 + k)
-        rand = lambda n: _B[rng.integers(0, 4, n)]
+        rand = lambda n: mh.ACGT[rng.integers(0, 4, n)]
         names, seqs = ["first_k-1"], [rand(k - 1)]
         gn, gs = synth.make_transcriptome(8, seed)
         first = {}
@@ -53,7 +51,7 @@ def txome(k, seed=TXOME_SEED):
             for n in random_lengths(k):
                 t = rand(n)
                 while any(t.size == s.size and t.tobytes() == s.tobytes() for s in seqs):
-                    t = _B[(np.searchsorted(_B, t) + 1) % 4]                    # (a 1-character transcript has four values)
+                    t = mh.ACGT[(np.searchsorted(mh.ACGT, t) + 1) % 4]                    # (a 1-character transcript has four values)
                 names.append("%s_%d" % (tag, n)); seqs.append(t)
         random_set("rnd")
         src = [gs[i] for i in rng.permutation(len(gs))[:6]]
@@ -65,27 +63,12 @@ def txome(k, seed=TXOME_SEED):
         names.append("last_k"); seqs.append(rand(k))
         assert len({s.tobytes() for s in seqs}) == len(seqs), "two equal transcripts: the indexer would drop one"
         return names, seqs
-    return _once(("ends_txome", k, seed), make)
+    return mh.once(("ends_txome", k, seed), make)
 
 
 def index_for(tmp_root, k, image, seed=TXOME_SEED):
     """txome(k) indexed at k; image: "dense" or "ph" (`quasiindex -p`).  The index holds every transcript, in file order."""
-    def make():
-        import rapmap_amd as ra
-        from rapmap_amd import synth
-        names, seqs = txome(k, seed)
-        d = _dir(tmp_root, "ends_k%d" % k)
-        fa = os.path.join(d, "txome.fa")
-        if not os.path.exists(fa):
-            synth.write_fasta(fa, names, seqs)
-        idx = _build(fa, os.path.join(d, "idx_%s" % image), k, image, threads=2)
-        qi = ra.QuasiIndex(idx)
-        try:
-            assert qi.txp_names == names and [int(x) for x in qi.txp_lens] == [s.size for s in seqs], "the index does not hold the transcripts as written"
-        finally:
-            qi.close()
-        return idx
-    return _once(("ends_index", k, image, seed), make)
+    return mh.once(("ends_index", k, image, seed), lambda: mh.index_of(tmp_root, "ends", k, image, *txome(k, seed)))
 
 
 def overhangs(L, k):
@@ -120,12 +103,12 @@ def reads(txps, L, k, seed=READS_SEED):
                 o = u.find(whole[ti], o + 1)
         for random_flanks in (True, False):
             if random_flanks:
-                fl, fr = _B[rng.integers(0, 4, F)], _B[rng.integers(0, 4, F)]
+                fl, fr = mh.ACGT[rng.integers(0, 4, F)], mh.ACGT[rng.integers(0, 4, F)]
             else:
-                before = np.concatenate([_B[rng.integers(0, 4, F)]] + list(txps[:ti]))
-                behind = np.concatenate(list(txps[ti + 1:]) + [_B[rng.integers(0, 4, F)]])
+                before = np.concatenate([mh.ACGT[rng.integers(0, 4, F)]] + list(txps[:ti]))
+                behind = np.concatenate(list(txps[ti + 1:]) + [mh.ACGT[rng.integers(0, 4, F)]])
                 fl, fr = before[-F:], behind[:F]
-            s = np.concatenate([fl, t, fr, _B[rng.integers(0, 4, 2)]])   # (two more: what a deletion pulls in)
+            s = np.concatenate([fl, t, fr, mh.ACGT[rng.integers(0, 4, 2)]])   # (two more: what a deletion pulls in)
             starts = [F - d for d in overhangs(L, k)] + [F + T - L + d for d in overhangs(L, k)]
             if T < L:
                 starts += [F - ((L - T) * j) // 5 for j in range(6)]
@@ -138,14 +121,14 @@ def reads(txps, L, k, seed=READS_SEED):
                     w = s[st:st + L].copy()
                     edited = False
                     if nread % 7 == 3:
-                        w[L // 2] = _B[(np.searchsorted(_B, w[L // 2]) + 1 + rng.integers(0, 3)) % 4]
+                        w[L // 2] = mh.ACGT[(np.searchsorted(mh.ACGT, w[L // 2]) + 1 + rng.integers(0, 3)) % 4]
                         edited = True
                     if nread % 11 == 5:
                         w = np.delete(s[st:st + L + 1], L // 2)
                         edited = True
                     nread += 1
                     if not fwd:
-                        w = _COMP[w[::-1]]
+                        w = mh.COMP[w[::-1]]
                     p = st - F
                     inside = max(0, min(p + L, T) - max(p, 0))
                     runs_on = any((p < 0 and o > 0 and u[o - 1] == s[F - 1]) or (p + L > T and o + T < u.size and u[o + T] == s[F + T]) for u, o in inside_of)
@@ -165,7 +148,7 @@ def reads_for(k, L, seed=READS_SEED):
         q1, o1 = pack(r1); q2, o2 = pack(r2)
         assert set(np.diff(o1)) == {L} and set(np.diff(o2)) == {L}
         return {"r1": r1, "r2": r2, "truth": truth, "q1": q1, "o1": o1, "q2": q2, "o2": o2, "n": len(r1), "lens": np.array([s.size for s in seqs], dtype=np.int64)}
-    return _once(("ends_reads_for", k, L, seed), make)
+    return mh.once(("ends_reads_for", k, L, seed), make)
 
 
 # ---- the checks
@@ -255,37 +238,18 @@ def covered_single(truth, k):
     return [a for a, b in covered([(e, e) for e in one], k, paired=False)]
 
 
-# ---- the option sets: (oracle's spelling, the emulation's and the library's spelling); "mimic*": made by mimic_opts()
+# ---- the option sets (mapping_harness.OPTION_SETS)
 
-OPTION_SETS = {
-    "default": ({}, {}),
-    "noSensitive": ({"sensitive": 0}, {"sensitive": 0}),
-    "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}),
-    "noDovetail": ({"noDovetail": 1}, {"no_dovetail": 1}),
-    "noOrphans": ({"noOrphans": 1}, {"no_orphans": 1}),
-    "noStrictCheck": ({"strictCheck": 0}, {"strict_check": 0}),
-    "z0.9": ({"quasiCov": 0.9}, {"quasi_cov": 0.9}),
-    "selAln": ({"selAln": 1}, {"sel_aln": 1}),
-    "selAln_hardFilter": ({"selAln": 1, "hardFilter": 1}, {"sel_aln": 1, "hard_filter": 1}),
-    "selAln_fullband": ({"selAln": 1, "dpBandwidth": -1}, {"sel_aln": 1, "dp_bandwidth": -1}),
-    "mimicBT2": None,
-    "mimicStrictBT2": None,
-}
+OPTION_SETS = ("default", "noSensitive", "fuzzy", "noDovetail", "noOrphans", "noStrictCheck", "z0.9", "selAln", "selAln_hardFilter", "selAln_fullband",
+               "mimicBT2", "mimicStrictBT2")
 FEW = ("default", "fuzzy", "selAln", "mimicBT2")
-
-
-def opts_for(variant, oracle_mod, default_opts):
-    """(the oracle's options, the options of the code under test: default_opts is emu.default_opts or rapmap_amd.default_opts)"""
-    if variant.startswith("mimic"):
-        strict = variant == "mimicStrictBT2"
-        mine = dict(sel_aln=1, aln_policy=2 if strict else 1, no_orphans=1, no_dovetail=1, consensus_slack=0.35, max_num_hits=1000)
-        if strict:
-            mine.update(min_score_fraction=0.8, match_score=1, mismatch_penalty=0, gap_open=25, gap_extend=25)
-        return oracle_mod.mimic_bt2_opts(strict=strict), default_opts(**mine)
-    oo, mo = OPTION_SETS[variant]
-    return oracle_mod.default_opts(**oo), default_opts(**mo)
 
 
 def report(what, n, res, got_reach):
     """the line every test prints per configuration: the record of what ran (profiles/txp_ends/results)"""
     print("%s: %d units, %d hits, pos<0 %d, past the end %d, on a transcript shorter than the read %d" % ((what, n, len(res.hits)) + tuple(got_reach)))
+
+
+def after_ref(res, rd, L, variant, what):
+    """mapping_harness.ref's hook: every oracle result of this data has its reach asserted and reported when it is computed"""
+    report("oracle, " + what, len(res.hit_offsets) - 1, res, assert_reach(res, rd["lens"], L, variant, what))

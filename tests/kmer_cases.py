@@ -5,7 +5,7 @@ The reference throughout is the oracle (oracle.Oracle(q5.load(idx))), which read
 own quasimap binary cannot be built in this project's image, so there is no golden SAM at another k; truth_check() below is
 the one check that does not go through the oracle.
 
-No test functions here.  Indices and read sets are built once per process and kept (the cache below); the test modules
+No test functions here.  Indices and read sets are built once per process and kept (mapping_harness.once); the test modules
 reach them through module-scoped fixtures that pass a directory of tmp_path_factory's."""
 import gzip
 import os
@@ -13,8 +13,9 @@ import shutil
 
 import numpy as np
 
-from conftest import GOLD, load_oracle
-from util import assert_hits_equal, pack
+import mapping_harness as mh
+from conftest import GOLD
+from util import pack
 
 KS = (15, 17, 21, 29)              # 15 / 17: either side of the 32 bits of a packed k-mer; 29: next to the maximum; 21: the common choice
 K_SMALL = 9                        # nearly every read trips the take-or-leave rule of the pair / lean kernels: default options only, never -s
@@ -33,48 +34,25 @@ EXPECT_LEFT = {
     (29, "dense"): {"pair": 529, "lean": 529}, (29, "ph"): {"pair": 529, "lean": 529},
 }
 
-_B = np.frombuffer(b"ACGT", dtype=np.uint8)
-_COMP = np.zeros(256, np.uint8)
-_COMP[:] = ord("N")
-for _a, _b in zip(b"ACGTacgt", b"TGCAtgca"):
-    _COMP[_a] = _b
-
-_cache = {}
-
-
-def _once(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
-
-
-def _dir(tmp_root, name):
-    d = os.path.join(str(tmp_root), name)
-    os.makedirs(d, exist_ok=True)
-    return d
-
-
-def _build(fasta, out, k, image, threads=4):
-    import rapmap_amd as ra
-    assert image in ("dense", "ph"), image
-    ra.build_index(fasta, out, k=k, threads=threads, perfect_hash=image == "ph")
-    return out
+# the option sets of the golden reads at k = 15, 17 and 29 (at k = 21: every one of mapping_harness.PLAIN_SETS), and the few of the other reads
+SOME = ("default", "noStrictCheck", "z0.9", "noSensitive", "fuzzy", "selAln")
+FEW = ("default", "noSensitive", "fuzzy", "selAln")
 
 
 # ---- synth_small (the golden transcriptome and its 4 234 adversarial pairs)
 
 def golden_fasta(tmp_root):
     def make():
-        fa = os.path.join(_dir(tmp_root, "golden"), "txome.fa")
+        fa = os.path.join(mh.subdir(tmp_root, "golden"), "txome.fa")
         with gzip.open(os.path.join(GOLD, "synth_small", "txome.fa.gz"), "rb") as g, open(fa, "wb") as o:
             shutil.copyfileobj(g, o)
         return fa
-    return _once("golden_fasta", make)
+    return mh.once("golden_fasta", make)
 
 
 def index_for(tmp_root, k, image):
     """the synth_small transcriptome indexed at k; image: "dense" or "ph" (`quasiindex -p`)"""
-    return _once(("golden", k, image), lambda: _build(golden_fasta(tmp_root), os.path.join(_dir(tmp_root, "golden"), "idx_k%d_%s" % (k, image)), k, image))
+    return mh.once(("golden", k, image), lambda: mh.build(golden_fasta(tmp_root), os.path.join(mh.subdir(tmp_root, "golden"), "idx_k%d_%s" % (k, image)), k, image))
 
 
 def golden_reads():
@@ -84,7 +62,7 @@ def golden_reads():
         n1, s1 = sam.read_fastq(os.path.join(GOLD, "synth_small", "reads_1.fastq.gz"))
         n2, s2 = sam.read_fastq(os.path.join(GOLD, "synth_small", "reads_2.fastq.gz"))
         return n1, s1, n2, s2, pack(s1) + pack(s2)
-    return _once("golden_reads", make)
+    return mh.once("golden_reads", make)
 
 
 # ---- a smaller transcriptome for reads beyond 128 characters and for the error-free pairs
@@ -94,15 +72,15 @@ def small_txome(tmp_root):
     def make():
         from rapmap_amd import synth
         names, txps = synth.make_transcriptome(60, seed=2121, paralog_frac=0.05)
-        fa = os.path.join(_dir(tmp_root, "small"), "txome.fa")
+        fa = os.path.join(mh.subdir(tmp_root, "small"), "txome.fa")
         synth.write_fasta(fa, names, txps)
         assert 100 < len(txps) < 1000 and sum(t.size for t in txps) < 1000000
         return {"fasta": fa, "names": names, "txps": txps}
-    return _once("small_txome", make)
+    return mh.once("small_txome", make)
 
 
 def small_index(tmp_root, k, image):
-    return _once(("small", k, image), lambda: _build(small_txome(tmp_root)["fasta"], os.path.join(_dir(tmp_root, "small"), "idx_k%d_%s" % (k, image)), k, image))
+    return mh.once(("small", k, image), lambda: mh.build(small_txome(tmp_root)["fasta"], os.path.join(mh.subdir(tmp_root, "small"), "idx_k%d_%s" % (k, image)), k, image))
 
 
 def long_reads(tmp_root, read_len, n, seed):
@@ -112,7 +90,7 @@ def long_reads(tmp_root, read_len, n, seed):
         txps = [t for t in small_txome(tmp_root)["txps"] if t.size >= 3 * read_len]
         s1, s2, off, _ = synth.make_reads(txps, n, seed=seed, read_len=read_len, err=0.01)
         return s1, off, s2, off
-    return _once(("long_reads", read_len, n, seed), make)
+    return mh.once(("long_reads", read_len, n, seed), make)
 
 
 def index_text(idx):
@@ -155,7 +133,7 @@ def edge_reads(idx, k, seed=5):
             t = ok[rng.integers(0, ok.size)]
             a = int(offsets[t] + rng.integers(0, ends[t] - offsets[t] - 280))
             f = text[a:a + L1].copy()
-            m = _COMP[text[a + 150:a + 150 + L2][::-1]].copy()
+            m = mh.COMP[text[a + 150:a + 150 + L2][::-1]].copy()
             for r in (f, m):
                 L = r.size
                 if L == 0:
@@ -183,7 +161,7 @@ def edge_reads(idx, k, seed=5):
                 f, m = m, f
             r1.append(bytes(f)); r2.append(bytes(m))
         return r1, r2
-    return _once(("edge_reads", idx, k, seed), make)
+    return mh.once(("edge_reads", idx, k, seed), make)
 
 
 def n_case_reads(idx, k, seed=5):
@@ -191,14 +169,6 @@ def n_case_reads(idx, k, seed=5):
     r1, r2 = edge_reads(idx, k, seed)
     keep = [i for i in range(len(r1)) if b"N" in r1[i] or b"N" in r2[i]]
     return [r1[i] for i in keep], [r2[i] for i in keep]
-
-
-def odd_single(r1, r2):
-    """single-end reads, an odd count: mate 1 of every pair but the last, and one mate 2"""
-    one = list(r1[:-1]) + list(r2[1:2])
-    if len(one) % 2 == 0:
-        one = one[:-1]
-    return one
 
 
 def has_window(read, k):
@@ -228,28 +198,28 @@ def run_reads(tmp_root, k):
         names, txps, spots = [], [], []
         runs = [(r, False) for r in range(k - 7, k + 10)] + [(2 * k + 2, False), (3 * k, False), (k, True), (k + 1, True), (2 * k, True), (k - 1, False), (k, False)]
         for i, (run, dinuc) in enumerate(runs):
-            base = _B[i % 4]
+            base = mh.ACGT[i % 4]
             mid = np.full(run, base, np.uint8)
             if dinuc:
-                mid = np.tile(np.array([base, _B[(i + 1) % 4]], np.uint8), (run + 1) // 2)[:run]
-            l = _B[rng.integers(0, 4, 150)]; r = _B[rng.integers(0, 4, 150)]
-            if l[-1] == base: l[-1] = _B[(i + 1) % 4]
-            if r[0] == mid[-1]: r[0] = _B[(i + 2) % 4] if _B[(i + 2) % 4] != mid[-1] else _B[(i + 3) % 4]
+                mid = np.tile(np.array([base, mh.ACGT[(i + 1) % 4]], np.uint8), (run + 1) // 2)[:run]
+            l = mh.ACGT[rng.integers(0, 4, 150)]; r = mh.ACGT[rng.integers(0, 4, 150)]
+            if l[-1] == base: l[-1] = mh.ACGT[(i + 1) % 4]
+            if r[0] == mid[-1]: r[0] = mh.ACGT[(i + 2) % 4] if mh.ACGT[(i + 2) % 4] != mid[-1] else mh.ACGT[(i + 3) % 4]
             txps.append(np.concatenate([l, mid, r])); names.append("run%d_%d%s" % (run, i, "d" if dinuc else "")); spots.append((150, run))
-        d = _dir(tmp_root, "runs_k%d" % k)
+        d = mh.subdir(tmp_root, "runs_k%d" % k)
         fa = os.path.join(d, "t.fa")
         synth.write_fasta(fa, names, txps)
-        idx = _build(fa, os.path.join(d, "idx"), k, "dense", threads=2)
+        idx = mh.build(fa, os.path.join(d, "idx"), k, "dense", threads=2)
         r1, r2 = [], []
         for t, (st, run) in zip(txps, spots):
             for back in list(range(0, 8)) + [17, 30]:
                 a0 = st - back
                 a = t[a0:a0 + 100].copy()
                 b0 = min(len(t) - 100, a0 + 120)
-                b = _COMP[t[b0:b0 + 100][::-1]]
+                b = mh.COMP[t[b0:b0 + 100][::-1]]
                 if back % 5 == 4:                               # a substitution right behind the run
                     p = min(99, back + run + 3)
-                    a[p] = _B[(np.searchsorted(_B, a[p]) + 1) % 4]
+                    a[p] = mh.ACGT[(np.searchsorted(mh.ACGT, a[p]) + 1) % 4]
                 if back in (3, 6, 30):                          # ... and an N in the flank: the run in a read that is not clean
                     a[0] = ord("N")
                 if back in (2, 5, 17):                          # ... or right in front of the run: the walk starts again on the run's first base
@@ -261,7 +231,7 @@ def run_reads(tmp_root, k):
         r1.append(b"A" * 100); r2.append(b"T" * 100)
         r1.append(b"A" * k + t[:100 - k].tobytes()); r2.append(b"C" * (k - 1) + t[:101 - k].tobytes())
         return {"fasta": fa, "idx": idx, "reads1": r1, "reads2": r2}
-    return _once(("run_reads", k), make)
+    return mh.once(("run_reads", k), make)
 
 
 def fuzz_reads(text, offsets, n, seed, max_len, k):
@@ -280,7 +250,7 @@ def fuzz_reads(text, offsets, n, seed, max_len, k):
         mates = []
         for m in range(2):
             L = int(rng.integers(0, max_len + 1)) if rng.random() < 0.15 else int(rng.integers(max(k, max_len // 3), max_len + 1))
-            seq = frag[:L].copy() if m == 0 else _COMP[frag[::-1][:L]].copy()
+            seq = frag[:L].copy() if m == 0 else mh.COMP[frag[::-1][:L]].copy()
             kind = rng.random()
             if seq.size and kind < 0.5:
                 w = rng.random(seq.size) < 0.015
@@ -301,47 +271,7 @@ def fuzz_reads(text, offsets, n, seed, max_len, k):
     return r1, r2
 
 
-# ---- the checks
-
-INT_COLS = ((0, "begin"), (1, "end"), (2, "len"), (3, "query_pos"), (5, "list"))
-
-
-def check(res, got, what, ints=None):
-    """hits and counters of `got` (an emulation or a device result) equal the oracle's `res`; ints = (offsets, records) where the
-    SA-interval records were kept: their five columns equal the oracle's too (res mapped with want_ints=True)"""
-    assert_hits_equal(res.hit_offsets, res.hits, got.hit_offsets, got.hits, what)
-    assert res.counters == got.counters, (what, res.counters, got.counters)
-    if ints is not None:
-        offs, recs = ints
-        assert np.array_equal(res.ints_offsets, offs), what + ": interval offsets"
-        for col, name in INT_COLS:
-            assert np.array_equal(res.ints[:, col], recs[name].astype(np.int32)), "%s: interval column %s" % (what, name)
-
-
-def check_stage_view(res, stage, what, max_num_hits=200):
-    """The merge of a stage view (map_pairs_stages: stage B without the caller-level bookkeeping) against the oracle's fused result `res`
-    under default options.  The one thing the caller's bookkeeping does there is drop the orphans of a unit that has more than maxNumHits
-    of them (RapMapSAMapper.cpp:534-536; unit_merge's `merge_only`): such a unit is empty in `res` and keeps its orphans in the stage view.
-    Every other unit's records equal the oracle's byte for byte; peHits, seHits, numReads and tooManyHits are the oracle's, totHits and
-    mappedUnits are the oracle's plus what those units keep.  -> the number of such units"""
-    so, ro = np.asarray(stage.hit_offsets), np.asarray(res.hit_offsets)
-    assert so.size == ro.size, what
-    sc, rc = np.diff(so), np.diff(ro)
-    differ = np.nonzero(sc != rc)[0]
-    kept = 0
-    for u in differ:
-        h = stage.hits[so[u]:so[u + 1]]
-        assert rc[u] == 0 and sc[u] > max_num_hits and not h["is_paired"].any() and (h["mate_status"] != 3).all(), \
-            "%s: unit %d has %d hits in the stage view, %d in the fused result" % (what, u, sc[u], rc[u])
-        kept += int(sc[u])
-    same = np.repeat(sc == rc, sc)
-    assert stage.hits[same].tobytes() == res.hits.tobytes(), what + ": hit records differ from the fused result"
-    want = dict(res.counters)
-    want["totHits"] += kept
-    want["mappedUnits"] += len(differ)
-    assert stage.counters == want, (what, stage.counters, want)
-    return len(differ)
-
+# ---- the check that does not go through the oracle
 
 def truth_pairs(tmp_root, n=2000, seed=99):
     """n error-free pairs of 2 x 100 characters off small_txome.  -> (q1, o, q2, o, truth); truth[i] = (sequence of the transcript the
@@ -357,13 +287,13 @@ def truth_pairs(tmp_root, n=2000, seed=99):
             sides = []
             for s in (s1, s2):
                 r = s[off[i]:off[i + 1]].tobytes()
-                rc = _COMP[np.frombuffer(r, np.uint8)[::-1]].tobytes()
+                rc = mh.COMP[np.frombuffer(r, np.uint8)[::-1]].tobytes()
                 occ = {True: _occurrences(t, r), False: _occurrences(t, rc)}
                 sides.append(occ)
             assert int(where[i, 1]) in sides[0][True] or int(where[i, 1]) in sides[1][True]
             truth.append((t, sides[0], sides[1]))
         return s1, off, s2, off, truth
-    return _once(("truth_pairs", n, seed), make)
+    return mh.once(("truth_pairs", n, seed), make)
 
 
 def _occurrences(t, r):

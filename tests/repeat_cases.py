@@ -10,16 +10,26 @@ through the suffix array.  reach() is a condition on the DATA, asked of the orac
 The seeds: txome(k, seed=TXOME_SEED) -- make_transcriptome(6, seed) for the ordinary genes, default_rng(seed * 1000 + k) for everything
 else; reads(..., seed=READS_SEED) -- default_rng(seed * 1000 + L * 32 + k) for overhangs and paddings.  Nothing else is random.
 
-No test functions here.  Indices and read sets are built once per process (kmer_cases' cache)."""
-import os
+No test functions here.  Indices and read sets are built once per process (mapping_harness.once)."""
 import re
 
 import numpy as np
 
-from kmer_cases import _B, _COMP, _build, _dir, _once, check, emu_left, odd_single  # noqa: F401  (used by the test modules)
+import mapping_harness as mh
 
 TXOME_SEED = 53
 READS_SEED = 11
+
+# Reads the pair and the lean kernel leave to the general kernel on reads_for(k, 100) under default options, and how many of the reads
+# they KEEP have their hit list from one interval that lists a transcript more than once (so their per-transcript minimum decided
+# something).  From the lane emulation (QM_EMU_LEAN_STATS=2); test_txp_repeats_gpu.py holds qm_ctx_stat(QM_STAT_LEAN_DEFERRED) to
+# "pair" / "lean".
+EXPECT_LEFT = {
+    (31, "dense"): {"pair": 2777, "lean": 1816, "pair_kept_repeated": 759, "lean_kept_repeated": 1582},
+    (31, "ph_compact"): {"pair": 2777, "lean": 1816, "pair_kept_repeated": 759, "lean_kept_repeated": 1582},
+    (21, "dense"): {"pair": 2976, "lean": 1944, "pair_kept_repeated": 720, "lean_kept_repeated": 1558},
+    (15, "dense"): {"pair": 3300, "lean": 2247, "pair_kept_repeated": 613, "lean_kept_repeated": 1453},
+}
 
 COPIES = (2, 3, 8, 9, 33, 63, 64, 65, 70, 130)      # either side of 8 (a byte of lanes), 32, 64 (a wavefront) and of 64 NS - P at NS = 3
 MAX_ARRAY = 9000                                    # characters: a (unit, copies) beyond it is left out
@@ -38,7 +48,7 @@ def pfcap(ns, L, k):
 
 
 def rc(a):
-    return _COMP[a[::-1]]
+    return mh.COMP[a[::-1]]
 
 
 def _primitive(u):
@@ -56,7 +66,7 @@ def txome(k, seed=TXOME_SEED):
     def make():
         from rapmap_amd import synth
         rng = np.random.default_rng(seed * 1000 + k)
-        rand = lambda n: _B[rng.integers(0, 4, n)]
+        rand = lambda n: mh.ACGT[rng.integers(0, 4, n)]
 
         def unit(n):
             u = rand(n)
@@ -97,27 +107,15 @@ def txome(k, seed=TXOME_SEED):
         walked += inverted
         assert len({s.tobytes() for s in seqs}) == len(seqs), "two equal transcripts: the indexer would drop one"
         return {"names": names, "seqs": seqs, "arrays": arrays, "inverted": set(inverted), "walked": walked, "genes": list(range(ngenes))}
-    return _once(("repeat_txome", k, seed), make)
+    return mh.once(("repeat_txome", k, seed), make)
 
 
 def index_for(tmp_root, k, image, seed=TXOME_SEED):
     """txome(k) indexed at k; image: "dense" or "ph" (`quasiindex -p`).  The index holds every transcript, in file order."""
     def make():
-        import rapmap_amd as ra
-        from rapmap_amd import synth
         tx = txome(k, seed)
-        d = _dir(tmp_root, "repeats_k%d" % k)
-        fa = os.path.join(d, "txome.fa")
-        if not os.path.exists(fa):
-            synth.write_fasta(fa, tx["names"], tx["seqs"])
-        idx = _build(fa, os.path.join(d, "idx_%s" % image), k, image, threads=2)
-        qi = ra.QuasiIndex(idx)
-        try:
-            assert qi.txp_names == tx["names"] and [int(x) for x in qi.txp_lens] == [s.size for s in tx["seqs"]], "the index does not hold the transcripts as written"
-        finally:
-            qi.close()
-        return idx
-    return _once(("repeat_index", k, image, seed), make)
+        return mh.index_of(tmp_root, "repeats", k, image, tx["names"], tx["seqs"])
+    return mh.once(("repeat_index", k, image, seed), make)
 
 
 def reads(tx, L, k, seed=READS_SEED):
@@ -132,7 +130,7 @@ def reads(tx, L, k, seed=READS_SEED):
     truth[i] = the two mates as they stand in reads1[i], reads2[i]: (transcript, forward?, edited?, characters in front of the transcript's
     start)."""
     rng = np.random.default_rng(seed * 1000 + L * 32 + k)
-    rand = lambda n: _B[rng.integers(0, 4, n)]
+    rand = lambda n: mh.ACGT[rng.integers(0, 4, n)]
     seqs = tx["seqs"]
     r1, r2, truth = [], [], []
 
@@ -145,7 +143,7 @@ def reads(tx, L, k, seed=READS_SEED):
         ea, eb = [t, True, False, over], [t, False, False, 0]
         kind = len(r1) % 4
         if kind == 1:
-            a[a.size // 2] = _B[(np.searchsorted(_B, a[a.size // 2]) + 1) % 4]
+            a[a.size // 2] = mh.ACGT[(np.searchsorted(mh.ACGT, a[a.size // 2]) + 1) % 4]
             ea[2] = True
         if kind == 2:
             a, b, ea, eb = b, a, eb, ea
@@ -184,7 +182,7 @@ def reads_for(k, L, seed=READS_SEED):
         q1, o1 = pack(r1); q2, o2 = pack(r2)
         assert max(np.diff(o1).max(), np.diff(o2).max()) == L
         return {"r1": r1, "r2": r2, "truth": truth, "q1": q1, "o1": o1, "q2": q2, "o2": o2, "n": len(r1), "lens": np.array([s.size for s in tx["seqs"]], dtype=np.int64)}
-    return _once(("repeat_reads_for", k, L, seed), make)
+    return mh.once(("repeat_reads_for", k, L, seed), make)
 
 
 def n_reads(k, L, every=23):
@@ -198,7 +196,7 @@ def n_reads(k, L, every=23):
             a[len(a) // 2] = ord("N"); b[len(b) // 3] = ord("N")
             r1.append(bytes(a)); r2.append(bytes(b))
         return r1, r2
-    return _once(("repeat_n_reads", k, L, every), make)
+    return mh.once(("repeat_n_reads", k, L, every), make)
 
 
 def mixed(k, L, extra):
@@ -212,11 +210,11 @@ def mixed(k, L, extra):
         a, b = T[st - 100:st - 100 + extra], rc(T[st - 40:st - 40 + extra])
         assert a.size == extra and b.size == extra
         return pack(rd["r1"] + [a.tobytes()]) + pack(rd["r2"] + [b.tobytes()])
-    return _once(("repeat_mixed", k, L, extra), make)
+    return mh.once(("repeat_mixed", k, L, extra), make)
 
 
 def single_truth(truth):
-    """the truth entries of odd_single(reads1, reads2)"""
+    """the truth entries of mh.odd_single(reads1, reads2)"""
     one = [a for a, b in truth[:-1]] + [truth[1][1]]
     return one[:-1] if len(one) % 2 == 0 else one
 
@@ -250,7 +248,7 @@ REACH = {(31, 100): (167, 3, 2647, 654, 389, 2248, 15), (21, 100): (147, 4, 2452
 def reach(ix, orc, oracle_mod, rd, L, k):
     """-> the tuple that REACH pins, asked of the ORACLE alone"""
     from util import pack
-    q, o = pack(odd_single(rd["r1"], rd["r2"]))
+    q, o = pack(mh.odd_single(rd["r1"], rd["r2"]))
     rs = orc.map_single(q, o, nthreads=4)
     rp = orc.map_pairs(rd["q1"], rd["o1"], rd["q2"], rd["o2"], nthreads=4)
     orphans = rp.hits[rp.hits["mate_status"] != 3]
@@ -347,7 +345,7 @@ def expected(tx, e, r, k):
 
 def _codes(a, k):
     """the k-mers of a string of A C G T as 2 k-bit numbers"""
-    v = np.searchsorted(_B, a).astype(np.uint64)
+    v = np.searchsorted(mh.ACGT, a).astype(np.uint64)
     n = a.size - k + 1
     c = np.zeros(max(n, 0), dtype=np.uint64)
     for j in range(k if n > 0 else 0):
@@ -416,7 +414,7 @@ def truth_check(hit_offsets, hits, rd, tx, k, single=False, min_checked=1000, mi
     At most 5 % of the eligible mates may be left out.  -> (eligible mates, checked, of them at a negative position, {why: left out})"""
     hits = np.asarray(hits)
     truth = rd["truth"]
-    units = [(i, (e,), (r,)) for i, (e, r) in enumerate(zip(single_truth(truth), odd_single(rd["r1"], rd["r2"])))] if single else \
+    units = [(i, (e,), (r,)) for i, (e, r) in enumerate(zip(single_truth(truth), mh.odd_single(rd["r1"], rd["r2"])))] if single else \
         [(i, truth[i], (rd["r1"][i], rd["r2"][i])) for i in range(rd["n"])]
     eligible = checked = negative = 0
     out, missing = {}, []
@@ -453,25 +451,8 @@ def truth_check(hit_offsets, hits, rd, tx, k, single=False, min_checked=1000, mi
     return eligible, checked, negative, out
 
 
-# ---- the option sets: ends_cases' and three more
-
-def option_sets():
-    import ends_cases as ec
-    s = dict(ec.OPTION_SETS)
-    s["m3"] = ({"maxNumHits": 3}, {"max_num_hits": 3})
-    s["maxInterval50"] = ({"maxInterval": 50}, {"max_interval": 50})
-    s["fuzzy_noDovetail"] = ({"fuzzy": 1, "noDovetail": 1}, {"fuzzy": 1, "no_dovetail": 1})
-    return s
-
+# ---- the option sets (mapping_harness.OPTION_SETS)
 
 VARIANTS = ("default", "noStrictCheck", "fuzzy", "fuzzy_noDovetail", "noSensitive", "noDovetail", "noOrphans", "m3", "maxInterval50", "z0.9", "selAln",
             "selAln_hardFilter", "mimicBT2", "mimicStrictBT2")
 FEW = ("default", "fuzzy", "maxInterval50", "selAln")
-
-
-def opts_for(variant, oracle_mod, default_opts):
-    import ends_cases as ec
-    if variant.startswith("mimic"):
-        return ec.opts_for(variant, oracle_mod, default_opts)
-    oo, mo = option_sets()[variant]
-    return oracle_mod.default_opts(**oo), default_opts(**mo)

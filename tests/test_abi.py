@@ -19,6 +19,17 @@ def test_symbols_exported(lib_built):
         assert hasattr(L, s), s
 
 
+def test_stat_names_match_the_header():
+    """QM_STAT_* and QM_EQC_STAT_* of the package are the two enums of include/qmap_mi355.h, name for name and value for value"""
+    import rapmap_amd as ra
+    hdr = open(os.path.join(ROOT, "include", "qmap_mi355.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = {name: int(value) for name, value in re.findall(r"\b(QM_(?:EQC_)?STAT_[A-Z0-9_]+)\s*=\s*(-?\d+)", hdr)}
+    mine = {name: value for name, value in vars(ra.api).items() if name.startswith(("QM_STAT_", "QM_EQC_STAT_"))}
+    assert len(declared) == 21 and declared == mine, (declared, mine)
+    assert all(getattr(ra, name) == value for name, value in mine.items())
+
+
 def test_defaults_match_reference_cli(lib_built):
     import rapmap_amd as ra
     o = ra.default_opts()

@@ -94,7 +94,7 @@ def test_hash_file_loads_in_the_references_container(big_index):
     """the reference's own spp::sparse_hash_map (oracle/_ref) finds every record of this hash.bin and none of 200 000 absent keys;
     where oracle/_ref cannot be built, its recorded verdict on these very bytes (tests/golden/reference_answers/)"""
     import rapmap_amd as ra
-    import test_oracle_ref as tor
+    import ref_answers as tor
     qi = ra.QuasiIndex(big_index)
     try:
         h = qi.raw("hash")
@@ -121,7 +121,7 @@ def test_hash_file_loads_in_the_references_container(big_index):
                         "absent": absent.size, "absent_found": int(fa_.sum())}
             finally:
                 R.ref_spp_free(hd)
-        a = tor.answers("spp_big_index_hash", live, tor._ref())
+        a = tor.answers("spp_big_index_hash", live, tor.load_ref())
         assert str(a["sha256"]) == str(tor.sha256(data)), "not the hash.bin the reference's container read"
         assert int(a["size"]) == K
         # every key found, with the interval bounds our loader sees (as the container's int32 bytes)

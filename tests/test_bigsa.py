@@ -50,8 +50,8 @@ def test_overflow_map_of_a_big_perfect_hash_index_loads_in_the_references_contai
     in place (oracle/_ref), must find every entry of the file the indexer wrote"""
     from conftest import _build_big
     from oracle import q5ph
-    import test_oracle_ref as tor
-    ref = tor._ref()          # None: the reference container's recorded answers for this very map (tests/golden/reference_answers/)
+    import ref_answers as tor
+    ref = tor.load_ref()          # None: the reference container's recorded answers for this very map (tests/golden/reference_answers/)
     rng = np.random.default_rng(5)
     unit = "".join("ACGT"[i] for i in rng.integers(0, 4, 400))
     fa = tmp_path / "rep.fa"

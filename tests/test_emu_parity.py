@@ -7,67 +7,39 @@ import os
 import numpy as np
 import pytest
 
+import emu
+import mapping_harness as mh
 from conftest import load_oracle
+from parity_cases import SEL_VARIANTS, dollar_reads, sel_reads
 from util import assert_hits_equal, pack
-
-VARIANTS = {
-    "default": ({}, {}),
-    "noStrictCheck": ({"strictCheck": 0}, {"strict_check": 0}),
-    "z0.9": ({"quasiCov": 0.9}, {"quasi_cov": 0.9}),
-    "m3": ({"maxNumHits": 3}, {"max_num_hits": 3}),
-    "noOrphans": ({"noOrphans": 1}, {"no_orphans": 1}),
-    "noDovetail": ({"noDovetail": 1}, {"no_dovetail": 1}),
-    "maxInterval50": ({"maxInterval": 50}, {"max_interval": 50}),
-    "noSensitive": ({"sensitive": 0}, {"sensitive": 0}),
-    "noSensitive_noStrict": ({"sensitive": 0, "strictCheck": 0}, {"sensitive": 0, "strict_check": 0}),
-    "noSensitive_z0.8": ({"sensitive": 0, "quasiCov": 0.8}, {"sensitive": 0, "quasi_cov": 0.8}),
-    "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}),
-    "fuzzy_noOrphans_m3": ({"fuzzy": 1, "noOrphans": 1, "maxNumHits": 3}, {"fuzzy": 1, "no_orphans": 1, "max_num_hits": 3}),
-    "fuzzy_noDovetail": ({"fuzzy": 1, "noDovetail": 1}, {"fuzzy": 1, "no_dovetail": 1}),
-    "fuzzy_noSensitive": ({"fuzzy": 1, "sensitive": 0}, {"fuzzy": 1, "sensitive": 0}),
-}
-
-
-def _emu(idx):
-    import emu
-    ix, orc = load_oracle(idx)
-    return ix, orc, emu.Emu(ix), emu
-
-
-def _cmp_ints(res, er):
-    oi, ei = res.ints, er.ints
-    assert np.array_equal(res.ints_offsets, er.int_offsets)
-    for col, name in ((0, "begin"), (1, "end"), (2, "len"), (3, "query_pos"), (5, "list")):
-        assert np.array_equal(oi[:, col], ei[name].astype(np.int32)), name
 
 
 def test_sample_data(sample_data, oracle_mod):
-    ix, orc, em, emu = _emu(sample_data["idx"])
+    ix, orc, em = mh.emu_of(sample_data["idx"])
     q1, o1 = pack(sample_data["reads1"]); q2, o2 = pack(sample_data["reads2"])
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=2, want_ints=True)
     er = em.map(q1, o1, q2, o2)
     assert er.status == 0
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, "sample_data")
     assert res.counters == er.counters
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
 
 
-@pytest.mark.parametrize("variant", sorted(VARIANTS))
+@pytest.mark.parametrize("variant", sorted(mh.PLAIN_SETS))
 def test_synth_small(synth_small, oracle_mod, variant):
-    ix, orc, em, emu = _emu(synth_small["idx"])
+    ix, orc, em = mh.emu_of(synth_small["idx"])
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
-    oo, eo = VARIANTS[variant]
+    oo, eo = mh.OPTION_SETS[variant]
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4, want_ints=True)
     er = em.map(q1, o1, q2, o2, opts=emu.default_opts(**eo))
     assert er.status == 0
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, variant)
     assert res.counters == er.counters
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
 
 
 def test_crowded_hash_buckets(synth_small, oracle_mod):
     """a table with ~1.4 keys per 2-slot bucket: lookups have to follow the overflow marks into later buckets"""
-    import emu
     ix, orc = load_oracle(synth_small["idx"])
     nb = 16
     while nb * 1.4 < ix.hkeys.size:
@@ -80,33 +52,20 @@ def test_crowded_hash_buckets(synth_small, oracle_mod):
     assert res.counters == er.counters
 
 
-def _dollar_reads(sd):
-    """reads with a '$' (the text's separator) spliced in, incl. right after the seed k-mer and at the last base"""
-    r1 = [bytearray(r) for r in sd["reads1"][:400]]
-    r2 = [bytearray(r) for r in sd["reads2"][:400]]
-    for i, r in enumerate(r1):
-        if len(r) > 40:
-            r[(31, 40, len(r) - 1, 5)[i % 4]] = ord("$")
-    for i, r in enumerate(r2[::3]):
-        if len(r) > 60:
-            r[60] = ord("$")
-    return [bytes(r) for r in r1], [bytes(r) for r in r2]
-
-
 def test_dollar_in_reads(synth_small, oracle_mod):
     """'$' in a query sends the MMP extension down the literal binary searches (SASearcher.hpp:154,180)"""
-    ix, orc, em, emu = _emu(synth_small["idx"])
-    r1, r2 = _dollar_reads(synth_small)
+    ix, orc, em = mh.emu_of(synth_small["idx"])
+    r1, r2 = dollar_reads(synth_small)
     q1, o1 = pack(r1); q2, o2 = pack(r2)
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=4, want_ints=True)
     er = em.map(q1, o1, q2, o2)
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, "dollar")
     assert res.counters == er.counters
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
 
 
 def test_single_end(synth_small, oracle_mod):
-    ix, orc, em, emu = _emu(synth_small["idx"])
+    ix, orc, em = mh.emu_of(synth_small["idx"])
     q, o = pack(synth_small["reads1"] + synth_small["reads2"])
     res = orc.map_single(q, o, nthreads=4)
     er = em.map(q, o)
@@ -126,12 +85,12 @@ def test_long_reads_ns4(synth_small, oracle_mod):
     a1, a2, aoff, _ = synth.make_reads(txps, 400, seed=6, read_len=151, err=0.02)
     q1 = np.concatenate([s1, a1]); q2 = np.concatenate([s2, a2])
     o = np.concatenate([off, aoff[1:] + off[-1]])
-    ix, orc, em, emu = _emu(synth_small["idx"])
+    ix, orc, em = mh.emu_of(synth_small["idx"])
     res = orc.map_pairs(q1, o, q2, o, nthreads=4, want_ints=True)
     er = em.map(q1, o, q2, o, ns=4)
     assert er.status == 0 and res.counters["totHits"] > 1000
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, "ns4")
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
     # single-end (the wide lean kernel's other instantiations are cross-checked inside the emulation: every read it takes, word for word)
     rs1 = orc.map_single(q2, o, nthreads=4)
     es1 = em.map(q2, o, ns=4)
@@ -150,7 +109,7 @@ def test_long_reads_ns4(synth_small, oracle_mod):
     er3 = em.map(a1, aoff, a2, aoff, ns=3)
     assert er3.status == 0
     assert_hits_equal(res3.hit_offsets, res3.hits, er3.hit_offsets, er3.hits, "ns3")
-    _cmp_ints(res3, er3)
+    mh.check_intervals(res3, er3.int_offsets, er3.ints)
     for oo, go in (({"sensitive": 0}, {"sensitive": 0}), ({"selAln": 1}, {"sel_aln": 1})):
         r = orc.map_pairs(a1, aoff, a2, aoff, opts=oracle_mod.default_opts(**oo), nthreads=4)
         e = em.map(a1, aoff, a2, aoff, opts=emu.default_opts(**go), ns=3)
@@ -163,7 +122,7 @@ def test_long_reads_ns4(synth_small, oracle_mod):
 
 
 def test_medium(synth_medium, oracle_mod):
-    ix, orc, em, emu = _emu(synth_medium["idx"])
+    ix, orc, em = mh.emu_of(synth_medium["idx"])
     n = 20000
     o = synth_medium["off"][: n + 1]
     q1 = synth_medium["seq1"][: o[-1]]; q2 = synth_medium["seq2"][: o[-1]]
@@ -171,7 +130,7 @@ def test_medium(synth_medium, oracle_mod):
     er = em.map(q1, o, q2, o)
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, "medium")
     assert res.counters == er.counters
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
 
 
 def test_selective_alignment_long_reads_many_suffixes(synth_medium, oracle_mod):
@@ -179,7 +138,7 @@ def test_selective_alignment_long_reads_many_suffixes(synth_medium, oracle_mod):
     suffixes, i.e. the lane-parallel sort / chaining over several 64-record chunks (and, beyond 256, lane 0's fallback)"""
     import rapmap_amd as ra
     from rapmap_amd import synth
-    ix, orc, em, emu = _emu(synth_medium["idx"])
+    ix, orc, em = mh.emu_of(synth_medium["idx"])
     qi = ra.QuasiIndex(synth_medium["idx"])
     text, offsets = qi.arrays()
     text = np.asarray(text); offsets = np.asarray(offsets, dtype=np.int64)
@@ -198,7 +157,7 @@ def test_selective_alignment_long_reads_many_suffixes(synth_medium, oracle_mod):
 def test_repeat_families(repeat_data, oracle_mod):
     """reads inside repeat cores: 40 / 300 / 1100 copies -> lists beyond the LDS lists (global scratch),
     > maxNumHits (tooManyHits) and >= maxInterval (skipped intervals)"""
-    ix, orc, em, emu = _emu(repeat_data["idx"])
+    ix, orc, em = mh.emu_of(repeat_data["idx"])
     q1, o1 = pack(repeat_data["reads1"]); q2, o2 = pack(repeat_data["reads2"])
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=4, want_ints=True)
     er = em.map(q1, o1, q2, o2)
@@ -212,14 +171,14 @@ def test_repeat_families(repeat_data, oracle_mod):
     assert fer.status == 0
     assert_hits_equal(fres.hit_offsets, fres.hits, fer.hit_offsets, fer.hits, "repeats-fuzzy")
     assert fres.counters == fer.counters
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
 
 
 @pytest.mark.parametrize("variant", ["default", "noSensitive", "fuzzy", "sel"])
 def test_homopolymer_runs(runs_data, oracle_mod, variant):
     """windows of k equal bases at every alignment: the setup's shortcut for reads without such a window must agree with
     the tabulating pass and with isHomoPolymer"""
-    ix, orc, em, emu = _emu(runs_data["idx"])
+    ix, orc, em = mh.emu_of(runs_data["idx"])
     q1, o1 = pack(runs_data["reads1"]); q2, o2 = pack(runs_data["reads2"])
     oo, eo = {"default": ({}, {}), "noSensitive": ({"sensitive": 0}, {"sensitive": 0}), "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}),
               "sel": ({"selAln": 1}, {"sel_aln": 1})}[variant]
@@ -230,13 +189,13 @@ def test_homopolymer_runs(runs_data, oracle_mod, variant):
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, "runs-" + variant)
     assert res.counters == er.counters
     if variant != "sel":
-        _cmp_ints(res, er)
+        mh.check_intervals(res, er.int_offsets, er.ints)
 
 
 def test_perfect_hash_index(synth_small, synth_small_ph, oracle_mod):
     """config 4: BooPHF cascade + FrugalBooMap text verification in the device source; hits must equal the
     dense-index oracle (the reference guarantees the same: SURVEY.md section 4)"""
-    ix, orc, em, emu = _emu(synth_small_ph["idx"])
+    ix, orc, em = mh.emu_of(synth_small_ph["idx"])
     assert ix.perfect and em.ph
     q1, o1 = pack(synth_small_ph["reads1"]); q2, o2 = pack(synth_small_ph["reads2"])
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=4, want_ints=True)
@@ -244,7 +203,7 @@ def test_perfect_hash_index(synth_small, synth_small_ph, oracle_mod):
     assert er.status == 0
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, "perfect-hash")
     assert res.counters == er.counters
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
     dix, dorc = load_oracle(synth_small["idx"])
     dres = dorc.map_pairs(q1, o1, q2, o2, nthreads=4)
     assert_hits_equal(dres.hit_offsets, dres.hits, er.hit_offsets, er.hits, "perfect-hash vs dense")
@@ -261,7 +220,7 @@ def test_selective_alignment_collector_intervals(synth_small, oracle_mod):
     the -s path is not on the device yet, so only the SA-interval hits are compared here."""
     from conftest import GOLD
     import samfmt as sam
-    ix, orc, em, emu = _emu(synth_small["idx"])
+    ix, orc, em = mh.emu_of(synth_small["idx"])
     n1, s1 = sam.read_fastq(os.path.join(GOLD, "synth_small", "next", "reads_indel_1.fastq.gz"))
     n2, s2 = sam.read_fastq(os.path.join(GOLD, "synth_small", "next", "reads_indel_2.fastq.gz"))
     for r1, r2 in ((synth_small["reads1"], synth_small["reads2"]), (s1, s2)):
@@ -269,32 +228,7 @@ def test_selective_alignment_collector_intervals(synth_small, oracle_mod):
         for ext in (7, 3):
             res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(selAln=1, maxMMPExtension=ext), nthreads=4, want_ints=True)
             er = em.map(q1, o1, q2, o2, opts=emu.default_opts(sel_aln=1, max_mmp_extension=ext))
-            _cmp_ints(res, er)
-
-
-SEL_VARIANTS = [
-    ("reads", dict(selAln=1), dict(sel_aln=1)),
-    ("indel", dict(selAln=1), dict(sel_aln=1)),
-    ("reads", dict(selAln=1, hardFilter=1), dict(sel_aln=1, hard_filter=1)),
-    ("indel", dict(selAln=1, maxMMPExtension=3, minScoreFraction=0.9), dict(sel_aln=1, max_mmp_extension=3, min_score_fraction=0.9)),
-    ("reads", dict(selAln=1, noOrphans=1, noDovetail=1, consensusSlack=0.35, maxNumHits=1000, alnPolicy=1),
-     dict(sel_aln=1, no_orphans=1, no_dovetail=1, consensus_slack=0.35, max_num_hits=1000, aln_policy=1)),          # --mimicBT2
-    ("indel", dict(selAln=1, consensusSlack=0.0, gapOpen=6, gapExtend=3, mismatchPenalty=-6, matchScore=3, dpBandwidth=5),
-     dict(sel_aln=1, consensus_slack=0.0, gap_open=6, gap_extend=3, mismatch_penalty=-6, match_score=3, dp_bandwidth=5)),
-    # without --strictCheck the other strand's turn depends on the two spot-check counts (hb >= ha): the lean collector's runs of
-    # capped MMPs book several hits' counts at once
-    ("reads", dict(selAln=1, strictCheck=0), dict(sel_aln=1, strict_check=0)),
-    ("indel", dict(selAln=1, strictCheck=0, maxMMPExtension=3), dict(sel_aln=1, strict_check=0, max_mmp_extension=3)),
-]
-
-
-def sel_reads(synth_small, which):
-    from conftest import GOLD
-    import samfmt as sam
-    if which == "reads":
-        return synth_small["reads1"], synth_small["reads2"]
-    nx = os.path.join(GOLD, "synth_small", "next")
-    return sam.read_fastq(os.path.join(nx, "reads_indel_1.fastq.gz"))[1], sam.read_fastq(os.path.join(nx, "reads_indel_2.fastq.gz"))[1]
+            mh.check_intervals(res, er.int_offsets, er.ints)
 
 
 @pytest.mark.parametrize("case", range(len(SEL_VARIANTS)))
@@ -302,7 +236,7 @@ def test_selective_alignment(synth_small, oracle_mod, case):
     """-s end to end in the device source: chaining + multi-position lists (stage A), position-list fuzzy merge, ksw2
     extension alignment, score gate and filter (stage B + C); hits incl. alignment scores and counters == oracle"""
     which, oo, eo = SEL_VARIANTS[case]
-    ix, orc, em, emu = _emu(synth_small["idx"])
+    ix, orc, em = mh.emu_of(synth_small["idx"])
     s1, s2 = sel_reads(synth_small, which)
     q1, o1 = pack(s1); q2, o2 = pack(s2)
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
@@ -320,7 +254,7 @@ def test_selective_alignment_repeats_take_the_slow_pass(repeat_data, oracle_mod)
     """-s on reads inside repeat cores: the 900-copy family brings more suffixes per strand than a wave's scratch holds
     (QM_SEL_CAP), so those reads are queued and redone on scratch sized for them -- same hits as the oracle, which (like the
     reference) treats them as any other read"""
-    ix, orc, em, emu = _emu(repeat_data["idx"])
+    ix, orc, em = mh.emu_of(repeat_data["idx"])
     q1, o1 = pack(repeat_data["reads1"]); q2, o2 = pack(repeat_data["reads2"])
     for oo, eo in ((dict(selAln=1), dict(sel_aln=1)), (dict(selAln=1, maxNumHits=5000, hardFilter=1), dict(sel_aln=1, max_num_hits=5000, hard_filter=1)),
                    (dict(selAln=1, maxNumHits=5000, consensusSlack=0.5), dict(sel_aln=1, max_num_hits=5000, consensus_slack=0.5))):
@@ -338,7 +272,7 @@ def test_selective_alignment_repeats_take_the_slow_pass(repeat_data, oracle_mod)
 @pytest.mark.parametrize("band", [34, 64, 120, -1])
 def test_selective_alignment_wide_bands(synth_small, oracle_mod, band):
     """--dpBandwidth beyond 33: the same ksw2 kernel on a larger column ring (128 / 512 slots)"""
-    ix, orc, em, emu = _emu(synth_small["idx"])
+    ix, orc, em = mh.emu_of(synth_small["idx"])
     s1, s2 = sel_reads(synth_small, "indel")
     q1, o1 = pack(s1); q2, o2 = pack(s2)
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(selAln=1, dpBandwidth=band), nthreads=4)
@@ -352,7 +286,7 @@ def test_reads_of_300_and_500_bp_take_the_eight_slot_kernels(synth_medium, oracl
     """reads longer than 256 bp (merged pairs, long-insert libraries): the NS=8 instantiations, default / --noSensitive / -s"""
     import rapmap_amd as ra
     from rapmap_amd import synth
-    ix, orc, em, emu = _emu(synth_medium["idx"])
+    ix, orc, em = mh.emu_of(synth_medium["idx"])
     qi = ra.QuasiIndex(synth_medium["idx"])
     text, offsets = qi.arrays()
     text = np.asarray(text); offsets = np.asarray(offsets, dtype=np.int64)
@@ -387,7 +321,7 @@ def test_selective_alignment_of_reads_beyond_512_bp(synth_medium, oracle_mod, va
     of 4096 slots holds every column of a 2048-base alignment (round 4; before, such a batch failed with QM_E_TOOLONG)"""
     from rapmap_amd import synth
     import rapmap_amd as ra
-    ix, orc, em, emu = _emu(synth_medium["idx"])
+    ix, orc, em = mh.emu_of(synth_medium["idx"])
     qi = ra.QuasiIndex(synth_medium["idx"])
     text, offsets = qi.arrays()
     text = np.asarray(text); offsets = np.asarray(offsets, dtype=np.int64)
@@ -422,7 +356,7 @@ def test_reads_beyond_512_bp_take_the_long_read_pass(synth_medium, synth_medium_
     from rapmap_amd import synth
     import rapmap_amd as ra
     idx = (synth_medium_ph if variant == "perfectHash" else synth_medium)["idx"]
-    ix, orc, em, emu = _emu(idx)
+    ix, orc, em = mh.emu_of(idx)
     qi = ra.QuasiIndex(synth_medium["idx"])
     text, offsets = qi.arrays()
     text = np.asarray(text); offsets = np.asarray(offsets, dtype=np.int64)
@@ -443,7 +377,7 @@ def test_reads_beyond_512_bp_take_the_long_read_pass(synth_medium, synth_medium_
     assert (er.status & 0xff) == 0, er.status
     assert_hits_equal(res.hit_offsets, res.hits, er.hit_offsets, er.hits, "long reads, %s" % variant)
     assert res.counters == er.counters
-    _cmp_ints(res, er)
+    mh.check_intervals(res, er.int_offsets, er.ints)
     long_units = [u for u in range(len(r1)) if len(r1[u]) > 512]
     assert sum(int(res.hit_offsets[u + 1] - res.hit_offsets[u]) > 0 for u in long_units) > len(long_units) // 2
     # one character too many: that read is skipped (empty result, counted), everything else is mapped as before (round 5: the call failed)
@@ -464,7 +398,6 @@ def test_one_diagonal_chaining_editions_equal_the_doubles():
     random groups of hits on one diagonal: equal query ends, hits without gain, a long first hit, short hits behind long gaps -- the cases
     in which the chain is NOT hit 0 <- hit 1 <- ... included.  Groups on two diagonals must be declined."""
     import ctypes as C
-    import emu
     lib = emu._lib()
     lib.qe_chain_diag_check.restype = C.c_int
     lib.qe_chain_diag_check.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int]
@@ -548,7 +481,7 @@ def test_selective_alignment_answers_known_without_ksw2(synth_medium, oracle_mod
     """sel_side_score's two rules -- the gapless path when it loses no more than one gap, and with two mismatches the best of the
     gapless path and the few one-gap paths that could beat it -- on reads whose edits sit where those paths differ: every
     alignment score (they decide the hits that survive) equals the oracle's, which runs ksw2 for all of them"""
-    ix, orc, em, emu = _emu(synth_medium["idx"])
+    ix, orc, em = mh.emu_of(synth_medium["idx"])
     r1, r2 = _edited_pairs(synth_medium["txps"], 3000, 99)
     q1, o1 = pack(r1); q2, o2 = pack(r2)
     conv = {"gapOpen": "gap_open", "gapExtend": "gap_extend", "matchScore": "match_score", "mismatchPenalty": "mismatch_penalty", "dpBandwidth": "dp_bandwidth"}

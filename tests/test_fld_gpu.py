@@ -129,11 +129,11 @@ def test_split_call(synth_medium, monkeypatch):
     torch.cuda.synchronize()
     monkeypatch.setenv("QM_SPLIT", "1")
     whole = mp.map_device(n, d1.data_ptr(), do.data_ptr(), d2.data_ptr(), do.data_ptr(), 100, fetch=True)
-    assert mp.stat(9) == n                                        # QM_STAT_PAIR_KERNEL_PAIRS: one unsplit call over all pairs
+    assert mp.stat(ra.QM_STAT_PAIR_KERNEL_PAIRS) == n                                        # QM_STAT_PAIR_KERNEL_PAIRS: one unsplit call over all pairs
     a = ra.FragLenDist(mp); a.add(mp)
     monkeypatch.setenv("QM_SPLIT_MIN", "1000"); monkeypatch.setenv("QM_SPLIT", "3")
     mp.map_device(n, d1.data_ptr(), do.data_ptr(), d2.data_ptr(), do.data_ptr(), 100, fetch=False)
-    assert mp.stat(9) == -1                                       # ... which a call mapped in parts reports as -1 (qmap_mi355.h)
+    assert mp.stat(ra.QM_STAT_PAIR_KERNEL_PAIRS) == -1                                       # ... which a call mapped in parts reports as -1 (qmap_mi355.h)
     b = ra.FragLenDist(mp); b.add(mp)
     ec, es = fc.classify(whole.hit_offsets, whole.hits, 1000)
     fc.assert_same(a.counts(), a.stat(), ec, es, "device-resident, unsplit")

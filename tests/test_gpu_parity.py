@@ -1,90 +1,45 @@
 """Parity of the HIP path (libqmap_mi355.so, called through its C ABI) against the oracle.
 Bit-exact: hit offsets, hit records, counters, SA-interval lists.  Run on the MI355X box: -m gpu."""
+import contextlib
 import hashlib
 import os
 
 import numpy as np
 import pytest
 
+import mapping_harness as mh
+import rapmap_amd as ra
 from conftest import GOLD, load_oracle
+from parity_cases import SEL_VARIANTS, dollar_reads, sel_reads
 from util import assert_hits_equal, pack
 
 pytestmark = pytest.mark.gpu
 
-VARIANTS = {
-    "default": ({}, {}),
-    "noStrictCheck": ({"strictCheck": 0}, {"strict_check": 0}),
-    "z0.9": ({"quasiCov": 0.9}, {"quasi_cov": 0.9}),
-    "m3": ({"maxNumHits": 3}, {"max_num_hits": 3}),
-    "noOrphans": ({"noOrphans": 1}, {"no_orphans": 1}),
-    "noDovetail": ({"noDovetail": 1}, {"no_dovetail": 1}),
-    "maxInterval50": ({"maxInterval": 50}, {"max_interval": 50}),
-    "noSensitive": ({"sensitive": 0}, {"sensitive": 0}),
-    "noSensitive_noStrict": ({"sensitive": 0, "strictCheck": 0}, {"sensitive": 0, "strict_check": 0}),
-    "noSensitive_z0.8": ({"sensitive": 0, "quasiCov": 0.8}, {"sensitive": 0, "quasi_cov": 0.8}),
-    "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}),
-    "fuzzy_noOrphans_m3": ({"fuzzy": 1, "noOrphans": 1, "maxNumHits": 3}, {"fuzzy": 1, "no_orphans": 1, "max_num_hits": 3}),
-    "fuzzy_noDovetail": ({"fuzzy": 1, "noDovetail": 1}, {"fuzzy": 1, "no_dovetail": 1}),
-    "fuzzy_noSensitive": ({"fuzzy": 1, "sensitive": 0}, {"fuzzy": 1, "sensitive": 0}),
-}
-
-
-def _gpu(idx, debug=True, ph_compact=False, pair_kernel=True):
-    """debug=True keeps the SA-interval records of a fused call (qm_fetch_intervals) -- and so runs the GENERAL stage-A kernel; the kernels the
-    headline is quoted on (the pair kernel, qm_lean_kernel) only run with debug=False: _headline() below"""
-    import rapmap_amd as ra
-    qi = ra.QuasiIndex(idx)
-    return qi, ra.QuasiMapper(qi, 0, debug=debug, ph_compact=ph_compact, pair_kernel=pair_kernel)
-
-
-HEADLINE_KERNELS = ["pair", "lean"]
-
-
-def _headline(idx, kernel, ph_compact=False):
-    """a mapper whose paired calls run the pair kernel (qm_duo.inl) or qm_lean_kernel alone (QM_CTX_NO_PAIR_KERNEL)"""
-    return _gpu(idx, debug=False, ph_compact=ph_compact, pair_kernel=kernel == "pair")
-
-
-def _check_headline(mp, kernel, n_pairs, expect_deferred=True, fuzzy=False, some_merged=True):
-    """the call just made went through the kernel it was meant for, and that kernel decided to leave some reads to the general one"""
-    assert mp.stat(3) == 2 * n_pairs, "the lean / pair kernel did not run"
-    deferred = mp.stat(4)
-    assert (0 < deferred < 2 * n_pairs) if expect_deferred else deferred >= 0, deferred
-    if kernel == "pair":
-        assert mp.stat(9) == n_pairs
-        merged = mp.stat(10)
-        assert merged == 0 if fuzzy else (1 if some_merged else 0) <= merged <= n_pairs - (deferred + 1) // 2, (merged, deferred)
-    else:
-        assert mp.stat(9) == -1
-    return deferred
-
-
-def _cmp_ints(res, offs, ints):
-    assert np.array_equal(res.ints_offsets, offs)
-    oi = res.ints
-    for col, name in ((0, "begin"), (1, "end"), (2, "len"), (3, "query_pos"), (5, "list")):
-        assert np.array_equal(oi[:, col], ints[name].astype(np.int32)), name
+@pytest.fixture
+def gpu():
+    """gpu(idx, ...) -> (QuasiIndex, QuasiMapper) of mapping_harness.gpu_mapper -- with kernel="pair" / "lean": of mapping_harness.headline --,
+    closed when the test ends"""
+    with contextlib.ExitStack() as stack:
+        yield lambda idx, kernel=None, **kw: stack.enter_context(mh.headline(idx, kernel, **kw) if kernel else mh.gpu_mapper(idx, **kw))
 
 
 def test_native_library_is_loaded(lib_built):
     """the extension the tests exercise is the in-tree HIP library, not a fallback"""
-    import rapmap_amd as ra
     ra.api.lib()
     maps = open("/proc/self/maps").read()
     assert "libqmap_mi355.so" in maps and "libamdhip64" in maps
 
 
-def test_sample_data_hits_and_sam_md5(sample_data, oracle_mod):
-    import rapmap_amd as ra
+def test_sample_data_hits_and_sam_md5(sample_data, oracle_mod, gpu):
     import samfmt as sam
     ix, orc = load_oracle(sample_data["idx"])
-    qi, mp = _gpu(sample_data["idx"])
+    qi, mp = gpu(sample_data["idx"])
     q1, o1 = pack(sample_data["reads1"]); q2, o2 = pack(sample_data["reads2"])
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=2, want_ints=True)
     gr = mp.map_pairs(q1, o1, q2, o2)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "sample_data")
     assert res.counters == gr.counters
-    _cmp_ints(res, *mp.intervals(len(o1) - 1))
+    mh.check_intervals(res, *mp.intervals(len(o1) - 1))
     body = "".join(sam.format_pair(sample_data["names1"][i], sample_data["reads1"][i], sample_data["names2"][i],
                                    sample_data["reads2"][i], gr.hits[gr.hit_offsets[i]:gr.hit_offsets[i + 1]],
                                    qi.txp_names, qi.txp_lens) for i in range(len(o1) - 1))
@@ -93,83 +48,80 @@ def test_sample_data_hits_and_sam_md5(sample_data, oracle_mod):
     assert hashlib.md5(text.encode()).hexdigest() == want
 
 
-@pytest.mark.parametrize("variant", sorted(VARIANTS))
-def test_synth_small(synth_small, oracle_mod, variant):
-    import rapmap_amd as ra
+@pytest.mark.parametrize("variant", sorted(mh.PLAIN_SETS))
+def test_synth_small(synth_small, oracle_mod, variant, gpu):
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"])
+    qi, mp = gpu(synth_small["idx"])
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
-    oo, go = VARIANTS[variant]
+    oo, go = mh.OPTION_SETS[variant]
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4, want_ints=True)
     gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, variant)
     assert res.counters == gr.counters
-    _cmp_ints(res, *mp.intervals(len(o1) - 1))
+    mh.check_intervals(res, *mp.intervals(len(o1) - 1))
 
 
-@pytest.mark.parametrize("kernel", HEADLINE_KERNELS)
-@pytest.mark.parametrize("variant", [v for v in sorted(VARIANTS) if "noSensitive" not in v])
-def test_synth_small_through_the_headline_kernels(synth_small, oracle_mod, variant, kernel):
+@pytest.mark.parametrize("kernel", mh.HEADLINE_KERNELS)
+@pytest.mark.parametrize("variant", [v for v in sorted(mh.PLAIN_SETS) if "noSensitive" not in v])
+def test_synth_small_through_the_headline_kernels(synth_small, oracle_mod, variant, kernel, gpu):
     """the adversarial golden reads (N's, lower case, IUPAC, reads shorter than k, reads across a `$`, repeat families, indels, ragged
     lengths) through the kernels the headline is quoted on: what they take must be right, and they must LEAVE the reads they are not
     built for (with debug=True these reads only ever met the general kernel)"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _headline(synth_small["idx"], kernel)
+    qi, mp = gpu(synth_small["idx"], kernel=kernel)
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
-    oo, go = VARIANTS[variant]
+    oo, go = mh.OPTION_SETS[variant]
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
     gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "%s through the %s kernel" % (variant, kernel))
     assert res.counters == gr.counters
-    deferred = _check_headline(mp, kernel, len(o1) - 1, fuzzy="fuzzy" in variant)
+    deferred = mh.check_headline(mp, kernel, len(o1) - 1, fuzzy="fuzzy" in variant)
     if variant == "default":
         assert deferred == 519, deferred          # (what the lane emulation of both kernels leaves on this set: tests/emu, QM_EMU_LEAN_STATS)
 
 
-@pytest.mark.parametrize("kernel", HEADLINE_KERNELS)
+@pytest.mark.parametrize("kernel", mh.HEADLINE_KERNELS)
 @pytest.mark.parametrize("variant", ["default", "noStrictCheck", "z0.9", "selAln", "selAln_noStrict"])
-def test_reads_with_N_take_the_N_aware_pass(synth_small, oracle_mod, variant, kernel, monkeypatch):
+def test_reads_with_N_take_the_N_aware_pass(synth_small, oracle_mod, variant, kernel, monkeypatch, gpu):
     """round 6: when enough reads of a batch were left for a character outside A C G T (QM_NPASS_MIN: 2 048, here 1), qm_lean_kernel's
     N-aware edition goes over the queue of what the first pass left before the general kernel does -- k-mers with an N stepped over
     (SACollector.hpp:172-181 with its `<=`, :497-512), MMPs ending at one.  Same hits, same counters; the golden set holds reads with an N
     right behind their first k-mer, all-N mates, IUPAC codes (those stay with the general kernel)."""
-    import rapmap_amd as ra
     monkeypatch.setenv("QM_NPASS_MIN", "1")
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _headline(synth_small["idx"], kernel)
+    qi, mp = gpu(synth_small["idx"], kernel=kernel)
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
-    oo, go = {"selAln": ({"selAln": 1}, {"sel_aln": 1}), "selAln_noStrict": ({"selAln": 1, "strictCheck": 0}, {"sel_aln": 1, "strict_check": 0})}.get(variant) or VARIANTS[variant]
+    oo, go = {"selAln": ({"selAln": 1}, {"sel_aln": 1}), "selAln_noStrict": ({"selAln": 1, "strictCheck": 0}, {"sel_aln": 1, "strict_check": 0})}.get(variant) or mh.OPTION_SETS[variant]
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
     gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "%s, N-aware pass behind the %s kernel" % (variant, kernel))
     assert res.counters == gr.counters
-    taken = mp.stat(15)
+    taken = mp.stat(ra.QM_STAT_N_PASS_READS)
     assert taken > 300, taken
     if variant == "default":
-        assert (taken, mp.stat(4)) == (389, 130), (taken, mp.stat(4))      # (the lane emulation: 519 reads left by the first pass, 130 by the second)
+        assert (taken, mp.stat(ra.QM_STAT_LEAN_DEFERRED)) == (389, 130), (taken, mp.stat(ra.QM_STAT_LEAN_DEFERRED))      # (the lane emulation: 519 reads left by the first pass, 130 by the second)
     # single-end: the queue names reads, not mates
     res1 = orc.map_single(q1, o1, opts=oracle_mod.default_opts(**oo), nthreads=4)
     gr1 = mp.map_reads(q1, o1, opts=ra.default_opts(**go))
     assert_hits_equal(res1.hit_offsets, res1.hits, gr1.hit_offsets, gr1.hits, "%s, single-end, N-aware pass" % variant)
-    assert res1.counters == gr1.counters and mp.stat(15) > 100
+    assert res1.counters == gr1.counters and mp.stat(ra.QM_STAT_N_PASS_READS) > 100
     monkeypatch.setenv("QM_NPASS_MIN", "-1")
     gr2 = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
     assert_hits_equal(res.hit_offsets, res.hits, gr2.hit_offsets, gr2.hits, "%s, no N-aware pass" % variant)
-    assert mp.stat(15) == 0
+    assert mp.stat(ra.QM_STAT_N_PASS_READS) == 0
 
 
-@pytest.mark.parametrize("kernel", HEADLINE_KERNELS)
-def test_sample_data_through_the_headline_kernels(sample_data, oracle_mod, kernel):
+@pytest.mark.parametrize("kernel", mh.HEADLINE_KERNELS)
+def test_sample_data_through_the_headline_kernels(sample_data, oracle_mod, kernel, gpu):
     import samfmt as sam
     ix, orc = load_oracle(sample_data["idx"])
-    qi, mp = _headline(sample_data["idx"], kernel)
+    qi, mp = gpu(sample_data["idx"], kernel=kernel)
     q1, o1 = pack(sample_data["reads1"]); q2, o2 = pack(sample_data["reads2"])
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=2)
     gr = mp.map_pairs(q1, o1, q2, o2)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "sample_data through the %s kernel" % kernel)
     assert res.counters == gr.counters
-    _check_headline(mp, kernel, len(o1) - 1, expect_deferred=False)
+    mh.check_headline(mp, kernel, len(o1) - 1, expect_deferred=False)
     body = "".join(sam.format_pair(sample_data["names1"][i], sample_data["reads1"][i], sample_data["names2"][i],
                                    sample_data["reads2"][i], gr.hits[gr.hit_offsets[i]:gr.hit_offsets[i + 1]],
                                    qi.txp_names, qi.txp_lens) for i in range(len(o1) - 1))
@@ -178,44 +130,41 @@ def test_sample_data_through_the_headline_kernels(sample_data, oracle_mod, kerne
     assert hashlib.md5(text.encode()).hexdigest() == want
 
 
-@pytest.mark.parametrize("kernel", HEADLINE_KERNELS)
-def test_dollar_repeats_and_runs_through_the_headline_kernels(synth_small, repeat_data, runs_data, oracle_mod, kernel):
+@pytest.mark.parametrize("kernel", mh.HEADLINE_KERNELS)
+def test_dollar_repeats_and_runs_through_the_headline_kernels(synth_small, repeat_data, runs_data, oracle_mod, kernel, gpu):
     """reads across a `$`, the > 200-hit and > 1000-interval repeat families (intervals wider than a wavefront, more suffixes than its lanes,
     hits on both strands, tooManyHits) and windows of k equal bases: every one of them a read these kernels must recognise and leave"""
-    import rapmap_amd as ra
-    from test_emu_parity import _dollar_reads
-    r1, r2 = _dollar_reads(synth_small)
+    r1, r2 = dollar_reads(synth_small)
     sets = [("dollar", synth_small["idx"], r1, r2), ("repeats", repeat_data["idx"], repeat_data["reads1"], repeat_data["reads2"]),
             ("runs", runs_data["idx"], runs_data["reads1"], runs_data["reads2"])]
     for name, idx, a, b in sets:
         ix, orc = load_oracle(idx)
-        qi, mp = _headline(idx, kernel)
+        qi, mp = gpu(idx, kernel=kernel)
         q1, o1 = pack(a); q2, o2 = pack(b)
         for oo, go in (({}, {}), ({"fuzzy": 1}, {"fuzzy": 1}), ({"maxNumHits": 5, "noDovetail": 1}, {"max_num_hits": 5, "no_dovetail": 1})):
             res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
             gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
             assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "%s %s through the %s kernel" % (name, oo, kernel))
             assert res.counters == gr.counters
-            _check_headline(mp, kernel, len(o1) - 1, expect_deferred=name != "dollar", fuzzy="fuzzy" in oo, some_merged=False)
+            mh.check_headline(mp, kernel, len(o1) - 1, expect_deferred=name != "dollar", fuzzy="fuzzy" in oo, some_merged=False)
         mp.close(); qi.close()
 
 
-def test_dollar_in_reads(synth_small, oracle_mod):
-    from test_emu_parity import _dollar_reads
+def test_dollar_in_reads(synth_small, oracle_mod, gpu):
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"])
-    r1, r2 = _dollar_reads(synth_small)
+    qi, mp = gpu(synth_small["idx"])
+    r1, r2 = dollar_reads(synth_small)
     q1, o1 = pack(r1); q2, o2 = pack(r2)
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=4, want_ints=True)
     gr = mp.map_pairs(q1, o1, q2, o2)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "dollar")
     assert res.counters == gr.counters
-    _cmp_ints(res, *mp.intervals(len(o1) - 1))
+    mh.check_intervals(res, *mp.intervals(len(o1) - 1))
 
 
-def test_single_end(synth_small, oracle_mod):
+def test_single_end(synth_small, oracle_mod, gpu):
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     q, o = pack(synth_small["reads1"] + synth_small["reads2"])
     res = orc.map_single(q, o, nthreads=4)
     gr = mp.map_reads(q, o)
@@ -223,7 +172,7 @@ def test_single_end(synth_small, oracle_mod):
     assert res.counters == gr.counters
 
 
-def test_long_reads_ns4(synth_small, oracle_mod):
+def test_long_reads_ns4(synth_small, oracle_mod, gpu):
     import gzip
     from rapmap_amd import synth
     txt = gzip.open(os.path.join(GOLD, "synth_small", "txome.fa.gz"), "rt").read().split("\n")
@@ -231,17 +180,16 @@ def test_long_reads_ns4(synth_small, oracle_mod):
     txps = [t for t in txps if t.size >= 600 and not (t == ord("N")).any()]
     s1, s2, off, _ = synth.make_reads(txps, 800, seed=5, read_len=250, err=0.01)
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"])
+    qi, mp = gpu(synth_small["idx"])
     res = orc.map_pairs(s1, off, s2, off, nthreads=4, want_ints=True)
     gr = mp.map_pairs(s1, off, s2, off)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "ns4")
-    _cmp_ints(res, *mp.intervals(len(off) - 1))
+    mh.check_intervals(res, *mp.intervals(len(off) - 1))
 
 
-def test_edge_batches(synth_small, oracle_mod):
-    import rapmap_amd as ra
+def test_edge_batches(synth_small, oracle_mod, gpu):
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     # empty batch
     z = np.zeros(0, np.uint8); zo = np.zeros(1, np.int64)
     gr = mp.map_pairs(z, zo, z, zo)
@@ -276,10 +224,10 @@ def test_edge_batches(synth_small, oracle_mod):
     assert mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(sel_aln=1, dp_bandwidth=120)).n_hits == 0   # ... whatever the band (round 4)
 
 
-def test_medium_full_parity_and_properties(synth_medium, oracle_mod):
+def test_medium_full_parity_and_properties(synth_medium, oracle_mod, gpu):
     """60k pairs against a ~5k-transcript index: full bit-exact parity, then size-independent properties."""
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     o = synth_medium["off"]; q1 = synth_medium["seq1"]; q2 = synth_medium["seq2"]
     res = orc.map_pairs(q1, o, q2, o, nthreads=8)
     gr = mp.map_pairs(q1, o, q2, o)
@@ -318,12 +266,11 @@ def test_medium_full_parity_and_properties(synth_medium, oracle_mod):
     assert np.array_equal(hp["frag_len"], sp["frag_len"])
 
 
-def test_host_buffers_chunked_upload(synth_medium, oracle_mod, monkeypatch):
+def test_host_buffers_chunked_upload(synth_medium, oracle_mod, monkeypatch, gpu):
     """qm_map_pairs / qm_map_reads on host buffers upload the reads chunk by chunk, every chunk's kernel behind its own
     copy: many small, ragged chunks (QM_HOST_CHUNK) must give what one launch gives -- paired, single-end and -s"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     n = 30000
     o = synth_medium["off"][: n + 1]
     q1 = synth_medium["seq1"][: o[-1]]; q2 = synth_medium["seq2"][: o[-1]]
@@ -395,11 +342,10 @@ def _fuzz_reads(text, offsets, n, seed, max_len):
 
 
 @pytest.mark.parametrize("max_len", [120, 250])
-def test_fuzz_ragged_reads(synth_medium, oracle_mod, max_len):
+def test_fuzz_ragged_reads(synth_medium, oracle_mod, max_len, gpu):
     """ragged, dirty reads through both read-length kernels (<= 128 bp, <= 256 bp): default, --noSensitive, fuzzy and -s"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     text, offsets = qi.arrays()
     n = 6000
     r1, r2 = _fuzz_reads(np.asarray(text), np.asarray(offsets, dtype=np.int64), n, 77 + max_len, max_len)
@@ -415,11 +361,11 @@ def test_fuzz_ragged_reads(synth_medium, oracle_mod, max_len):
     assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "fuzz single-end -s len<=%d" % max_len)
 
 
-def test_device_resident_inputs(synth_medium, oracle_mod):
+def test_device_resident_inputs(synth_medium, oracle_mod, gpu):
     """qm_map_device: reads already in HBM (the path bench.py times)"""
     import torch
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     n = 5000
     o = synth_medium["off"][: n + 1]
     q1 = synth_medium["seq1"][: o[-1]]; q2 = synth_medium["seq2"][: o[-1]]
@@ -432,14 +378,13 @@ def test_device_resident_inputs(synth_medium, oracle_mod):
     assert gr.map_kernel_ms > 0
 
 
-def test_device_resident_batch_in_parts(synth_medium, oracle_mod, monkeypatch):
+def test_device_resident_batch_in_parts(synth_medium, oracle_mod, monkeypatch, gpu):
     """qm_map_device on a large batch maps it as parts in flight together on helper contexts (map_device_split); forced onto a
     small one: offsets, hits and counters are those of the unsplit call and the oracle's -- default, -s, single-end, and an
     uneven number of parts"""
     import torch
-    import rapmap_amd as ra
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     n = 20001
     o = synth_medium["off"][: n + 1]
     q1 = synth_medium["seq1"][: o[-1]]; q2 = synth_medium["seq2"][: o[-1]]
@@ -466,16 +411,15 @@ def test_device_resident_batch_in_parts(synth_medium, oracle_mod, monkeypatch):
     assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "in parts, single-end")
 
 
-def test_batch_in_parts_bookkeeping(synth_medium, monkeypatch):
+def test_batch_in_parts_bookkeeping(synth_medium, monkeypatch, gpu):
     """What a call mapped in parts reports besides its hits (map_device_split): the skipped reads of every part as reads of the
     whole batch, the statistics summed over the parts (the pair kernel's pair count stays -1: qmap_mi355.h), with -s the
     alignment statistics of the unsplit call.  Three reads beyond QM_MAX_LONG_READ_LEN, one in each of three parts, are skipped;
     with max_read_len bounding them the call takes the general kernels (QM_STAT_LEAN_READS is -1, split or not), so the sum of
     the parts' lean reads is checked on the same batch without them."""
     import torch
-    import rapmap_amd as ra
     ix, _ = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     n = 3001
     o = synth_medium["off"]
     r1 = [synth_medium["seq1"][o[i]: o[i + 1]].tobytes() for i in range(n)]
@@ -506,18 +450,17 @@ def test_batch_in_parts_bookkeeping(synth_medium, monkeypatch):
                 assert stat[6:9] == wstat[6:9], (stat, wstat)
 
 
-def test_repeat_families(repeat_data, oracle_mod):
+def test_repeat_families(repeat_data, oracle_mod, gpu):
     """lists beyond a lane's private memory (wave fix-up), beyond LDS (global scratch), tooManyHits, maxInterval"""
     ix, orc = load_oracle(repeat_data["idx"])
-    qi, mp = _gpu(repeat_data["idx"])
+    qi, mp = gpu(repeat_data["idx"])
     q1, o1 = pack(repeat_data["reads1"]); q2, o2 = pack(repeat_data["reads2"])
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=4, want_ints=True)
     gr = mp.map_pairs(q1, o1, q2, o2)
     assert res.counters["tooManyHits"] > 0
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "repeats")
     assert res.counters == gr.counters
-    _cmp_ints(res, *mp.intervals(len(o1) - 1))
-    import rapmap_amd as ra
+    mh.check_intervals(res, *mp.intervals(len(o1) - 1))
     fres = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(fuzzy=1), nthreads=4)
     fgr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(fuzzy=1))
     assert_hits_equal(fres.hit_offsets, fres.hits, fgr.hit_offsets, fgr.hits, "repeats-fuzzy")
@@ -525,12 +468,11 @@ def test_repeat_families(repeat_data, oracle_mod):
 
 
 @pytest.mark.parametrize("variant", ["default", "noSensitive", "fuzzy", "sel"])
-def test_homopolymer_runs(runs_data, oracle_mod, variant):
+def test_homopolymer_runs(runs_data, oracle_mod, variant, gpu):
     """windows of k equal bases at every alignment of the four-characters-per-lane strand setup (its shortcut for reads
     without such a window against the tabulating pass and isHomoPolymer, Kmer.hpp:484-487)"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(runs_data["idx"])
-    qi, mp = _gpu(runs_data["idx"])
+    qi, mp = gpu(runs_data["idx"])
     q1, o1 = pack(runs_data["reads1"]); q2, o2 = pack(runs_data["reads2"])
     oo, go = {"default": ({}, {}), "noSensitive": ({"sensitive": 0}, {"sensitive": 0}), "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}),
               "sel": ({"selAln": 1}, {"sel_aln": 1})}[variant]
@@ -540,24 +482,23 @@ def test_homopolymer_runs(runs_data, oracle_mod, variant):
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "runs-" + variant)
     assert res.counters == gr.counters
     if variant != "sel":
-        _cmp_ints(res, *mp.intervals(len(o1) - 1))
+        mh.check_intervals(res, *mp.intervals(len(o1) - 1))
 
 
 @pytest.mark.parametrize("compact", [False, True])
-def test_perfect_hash_index(synth_small, synth_small_ph, oracle_mod, compact):
+def test_perfect_hash_index(synth_small, synth_small_ph, oracle_mod, compact, gpu):
     """config 4: `quasiindex -p` index through the HIP path == dense-index oracle; both device images of the index: the
     default (expanded into the one-sector bucket table after every record was checked through the BooPHF walk) and the
     compact one (QM_CTX_PH_COMPACT: the BooPHF levels walked per lookup, as FrugalBooMap::find does)"""
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small_ph["idx"], ph_compact=compact)
+    qi, mp = gpu(synth_small_ph["idx"], ph_compact=compact)
     assert qi.perfect_hash
     q1, o1 = pack(synth_small_ph["reads1"]); q2, o2 = pack(synth_small_ph["reads2"])
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=4, want_ints=True)
     gr = mp.map_pairs(q1, o1, q2, o2)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "perfect-hash")
     assert res.counters == gr.counters
-    _cmp_ints(res, *mp.intervals(len(o1) - 1))
-    import rapmap_amd as ra
+    mh.check_intervals(res, *mp.intervals(len(o1) - 1))
     for oo, go in (({"sensitive": 0}, {"sensitive": 0}), ({"fuzzy": 1, "strictCheck": 0}, {"fuzzy": 1, "strict_check": 0})):
         r2 = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
         g2 = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
@@ -566,13 +507,11 @@ def test_perfect_hash_index(synth_small, synth_small_ph, oracle_mod, compact):
 
 
 @pytest.mark.parametrize("case", range(6))
-def test_selective_alignment(synth_small, oracle_mod, case):
+def test_selective_alignment(synth_small, oracle_mod, case, gpu):
     """config 5 (-s) through the C ABI: hits incl. alignment scores and counters == oracle, paired and single-end"""
-    import rapmap_amd as ra
-    from test_emu_parity import SEL_VARIANTS, sel_reads
     which, oo, go = SEL_VARIANTS[case]
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     s1, s2 = sel_reads(synth_small, which)
     q1, o1 = pack(s1); q2, o2 = pack(s2)
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
@@ -585,13 +524,12 @@ def test_selective_alignment(synth_small, oracle_mod, case):
     assert rs.counters == gs.counters
 
 
-def test_selective_alignment_in_chunks(synth_small, oracle_mod, monkeypatch):
+def test_selective_alignment_in_chunks(synth_small, oracle_mod, monkeypatch, gpu):
     """stage B/C of -s in four chunks of units (the plan kernels of the later chunks on a stream of their own under the ksw2
     kernel of the earlier ones): what 10 M-pair batches do, forced onto a small one"""
-    import rapmap_amd as ra
     monkeypatch.setenv("QM_SEL_CHUNK_UNITS", "500")
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
     for oo, go in (({"selAln": 1}, {"sel_aln": 1}), ({"selAln": 1, "hardFilter": 1, "maxNumHits": 5}, {"sel_aln": 1, "hard_filter": 1, "max_num_hits": 5})):
         res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
@@ -603,11 +541,10 @@ def test_selective_alignment_in_chunks(synth_small, oracle_mod, monkeypatch):
     assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "-s in chunks, single-end")
 
 
-def test_selective_alignment_medium(synth_medium, oracle_mod):
+def test_selective_alignment_medium(synth_medium, oracle_mod, gpu):
     """-s on 20 k pairs against the ~5 k-transcript index"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     n = 20000
     o = synth_medium["off"][: n + 1]
     q1 = synth_medium["seq1"][: o[-1]]; q2 = synth_medium["seq2"][: o[-1]]
@@ -617,15 +554,14 @@ def test_selective_alignment_medium(synth_medium, oracle_mod):
     assert res.counters == gr.counters
     # qm_ctx_stat 6 / 7: alignment questions beyond PERFECT chains, and the ksw2 alignments run for them -- with 1 % substitutions most
     # questions are answered by the alignment cache, the ungapped branch or sel_side_score's two rules
-    asked, ran = mp.stat(6), mp.stat(7)
+    asked, ran = mp.stat(ra.QM_STAT_SEL_QUESTIONS), mp.stat(ra.QM_STAT_KSW2_ALIGNMENTS)
     assert asked > n and 0 < ran < asked / 3, (asked, ran)
 
 
-def test_selective_alignment_list_kernels_agree(synth_medium, repeat_data, oracle_mod, monkeypatch):
+def test_selective_alignment_list_kernels_agree(synth_medium, repeat_data, oracle_mod, monkeypatch, gpu):
     """-s: the list kernel that shares a wavefront among several reads (qm_selpack.inl) and the one-read-per-wavefront kernel
     (QM_SEL_PACK=0: every read) leave the same words for every read, and the hits are the oracle's either way; the repeat
     families bring reads the packed kernel hands on (hits on both strands, more than 64 suffixes)"""
-    import rapmap_amd as ra
     n = 12000
     o = synth_medium["off"][: n + 1]
     sets = [(synth_medium["idx"], synth_medium["seq1"][: o[-1]], o, synth_medium["seq2"][: o[-1]], o)]
@@ -633,7 +569,7 @@ def test_selective_alignment_list_kernels_agree(synth_medium, repeat_data, oracl
     sets.append((repeat_data["idx"], q1, o1, q2, o2))
     for idx, a, oa, b, ob in sets:
         ix, orc = load_oracle(idx)
-        qi, mp = _gpu(idx, debug=True)
+        qi, mp = gpu(idx, debug=True)
         res = orc.map_pairs(a, oa, b, ob, opts=oracle_mod.default_opts(selAln=1, consensusSlack=0.35), nthreads=8)
         words = {}
         for knob in ("1", "0"):
@@ -649,7 +585,6 @@ def test_selective_alignment_list_kernels_agree(synth_medium, repeat_data, oracl
 
 
 def _medium_txps(idx, min_len=700, cap=1500):
-    import rapmap_amd as ra
     qi = ra.QuasiIndex(idx)
     text, offsets = qi.arrays()
     text = np.asarray(text); offsets = np.asarray(offsets, dtype=np.int64)
@@ -659,14 +594,13 @@ def _medium_txps(idx, min_len=700, cap=1500):
 
 @pytest.mark.parametrize("variant", ["default", "noSensitive", "fuzzy", "selAln", "perfectHash", "perfectHash_noSensitive", "perfectHash_selAln",
                                      "perfectHashCompact", "perfectHashCompact_noSensitive", "perfectHashCompact_selAln"])
-def test_reads_150bp_take_the_three_slot_kernels(synth_medium, synth_medium_ph, oracle_mod, variant):
+def test_reads_150bp_take_the_three_slot_kernels(synth_medium, synth_medium_ph, oracle_mod, variant, gpu):
     """2 x 150 bp (every read 129..192 bp long): the NS=3 instantiations of stage A -- dense / -p, default / --noSensitive /
     fuzzy / -s -- none of which the 100 bp and 250 bp cases reach"""
-    import rapmap_amd as ra
     from rapmap_amd import synth
     ph = variant.startswith("perfectHash")
     ix, orc = load_oracle(synth_medium["idx"])                # the oracle maps on the dense index: same hits by construction
-    qi, mp = _gpu((synth_medium_ph if ph else synth_medium)["idx"], debug=False, ph_compact="Compact" in variant)
+    qi, mp = gpu((synth_medium_ph if ph else synth_medium)["idx"], debug=False, ph_compact="Compact" in variant)
     assert qi.perfect_hash == ph
     s1, s2, off, _ = synth.make_reads(_medium_txps(synth_medium["idx"]), 6000, seed=150, read_len=150, err=0.01)
     # ragged lengths inside the slot range, so that nothing rides on "exactly 150"
@@ -692,12 +626,10 @@ def test_reads_150bp_take_the_three_slot_kernels(synth_medium, synth_medium_ph, 
 
 
 @pytest.mark.parametrize("band", [34, 40, 64, 120, 1000, -1])
-def test_selective_alignment_wide_bands(synth_small, synth_medium, oracle_mod, band):
+def test_selective_alignment_wide_bands(synth_small, synth_medium, oracle_mod, band, gpu):
     """--dpBandwidth beyond 33 runs the same four-per-wavefront ksw2 kernel on a larger column ring"""
-    import rapmap_amd as ra
-    from test_emu_parity import sel_reads
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     s1, s2 = sel_reads(synth_small, "indel")
     q1, o1 = pack(s1); q2, o2 = pack(s2)
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(selAln=1, dpBandwidth=band), nthreads=4)
@@ -706,7 +638,7 @@ def test_selective_alignment_wide_bands(synth_small, synth_medium, oracle_mod, b
     assert res.counters == gr.counters
     # and on 250 bp reads (the longest alignments: 256 x 276 cells inside the band)
     ix2, orc2 = load_oracle(synth_medium["idx"])
-    qi2, mp2 = _gpu(synth_medium["idx"], debug=False)
+    qi2, mp2 = gpu(synth_medium["idx"], debug=False)
     from rapmap_amd import synth
     a1, a2, ao, _ = synth.make_reads(_medium_txps(synth_medium["idx"]), 1500, seed=250 + band, read_len=250, err=0.02)
     r2 = orc2.map_pairs(a1, ao, a2, ao, opts=oracle_mod.default_opts(selAln=1, dpBandwidth=band), nthreads=8)
@@ -714,18 +646,17 @@ def test_selective_alignment_wide_bands(synth_small, synth_medium, oracle_mod, b
     assert_hits_equal(r2.hit_offsets, r2.hits, g2.hit_offsets, g2.hits, "selAln 250 bp band %d" % band)
 
 
-def test_selective_alignment_repeats_take_the_slow_pass(repeat_data, oracle_mod):
+def test_selective_alignment_repeats_take_the_slow_pass(repeat_data, oracle_mod, gpu):
     """-s, reads inside a 900-copy repeat: more suffixes per strand than a wave's scratch (QM_SEL_CAP) -- queued and redone
     on scratch sized for them; the batch must not fail and the hits must be the oracle's"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(repeat_data["idx"])
-    qi, mp = _gpu(repeat_data["idx"], debug=False)
+    qi, mp = gpu(repeat_data["idx"], debug=False)
     q1, o1 = pack(repeat_data["reads1"]); q2, o2 = pack(repeat_data["reads2"])
     for oo, go in ((dict(selAln=1), dict(sel_aln=1)), (dict(selAln=1, maxNumHits=5000, hardFilter=1), dict(sel_aln=1, max_num_hits=5000, hard_filter=1)),
                    (dict(selAln=1, maxNumHits=5000, consensusSlack=0.5), dict(sel_aln=1, max_num_hits=5000, consensus_slack=0.5))):
         res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
         gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
-        assert mp.stat(2) > 0, "no read took the slow pass"
+        assert mp.stat(ra.QM_STAT_SLOW_READS) > 0, "no read took the slow pass"
         assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "repeats -s %s" % oo)
         assert res.counters == gr.counters
     rs = orc.map_single(q1, o1, opts=oracle_mod.default_opts(selAln=1, maxNumHits=5000), nthreads=4)
@@ -733,7 +664,7 @@ def test_selective_alignment_repeats_take_the_slow_pass(repeat_data, oracle_mod)
     assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "repeats -s single-end")
 
 
-def test_list_buffer_overflow_relaunches_stage_a(repeat_data, oracle_mod):
+def test_list_buffer_overflow_relaunches_stage_a(repeat_data, oracle_mod, gpu):
     """a batch whose per-read hit lists outgrow the buffer sized for an ordinary batch (every read sits in a 300- or 900-copy
     repeat): stage A flags the overflow, the host grows the buffer and redoes the batch -- same results, and the relaunch
     is visible in qm_ctx_stat"""
@@ -744,9 +675,9 @@ def test_list_buffer_overflow_relaunches_stage_a(repeat_data, oracle_mod):
     ref = orc.map_pairs(a1, ao1, a2, ao2, nthreads=4)
     reps = 12000                                                           # 288 000 pairs, ~340 M list words (the default buffer of a batch this size: 270 M)
     q1, o1 = pack(u1 * reps); q2, o2 = pack(u2 * reps)
-    qi, mp = _gpu(repeat_data["idx"], debug=False)                        # a fresh context: the list buffer starts at its default size
+    qi, mp = gpu(repeat_data["idx"], debug=False)                        # a fresh context: the list buffer starts at its default size
     gr = mp.map_pairs(q1, o1, q2, o2)
-    assert mp.stat(0) >= 1, "the batch fitted: no relaunch was exercised (list words %d)" % mp.stat(1)
+    assert mp.stat(ra.QM_STAT_RELAUNCHES) >= 1, "the batch fitted: no relaunch was exercised (list words %d)" % mp.stat(ra.QM_STAT_LIST_WORDS)
     nu = len(core)
     cnt = np.diff(gr.hit_offsets).reshape(reps, nu)
     assert (cnt == np.diff(ref.hit_offsets)[None, :]).all()
@@ -756,17 +687,16 @@ def test_list_buffer_overflow_relaunches_stage_a(repeat_data, oracle_mod):
     assert gr.counters["numReads"] == reps * nu and gr.counters["tooManyHits"] == reps * ref.counters["tooManyHits"]
     # the grown buffer serves the next call without another relaunch
     gr2 = mp.map_pairs(q1, o1, q2, o2)
-    assert mp.stat(0) == 0 and gr2.hits.tobytes() == gr.hits.tobytes()
+    assert mp.stat(ra.QM_STAT_RELAUNCHES) == 0 and gr2.hits.tobytes() == gr.hits.tobytes()
 
 
 @pytest.mark.parametrize("mode", ["plain", "fuzzy", "chain", "noSensitive"])
-def test_stage_entry_points_compose_to_the_fused_path(synth_small, oracle_mod, mode):
+def test_stage_entry_points_compose_to_the_fused_path(synth_small, oracle_mod, mode, gpu):
     """SACollector::operator(), hitsToMappingsSimple and mergeLeftRightHits[Fuzzy] as device calls of their own
     (qm_collect_reads -> qm_hits_to_mappings -> qm_merge_lists): intervals == the oracle's, and the three chained give what
     the fused pass (qm_map_pairs_stages) gives"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
     n = len(o1) - 1
     go = {"plain": {}, "fuzzy": {"fuzzy": 1}, "chain": {"sel_aln": 1, "fuzzy": 1}, "noSensitive": {"sensitive": 0}}[mode]
@@ -819,16 +749,15 @@ def test_stage_entry_points_compose_to_the_fused_path(synth_small, oracle_mod, m
 
 
 @pytest.mark.parametrize("L", [300, 500])
-def test_reads_longer_than_256_bp(synth_medium, synth_medium_ph, oracle_mod, L):
+def test_reads_longer_than_256_bp(synth_medium, synth_medium_ph, oracle_mod, L, gpu):
     """2 x 300 and 2 x 500 bp (merged pairs, long-insert libraries): the eight-slot kernels -- dense / -p, default /
     --noSensitive / -s -- instead of QM_E_TOOLONG; a batch that mixes them with short reads runs on the same kernels"""
-    import rapmap_amd as ra
     from rapmap_amd import synth
     ix, orc = load_oracle(synth_medium["idx"])
     txps = _medium_txps(synth_medium["idx"], min_len=1200, cap=800)
     s1, s2, off, _ = synth.make_reads(txps, 1500, seed=3 + L, read_len=L, err=0.015)
     for idx, compact in ((synth_medium["idx"], False), (synth_medium_ph["idx"], True)):
-        qi, mp = _gpu(idx, debug=False, ph_compact=compact)
+        qi, mp = gpu(idx, debug=False, ph_compact=compact)
         for oo, go in (({}, {}), ({"sensitive": 0}, {"sensitive": 0}), ({"selAln": 1}, {"sel_aln": 1}), ({"fuzzy": 1}, {"fuzzy": 1})):
             res = orc.map_pairs(s1, off, s2, off, opts=oracle_mod.default_opts(**oo), nthreads=8)
             gr = mp.map_pairs(s1, off, s2, off, opts=ra.default_opts(**go))
@@ -840,18 +769,17 @@ def test_reads_longer_than_256_bp(synth_medium, synth_medium_ph, oracle_mod, L):
     r1 = [s1[off[i]:off[i + 1]].tobytes() for i in range(300)] + [a1[ao[i]:ao[i + 1]].tobytes() for i in range(1000)]
     r2 = [s2[off[i]:off[i + 1]].tobytes() for i in range(300)] + [a2[ao[i]:ao[i + 1]].tobytes() for i in range(1000)]
     q1, o1 = pack(r1); q2, o2 = pack(r2)
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=8)
     gr = mp.map_pairs(q1, o1, q2, o2)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "mixed lengths")
 
 
 @pytest.mark.parametrize("variant", ["selAln", "selAln_band40", "selAln_band20", "selAln_noSensitive", "selAln_perfectHash", "mimicBT2", "selAln_band120", "selAln_fullband"])
-def test_selective_alignment_of_reads_beyond_512_bp(synth_medium, synth_medium_ph, oracle_mod, variant):
+def test_selective_alignment_of_reads_beyond_512_bp(synth_medium, synth_medium_ph, oracle_mod, variant, gpu):
     """-s on a batch that mixes 2 x 100 bp pairs with reads of 513 .. 2048 bp (the reference aligns any length): the collector sets
     the long reads aside, a second small launch of the 32-slot chain-scoring collector delivers their intervals, the list kernel
     and the plan are length-blind, and the ksw2 row kernel runs in its long-image editions (register, 64- and 128-slot rings)"""
-    import rapmap_amd as ra
     from rapmap_amd import synth
     ph = variant == "selAln_perfectHash"
     idx = (synth_medium_ph if ph else synth_medium)["idx"]
@@ -878,7 +806,7 @@ def test_selective_alignment_of_reads_beyond_512_bp(synth_medium, synth_medium_p
                   "selAln_fullband": ({"selAln": 1, "dpBandwidth": -1}, {"sel_aln": 1, "dp_bandwidth": -1})}[variant]
         oopts = oracle_mod.default_opts(**oo); gopts = ra.default_opts(**go)
     res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=8)
-    qi, mp = _gpu(idx, debug=False)
+    qi, mp = gpu(idx, debug=False)
     gr = mp.map_pairs(q1, o1, q2, o2, opts=gopts)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "-s long reads, %s" % variant)
     assert res.counters == gr.counters
@@ -897,12 +825,11 @@ def test_selective_alignment_of_reads_beyond_512_bp(synth_medium, synth_medium_p
 
 
 @pytest.mark.parametrize("variant", ["default", "noSensitive", "fuzzy", "perfectHash", "perfectHashCompact"])
-def test_reads_beyond_512_bp_take_the_long_read_pass(synth_medium, synth_medium_ph, oracle_mod, variant):
+def test_reads_beyond_512_bp_take_the_long_read_pass(synth_medium, synth_medium_ph, oracle_mod, variant, gpu):
     """a batch of 2 x 100 bp pairs with reads of 600 .. 2048 bp among them (the reference takes any std::string,
     include/SACollector.hpp:108): the short reads run on the two-slot kernels, the long ones are set aside by that launch and
     mapped by a second, small launch of the 32-slot kernels; hits and counters equal the oracle's.  With -s, and beyond 2048
     characters, the call fails loudly instead."""
-    import rapmap_amd as ra
     from rapmap_amd import synth
     ph = variant.startswith("perfectHash")
     idx = (synth_medium_ph if ph else synth_medium)["idx"]
@@ -920,12 +847,12 @@ def test_reads_beyond_512_bp_take_the_long_read_pass(synth_medium, synth_medium_
     oo, go = {"default": ({}, {}), "noSensitive": ({"sensitive": 0}, {"sensitive": 0}), "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}),
               "perfectHash": ({}, {}), "perfectHashCompact": ({}, {})}[variant]
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=8, want_ints=True)
-    qi, mp = _gpu(idx, debug=True, ph_compact=variant == "perfectHashCompact")
+    qi, mp = gpu(idx, debug=True, ph_compact=variant == "perfectHashCompact")
     gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "long reads, %s" % variant)
     assert res.counters == gr.counters
     long_units = [u for u in range(len(r1)) if len(r1[u]) > 512 or len(r2[u]) > 512]
-    assert mp.stat(2) == sum((len(r1[u]) > 512) + (len(r2[u]) > 512) for u in long_units)       # QM_STAT_SLOW_READS: the reads of the second launch
+    assert mp.stat(ra.QM_STAT_SLOW_READS) == sum((len(r1[u]) > 512) + (len(r2[u]) > 512) for u in long_units)       # QM_STAT_SLOW_READS: the reads of the second launch
     assert sum(int(res.hit_offsets[u + 1] - res.hit_offsets[u]) > 0 for u in long_units) > len(long_units) // 2
     io, ints = mp.intervals(len(r1))                         # the SA-interval lists of the fused pass, long reads included
     assert np.array_equal(io, res.ints_offsets)
@@ -958,13 +885,12 @@ def test_reads_beyond_512_bp_take_the_long_read_pass(synth_medium, synth_medium_
 
 
 @pytest.mark.parametrize("variant", ["default", "fuzzy", "selAln", "noSensitive"])
-def test_two_bit_packed_reads_map_like_their_characters(synth_small, oracle_mod, variant):
+def test_two_bit_packed_reads_map_like_their_characters(synth_small, oracle_mod, variant, gpu):
     """qm_map_pairs_packed / qm_map_reads_packed (2-bit packed batches over PCIe, unpacked on the device): the dirty
     reads of synth_small -- N, lower case, IUPAC, U, '$', reads shorter than k, ragged lengths -- give the oracle's hits and
     counters bit for bit, as the plain-character calls do"""
-    import rapmap_amd as ra
     ix, orc = load_oracle(synth_small["idx"])
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
     oo, go = {"default": ({}, {}), "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}), "selAln": ({"selAln": 1}, {"sel_aln": 1}),
               "noSensitive": ({"sensitive": 0}, {"sensitive": 0})}[variant]
@@ -983,7 +909,6 @@ def test_two_bit_packed_reads_map_like_their_characters(synth_small, oracle_mod,
 def _lean_edge_reads(idx, n=600, seed=5):
     """reads that walk the lean kernel's edges: every length from below k to 128 (a 128-character perfect match runs past the SaExt
     window), lower case, N's, long runs of one base, two errors, reverse-complemented mates, empty reads"""
-    import rapmap_amd as ra
     rng = np.random.default_rng(seed)
     qi = ra.QuasiIndex(idx)
     text, offsets = qi.arrays()
@@ -1015,56 +940,53 @@ def _lean_edge_reads(idx, n=600, seed=5):
 
 
 @pytest.mark.parametrize("variant", ["default", "noStrictCheck", "quasiCov", "fuzzy", "maxInterval3", "noOrphans"])
-def test_lean_kernel_edges_match_the_oracle(synth_medium, oracle_mod, variant):
+def test_lean_kernel_edges_match_the_oracle(synth_medium, oracle_mod, variant, gpu):
     """the lean stage-A kernel (two reads per wavefront; qm_lean.inl) on reads at its edges, paired and single-end with an odd count:
     what it takes and what it leaves to the general kernel must add up to the oracle's hits"""
-    import rapmap_amd as ra
     oo, go = {"default": ({}, {}), "noStrictCheck": ({"strictCheck": 0}, {"strict_check": 0}), "quasiCov": ({"quasiCov": 0.7}, {"quasi_cov": 0.7}),
               "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}), "maxInterval3": ({"maxInterval": 3}, {"max_interval": 3}),
               "noOrphans": ({"noOrphans": 1}, {"no_orphans": 1})}[variant]
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=False)
+    qi, mp = gpu(synth_medium["idx"], debug=False)
     r1, r2 = _lean_edge_reads(synth_medium["idx"])
     q1, o1 = pack(r1); q2, o2 = pack(r2)
     res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4)
     gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "lean edges %s" % variant)
     assert res.counters == gr.counters
-    assert mp.stat(3) == 2 * len(r1), "the lean kernel was not the one launched"
-    assert 0 < mp.stat(4) < 2 * len(r1), "expected some reads left to the general kernel, and most taken"
+    assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * len(r1), "the lean kernel was not the one launched"
+    assert 0 < mp.stat(ra.QM_STAT_LEAN_DEFERRED) < 2 * len(r1), "expected some reads left to the general kernel, and most taken"
     one = r1[:-1] + r2[1:2]                                 # single-end, an odd number of reads
     qs, os_ = pack(one)
     if "fuzzy" not in go and "no_orphans" not in go:
         rs = orc.map_single(qs, os_, opts=oracle_mod.default_opts(**oo), nthreads=4)
         gs = mp.map_reads(qs, os_, opts=ra.default_opts(**go))
         assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "lean edges single-end %s" % variant)
-        assert mp.stat(3) == len(one)
+        assert mp.stat(ra.QM_STAT_LEAN_READS) == len(one)
 
 
-def test_lean_kernel_on_the_compact_perfect_hash_image(synth_medium, synth_medium_ph, oracle_mod):
-    import rapmap_amd as ra
+def test_lean_kernel_on_the_compact_perfect_hash_image(synth_medium, synth_medium_ph, oracle_mod, gpu):
     ix, orc = load_oracle(synth_medium_ph["idx"])
-    qi, mp = _gpu(synth_medium_ph["idx"], debug=False, ph_compact=True)
+    qi, mp = gpu(synth_medium_ph["idx"], debug=False, ph_compact=True)
     r1, r2 = _lean_edge_reads(synth_medium["idx"], n=400, seed=6)
     q1, o1 = pack(r1); q2, o2 = pack(r2)
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=4)
     gr = mp.map_pairs(q1, o1, q2, o2)
     assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "lean edges, compact -p")
-    assert res.counters == gr.counters and mp.stat(3) == 2 * len(r1)
+    assert res.counters == gr.counters and mp.stat(ra.QM_STAT_LEAN_READS) == 2 * len(r1)
     gs = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(sel_aln=1))
     rs = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(selAln=1), nthreads=4)
     assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "lean edges, compact -p, -s")
 
 
 @pytest.mark.gpu
-def test_general_kernel_scratch_by_slot(synth_medium, oracle_mod, monkeypatch):
+def test_general_kernel_scratch_by_slot(synth_medium, oracle_mod, monkeypatch, gpu):
     """the general kernels' device-memory scratch handed out by slot (ReadBatch::gslots: a wave takes a free slot of its XCD when it starts
     and returns it when it ends -- what an oversubscribed launch over a large batch does), forced here for a launch that would not need
     it (QM_GSCR_SLOTS): the interval-keeping stage view of the call surface, whose intervals, lists and hits all equal the oracle's"""
-    import rapmap_amd as ra
     monkeypatch.setenv("QM_GSCR_SLOTS", "1")
     ix, orc = load_oracle(synth_medium["idx"])
-    qi, mp = _gpu(synth_medium["idx"], debug=True)        # debug: intervals kept -> the general kernel, not the lean one
+    qi, mp = gpu(synth_medium["idx"], debug=True)        # debug: intervals kept -> the general kernel, not the lean one
     n = 30000
     o = synth_medium["off"][: n + 1]
     q1 = synth_medium["seq1"][: o[-1]]; q2 = synth_medium["seq2"][: o[-1]]
@@ -1073,20 +995,18 @@ def test_general_kernel_scratch_by_slot(synth_medium, oracle_mod, monkeypatch):
         gr = mp.map_pairs(q1, o, q2, o)
         assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "scratch slots, call %d" % rep)
         assert res.counters == gr.counters
-        assert mp.stat(3) == -1, "expected the general kernel"
+        assert mp.stat(ra.QM_STAT_LEAN_READS) == -1, "expected the general kernel"
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("max_len", [150, 256])
-def test_wide_lean_kernel_single_end_and_paired(synth_medium, synth_medium_ph, oracle_mod, max_len):
+def test_wide_lean_kernel_single_end_and_paired(synth_medium, synth_medium_ph, oracle_mod, max_len, gpu):
     """the lean kernel's wide edition (one read of up to 256 characters per wavefront, qm_lean.inl WIDE) on ragged reads with substitutions,
     indels, N's and lower case: paired and single-end (an odd count), lists and the -s collector, dense table and compact -p image --
     what it takes and what it leaves to the general kernel add up to the oracle's hits"""
-    import rapmap_amd as ra
     for idx, compact in ((synth_medium["idx"], False), (synth_medium_ph["idx"], True)):
         ix, orc = load_oracle(idx)
-        qi = ra.QuasiIndex(idx)
-        mp = ra.QuasiMapper(qi, 0, debug=False, ph_compact=compact)
+        qi, mp = gpu(idx, debug=False, ph_compact=compact)
         text, offsets = ra.QuasiIndex(synth_medium["idx"]).arrays()
         r1, r2 = _fuzz_reads(np.asarray(text), np.asarray(offsets, dtype=np.int64), 3001, 4200 + max_len, max_len)
         q1, o1 = pack(r1); q2, o2 = pack(r2)
@@ -1096,8 +1016,8 @@ def test_wide_lean_kernel_single_end_and_paired(synth_medium, synth_medium_ph, o
             assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "wide lean, paired %s compact=%s" % (oo, compact))
             assert res.counters == gr.counters
             if not oo:
-                assert mp.stat(3) == 2 * len(r1), "the lean kernel was not the one launched"
-                assert 0 < mp.stat(4) < len(r1), "expected most reads taken, some left to the general kernel"
+                assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * len(r1), "the lean kernel was not the one launched"
+                assert 0 < mp.stat(ra.QM_STAT_LEAN_DEFERRED) < len(r1), "expected most reads taken, some left to the general kernel"
             rs = orc.map_single(q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=8)
             gs = mp.map_reads(q2, o2, opts=ra.default_opts(**go))
             assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "wide lean, single-end %s compact=%s" % (oo, compact))
@@ -1106,14 +1026,12 @@ def test_wide_lean_kernel_single_end_and_paired(synth_medium, synth_medium_ph, o
 
 
 @pytest.mark.gpu
-def test_extension_tables_match_the_byte_per_character_builders(synth_medium, oracle_mod, monkeypatch):
+def test_extension_tables_match_the_byte_per_character_builders(synth_medium, oracle_mod, monkeypatch, gpu):
     """round 6 builds SaExt / SaExt2 / sanext out of a 2-bit image of the text (two or three sectors per entry instead of 82); QM_TABLE_CHECK=1
     holds every entry against the byte-per-character builders of rounds 3-5 on the device and fails the build on a difference"""
-    import rapmap_amd as ra
     monkeypatch.setenv("QM_TABLE_CHECK", "1")
     ix, orc = load_oracle(synth_medium["idx"])
-    qi = ra.QuasiIndex(synth_medium["idx"])
-    mp = ra.QuasiMapper(qi, 0, wide_reads=True)            # SaExt with the replica, SaExt2 because asked
+    qi, mp = gpu(synth_medium["idx"], debug=False, wide_reads=True)            # SaExt with the replica, SaExt2 because asked
     n = 2000
     q1, q2, o = synth_medium["seq1"][: n * 100], synth_medium["seq2"][: n * 100], synth_medium["off"][: n + 1]
     gr = mp.map_pairs(q1, o, q2, o, opts=ra.default_opts(sel_aln=1))       # sanext at the first -s call
@@ -1125,27 +1043,25 @@ def test_extension_tables_match_the_byte_per_character_builders(synth_medium, or
     gw = mp.map_pairs(s1, off, s2, off)
     rw = orc.map_pairs(s1, off, s2, off, nthreads=4)
     assert_hits_equal(rw.hit_offsets, rw.hits, gw.hit_offsets, gw.hits, "150 bp with checked tables")
-    assert mp.stat(3) == 2 * 500, "the wide lean kernel did not run: no SaExt2"
-    mp.close(); qi.close()
+    assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * 500, "the wide lean kernel did not run: no SaExt2"
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["plain", "fuzzy"])
-def test_stage_view_without_intervals_and_packed(synth_small, oracle_mod, mode):
+def test_stage_view_without_intervals_and_packed(synth_small, oracle_mod, mode, gpu):
     """QM_STAGES_NO_INTERVALS / qm_map_pairs_stages_packed (round 6): everything of the stage view but the interval records -- foundHit, the per-read
     lists, the merge's hits and tooMany flags -- equals the full pass's, with the reads as characters or 2-bit packed; the pass ran on the
     pair / lean kernels (the full one keeps intervals: general kernel)"""
-    import rapmap_amd as ra
-    qi, mp = _gpu(synth_small["idx"], debug=False)
+    qi, mp = gpu(synth_small["idx"], debug=False)
     q1, o1 = pack(synth_small["reads1"]); q2, o2 = pack(synth_small["reads2"])
     n = len(o1) - 1
     opts = ra.default_opts(**({"fuzzy": 1} if mode == "fuzzy" else {}))
     full = mp.map_pairs_stages(q1, o1, q2, o2, opts=opts)
     vf = {k: (np.array(v, copy=True) if hasattr(v, "shape") else v) for k, v in mp.fetch_stages(pinned=False).items()}
-    assert mp.stat(3) == -1
+    assert mp.stat(ra.QM_STAT_LEAN_READS) == -1
     for packed in (False, True):
         light = mp.map_pairs_stages(q1, o1, q2, o2, opts=opts, no_intervals=True, packed=packed)
-        assert mp.stat(3) == 2 * n and mp.stat(4) > 0, "the lean / pair kernel did not run"
+        assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * n and mp.stat(ra.QM_STAT_LEAN_DEFERRED) > 0, "the lean / pair kernel did not run"
         v = mp.fetch_stages(pinned=packed)
         assert np.array_equal(light.hit_offsets, full.hit_offsets) and light.hits.tobytes() == full.hits.tobytes() and light.counters == full.counters
         assert int(v["iv_off"][-1]) == 0 and v["iv"].size == 0
@@ -1154,4 +1070,3 @@ def test_stage_view_without_intervals_and_packed(synth_small, oracle_mod, mode):
         assert np.array_equal(v["hit_off"], vf["hit_off"]) and v["hits"].tobytes() == vf["hits"].tobytes()
         assert np.array_equal(v["too_many"], vf["too_many"])
         mp._arena_cap = 0
-    mp.close(); qi.close()

@@ -6,24 +6,10 @@ The reference is the oracle, which reads k from the index header: the reference'
 golden SAM at another k.  test_error_free_pairs_* is the one check that does not go through the oracle."""
 import pytest
 
+import emu
 import kmer_cases as kc
-from test_emu_parity import VARIANTS
+import mapping_harness as mh
 from util import pack
-
-SOME = {v: VARIANTS[v] for v in ("default", "noStrictCheck", "z0.9", "noSensitive", "fuzzy")}
-SOME["selAln"] = ({"selAln": 1}, {"sel_aln": 1})
-FEW = {v: SOME[v] for v in ("default", "noSensitive", "fuzzy", "selAln")}
-
-_emus = {}
-
-
-def _emu(idx):
-    """(oracle, emulation) of an index, kept for the process: the emulation's extension tables are built once per index"""
-    import emu
-    if idx not in _emus:
-        ix, orc = kc.load_oracle(idx)
-        _emus[idx] = (orc, emu.Emu(ix))
-    return _emus[idx]
 
 
 @pytest.fixture(scope="module")
@@ -33,27 +19,25 @@ def root(tmp_path_factory, lib_built, oracle_mod):
 
 def _run(idx, oracle_mod, q1, o1, q2, o2, variant, what, ns=2, ints=True):
     """one paired call through the oracle and the emulation"""
-    import emu
-    orc, em = _emu(idx)
-    oo, eo = SOME[variant] if variant in SOME else VARIANTS[variant]
+    ix, orc, em = mh.emu_of(idx)
+    oopts, eopts = mh.opts_for(variant, oracle_mod, emu.default_opts)
     ints = ints and variant != "selAln"
-    res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=4, want_ints=ints)
-    er = em.map(q1, o1, q2, o2, opts=emu.default_opts(**eo), ns=ns)
+    res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=4, want_ints=ints)
+    er = em.map(q1, o1, q2, o2, opts=eopts, ns=ns)
     assert er.status == 0, (what, er.status)
-    kc.check(res, er, what, ints=(er.int_offsets, er.ints) if ints else None)
+    mh.check_emu(res, er, what, ints=ints)
     return res, er
 
 
 def _run_single(idx, oracle_mod, reads, variant, what, ns=2):
-    import emu
-    orc, em = _emu(idx)
-    oo, eo = SOME[variant]
+    ix, orc, em = mh.emu_of(idx)
+    oopts, eopts = mh.opts_for(variant, oracle_mod, emu.default_opts)
     q, o = pack(reads)
     assert (len(o) - 1) % 2 == 1
-    res = orc.map_single(q, o, opts=oracle_mod.default_opts(**oo), nthreads=4)
-    er = em.map(q, o, opts=emu.default_opts(**eo), ns=ns)
+    res = orc.map_single(q, o, opts=oopts, nthreads=4)
+    er = em.map(q, o, opts=eopts, ns=ns)
     assert er.status == 0, (what, er.status)
-    kc.check(res, er, what)
+    mh.check(res, er, what)
     return res, er
 
 
@@ -73,14 +57,14 @@ def _golden(root, oracle_mod, k, image, variant, capfd, monkeypatch):
 
 
 @pytest.mark.parametrize("image", ["dense", "ph"])
-@pytest.mark.parametrize("variant", sorted(VARIANTS))
+@pytest.mark.parametrize("variant", sorted(mh.PLAIN_SETS))
 def test_golden_reads_k21(root, oracle_mod, variant, image, capfd, monkeypatch):
     """synth_small's adversarial pairs at k = 21, every option variant of test_emu_parity, dense and -p"""
     _golden(root, oracle_mod, 21, image, variant, capfd, monkeypatch)
 
 
 @pytest.mark.parametrize("image", ["dense", "ph"])
-@pytest.mark.parametrize("variant", sorted(SOME))
+@pytest.mark.parametrize("variant", sorted(kc.SOME))
 @pytest.mark.parametrize("k", [15, 17, 29])
 def test_golden_reads_other_k(root, oracle_mod, k, variant, image, capfd, monkeypatch):
     _golden(root, oracle_mod, k, image, variant, capfd, monkeypatch)
@@ -94,7 +78,7 @@ def test_golden_reads_k9_nearly_everything_is_left(root, oracle_mod, capfd, monk
     assert 0 < nreads - left["pair"] < nreads // 4, left
 
 
-@pytest.mark.parametrize("variant", sorted(FEW))
+@pytest.mark.parametrize("variant", sorted(kc.FEW))
 @pytest.mark.parametrize("k", kc.KS)
 def test_edge_reads(root, oracle_mod, k, variant):
     """mates of length k - 1 .. k + 2, 2 k - 1 .. 2 k + 1 and around the 64- and 128-character slots, with an N at k, k - 1, L - k - 1, a run
@@ -104,10 +88,10 @@ def test_edge_reads(root, oracle_mod, k, variant):
     q1, o1 = pack(r1); q2, o2 = pack(r2)
     res, er = _run(idx, oracle_mod, q1, o1, q2, o2, variant, "edge reads, k=%d %s" % (k, variant))
     assert res.counters["peHits"] > len(r1) // 4
-    _run_single(idx, oracle_mod, kc.odd_single(r1, r2), variant, "edge reads single-end, k=%d %s" % (k, variant))
+    _run_single(idx, oracle_mod, mh.odd_single(r1, r2), variant, "edge reads single-end, k=%d %s" % (k, variant))
 
 
-@pytest.mark.parametrize("variant", sorted(FEW))
+@pytest.mark.parametrize("variant", sorted(kc.FEW))
 @pytest.mark.parametrize("k", kc.KS)
 def test_run_reads(root, oracle_mod, k, variant, capfd, monkeypatch):
     """homopolymer runs of k - 7 .. k + 9 at every alignment of the four-characters-per-lane packing: the pair / lean kernels' rule
@@ -128,7 +112,7 @@ def test_run_reads(root, oracle_mod, k, variant, capfd, monkeypatch):
         print("k=%d: %d reads, %d hold a window of k equal bases or an N, left: %s" % (k, 2 * len(r1), windows, left))
         assert 0 < windows < left["pair"] < 2 * len(r1) - 50, (windows, left)
         assert windows < left["lean_first_pass"] < 2 * len(r1) - 50, (windows, left)
-    _run_single(rd["idx"], oracle_mod, kc.odd_single(r1, r2), variant, "run reads single-end, k=%d %s" % (k, variant))
+    _run_single(rd["idx"], oracle_mod, mh.odd_single(r1, r2), variant, "run reads single-end, k=%d %s" % (k, variant))
 
 
 @pytest.mark.parametrize("read_len,ns,n", [(150, 3, 500), (250, 4, 300)])
@@ -141,11 +125,11 @@ def test_long_reads_take_the_wide_editions(root, oracle_mod, k, read_len, ns, n)
     res, er = _run(idx, oracle_mod, q1, o1, q2, o2, "default", "%d bp, k=%d" % (read_len, k), ns=ns)
     assert res.counters["totHits"] > n
     _run(idx, oracle_mod, q1, o1, q2, o2, "selAln", "%d bp -s, k=%d" % (read_len, k), ns=ns)
-    orc, em = _emu(idx)
+    ix, orc, em = mh.emu_of(idx)
     rs = orc.map_single(q2[: o2[-2]], o2[:-1], nthreads=4)
     es = em.map(q2[: o2[-2]], o2[:-1], ns=ns)
     assert es.status == 0
-    kc.check(rs, es, "%d bp single-end, k=%d" % (read_len, k))
+    mh.check(rs, es, "%d bp single-end, k=%d" % (read_len, k))
 
 
 @pytest.mark.parametrize("k", kc.KS)
@@ -154,7 +138,7 @@ def test_error_free_pairs_hold_their_true_position(root, oracle_mod, k):
     for the mates' characters; no oracle, no suffix array)"""
     idx = kc.small_index(root, k, "dense")
     q1, o1, q2, o2, truth = kc.truth_pairs(root)
-    orc, em = _emu(idx)
+    ix, orc, em = mh.emu_of(idx)
     er = em.map(q1, o1, q2, o2)
     assert er.status == 0
     kc.truth_check(er.hit_offsets, er.hits, truth, kc.txp_seqs_of(idx))

@@ -6,7 +6,6 @@ under the lane emulation in test_kmer_lengths.py.
 
 The reference is the oracle, which reads k from the index header: the reference's own binary cannot be built here, so there is no
 golden SAM at another k.  test_error_free_pairs_* is the one check that does not go through the oracle."""
-import contextlib
 import os
 import subprocess
 import sys
@@ -15,25 +14,12 @@ import numpy as np
 import pytest
 
 import kmer_cases as kc
+import mapping_harness as mh
+import rapmap_amd as ra
 from conftest import GOLD, ROOT, load_oracle
-from test_emu_parity import VARIANTS
-from test_gpu_parity import _check_headline
 from util import pack
 
 pytestmark = pytest.mark.gpu
-
-FEW = {v: VARIANTS[v] for v in ("default", "noSensitive", "fuzzy")}
-FEW["selAln"] = ({"selAln": 1}, {"sel_aln": 1})
-HEADLINE_KERNELS = ["pair", "lean"]
-QM_STAT_N_PASS_READS = 15           # include/qmap_mi355.h
-
-_oracles = {}
-
-
-def _oracle(idx):
-    if idx not in _oracles:
-        _oracles[idx] = load_oracle(idx)[1]
-    return _oracles[idx]
 
 
 @pytest.fixture(scope="module")
@@ -41,30 +27,8 @@ def root(tmp_path_factory, lib_built, oracle_mod):
     return tmp_path_factory.mktemp("kmer_lengths_gpu")
 
 
-@contextlib.contextmanager
-def _gpu(idx, debug=True, ph_compact=False, pair_kernel=True, wide_reads=False):
-    """as test_gpu_parity._gpu: debug=True keeps the SA-interval records and so runs the GENERAL stage-A kernel; closed on the way out"""
-    import rapmap_amd as ra
-    qi = ra.QuasiIndex(idx)
-    try:
-        mp = ra.QuasiMapper(qi, 0, debug=debug, ph_compact=ph_compact, pair_kernel=pair_kernel, wide_reads=wide_reads)
-        try:
-            yield qi, mp
-        finally:
-            mp.close()
-    finally:
-        qi.close()
-
-
-def _headline(idx, kernel, ph_compact=False):
-    """as test_gpu_parity._headline: paired calls run the pair kernel (qm_duo.inl) or qm_lean_kernel alone"""
-    return _gpu(idx, debug=False, ph_compact=ph_compact, pair_kernel=kernel == "pair")
-
-
-def _opts(oracle_mod, pair):
-    import rapmap_amd as ra
-    oo, go = pair
-    return oracle_mod.default_opts(**oo), ra.default_opts(**go)
+def _opts(oracle_mod, variant):
+    return mh.opts_for(variant, oracle_mod, ra.default_opts)
 
 
 @pytest.mark.parametrize("image", ["dense", "ph"])
@@ -72,22 +36,22 @@ def _opts(oracle_mod, pair):
 def test_general_kernel(root, oracle_mod, k, image):
     """the golden reads through the general stage-A kernel (intervals kept): hits, counters and the interval lists"""
     idx = kc.index_for(root, k, image)
-    orc = _oracle(idx)
+    orc = mh.oracle_of(idx)[1]
     q1, o1, q2, o2 = kc.golden_reads()[4]
-    with _gpu(idx, debug=True) as (qi, mp):
+    with mh.gpu_mapper(idx, debug=True) as (qi, mp):
         assert qi.perfect_hash == (image == "ph")
-        for variant in sorted(FEW):
-            oopts, gopts = _opts(oracle_mod, FEW[variant])
+        for variant in sorted(kc.FEW):
+            oopts, gopts = _opts(oracle_mod, variant)
             ints = variant != "selAln"
             res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=8, want_ints=ints)
             gr = mp.map_pairs(q1, o1, q2, o2, opts=gopts)
             if ints:                                     # (with -s the lean kernel's collector edition writes the interval records itself)
-                assert mp.stat(3) == -1, "expected the general kernel"
-            kc.check(res, gr, "general kernel, k=%d %s %s" % (k, image, variant), ints=mp.intervals(len(o1) - 1) if ints else None)
+                assert mp.stat(ra.QM_STAT_LEAN_READS) == -1, "expected the general kernel"
+            mh.check(res, gr, "general kernel, k=%d %s %s" % (k, image, variant), ints=mp.intervals(len(o1) - 1) if ints else None)
             assert res.counters["peHits"] > 1000
 
 
-@pytest.mark.parametrize("kernel", HEADLINE_KERNELS)
+@pytest.mark.parametrize("kernel", mh.HEADLINE_KERNELS)
 @pytest.mark.parametrize("k", kc.KS)
 def test_headline_kernels(root, oracle_mod, k, kernel):
     """the golden reads through the pair kernel and qm_lean_kernel: what they take is right, they leave what they are not built for, and
@@ -95,29 +59,29 @@ def test_headline_kernels(root, oracle_mod, k, kernel):
     q1, o1, q2, o2 = kc.golden_reads()[4]
     n = len(o1) - 1
     idx = kc.index_for(root, k, "dense")
-    orc = _oracle(idx)
-    with _headline(idx, kernel) as (qi, mp):
+    orc = mh.oracle_of(idx)[1]
+    with mh.headline(idx, kernel) as (qi, mp):
         for variant in ("default", "noStrictCheck", "z0.9"):
-            oopts, gopts = _opts(oracle_mod, VARIANTS[variant])
+            oopts, gopts = _opts(oracle_mod, variant)
             res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=8)
             gr = mp.map_pairs(q1, o1, q2, o2, opts=gopts)
-            kc.check(res, gr, "%s kernel, k=%d %s" % (kernel, k, variant))
-            deferred = _check_headline(mp, kernel, n)
+            mh.check(res, gr, "%s kernel, k=%d %s" % (kernel, k, variant))
+            deferred = mh.check_headline(mp, kernel, n)
             if variant == "default":
                 assert deferred == kc.EXPECT_LEFT[(k, "dense")][kernel], deferred
     # the compact -p image: the host never picks the pair kernel there (plan_stage_a: a lane per position would serialise the two BooPHF
     # walks), so either mapper runs qm_lean_kernel's PH edition
     idx = kc.index_for(root, k, "ph")
-    orc = _oracle(idx)
-    with _headline(idx, kernel, ph_compact=True) as (qi, mp):
+    orc = mh.oracle_of(idx)[1]
+    with mh.headline(idx, kernel, ph_compact=True) as (qi, mp):
         assert qi.perfect_hash
         res = orc.map_pairs(q1, o1, q2, o2, nthreads=8)
         gr = mp.map_pairs(q1, o1, q2, o2)
-        kc.check(res, gr, "%s kernel, compact -p, k=%d" % (kernel, k))
-        assert _check_headline(mp, "lean", n) == kc.EXPECT_LEFT[(k, "ph")]["lean"]
+        mh.check(res, gr, "%s kernel, compact -p, k=%d" % (kernel, k))
+        assert mh.check_headline(mp, "lean", n) == kc.EXPECT_LEFT[(k, "ph")]["lean"]
 
 
-@pytest.mark.parametrize("kernel", HEADLINE_KERNELS + ["general"])
+@pytest.mark.parametrize("kernel", mh.HEADLINE_KERNELS + ["general"])
 @pytest.mark.parametrize("k", kc.KS)
 def test_edge_and_run_reads(root, oracle_mod, k, kernel):
     """kmer_cases.edge_reads and run_reads through both headline kernels, and through the general kernel with --noSensitive: paired, and
@@ -125,58 +89,58 @@ def test_edge_and_run_reads(root, oracle_mod, k, kernel):
     gidx = kc.index_for(root, k, "dense")
     rd = kc.run_reads(root, k)
     for name, idx, (r1, r2) in (("edge", gidx, kc.edge_reads(gidx, k)), ("run", rd["idx"], (rd["reads1"], rd["reads2"]))):
-        orc = _oracle(idx)
+        orc = mh.oracle_of(idx)[1]
         q1, o1 = pack(r1); q2, o2 = pack(r2)
-        qs, os_ = pack(kc.odd_single(r1, r2))
+        qs, os_ = pack(mh.odd_single(r1, r2))
         assert (len(os_) - 1) % 2 == 1
         what = "%s reads, %s kernel, k=%d" % (name, kernel, k)
         if kernel == "general":
-            oopts, gopts = _opts(oracle_mod, VARIANTS["noSensitive"])
-            with _gpu(idx, debug=True) as (qi, mp):
+            oopts, gopts = _opts(oracle_mod, "noSensitive")
+            with mh.gpu_mapper(idx, debug=True) as (qi, mp):
                 res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=4, want_ints=True)
                 gr = mp.map_pairs(q1, o1, q2, o2, opts=gopts)
-                assert mp.stat(3) == -1
-                kc.check(res, gr, what, ints=mp.intervals(len(o1) - 1))
+                assert mp.stat(ra.QM_STAT_LEAN_READS) == -1
+                mh.check(res, gr, what, ints=mp.intervals(len(o1) - 1))
                 rs = orc.map_single(qs, os_, opts=oopts, nthreads=4)
                 gs = mp.map_reads(qs, os_, opts=gopts)
-                kc.check(rs, gs, what + ", single-end")
+                mh.check(rs, gs, what + ", single-end")
         else:
-            with _headline(idx, kernel) as (qi, mp):
+            with mh.headline(idx, kernel) as (qi, mp):
                 res = orc.map_pairs(q1, o1, q2, o2, nthreads=4)
                 gr = mp.map_pairs(q1, o1, q2, o2)
-                kc.check(res, gr, what)
-                _check_headline(mp, kernel, len(r1), some_merged=False)
+                mh.check(res, gr, what)
+                mh.check_headline(mp, kernel, len(r1), some_merged=False)
                 rs = orc.map_single(qs, os_, nthreads=4)
                 gs = mp.map_reads(qs, os_)
-                kc.check(rs, gs, what + ", single-end")
-                assert mp.stat(3) == len(os_) - 1 and 0 < mp.stat(4) < len(os_) - 1
+                mh.check(rs, gs, what + ", single-end")
+                assert mp.stat(ra.QM_STAT_LEAN_READS) == len(os_) - 1 and 0 < mp.stat(ra.QM_STAT_LEAN_DEFERRED) < len(os_) - 1
 
 
-@pytest.mark.parametrize("kernel", HEADLINE_KERNELS)
+@pytest.mark.parametrize("kernel", mh.HEADLINE_KERNELS)
 @pytest.mark.parametrize("k", [15, 21])
 def test_n_aware_pass(root, oracle_mod, k, kernel, monkeypatch):
     """the golden reads and edge_reads' N cases (an N at k, at k - 1, at L - k - 1) with the N-aware edition of qm_lean_kernel going over
     what the first pass left (QM_NPASS_MIN=1: also on a small batch): kmask = (1 << k) - 1 and (nb >> k) & 1 at k below 31"""
     monkeypatch.setenv("QM_NPASS_MIN", "1")
     idx = kc.index_for(root, k, "dense")
-    orc = _oracle(idx)
+    orc = mh.oracle_of(idx)[1]
     g = kc.golden_reads()
     n1, n2 = kc.n_case_reads(idx, k)
     assert len(n1) > 100
     q1, o1 = pack(list(g[1]) + n1); q2, o2 = pack(list(g[3]) + n2)
-    with _headline(idx, kernel) as (qi, mp):
+    with mh.headline(idx, kernel) as (qi, mp):
         for variant in ("default", "selAln"):
-            oopts, gopts = _opts(oracle_mod, FEW[variant])
+            oopts, gopts = _opts(oracle_mod, variant)
             res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=8)
             gr = mp.map_pairs(q1, o1, q2, o2, opts=gopts)
-            kc.check(res, gr, "N-aware pass behind the %s kernel, k=%d %s" % (kernel, k, variant))
-            taken = mp.stat(QM_STAT_N_PASS_READS)
+            mh.check(res, gr, "N-aware pass behind the %s kernel, k=%d %s" % (kernel, k, variant))
+            taken = mp.stat(ra.QM_STAT_N_PASS_READS)
             assert taken > 100, taken
-        qs, os_ = pack(kc.odd_single(n1, n2))
+        qs, os_ = pack(mh.odd_single(n1, n2))
         rs = orc.map_single(qs, os_, nthreads=4)
         gs = mp.map_reads(qs, os_)
-        kc.check(rs, gs, "N-aware pass, single-end, k=%d" % k)
-        assert mp.stat(QM_STAT_N_PASS_READS) > 0
+        mh.check(rs, gs, "N-aware pass, single-end, k=%d" % k)
+        assert mp.stat(ra.QM_STAT_N_PASS_READS) > 0
 
 
 @pytest.mark.parametrize("k", [15, 21, 29])
@@ -184,21 +148,20 @@ def test_table_builders(root, oracle_mod, k, monkeypatch):
     """SaExt / SaExt2 / sanext are built from a 2-bit image of the text at SA[i] + k; QM_TABLE_CHECK=1 holds every entry against the
     byte-per-character builders on the device and fails the build on a difference.  One -s call (sanext), one call with 150-character
     reads (the wide table is there and the wide lean kernel ran)"""
-    import rapmap_amd as ra
     monkeypatch.setenv("QM_TABLE_CHECK", "1")
     idx = kc.small_index(root, k, "dense")
-    orc = _oracle(idx)
-    with _gpu(idx, debug=False, wide_reads=True) as (qi, mp):
+    orc = mh.oracle_of(idx)[1]
+    with mh.gpu_mapper(idx, debug=False, wide_reads=True) as (qi, mp):
         q1, o1, q2, o2 = kc.long_reads(root, 100, 1500, seed=7)
         gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(sel_aln=1))
         res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(selAln=1), nthreads=8)
-        kc.check(res, gr, "-s with checked tables, k=%d" % k)
+        mh.check(res, gr, "-s with checked tables, k=%d" % k)
         assert res.counters["totHits"] > 1000
         w1, wo1, w2, wo2 = kc.long_reads(root, 150, 500, seed=77)
         gw = mp.map_pairs(w1, wo1, w2, wo2)
         rw = orc.map_pairs(w1, wo1, w2, wo2, nthreads=8)
-        kc.check(rw, gw, "150 bp with checked tables, k=%d" % k)
-        assert mp.stat(3) == 2 * 500, "the wide lean kernel did not run: no SaExt2"
+        mh.check(rw, gw, "150 bp with checked tables, k=%d" % k)
+        assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * 500, "the wide lean kernel did not run: no SaExt2"
 
 
 @pytest.mark.parametrize("max_len", [150, 256])
@@ -213,38 +176,38 @@ def test_wide_lean_kernel(root, oracle_mod, k, max_len):
     assert 128 < int(np.diff(o1).max()) <= max_len
     for image, compact in (("dense", False), ("ph", True)):
         idx = kc.small_index(root, k, image)
-        orc = _oracle(idx)
-        with _gpu(idx, debug=False, ph_compact=compact) as (qi, mp):
+        orc = mh.oracle_of(idx)[1]
+        with mh.gpu_mapper(idx, debug=False, ph_compact=compact) as (qi, mp):
             for variant in ("default", "selAln"):
-                oopts, gopts = _opts(oracle_mod, FEW[variant])
+                oopts, gopts = _opts(oracle_mod, variant)
                 what = "wide lean, k=%d, <= %d, %s %s" % (k, max_len, image, variant)
                 res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=8)
                 gr = mp.map_pairs(q1, o1, q2, o2, opts=gopts)
-                kc.check(res, gr, what)
+                mh.check(res, gr, what)
                 if variant == "default":
-                    assert mp.stat(3) == 2 * n, "the lean kernel was not the one launched"
-                    assert 0 < mp.stat(4) < n, "expected most reads taken, some left to the general kernel"
+                    assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * n, "the lean kernel was not the one launched"
+                    assert 0 < mp.stat(ra.QM_STAT_LEAN_DEFERRED) < n, "expected most reads taken, some left to the general kernel"
                 rs = orc.map_single(q2, o2, opts=oopts, nthreads=8)
                 gs = mp.map_reads(q2, o2, opts=gopts)
-                kc.check(rs, gs, what + ", single-end")
+                mh.check(rs, gs, what + ", single-end")
 
 
 def test_packed_upload_k21(root, oracle_mod):
     """qm_map_pairs_packed (reads sent 2-bit packed, unpacked on the device) gives what qm_map_pairs gives, at k = 21"""
     idx = kc.index_for(root, 21, "dense")
-    orc = _oracle(idx)
+    orc = mh.oracle_of(idx)[1]
     q1, o1, q2, o2 = kc.golden_reads()[4]
-    with _gpu(idx, debug=False) as (qi, mp):
+    with mh.gpu_mapper(idx, debug=False) as (qi, mp):
         for variant in ("default", "selAln"):
-            oopts, gopts = _opts(oracle_mod, FEW[variant])
+            oopts, gopts = _opts(oracle_mod, variant)
             res = orc.map_pairs(q1, o1, q2, o2, opts=oopts, nthreads=8)
             plain = mp.map_pairs(q1, o1, q2, o2, opts=gopts)
             hits, offs, ctr = plain.hits.copy(), plain.hit_offsets.copy(), dict(plain.counters)
             gr = mp.map_pairs_packed(q1, o1, q2, o2, opts=gopts)
             assert np.array_equal(offs, gr.hit_offsets) and hits.tobytes() == gr.hits.tobytes() and ctr == gr.counters
-            kc.check(res, gr, "packed pairs, k=21 %s" % variant)
+            mh.check(res, gr, "packed pairs, k=21 %s" % variant)
         rs = orc.map_single(q2, o2, nthreads=8)
-        kc.check(rs, mp.map_reads_packed(q2, o2), "packed single-end, k=21")
+        mh.check(rs, mp.map_reads_packed(q2, o2), "packed single-end, k=21")
 
 
 def test_stage_view_k21(root, oracle_mod):
@@ -254,29 +217,27 @@ def test_stage_view_k21(root, oracle_mod):
     caller's bookkeeping drops (kmer_cases.check_stage_view).  The interval-keeping pass's intervals are the oracle's, and the pass
     without intervals equals it in every other stage output: foundHit, lists, hits, tooMany flags."""
     idx = kc.index_for(root, 21, "dense")
-    orc = _oracle(idx)
+    orc = mh.oracle_of(idx)[1]
     q1, o1, q2, o2 = kc.golden_reads()[4]
     n = len(o1) - 1
     res = orc.map_pairs(q1, o1, q2, o2, nthreads=8, want_ints=True)
-    with _gpu(idx, debug=False) as (qi, mp):
+    with mh.gpu_mapper(idx, debug=False) as (qi, mp):
         fused = mp.map_pairs(q1, o1, q2, o2)
-        kc.check(res, fused, "fused driver path, k=21")
+        mh.check(res, fused, "fused driver path, k=21")
         fused_hits, fused_off, fused_ctr = fused.hits.copy(), fused.hit_offsets.copy(), dict(fused.counters)
         full = mp.map_pairs_stages(q1, o1, q2, o2)
-        kc.check_stage_view(res, full, "stage view with intervals, k=21")
+        mh.check_stage_view(res, full, "stage view with intervals, k=21")
         vf = {key: (np.array(v, copy=True) if hasattr(v, "shape") else v) for key, v in mp.fetch_stages(pinned=False).items()}
-        assert mp.stat(3) == -1
+        assert mp.stat(ra.QM_STAT_LEAN_READS) == -1
         fo, fi = mp.intervals(n)
-        assert np.array_equal(fo, res.ints_offsets)
-        for col, name in kc.INT_COLS:
-            assert np.array_equal(res.ints[:, col], fi[name].astype(np.int32)), name
+        mh.check_intervals(res, fo, fi, "stage view with intervals, k=21")
         full_hits, full_off, full_ctr = full.hits.copy(), full.hit_offsets.copy(), dict(full.counters)
         for packed in (False, True):
             light = mp.map_pairs_stages(q1, o1, q2, o2, no_intervals=True, packed=packed)
-            assert mp.stat(3) == 2 * n and mp.stat(4) == kc.EXPECT_LEFT[(21, "dense")]["pair"], "the lean / pair kernel did not run"
+            assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * n and mp.stat(ra.QM_STAT_LEAN_DEFERRED) == kc.EXPECT_LEFT[(21, "dense")]["pair"], "the lean / pair kernel did not run"
             v = mp.fetch_stages(pinned=packed)
             assert np.array_equal(light.hit_offsets, full_off) and light.hits.tobytes() == full_hits.tobytes() and light.counters == full_ctr
-            dropped = kc.check_stage_view(res, light, "stage view without intervals, packed=%s, k=21" % packed)
+            dropped = mh.check_stage_view(res, light, "stage view without intervals, packed=%s, k=21" % packed)
             if dropped == 0:                             # nothing for the caller's bookkeeping to do: the fused result itself
                 assert np.array_equal(light.hit_offsets, fused_off) and light.hits.tobytes() == fused_hits.tobytes() and light.counters == fused_ctr
             assert int(v["iv_off"][-1]) == 0 and v["iv"].size == 0
@@ -293,9 +254,9 @@ def test_error_free_pairs_hold_their_true_position(root, oracle_mod, k):
     the mates' characters; no oracle, no suffix array)"""
     idx = kc.small_index(root, k, "dense")
     q1, o1, q2, o2, truth = kc.truth_pairs(root)
-    with _gpu(idx, debug=False) as (qi, mp):
+    with mh.gpu_mapper(idx, debug=False) as (qi, mp):
         gr = mp.map_pairs(q1, o1, q2, o2)
-        assert mp.stat(3) == 2 * len(truth)
+        assert mp.stat(ra.QM_STAT_LEAN_READS) == 2 * len(truth)
         kc.truth_check(gr.hit_offsets, gr.hits, truth, kc.txp_seqs_of(idx))
 
 

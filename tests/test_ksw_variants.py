@@ -15,37 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, os.path.join(HERE, "emu"))
 from oracle import oracle  # noqa: E402
 import emu  # noqa: E402
-
-
-def _mutate(rng, q, tlen, sub=0.05, indel=0.02, nfrac=0.01):
-    out = []
-    i = 0
-    while len(out) < tlen:
-        r = rng.random()
-        if r < indel:            # insertion in the target
-            out.append(rng.integers(0, 4))
-        elif r < 2 * indel:      # deletion
-            i += 1
-        else:
-            c = q[i % len(q)]
-            if rng.random() < sub:
-                c = rng.integers(0, 4)
-            if rng.random() < nfrac:
-                c = 4
-            out.append(c); i += 1
-    return np.array(out[:tlen], dtype=np.uint8)
-
-
-def _cases(seed, n):
-    rng = np.random.default_rng(seed)
-    for it in range(n):
-        qlen = int(rng.integers(1, 141))
-        tlen = int(rng.integers(1, 161)) if it % 3 else min(160, qlen + 20)
-        q = rng.integers(0, 4, qlen).astype(np.uint8)
-        if rng.random() < 0.1:
-            q[rng.integers(0, qlen)] = 4
-        t = _mutate(rng, q, tlen) if rng.random() < 0.85 else rng.integers(0, 5, tlen).astype(np.uint8)
-        yield q, t
+from parity_cases import ksw_cases, ksw_mutate  # noqa: E402
 
 
 # (match, mismatch, gap open, gap extend, band): bands <= 15 run on the register edition of the row kernel ("32"), <= 33 on the
@@ -73,7 +43,7 @@ def test_ksw_rows_kernel_four_at_a_time(scheme):
     a, b, q_, e_, w = scheme
     ol = oracle._lib(); el = emu._lib()
     ol.qo_ksw_extz2.restype = C.c_int
-    cases = list(_cases(4321 + w, 400))
+    cases = list(ksw_cases(4321 + w, 400))
     rng = np.random.default_rng(5)
     bad = []
     for i in range(0, len(cases), 4):
@@ -94,7 +64,7 @@ def test_ksw_rows_every_ring_gives_the_same_scores(ring):
     register edition, bands up to 15 only"""
     ol = oracle._lib(); el = emu._lib()
     ol.qo_ksw_extz2.restype = C.c_int
-    cases = list(_cases(99, 200))
+    cases = list(ksw_cases(99, 200))
     for w in ((15, 7) if ring == 32 else (15, 33)):
         for i in range(0, len(cases), 4):
             grp = cases[i:i + 4]
@@ -114,7 +84,7 @@ def test_ksw_rows_longest_alignments(qmax):
         grp = []
         for _ in range(4):
             q = rng.integers(0, 4, int(rng.integers(qmax - 26, qmax + 1))).astype(np.uint8)
-            t = _mutate(rng, q, len(q) + 20, sub=0.03, indel=0.01)
+            t = ksw_mutate(rng, q, len(q) + 20, sub=0.03, indel=0.01)
             grp.append((q, t))
         out = _rows(el, grp, 2, -4, 4, 2, w)
         for k, (qq, tt) in enumerate(grp):
@@ -162,7 +132,7 @@ def test_ksw_rows_same_shape_wavefronts(scheme):
                 q = rng.integers(0, 4, qlen).astype(np.uint8)
                 if rng.random() < 0.2:
                     q[rng.integers(0, qlen)] = 4
-                t = _mutate(rng, q, tlen) if rng.random() < 0.85 else rng.integers(0, 5, tlen).astype(np.uint8)
+                t = ksw_mutate(rng, q, tlen) if rng.random() < 0.85 else rng.integers(0, 5, tlen).astype(np.uint8)
                 grp.append((q, t))
             out = _rows(el, grp, a, b, q_, e_, w)
             for k, (qq, tt) in enumerate(grp):
@@ -190,7 +160,7 @@ def test_ksw_rows_eight_per_wavefront(scheme):
                 q = rng.integers(0, 4, qlen).astype(np.uint8)
                 if rng.random() < 0.2:
                     q[rng.integers(0, qlen)] = 4
-                t = _mutate(rng, q, tlen) if rng.random() < 0.85 else rng.integers(0, 5, tlen).astype(np.uint8)
+                t = ksw_mutate(rng, q, tlen) if rng.random() < 0.85 else rng.integers(0, 5, tlen).astype(np.uint8)
                 grp.append((q, t))
             dummy = np.zeros(1, dtype=np.uint8)
             qp = (C.c_void_p * 8)(*[g[0].ctypes.data for g in grp] + [dummy.ctypes.data] * (8 - n))
