@@ -46,8 +46,6 @@ hipError_t qmk_h2m(const void* dev_index, const void* read_batch, int grid, int 
 // the -s list kernel, several reads per wavefront; reads it leaves for qmk_h2m are queued in todoq (count: scalar slot QM_SC_TODO)
 // ... its wide edition over the queue `ids` (*nids entries) the narrow kernel left; what it hands on goes to todoq (count: QM_SC_TODO2)
 hipError_t qmk_h2m_packw(const void* dev_index, const void* read_batch, const long long* ids, const unsigned long long* nids, long long* todoq, int grid, int num_cu, hipStream_t st);
-// dst[i] = src[i] + add, i < n (a part's hit offsets into the whole batch's: map_device_split)
-hipError_t qmk_rebase_offsets(const long long* src, long long* dst, long long n, long long add, hipStream_t st);
 hipError_t qmk_h2m_pack(const void* dev_index, const void* read_batch, long long* todoq, int grid, int num_cu, hipStream_t st);
 hipError_t qmk_sel_merge(const void* pair_batch, const void* sel_batch, hipStream_t st);
 size_t qmk_sel_scratch_bytes(void);
@@ -69,7 +67,8 @@ hipError_t qmk_pair_write(const void* pair_batch, hipStream_t st);
 hipError_t qmk_unpack_reads(const unsigned char* packed, const long long* off, long long n, long long total_chars, unsigned char* seq,
                             const void* exc, long long n_exc, hipStream_t st);
 size_t qmk_scan_temp_bytes(long long n);
-hipError_t qmk_scan_counts(void* temp, size_t temp_bytes, const unsigned int* cnt, long long* offs, long long n,
+// offs[i] = init + cnt[0] + ... + cnt[i - 1], i < n (init: the hits in front of a part of a split call, map_device_split; otherwise 0)
+hipError_t qmk_scan_counts(void* temp, size_t temp_bytes, const unsigned int* cnt, long long* offs, long long n, long long init,
                            hipStream_t st);
 // the same over (cnt & 0x7fffffff): list lengths carry the foundHit flag in bit 31
 hipError_t qmk_scan_counts_masked(void* temp, size_t temp_bytes, const unsigned int* cnt, long long* offs, long long n, hipStream_t st);

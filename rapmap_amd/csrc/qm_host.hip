@@ -254,12 +254,18 @@ struct SplitPool {
   }
   ~SplitPool() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); for (auto& t : th) t.join(); }
 };
-// where the parts of a split call meet: every part brings its hit count once its units are counted; the last one sizes the
-// caller's result array, then each part writes its hits behind those of the parts before it
+// where the parts of a split call meet.  The parts finish in order: part p scans its counts from the sum of the totals of the parts
+// before it (wait_base), so its offsets are the caller's own, and writes its hits into the caller's array as soon as that array holds
+// base + own total records (place: `early`) -- it waits for no part behind it.  The array is grown or replaced only while no write into
+// it is in flight: a part that finds it too small waits for every total and for the early writers to finish, the first one through sizes
+// the array, and a part that wrote early into the array that was replaced writes again (settle).
 struct SplitJoin {
   qm_ctx* owner; int K; std::mutex mu; std::condition_variable cv;
-  long long total[8] = {0}, base[9] = {0}; int arrived = 0; bool ready = false; int failed = 0;
-  int arrive(int part, long long tot, long long& b, qm_hit*& dst);
+  long long total[8] = {0}, base[9] = {0}; bool have[8] = {false}; int arrived = 0, inflight = 0; bool needGrow = false, sized = false; int failed = 0;
+  int wait_base(int part, long long& b);
+  int place(int part, long long tot, qm_hit*& dst, bool& early);
+  int settle(int part, bool early, bool& again, qm_hit*& dst);
+  int failure() { return failed == QM_E_NOMEM ? fail(QM_E_NOMEM, "hipMalloc of the result array failed") : fail(failed, "another part of the batch failed"); }
   void abort(int rc) { std::lock_guard<std::mutex> lk(mu); if (!failed) failed = rc ? rc : QM_E_STATE; cv.notify_all(); }
   // stage A one part after the other (stagger): part i starts its stage A when part i - 1 has finished its own, so that a part's
   // stage A (scalar unit, waiting) runs beside the alignments of the part before it (VALU) instead of beside another stage A
@@ -773,7 +779,7 @@ struct RunReq {
   int shortLen = 0;               // the longest read that is not beyond QM_MAX_READ_LEN (0: unknown)
   // QM_RUN_FROM_INTERVALS: device arrays
   const qm_sa_interval_hit* ivIn = nullptr; const long long* ivInOff = nullptr; const int* lenIn = nullptr; const unsigned char* foundIn = nullptr;
-  SplitJoin* join = nullptr; int part = 0;   // one part of a split call (map_device_split): the hits go to the caller's array
+  SplitJoin* join = nullptr; int part = 0; int64_t u0 = 0;   // one part of a split call (map_device_split), units u0 .. of the batch: hits and offsets go to the caller's arrays
   bool noDuo = false;             // this part takes qm_lean_kernel even where the pair kernel could (map_device_split: parts of both kinds in flight)
 };
 
@@ -1249,7 +1255,7 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   if (o->sel_aln) {
     // -s: merge + selective alignment + filter per unit into temp slots, then compaction (qm_sel.inl)
     HIPCHK(qmk_sel_slots(&P, c->stream));
-    HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_cnt, c->d_offs, n + 1, c->stream));
+    HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_cnt, c->d_offs, n + 1, 0, c->stream));
     if ((rc = c->d_toff.ensure(n + 1))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_toff, c->d_offs, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, c->stream));
     long long slots = 0;
@@ -1317,9 +1323,16 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   } else {
     HIPCHK(qmk_pair_count(&P, c->stream));
   }
-  HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_cnt, c->d_offs, n + 1, c->stream));
+  // one part of a split call: the scan starts from the hits of the parts before this one and writes straight into the caller's offsets
+  // (entry n, the closing one, is also the first entry of the part behind this one, which writes the same number there)
+  long long base = 0; long long* offsOut = c->d_offs;
+  if (rq.join) {
+    if ((rc = rq.join->wait_base(rq.part, base))) return rc;
+    offsOut = rq.join->owner->d_offs + rq.u0;
+  }
+  HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_cnt, offsOut, n + 1, base, c->stream));
   total = 0;
-  HIPCHK(hipMemcpyAsync(&total, c->d_offs + n, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&total, offsOut + n, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(hscal, c->d_scal, QM_SC_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   u64 h[3 * QM_SEL_CHUNKS_B];
   const bool selStats = o->sel_aln && !rq.mergeOnly;
@@ -1331,13 +1344,25 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
     if (dbg) fprintf(stderr, "[qm -s] %lld units: %lld alignment questions beyond PERFECT chains, %lld ksw2 alignments, %lld strip alignments\n", (long long)n, (long long)c->stats.selQuestions, (long long)c->stats.kswTasks, (long long)c->stats.stripTasks);
   }
   if (rq.join) {
-    long long b = 0; qm_hit* dst = nullptr;
-    if ((rc = rq.join->arrive(rq.part, total, b, dst))) return rc;
-    P.hits = dst + b;
-  } else {
-    if ((rc = c->d_hits.ensure((int64_t)total + 1, total / 8))) return rc;
-    P.hits = c->d_hits;
+    // the offsets are the caller's own (absolute), so the records go to the caller's array itself; written now if it has the room,
+    // and once more if a part behind this one had it replaced (SplitJoin)
+    total -= base;
+    qm_hit* dst = nullptr; bool early = false, again = false;
+    if ((rc = rq.join->place(rq.part, total, dst, early))) return rc;
+    P.offs = offsOut;
+    for (int pass = 0; pass < 2; ++pass) {
+      P.hits = dst;
+      if (o->sel_aln) HIPCHK(qmk_sel_compact(&P, c->d_tmp, c->d_toff, c->stream));
+      else HIPCHK(qmk_pair_write(&P, c->stream));
+      if (pass) break;
+      HIPCHK(hipStreamSynchronize(c->stream));
+      if ((rc = rq.join->settle(rq.part, early, again, dst))) return rc;
+      if (!again) break;
+    }
+    return QM_OK;
   }
+  if ((rc = c->d_hits.ensure((int64_t)total + 1, total / 8))) return rc;
+  P.hits = c->d_hits;
   if (o->sel_aln) HIPCHK(qmk_sel_compact(&P, c->d_tmp, c->d_toff, c->stream));
   else HIPCHK(qmk_pair_write(&P, c->stream));
   return QM_OK;
@@ -1387,7 +1412,7 @@ static int map_device_impl(qm_ctx* c, const qm_opts* o, int64_t n, const void* d
     }
     HIPCHK(hipMemsetAsync(c->d_ivcnt + nreads, 0, sizeof(uint32_t), c->stream));
     HIPCHK(hipMemsetAsync(c->d_lcnt + nreads, 0, sizeof(uint32_t), c->stream));
-    HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_ivcnt, c->d_ivcsr, nreads + 1, c->stream));
+    HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_ivcnt, c->d_ivcsr, nreads + 1, 0, c->stream));
     HIPCHK(qmk_scan_counts_masked(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_lcnt, c->d_lcsr, nreads + 1, c->stream));
     HIPCHK(hipMemcpyAsync(&c->h_tot[0], c->d_ivcsr + nreads, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(&c->h_tot[1], c->d_lcsr + nreads, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
@@ -1405,18 +1430,52 @@ static int map_device_impl(qm_ctx* c, const qm_opts* o, int64_t n, const void* d
   return QM_OK;
 }
 
-int SplitJoin::arrive(int part, long long tot, long long& b, qm_hit*& dst) {
+// the hits of the parts before `part`, once all of them have brought their totals (or a part has failed: no total may come)
+int SplitJoin::wait_base(int part, long long& b) {
   std::unique_lock<std::mutex> lk(mu);
-  total[part] = tot;
-  if (++arrived == K && !failed) {
+  cv.wait(lk, [&] { if (failed) return true; for (int i = 0; i < part; ++i) if (!have[i]) return false; return true; });
+  if (failed) return failure();
+  b = 0;
+  for (int i = 0; i < part; ++i) b += total[i];
+  return QM_OK;
+}
+
+// part `part` has `tot` hits: where may it write them?  early: into the array as it stands, now (counted in `inflight` until settle()).
+// Otherwise -- the array is too small for base + tot records, or another part found it so -- the part waits until every total is known
+// and no early write is in flight; the first part through sizes the array for the whole batch.
+int SplitJoin::place(int part, long long tot, qm_hit*& dst, bool& early) {
+  std::unique_lock<std::mutex> lk(mu);
+  total[part] = tot; have[part] = true; ++arrived;
+  long long b = 0;
+  for (int i = 0; i < part; ++i) b += total[i];
+  cv.notify_all();
+  if (failed) return failure();
+  early = !needGrow && owner->d_hits.p && owner->d_hits.cap >= b + tot + 1;
+  if (early) { ++inflight; dst = owner->d_hits; return QM_OK; }
+  needGrow = true;
+  cv.wait(lk, [&] { return failed || (arrived == K && inflight == 0); });
+  if (failed) return failure();
+  if (!sized) {
     for (int i = 0; i < K; ++i) base[i + 1] = base[i] + total[i];
     const int rc = owner->d_hits.ensure((int64_t)base[K] + 1, base[K] / 8);
-    if (rc) failed = rc; else ready = true;
+    if (rc) { failed = rc; cv.notify_all(); return failure(); }
+    sized = true;
     cv.notify_all();
   }
-  cv.wait(lk, [&] { return ready || failed; });
-  if (failed) return failed == QM_E_NOMEM ? fail(QM_E_NOMEM, "hipMalloc of the result array failed") : fail(failed, "another part of the batch failed");
-  b = base[part]; dst = owner->d_hits;
+  dst = owner->d_hits;
+  return QM_OK;
+}
+
+// part `part` has written its hits and synchronised.  again: it wrote early and the array has been replaced since -- write once more, to dst.
+// (Whether the array is replaced is known once every part has brought its total.)
+int SplitJoin::settle(int part, bool early, bool& again, qm_hit*& dst) {
+  std::unique_lock<std::mutex> lk(mu);
+  if (early) { --inflight; cv.notify_all(); }
+  again = false;
+  if (!early) return failed ? failure() : QM_OK;
+  cv.wait(lk, [&] { return failed || (arrived == K && (!needGrow || sized)); });
+  if (failed) return failure();
+  if (needGrow) { again = true; dst = owner->d_hits; }
   return QM_OK;
 }
 
@@ -1424,7 +1483,8 @@ int SplitJoin::arrive(int part, long long tot, long long& b, qm_hit*& dst) {
 // in flight together: the tail of one part's persistent stage-A grid, its scans, its host round trips and (with -s) its
 // VALU-bound alignment kernels run under the other parts' stage A, which is bound by the scalar unit and by waiting
 // (profiles/r04/sel_overlap.txt).  Units, hits and counters are those of one call: part i maps units [n i / K, n (i + 1) / K),
-// its hits land in the caller's array behind those of the parts before it, its offsets are rebased into the caller's.
+// its hits land in the caller's array behind those of the parts before it and its offsets are the caller's own: a part scans its counts
+// from the hits in front of it and depends on the parts before it alone (SplitJoin) -- the part that finishes first should be part 0.
 static int map_device_split(qm_ctx* c, const qm_opts* o, int K, int64_t n, const void* d_seq1, const void* d_off1, const void* d_seq2,
                             const void* d_off2, int32_t max_read_len, int64_t* n_hits, qm_counters* counters) {
   int rc;
@@ -1441,29 +1501,28 @@ static int map_device_split(qm_ctx* c, const qm_opts* o, int K, int64_t n, const
   int64_t nh[8] = {0}; qm_counters ctr[8]; int rcs[8] = {0}; char errs[8][256];
   memset(ctr, 0, sizeof(ctr));
   const bool paired = d_seq2 != nullptr;
-  static const int firstPct = [] { const char* e = getenv("QM_SPLIT_FIRST"); const int v = e ? atoi(e) : 0; return v > 0 && v < 100 ? v : 0; }();   // (tuning knob: two parts of unequal size)
+  // QM_SPLIT_FIRST: two parts of unequal size -- the share of PART 0 in per cent, which by default is the qm_lean_kernel part (the pair
+  // kernel's share is the rest); unset: halves
+  static const int firstPct = [] { const char* e = getenv("QM_SPLIT_FIRST"); const int v = e ? atoi(e) : 0; return v > 0 && v < 100 ? v : 0; }();
+  auto first_unit = [&](int i) { return (K == 2 && firstPct > 0) ? (i == 0 ? (int64_t)0 : (i == 1 ? n * firstPct / 100 : n)) : n * i / K; };
   // Which parts take the pair kernel (a bit per part; QM_DUO_PARTS): the others take qm_lean_kernel.  The pair kernel is bound by the
   // vector units (919 VALU + 470 scalar-side instructions per pair), qm_lean_kernel by the CU's scalar unit (756 + 1 125): with a part
   // of each kind in flight the two kinds of wavefront share every CU and each loads the unit the other leaves idle -- 492 M pairs/s
   // against 447 (all parts the pair kernel) and 473 (all parts qm_lean_kernel), profiles/r06/exp_mix.txt
-  static const int duoParts = [] { const char* e = getenv("QM_DUO_PARTS"); return e ? atoi(e) : 0x55; }();   // default: every other part
+  // The default is every other part from part 1 on: part 0 takes qm_lean_kernel, which finishes first (17.8 against 19.7 ms on the headline
+  // batch), so its scan, its round trip and its write pass are over before the pair-kernel part behind it needs its total.  Which kernel maps
+  // which pairs does not change the hits.
+  static const int duoParts = [] { const char* e = getenv("QM_DUO_PARTS"); return e ? atoi(e) : 0xAA; }();
   begin_call(c);
   HIPCHK(hipEventRecord(c->evA, c->stream));
   c->pool->run(K, [&](int i) {
     qm_ctx* h = c->helpers[(size_t)i];
-    int64_t u0 = n * i / K, u1 = n * (i + 1) / K;
-    if (K == 2 && firstPct > 0) { const int64_t cut = n * firstPct / 100; u0 = i == 0 ? 0 : cut; u1 = i == 0 ? cut : n; }
-    RunReq rq; rq.join = &J; rq.part = i;
+    const int64_t u0 = first_unit(i), u1 = first_unit(i + 1);
+    RunReq rq; rq.join = &J; rq.part = i; rq.u0 = u0;
     rq.noDuo = ((duoParts >> i) & 1) == 0;
     errs[i][0] = 0;
     int r = map_device_impl(h, o, u1 - u0, d_seq1, (const long long*)d_off1 + u0, d_seq2, d_seq2 ? (const long long*)d_off2 + u0 : nullptr,
                             max_read_len, &nh[i], &ctr[i], nullptr, rq);
-    if (r == QM_OK) {
-      // this part's offsets into the caller's array (the last part also writes the closing one)
-      hipError_t e = qmk_rebase_offsets(h->d_offs, c->d_offs + u0, (u1 - u0) + (i == K - 1 ? 1 : 0), J.base[i], h->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-      if (e != hipSuccess) r = fail(QM_E_NOGPU, "rebasing a part's offsets: %s", hipGetErrorString(e));
-    }
     if (r != QM_OK) { snprintf(errs[i], sizeof(errs[i]), "%s", g_err); J.abort(r); }
     rcs[i] = r;
   });
@@ -1480,14 +1539,15 @@ static int map_device_split(qm_ctx* c, const qm_opts* o, int K, int64_t n, const
   c->last.mapMs = last > first ? last - first : 0;
   float ms = 0; hipEventElapsedTime(&ms, c->evA, c->evB); c->last.totalMs = ms;
   qm_counters sum; memset(&sum, 0, sizeof(sum));
+  long long hits = 0;
   for (int i = 0; i < K; ++i) {
     sum += ctr[i];
-    int64_t u0 = n * i / K;
-    if (K == 2 && firstPct > 0) u0 = i == 0 ? 0 : n * firstPct / 100;
+    const int64_t u0 = first_unit(i);
     c->stats.add_part(c->helpers[(size_t)i]->stats, paired ? 2 * u0 : u0);
+    hits += J.total[i];
   }
-  c->last.units = n; c->last.hits = J.base[K]; c->last.paired = paired;
-  if (n_hits) *n_hits = J.base[K];
+  c->last.units = n; c->last.hits = hits; c->last.paired = paired;
+  if (n_hits) *n_hits = hits;
   if (counters) *counters = sum;
   return QM_OK;
 }

@@ -743,15 +743,6 @@ hipError_t qmk_h2m(const void* ixp, const void* bp, int grid, int num_cu, hipStr
   else hipLaunchKernelGGL(qm_h2m_kernel<0>, dim3(g), dim3(256), 0, st, ix, B);
   return hipGetLastError();
 }
-__global__ __launch_bounds__(256) void qm_rebase_offsets_kernel(const long long* src, long long* dst, long long n, long long add) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dst[i] = src[i] + add;
-}
-hipError_t qmk_rebase_offsets(const long long* src, long long* dst, long long n, long long add, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(qm_rebase_offsets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, n, add);
-  return hipGetLastError();
-}
 hipError_t qmk_h2m_pack(const void* ixp, const void* bp, long long* todoq, int grid, int num_cu, hipStream_t st) {
   const DevIndex& ix = *(const DevIndex*)ixp;
   const ReadBatch& B = *(const ReadBatch*)bp;
@@ -886,9 +877,9 @@ size_t qmk_scan_temp_bytes(long long n) {
   return bytes;
 }
 
-hipError_t qmk_scan_counts(void* temp, size_t temp_bytes, const u32* cnt, long long* offs, long long n, hipStream_t st) {
+hipError_t qmk_scan_counts(void* temp, size_t temp_bytes, const u32* cnt, long long* offs, long long n, long long init, hipStream_t st) {
   auto it = rocprim::make_transform_iterator(cnt, U32ToI64());
-  return rocprim::exclusive_scan(temp, temp_bytes, it, offs, 0LL, (size_t)n, rocprim::plus<long long>(), st);
+  return rocprim::exclusive_scan(temp, temp_bytes, it, offs, init, (size_t)n, rocprim::plus<long long>(), st);
 }
 
 hipError_t qmk_scan_counts_masked(void* temp, size_t temp_bytes, const u32* cnt, long long* offs, long long n, hipStream_t st) {

@@ -227,9 +227,9 @@ QM_DEV void lean_probe(const DevIndex& ix, const QM_LDS(u64)* pk2, const QM_LDS(
 // is represented by the entry with the smallest position, the earlier interval in processing order on ties (the first smallest
 // interval first: :636-641, :309-313; one interval: the stable sort + std::unique of :757-803).  Survivors go out in ascending
 // transcript order: slot = number of surviving entries with a smaller transcript id.
-QM_DEV int lean_h2m(const QM_LDS(LeanSuf)* suf, const LeanStrand& S, bool isRC, LV<u64>& elem, LV<bool>& keep, LV<int>& slot) {
+// This edition: one scalar-indexed trip per suffix (four lane reads each), and a second loop over the survivors when a transcript was dropped.
+QM_DEV int lean_h2m_loop(const QM_LDS(LeanSuf)* suf, const LeanStrand& S, bool isRC, LV<u64>& elem, LV<bool>& keep, LV<int>& slot) {
   const int n = S.sufN, m = S.n;
-  QM_CNT(12, 1); QM_CNT(13, n);
   LV<u32> tid, pos, ordl, ivb, seen, less;
   QM_LANES(l) {
     const QM_LDS(LeanSuf)* e = suf + (l < n ? l : 0);
@@ -263,6 +263,81 @@ QM_DEV int lean_h2m(const QM_LDS(LeanSuf)* suf, const LeanStrand& S, bool isRC, 
     }
   }
   return cnt;
+}
+
+// The same pass as 8 x 8 tiles over the wavefront, for n <= 32 (ONE: n <= 8, a single tile in straight-line code).  The stash is rewritten
+// as {transcript, interval bit, order * 64 + index, position} (unused slots: a transcript id no suffix has, no bit); in the round of row block
+// ib and column block jb lane l compares suffix 8 ib + (l >> 3) with suffix 8 jb + (l & 7), both read from the stash.  "A better entry of my
+// transcript exists" and "an entry with a smaller transcript id exists" are two ballots -- lane i of the row block takes byte i & 7 of each --,
+// "the intervals that saw my transcript" is an OR over the eight lanes of a tile row (row8_or) that lane i fetches from lane 8 (i & 7), and the
+// slot is the number of survivors among the entries with a smaller id: popc(lt & keep mask), the pair kernel's way (qm_duo.inl) -- no second loop.
+template <bool ONE>
+QM_DEV int lean_h2m_tiles(QM_LDS(LeanSuf)* suf, const LeanStrand& S, bool isRC, LV<u64>& elem, LV<bool>& keep, LV<int>& slot) {
+  const int n = S.sufN, m = S.n;
+  LV<u32> wt, wb, wk, wp;
+  QM_LANES(l) {
+    const QM_LDS(LeanSuf)* e = suf + l;                  // (slots n .. hold whatever they held: their lanes keep nothing, and what they write matches no suffix)
+    const u32 t = e->tid, ps = e->pos, qp = e->qp, iv = e->iv;
+    const u32 ord = iv == (u32)S.minIdx ? 0u : (iv < (u32)S.minIdx ? iv + 1u : iv);
+    wt[l] = l < n ? t : 0xffffffffu; wb[l] = l < n ? (1u << (iv & 31u)) : 0u; wk[l] = ord * 64u + (u32)l; wp[l] = ps;
+    elem[l] = mk_elem(t, isRC, (int)(ps - qp));          // pos - queryPos (:315, :761-767)
+  }
+  wave_fence();
+  QM_LANES(l) { QM_LDS(LeanSuf)* d = suf + l; d->tid = wt[l]; d->pos = wb[l]; d->qp = wk[l]; d->iv = wp[l]; }
+  wave_fence();
+  LV<u32> ltm, seen; LV<bool> worse; LV<int> sh8;
+  QM_LANES(l) { ltm[l] = 0; seen[l] = 0; worse[l] = false; sh8[l] = 8 * (l & 7); }   // sh8: where a lane's tile row sits in a ballot, and the lane that holds the row's OR
+  const int nb = ONE ? 1 : (n + 7) >> 3;
+  for (int ib = 0; ib < nb; ++ib) {
+    LV<u32> ti, acc, ltr; LV<u64> ki;
+    QM_LANES(l) {
+      const QM_LDS(LeanSuf)* e = suf + 8 * ib + (l >> 3);
+      ti[l] = e->tid; ki[l] = ((u64)e->iv << 32) | (u64)e->qp; acc[l] = 0; ltr[l] = 0;
+    }
+    u64 wrow = 0;
+    for (int jb = 0; jb < nb; ++jb) {
+      LV<bool> eq, bt, lt;
+      QM_LANES(l) {
+        const QM_LDS(LeanSuf)* e = suf + 8 * jb + (l & 7);
+        const u32 tj = e->tid, bj = e->pos; const u64 kj = ((u64)e->iv << 32) | (u64)e->qp;
+        eq[l] = tj == ti[l];
+        bt[l] = kj < ki[l];
+        lt[l] = tj < ti[l];
+        acc[l] |= eq[l] ? bj : 0u;
+      }
+      wrow |= ballot(eq) & ballot(bt);                     // (two compares' masks and a scalar AND: the ballot of an AND goes through a register)
+      const u64 lm = ballot(lt);
+      QM_LANES(l) { ltr[l] |= ((u32)(lm >> sh8[l]) & 0xffu) << (8 * jb); }
+    }
+    row8_or(acc);
+    LV<u32> got;
+    wave_read(acc, sh8, got);
+    QM_LANES(l) {
+      if (ONE || (l >> 3) == ib) {                         // (ONE: lanes 8 .. hold nothing, and keep nothing below)
+        seen[l] = got[l]; ltm[l] = ltr[l]; worse[l] = ((u32)(wrow >> sh8[l]) & 0xffu) != 0;
+      }
+    }
+  }
+  const u32 all = m >= 32 ? 0xffffffffu : ((1u << m) - 1u);
+  QM_LANES(l) { keep[l] = l < n && !worse[l] && seen[l] == all; }
+  const u64 km = ballot(keep);
+  QM_LANES(l) { slot[l] = popc32(ltm[l] & (u32)km); }
+  return popc64(km);
+}
+
+// n in [QM_H2M_TILE_LO, QM_H2M_TILE_HI] takes the tiles, everything else the loop.  Compiled for gfx950 (qm_lean_kernel<true, false, false>), vector +
+// scalar-side instructions: the loop is 20 + 16 and 18 + 9 per suffix; one tile (n <= 8) 41 + 15 in all; several tiles 22 + 14, 23 + 6 per row block of
+// eight and 11 + 6 per round.  The tiles are cheaper from n = 2 on; at 1 and 2 the difference is small and the loop makes one trip through
+// LDS where the tile makes four in a row, and builds with the bound at 1, 2 and 3 were not to be told apart on the headline: the loop keeps those.
+// Beyond 32 suffixes a lane's mask of smaller transcript ids does not fit a register.
+#define QM_H2M_TILE_LO 3
+#define QM_H2M_TILE_HI 32
+QM_DEV int lean_h2m(QM_LDS(LeanSuf)* suf, const LeanStrand& S, bool isRC, LV<u64>& elem, LV<bool>& keep, LV<int>& slot) {
+  const int n = S.sufN;
+  QM_CNT(12, 1); QM_CNT(13, n);
+  if (n >= QM_H2M_TILE_LO && n <= 8) return lean_h2m_tiles<true>(suf, S, isRC, elem, keep, slot);
+  if (n >= QM_H2M_TILE_LO && n <= QM_H2M_TILE_HI) return lean_h2m_tiles<false>(suf, S, isRC, elem, keep, slot);
+  return lean_h2m_loop(suf, S, isRC, elem, keep, slot);
 }
 
 struct PairCtr { u32 pe, se, tot, reads, tooMany, mapped; };   // HitCounters of a pair merged in its wavefront / of all such pairs of a wave (wave-uniform)

@@ -174,6 +174,10 @@ QM_DEV void half_ballot(const LV<bool>& b, LV<u32>& out) { const u64 m = ballot(
 // out[l] = x[lane idx[l] of l's half]
 QM_DEV void half_read(const LV<u32>& x, const LV<int>& idx, LV<u32>& out) { LV<u32> t; for (int l = 0; l < 64; ++l) t.v[l] = x.v[(l & 32) + (idx.v[l] & 31)]; out = t; }
 QM_DEV void wave_read(const LV<u32>& x, const LV<int>& idx, LV<u32>& out) { LV<u32> t; for (int l = 0; l < 64; ++l) t.v[l] = x.v[idx.v[l] & 63]; out = t; }
+// every lane gets the OR over its aligned group of 8 lanes (lean_h2m: a row of an 8 x 8 tile)
+QM_DEV void row8_or(LV<u32>& x) {
+  for (int b = 0; b < 64; b += 8) { u32 m = 0; for (int l = b; l < b + 8; ++l) m |= x.v[l]; for (int l = b; l < b + 8; ++l) x.v[l] = m; }
+}
 // every lane gets the maximum over its half
 QM_DEV void half_max(LV<int>& x) {
   for (int b = 0; b < 64; b += 32) { int m = x.v[b]; for (int l = b + 1; l < b + 32; ++l) m = x.v[l] > m ? x.v[l] : m; for (int l = b; l < b + 32; ++l) x.v[l] = m; }
@@ -362,6 +366,14 @@ QM_DEV void wave_read(const LV<u32>& x, const LV<int>& idx, LV<u32>& out) {
 }
 QM_DEV void half_read(const LV<u32>& x, const LV<int>& idx, LV<u32>& out) {
   out.v[0] = (u32)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 32) + (u32)(idx.v[0] & 31)) << 2), (int)x.v[0]);
+}
+// the butterfly of group_min over 8 lanes with OR: lanes ^1, lanes ^2, the mirror image within 8; all 64 lanes must be active
+QM_DEV void row8_or(LV<u32>& x) {
+  int v = (int)x.v[0];                                       // (every lane has a source: no old value to keep, the move folds into the v_or)
+  v |= __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);    // quad_perm:[1,0,3,2]
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);    // quad_perm:[2,3,0,1]
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);   // row_half_mirror
+  x.v[0] = (u32)v;
 }
 QM_DEV void half_max(LV<int>& x) {
   int v = x.v[0], t;
