@@ -648,4 +648,13 @@ QM_DEV void duo_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, Duo
   }
 }
 
+// The runtime flags of a launch -> the instantiation, f(PH, COV), as lean_dispatch does it for the lean kernel
+// (cov: --quasiCoverage, the walks also add up their coverage)
+template <class Fn>
+inline auto duo_dispatch(bool ph, bool cov, Fn&& f) {
+  typedef std::true_type Y; typedef std::false_type N;
+  if (cov) return ph ? f(Y(), Y()) : f(N(), Y());
+  return ph ? f(Y(), N()) : f(N(), N());
+}
+
 }  // namespace qm

@@ -683,7 +683,7 @@ static int build_replica(const qm_index* ix, int device, bool phCompact, hipStre
     {
       DevIndex dix; memset(&dix, 0, sizeof(dix));
       dix.text = R.text; dix.n = ix->n; dix.SA = R.SA; dix.nSA = ix->nSA; dix.k = ix->k;
-      HIPCHK(qmk_build_phrecs(dD, dL, ix->phNelem, &dix, dRec, stream));
+      HIPCHK(qmk_build_phrecs(dD, dL, ix->phNelem, dix, dRec, stream));
       HIPCHK(hipStreamSynchronize(stream));
       dD.release(); dL.release();
     }
@@ -729,7 +729,7 @@ static int build_replica(const qm_index* ix, int device, bool phCompact, hipStre
       if ((rc = R.slots.ensure((int64_t)(R.cap * sizeof(Bucket)))) || (rc = dBad.ensure(1))) return rc;
       DevIndex dix; memset(&dix, 0, sizeof(dix));
       dix.text = R.text; dix.n = ix->n; dix.SA = R.SA; dix.nSA = ix->nSA; dix.k = ix->k; dix.ph = R.ph; dix.phv = P;
-      HIPCHK(qmk_build_slots_from_ph(&dix, (long long)ix->phNelem, R.slots, R.cap, dBad, stream));
+      HIPCHK(qmk_build_slots_from_ph(dix, (long long)ix->phNelem, R.slots, R.cap, dBad, stream));
       HIPCHK(hipMemcpyAsync(&hBad, dBad, sizeof(hBad), hipMemcpyDeviceToHost, stream));
       HIPCHK(hipStreamSynchronize(stream));
       if (hBad) return fail(QM_E_IO, "hash_info.bph / hash_info.val: %llu k-mers are not found by the perfect hash they were stored with", hBad);
@@ -812,13 +812,13 @@ static bool ensure_saext2(qm_ctx* c) {
     // room for the table AND a margin for the work buffers of the replica's contexts (lists, hits, scratch: they grow with the batches);
     // a replica that cannot spare it stays with the general kernels for such reads
     size_t freeB = 0, totalB = 0;
-    const size_t need = (size_t)c->ix->nSA * qmk_saext2_bytes(), margin = (size_t)8 << 30;
+    const size_t need = (size_t)c->ix->nSA * sizeof(SaExt2), margin = (size_t)8 << 30;
     if (hipMemGetInfo(&freeB, &totalB) != hipSuccess || freeB < need + margin) { (void)hipGetLastError(); return false; }
     if (R.saext2.ensure((int64_t)need)) { (void)hipGetLastError(); return false; }
     hipError_t e = qmk_build_saext2(R.text, c->ix->n, R.SA, c->ix->nSA, c->ix->k, R.sainfo, R.saext2, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { R.saext2.release(); (void)hipGetLastError(); return false; }
-    R.devBytes += c->ix->nSA * (int64_t)qmk_saext2_bytes();
+    R.devBytes += c->ix->nSA * (int64_t)sizeof(SaExt2);
   }
   c->d_saext2 = R.saext2; c->devBytes = R.devBytes;
   return c->d_saext2 != nullptr;
@@ -875,7 +875,7 @@ static bool lean_first(const StagePlan& p) { return p.first == SK_LEAN || p.firs
 static int plan_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, bool paired, int64_t n, int ns, StagePlan& p) {
   p.paired = paired; p.n = n; p.nreads = paired ? 2 * n : n; p.ns = ns;
   p.phc = c->rep->ph ? 1 : 0;                                // (the compact -p image: its kernels take a larger grid)
-  p.grid = qmk_map_grid_ex(p.nreads, c->numCU, p.phc); p.gslots = nullptr; p.ngslots = 0;
+  p.grid = map_grid(p.nreads, c->numCU, p.phc); p.gslots = nullptr; p.ngslots = 0;
   // The lean kernel (qm_lean.inl: two reads per wavefront and iteration, reads of up to 128 clean characters) takes the fused default
   // call on a dense table; the reads it marks instead of mapping go through the general kernel in a second, small launch (pass_lean_leftovers).
   // It owns no per-wave scratch in device memory: that is only reserved -- for the small grid -- when the second launch happens.
@@ -919,7 +919,7 @@ static int reserve_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, StageP
   if (!lean_first(p)) {
     // the general kernels' scratch (gscr_for); when even that does not fit next to the index, the launch falls back to the resident grid
     rc = gscr_for(c, p.grid, p.gslots, p.ngslots);
-    if (rc == QM_E_NOMEM) { p.grid = qmk_resident_grid(p.nreads, c->numCU); rc = gscr_for(c, p.grid, p.gslots, p.ngslots); }
+    if (rc == QM_E_NOMEM) { p.grid = resident_grid(p.nreads, c->numCU); rc = gscr_for(c, p.grid, p.gslots, p.ngslots); }
     if (rc) return rc;
   }
   // lists and interval records come from chunked bump allocators: up to one open chunk per wave
@@ -931,7 +931,7 @@ static int reserve_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, StageP
   }
   if (p.wantFound && (rc = c->d_found.ensure(p.nreads + 1))) return rc;
   // -s: per-wave scratch for chaining (qm_sel.inl; the list kernels' grids stay within residency)
-  if (o->sel_aln && (rc = c->d_selscr.ensure((int64_t)qmk_resident_grid(p.nreads, c->numCU) * 4 * (int64_t)qmk_sel_scratch_bytes()))) return rc;
+  if (o->sel_aln && (rc = c->d_selscr.ensure((int64_t)resident_grid(p.nreads, c->numCU) * 4 * (int64_t)sizeof(SelScratch)))) return rc;
   return QM_OK;
 }
 
@@ -978,12 +978,11 @@ static int launch_first(qm_ctx* c, const StagePlan& p, const RunReq& rq, const D
     if (C.found_out) C.found_out = B.found_out + r0;
     if (C.pair_cnt) C.pair_cnt = B.pair_cnt + u0;
     C.read_base = r0;                                 // (what the launch calls read 0: for the skip list)
-    const int g = feeder ? qmk_map_grid_ex(r1 - r0, c->numCU, p.phc) : p.grid;
-    if (p.first == SK_DUO) HIPCHK(qmk_launch_duo(&ix, &C, c->numCU, c->stream));
-    else if (p.first == SK_LEAN || p.first == SK_LEAN_SEL) HIPCHK(qmk_launch_lean(&ix, &C, c->numCU, c->stream));
-    else if (p.first == SK_H2M) HIPCHK(qmk_h2m(&ix, &C, g, c->numCU, c->stream));
-    else if (p.twoPass) HIPCHK(qmk_map_reads_ex(&ix, &C, p.ns, 1, g, c->numCU, c->stream));
-    else HIPCHK(qmk_map_reads(&ix, &C, rq.mode == QM_RUN_COLLECT ? -1 : p.ns, g, c->numCU, c->stream));
+    const int g = feeder ? map_grid(r1 - r0, c->numCU, p.phc) : p.grid;
+    if (p.first == SK_DUO) HIPCHK(qmk_launch_duo(ix, C, c->numCU, c->stream));
+    else if (p.first == SK_LEAN || p.first == SK_LEAN_SEL) HIPCHK(qmk_launch_lean(ix, C, c->numCU, c->stream));
+    else if (p.first == SK_H2M) HIPCHK(qmk_h2m(ix, C, g, c->numCU, c->stream));
+    else HIPCHK(qmk_map_reads(ix, C, p.ns, p.twoPass ? RL_CHAIN_COLLECT : rq.mode == QM_RUN_COLLECT ? RL_ENTRY_COLLECT : RL_FUSED, g, c->numCU, c->stream));
   }
   return QM_OK;
 }
@@ -1033,7 +1032,7 @@ static int pass_n_aware(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const
   HIPCHK(hipMemsetAsync(c->d_scal + QM_SC_DEFER0, 0, 4 * sizeof(u64), c->stream));
 #endif
   HIPCHK(hipEventRecord(c->evP0, c->stream));
-  HIPCHK(qmk_launch_lean_nq(&ix, &Q, c->numCU, c->stream));
+  HIPCHK(qmk_launch_lean_nq(ix, Q, c->numCU, c->stream));
   HIPCHK(hipEventRecord(c->evP1, c->stream));
   if ((rc = read_scalars(c, hscal, &extraMs))) return rc;
   c->stats.nPass = nq - (int64_t)hscal[QM_SC_LEANQ];
@@ -1056,34 +1055,34 @@ static int pass_lean_leftovers(qm_ctx* c, const StagePlan& p, const DevIndex& ix
   if (p.first == SK_LEAN_SEL) {
     // -s: the general chain-scoring collector, before the list kernels go over all reads and inside the call's ev0 .. ev1; its scalars come
     // down with theirs.  It borrows the scratch reserved for the first launch (p.grid blocks), so it stays within that grid.
-    const int g2 = qmk_map_grid_ex(nq, c->numCU, p.phc);
-    HIPCHK(qmk_map_reads_ex(&ix, &Q, p.ns, 1, g2 < p.grid ? g2 : p.grid, c->numCU, c->stream));
+    const int g2 = map_grid(nq, c->numCU, p.phc);
+    HIPCHK(qmk_map_reads(ix, Q, p.ns, RL_CHAIN_COLLECT, g2 < p.grid ? g2 : p.grid, c->numCU, c->stream));
     return QM_OK;
   }
   // the default call: the general kernels' scratch does not exist yet (B was filled in without it) and is reserved for this launch's own
   // grid -- the dense table's, on the compact -p image too.  The launch comes after ev1: timed by itself.
-  const int g2 = qmk_map_grid_ex(nq, c->numCU, 0);
+  const int g2 = map_grid(nq, c->numCU, false);
   if ((rc = gscr_for(c, g2, Q.gslots, Q.ngslots))) return rc;
   Q.gscratch = c->d_gscr;
   HIPCHK(hipEventRecord(c->evP0, c->stream));
-  HIPCHK(qmk_map_reads(&ix, &Q, p.ns, g2, c->numCU, c->stream));
+  HIPCHK(qmk_map_reads(ix, Q, p.ns, RL_FUSED, g2, c->numCU, c->stream));
   HIPCHK(hipEventRecord(c->evP1, c->stream));
   return read_scalars(c, hscal, &extraMs);
 }
 
 // Reads longer than the slot class of the first launch (always: longer than QM_MAX_READ_LEN) were set aside (map_read): gathered and
-// mapped by the 32-slot kernels (ns32: 32; -32: their collector alone) -- a second, small launch; everything it writes (lists, intervals,
+// mapped by the 32-slot kernels (what: RL_LONG, or RL_LONG_COLLECT for their collector alone) -- a second, small launch; everything it writes (lists, intervals,
 // foundHit) goes where the first pass would have put it.
-static int pass_long_reads(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const ReadBatch& B, u64* hscal, int ns32) {
+static int pass_long_reads(qm_ctx* c, const StagePlan& p, const DevIndex& ix, const ReadBatch& B, u64* hscal, ReadLaunch what) {
   const int64_t nl = (int64_t)hscal[QM_SC_SLOWCNT];
   if (nl <= 0 || !stage_ok(hscal)) return QM_OK;
   int rc; ReadBatch Q;
   if ((rc = gather_queue(c, QM_LCNT_SLOW, nl, B, Q))) return rc;
   c->stats.slowReads = nl;
   // the launch uses the scratch of the first one, so it stays within its grid; after a lean kernel, which has none, the scratch is reserved here
-  const int g2 = qmk_map_grid_ex(nl, c->numCU, p.phc), g = g2 < p.grid ? g2 : p.grid;
+  const int g2 = map_grid(nl, c->numCU, p.phc), g = g2 < p.grid ? g2 : p.grid;
   if (lean_first(p)) { if ((rc = gscr_for(c, g, Q.gslots, Q.ngslots))) return rc; Q.gscratch = c->d_gscr; }
-  HIPCHK(qmk_map_reads(&ix, &Q, ns32, g, c->numCU, c->stream));
+  HIPCHK(qmk_map_reads(ix, Q, p.ns, what, g, c->numCU, c->stream));
   if (!p.twoPass) return read_scalars(c, hscal);
   // fused -s: the list kernels run next; their own slow queue (reads whose intervals overflow their scratch: pass_sel_slow) starts from zero
   static_assert(QM_SC_SLOWMAX == QM_SC_SLOWCNT + 1, "the queue's count and its largest entry: one memset");
@@ -1095,7 +1094,7 @@ static int pass_long_reads(qm_ctx* c, const StagePlan& p, const DevIndex& ix, co
 static int run_list_kernels(qm_ctx* c, const StagePlan& p, const RunReq& rq, const DevIndex& ix, const ReadBatch& H) {
   if (!p.twoPass || p.nreads <= 0) return QM_OK;
   const char* pe = getenv("QM_SEL_PACK");              // 0: the one-read-per-wavefront list kernel for every read (A/B timing, tests)
-  if (pe && atoi(pe) == 0) { HIPCHK(qmk_h2m(&ix, &H, p.grid, c->numCU, c->stream)); return QM_OK; }
+  if (pe && atoi(pe) == 0) { HIPCHK(qmk_h2m(ix, H, p.grid, c->numCU, c->stream)); return QM_OK; }
   int rc;
   // several reads per wavefront first (qm_selpack.inl); what that kernel cannot take -- hits on both strands, more than 64
   // intervals or suffixes -- it queues, and the one-read-per-wavefront kernel runs over the queue (its length stays on the device)
@@ -1104,13 +1103,13 @@ static int run_list_kernels(qm_ctx* c, const StagePlan& p, const RunReq& rq, con
   // A batch of reads beyond 192 characters goes to the wide edition directly: hardly any of them fits the narrow one's 64 lanes
   if ((rc = c->d_todoq2.ensure(p.nreads))) return rc;
   static const int wideFrom = [] { const char* e = getenv("QM_SEL_WIDE_FROM"); return e ? atoi(e) : 192; }();   // (tuning knob)
-  if (rq.shortLen > wideFrom) HIPCHK(qmk_h2m_packw(&ix, &H, nullptr, nullptr, c->d_todoq2, p.grid, c->numCU, c->stream));
+  if (rq.shortLen > wideFrom) HIPCHK(qmk_h2m_packw(ix, H, nullptr, nullptr, c->d_todoq2, p.grid, c->numCU, c->stream));
   else {
-    HIPCHK(qmk_h2m_pack(&ix, &H, c->d_todoq, p.grid, c->numCU, c->stream));
-    HIPCHK(qmk_h2m_packw(&ix, &H, c->d_todoq, (const unsigned long long*)(c->d_scal + QM_SC_TODO), c->d_todoq2, p.grid, c->numCU, c->stream));
+    HIPCHK(qmk_h2m_pack(ix, H, c->d_todoq, p.grid, c->numCU, c->stream));
+    HIPCHK(qmk_h2m_packw(ix, H, c->d_todoq, (const unsigned long long*)(c->d_scal + QM_SC_TODO), c->d_todoq2, p.grid, c->numCU, c->stream));
   }
   ReadBatch T = H; T.slowq = c->d_todoq2; T.nreads_dev = c->d_scal + QM_SC_TODO2;
-  HIPCHK(qmk_h2m(&ix, &T, p.grid, c->numCU, c->stream));
+  HIPCHK(qmk_h2m(ix, T, p.grid, c->numCU, c->stream));
   return QM_OK;
 }
 
@@ -1123,18 +1122,17 @@ static int pass_sel_slow(qm_ctx* c, const qm_opts* o, const RunReq& rq, const De
   int rc; ReadBatch Q;
   const int64_t need = (((int64_t)hscal[QM_SC_SLOWMAX] + 63) / 64) * 64 + 64;
   if ((rc = gather_queue(c, QM_LCNT_SLOW, ns_, H, Q))) return rc;
-  const unsigned long long per = (qmk_sel_dyn_bytes(need) + 255) & ~255ULL;
+  const unsigned long long per = (SelScratchDyn::bytes_for(need) + 255) & ~255ULL;
   int64_t waves = ns_ < 256 ? ns_ : 256;
   while (waves > 4 && (unsigned long long)waves * per > (8ULL << 30)) waves /= 2;      // at most 8 GB of scratch
   const int sgrid = (int)((waves + 3) / 4);
   if ((rc = c->d_dynmem.ensure((int64_t)((unsigned long long)sgrid * 4 * per)))) return rc;
-  const size_t sb = qmk_sel_dyn_struct_bytes();
-  std::vector<unsigned char> hd((size_t)sgrid * 4 * sb);
-  for (int w = 0; w < sgrid * 4; ++w) qmk_sel_dyn_bind(hd.data() + (size_t)w * sb, c->d_dynmem + (unsigned long long)w * per, need);
-  if ((rc = c->d_dyn.ensure((int64_t)hd.size()))) return rc;
-  HIPCHK(hipMemcpyAsync(c->d_dyn, hd.data(), hd.size(), hipMemcpyHostToDevice, c->stream));
+  std::vector<SelScratchDyn> hd((size_t)sgrid * 4);       // host image of every wave's struct over its share of the device memory
+  for (int w = 0; w < sgrid * 4; ++w) hd[w].bind(c->d_dynmem + (unsigned long long)w * per, need);
+  if ((rc = c->d_dyn.ensure((int64_t)(hd.size() * sizeof(SelScratchDyn))))) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_dyn, hd.data(), hd.size() * sizeof(SelScratchDyn), hipMemcpyHostToDevice, c->stream));
   Q.dyn = (SelScratchDyn*)c->d_dyn.p; Q.iv_out = nullptr; Q.found_out = nullptr;   // (intervals and foundHit: already written by the first pass)
-  HIPCHK(qmk_h2m(&ix, &Q, sgrid, c->numCU, c->stream));
+  HIPCHK(qmk_h2m(ix, Q, sgrid, c->numCU, c->stream));
   if ((rc = read_scalars(c, hscal))) return rc;           // (hd is a local: the copy above is done)
   c->stats.slowReads = ns_;
   return QM_OK;
@@ -1189,12 +1187,12 @@ static int run_stage_a(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
       c->stats.leanReads = nreads;
     }
     // fused -s with reads beyond QM_MAX_READ_LEN in the batch: the counts come down once more, so that the 32-slot collector has their intervals ready for the list kernels
-    if (p.twoPass && rq.longReads && nreads > 0 && ((rc = read_scalars(c, hscal)) || (rc = pass_long_reads(c, p, ix, B, hscal, -32)))) return rc;
+    if (p.twoPass && rq.longReads && nreads > 0 && ((rc = read_scalars(c, hscal)) || (rc = pass_long_reads(c, p, ix, B, hscal, RL_LONG_COLLECT)))) return rc;
     if ((rc = run_list_kernels(c, p, rq, ix, H))) return rc;
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     if ((rc = read_scalars(c, hscal))) return rc;
     if (lean_first(p) && ((rc = pass_n_aware(c, p, ix, B, hscal, extraMs)) || (rc = pass_lean_leftovers(c, p, ix, B, hscal, extraMs)))) return rc;
-    if ((!o->sel_aln || rq.mode == QM_RUN_COLLECT) && rq.mode != QM_RUN_FROM_INTERVALS && (rc = pass_long_reads(c, p, ix, B, hscal, rq.mode == QM_RUN_COLLECT ? -32 : 32))) return rc;
+    if ((!o->sel_aln || rq.mode == QM_RUN_COLLECT) && rq.mode != QM_RUN_FROM_INTERVALS && (rc = pass_long_reads(c, p, ix, B, hscal, rq.mode == QM_RUN_COLLECT ? RL_LONG_COLLECT : RL_LONG))) return rc;
     if ((rc = pass_sel_slow(c, o, rq, ix, H, hscal))) return rc;
 #ifdef QM_TIMING
     {                                                    // the phase sums of the -DQM_TIMING kernels: stage A's, qm_h2m_kernel's, the packed list kernels'
@@ -1254,7 +1252,7 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   HIPCHK(hipMemsetAsync(c->d_cnt + n, 0, sizeof(uint32_t), c->stream));
   if (o->sel_aln) {
     // -s: merge + selective alignment + filter per unit into temp slots, then compaction (qm_sel.inl)
-    HIPCHK(qmk_sel_slots(&P, c->stream));
+    HIPCHK(qmk_sel_slots(P, c->stream));
     HIPCHK(qmk_scan_counts(c->d_scanTmp, (size_t)c->d_scanTmp.cap, c->d_cnt, c->d_offs, n + 1, 0, c->stream));
     if ((rc = c->d_toff.ensure(n + 1))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_toff, c->d_offs, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -1286,12 +1284,12 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
     { static const int noDiag = [] { const char* e = getenv("QM_SEL_NO_DIAG"); return e ? atoi(e) : 0; }(); A.no_diag = noDiag; }
     HIPCHK(hipMemsetAsync(c->d_cnt + n, 0, sizeof(uint32_t), c->stream));
     if (rq.mergeOnly) {
-      HIPCHK(qmk_sel_merge(&P, &A, c->stream));            // the merge alone: no alignment, chain statuses stay in aln_score
+      HIPCHK(qmk_sel_merge(P, A, c->stream));            // the merge alone: no alignment, chain statuses stay in aln_score
     } else {
       // plan (per unit) -> ksw2 extension alignments, four per wavefront, any band -> finish (per unit)
       if ((rc = c->d_tref.ensure(2 * slots + 2))) return rc;
-      if ((rc = c->d_tasks.ensure((2 * slots + 2 * K + 2) * (int64_t)qmk_sel_task_bytes()))) return rc;
-      if ((rc = c->d_sides.ensure((2 * slots + 2 * K + 2) * (int64_t)qmk_sel_side_bytes()))) return rc;
+      if ((rc = c->d_tasks.ensure((2 * slots + 2 * K + 2) * (int64_t)sizeof(SelTask)))) return rc;
+      if ((rc = c->d_sides.ensure((2 * slots + 2 * K + 2) * (int64_t)sizeof(SelSide)))) return rc;
       if ((rc = c->d_torder.ensure(2 * (2 * slots + 2 * K + 2)))) return rc;      // (two order lists per chunk: ksw2, strip)
       static const bool noStrip = [] { const char* e = getenv("QM_SEL_NO_STRIP"); return e && atoi(e) != 0; }();
       A.tref = c->d_tref;
@@ -1306,22 +1304,22 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
       hipStream_t planStream = K > 1 && !serial ? c->planStream : c->stream;
       for (int i = 0; i < K; ++i) {
         Ak[i] = A; Ak[i].u0 = cu[i]; Ak[i].u1 = cu[i + 1];
-        Ak[i].tasks = (SelTask*)(c->d_tasks + (size_t)(2 * cslot[i] + 2 * i) * qmk_sel_task_bytes());   // at most two tasks per slot
+        Ak[i].tasks = (SelTask*)(c->d_tasks + (size_t)(2 * cslot[i] + 2 * i) * sizeof(SelTask));   // at most two tasks per slot
         Ak[i].ntasks = c->d_ntk + i;
-        Ak[i].sides = (SelSide*)(c->d_sides + (size_t)(2 * cslot[i] + 2 * i) * qmk_sel_side_bytes());       // ... and at most two questions
+        Ak[i].sides = (SelSide*)(c->d_sides + (size_t)(2 * cslot[i] + 2 * i) * sizeof(SelSide));       // ... and at most two questions
         Ak[i].nsides = c->d_ntk + QM_SEL_CHUNKS_B + i;
         Ak[i].torder = c->d_torder + (size_t)(2 * cslot[i] + 2 * i);
         if (!noStrip) { Ak[i].torder2 = c->d_torder + (size_t)(2 * slots + 2 * K + 2) + (size_t)(2 * cslot[i] + 2 * i); Ak[i].ntasks2 = c->d_ntk + 2 * QM_SEL_CHUNKS_B + i; }
-        HIPCHK(qmk_sel_plan(&P, &Ak[i], c->numCU, planStream));
+        HIPCHK(qmk_sel_plan(P, Ak[i], c->numCU, planStream));
         if (K > 1) HIPCHK(hipEventRecord(c->evPlan[i], planStream));
       }
       for (int i = 0; i < K; ++i) {
         if (K > 1) HIPCHK(hipStreamWaitEvent(c->stream, c->evPlan[i], 0));
-        HIPCHK(qmk_sel_align_finish(&P, &Ak[i], c->numCU, c->stream));
+        HIPCHK(qmk_sel_align_finish(P, Ak[i], c->numCU, c->stream));
       }
     }
   } else {
-    HIPCHK(qmk_pair_count(&P, c->stream));
+    HIPCHK(qmk_pair_count(P, c->stream));
   }
   // one part of a split call: the scan starts from the hits of the parts before this one and writes straight into the caller's offsets
   // (entry n, the closing one, is also the first entry of the part behind this one, which writes the same number there)
@@ -1352,8 +1350,8 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
     P.offs = offsOut;
     for (int pass = 0; pass < 2; ++pass) {
       P.hits = dst;
-      if (o->sel_aln) HIPCHK(qmk_sel_compact(&P, c->d_tmp, c->d_toff, c->stream));
-      else HIPCHK(qmk_pair_write(&P, c->stream));
+      if (o->sel_aln) HIPCHK(qmk_sel_compact(P, c->d_tmp, c->d_toff, c->stream));
+      else HIPCHK(qmk_pair_write(P, c->stream));
       if (pass) break;
       HIPCHK(hipStreamSynchronize(c->stream));
       if ((rc = rq.join->settle(rq.part, early, again, dst))) return rc;
@@ -1363,8 +1361,8 @@ static int run_stage_b(qm_ctx* c, const qm_opts* o, const RunReq& rq, int64_t n,
   }
   if ((rc = c->d_hits.ensure((int64_t)total + 1, total / 8))) return rc;
   P.hits = c->d_hits;
-  if (o->sel_aln) HIPCHK(qmk_sel_compact(&P, c->d_tmp, c->d_toff, c->stream));
-  else HIPCHK(qmk_pair_write(&P, c->stream));
+  if (o->sel_aln) HIPCHK(qmk_sel_compact(P, c->d_tmp, c->d_toff, c->stream));
+  else HIPCHK(qmk_pair_write(P, c->stream));
   return QM_OK;
 }
 

@@ -578,8 +578,6 @@ __global__ __launch_bounds__(256) void qm_stage_gather_kernel(long long nreads, 
 
 using namespace qm;
 
-extern "C" {
-
 hipError_t qmk_build_sainfo(const unsigned int* SA, long long nSA, const unsigned int* offsets, long long T, void* out, hipStream_t st) {
   hipLaunchKernelGGL(build_sainfo_kernel, dim3(4096), dim3(256), 0, st, SA, nSA, offsets, T, (SaInfo*)out);
   return hipGetLastError();
@@ -639,7 +637,6 @@ hipError_t qmk_build_saext2(const unsigned char* text, long long n, const unsign
   hipFree(T);
   return e != hipSuccess ? e : e2;
 }
-size_t qmk_saext2_bytes(void) { return sizeof(SaExt2); }
 hipError_t qmk_build_sanext(const unsigned char* text, long long n, const unsigned int* SA, long long nSA, int k, unsigned int* out, hipStream_t st) {
   if (nSA <= 0) return hipSuccess;
   u64 *T = nullptr, *V = nullptr;
@@ -663,18 +660,18 @@ hipError_t qmk_build_slots(const void* recs, long long K, void* slots, unsigned 
   return hipGetLastError();
 }
 
-hipError_t qmk_build_slots_from_ph(const void* dev_index, long long n, void* slots, unsigned long long cap, unsigned long long* d_bad, hipStream_t st) {
+hipError_t qmk_build_slots_from_ph(const DevIndex& ix, long long n, void* slots, unsigned long long cap, unsigned long long* d_bad, hipStream_t st) {
   hipError_t e = hipMemsetAsync(slots, 0xff, cap * sizeof(Bucket), st);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), st);
   if (e != hipSuccess) return e;
-  if (n > 0) hipLaunchKernelGGL(build_slots_from_ph_kernel, dim3(4096), dim3(256), 0, st, *(const DevIndex*)dev_index, n, (Bucket*)slots, cap - 1, d_bad);
+  if (n > 0) hipLaunchKernelGGL(build_slots_from_ph_kernel, dim3(4096), dim3(256), 0, st, ix, n, (Bucket*)slots, cap - 1, d_bad);
   return hipGetLastError();
 }
 
-hipError_t qmk_build_phrecs(const unsigned int* data, const unsigned char* lens, long long n, const void* dev_index, void* out, hipStream_t st) {
+hipError_t qmk_build_phrecs(const unsigned int* data, const unsigned char* lens, long long n, const DevIndex& ix, void* out, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(build_phrec_kernel, dim3(4096), dim3(256), 0, st, data, lens, n, *(const DevIndex*)dev_index, (PhRec*)out);
+  hipLaunchKernelGGL(build_phrec_kernel, dim3(4096), dim3(256), 0, st, data, lens, n, ix, (PhRec*)out);
   return hipGetLastError();
 }
 
@@ -684,109 +681,49 @@ hipError_t qmk_build_phfilter(const void* recs, long long n, void* filter, unsig
   return hipGetLastError();
 }
 
-int qmk_grid_oversub(void) {
-  static const int m = [] { const char* e = getenv("QM_GRID_OVERSUB"); return e && atoi(e) > 0 && atoi(e) <= 16 ? atoi(e) : 4; }();
-  return m;
-}
-// the compact -p kernels (BooPHF walked per lookup: reads differ more in work) keep gaining up to twelve times the
-// resident blocks: 181.9 / 185.5 / 187.4 / 189.1 / 189.0 M pairs/s at 4 / 6 / 8 / 12 / 16 (profiles/r04/ph_oversub.txt)
-int qmk_grid_oversub_ph(void) {
-  static const int m = [] { const char* e = getenv("QM_GRID_OVERSUB_PH"); return e && atoi(e) > 0 && atoi(e) <= 16 ? atoi(e) : (getenv("QM_GRID_OVERSUB") ? qmk_grid_oversub() : 12); }();
-  return m;
-}
-int qmk_resident_grid(long long nreads, int num_cu) {
-  long long want = (nreads + 3) / 4;
-  long long cap = (long long)num_cu * QMK_BLOCKS_PER_CU;
-  return (int)(want < cap ? (want > 0 ? want : 1) : cap);
-}
-int qmk_map_grid(long long nreads, int num_cu) { return qmk_map_grid_ex(nreads, num_cu, 0); }
-int qmk_map_grid_ex(long long nreads, int num_cu, int ph_compact) {
-  long long want = (nreads + 3) / 4;
-  long long cap = (long long)num_cu * QMK_BLOCKS_PER_CU * (ph_compact ? qmk_grid_oversub_ph() : qmk_grid_oversub());
-  return (int)(want < cap ? (want > 0 ? want : 1) : cap);
+// stage A: the launch and the slot class pick the translation unit that holds the instantiations (qm_read_kernel.inl)
+hipError_t qmk_map_reads(const DevIndex& ix, const ReadBatch& B, int ns, ReadLaunch what, int grid, int num_cu, hipStream_t st) {
+  if (what == RL_LONG || what == RL_LONG_COLLECT) return qmk_launch_reads_ns32(ix, B, what == RL_LONG_COLLECT, grid, num_cu, st);
+  if (what == RL_ENTRY_COLLECT) return qmk_launch_reads_ns8(ix, B, true, grid, num_cu, st);
+  const bool collect = what == RL_CHAIN_COLLECT;
+  if (ns == 2) return qmk_launch_reads_ns2(ix, B, collect, grid, num_cu, st);
+  if (ns == 3) return qmk_launch_reads_ns3(ix, B, collect, grid, num_cu, st);
+  if (ns > 4) return qmk_launch_reads_ns8(ix, B, collect, grid, num_cu, st);
+  return qmk_launch_reads_ns4(ix, B, collect, grid, num_cu, st);
 }
 
-// The stage-A kernels are persistent grids: every wave strides over the reads.  Launched with exactly the blocks that are
-// resident at once, the reads are divided statically and the launch lasts as long as its slowest wave -- 13 % longer than the
-// average one on config 2.  Launched with QM_GRID_OVERSUB (4) times that many, a block owns a quarter of the reads and the
-// hardware hands out the blocks as slots free up: 41.6 -> 36.1 ms (profiles/r04/grid_oversub.txt; 8x: the same).  The occupancy
-// of the chosen instantiation (VGPR/LDS dependent) decides the resident count.
-// stage A: the slot-count class picks the translation unit that holds its instantiations (qm_read_kernel.inl).
-// ns < 0: the "collector only" stage entry, on the eight-slot kernels (every read length up to QM_MAX_READ_LEN).
-// collect: collector-only kernels (ns < 0: those of the stage entry, eight slots; otherwise the chain-scoring ones of slot count ns)
-hipError_t qmk_map_reads(const void* ixp, const void* bp, int ns, int grid, int num_cu, hipStream_t st) { return qmk_map_reads_ex(ixp, bp, ns, 0, grid, num_cu, st); }
-hipError_t qmk_map_reads_ex(const void* ixp, const void* bp, int ns, int collect, int grid, int num_cu, hipStream_t st) {
-  if (ns == -32) return qmk_launch_reads_ns32(ixp, bp, 1, grid, num_cu, st);   // long-read pass of the collector-only stage entry
-  if (ns == 32) return qmk_launch_reads_ns32(ixp, bp, 0, grid, num_cu, st);    // long-read pass (reads of 513 .. 2048 characters)
-  if (ns < 0) return qmk_launch_reads_ns8(ixp, bp, 1, grid, num_cu, st);
-  if (collect) {
-    if (ns == 2) return qmk_launch_reads_ns2(ixp, bp, 1, grid, num_cu, st);
-    if (ns == 3) return qmk_launch_reads_ns3(ixp, bp, 1, grid, num_cu, st);
-    if (ns > 4) return qmk_launch_reads_ns8(ixp, bp, 1, grid, num_cu, st);
-    return qmk_launch_reads_ns4(ixp, bp, 1, grid, num_cu, st);
-  }
-  if (ns == 2) return qmk_launch_reads_ns2(ixp, bp, 0, grid, num_cu, st);
-  if (ns == 3) return qmk_launch_reads_ns3(ixp, bp, 0, grid, num_cu, st);
-  if (ns > 4) return qmk_launch_reads_ns8(ixp, bp, 0, grid, num_cu, st);
-  return qmk_launch_reads_ns4(ixp, bp, 0, grid, num_cu, st);
-}
-
-hipError_t qmk_h2m(const void* ixp, const void* bp, int grid, int num_cu, hipStream_t st) {
-  const DevIndex& ix = *(const DevIndex*)ixp;
-  const ReadBatch& B = *(const ReadBatch*)bp;
-  static int nbSel = 0, nbPlain = 0;                         // persistent grids: no more blocks than are resident at once
-  if (nbSel == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbSel, qm_h2m_kernel<QM_F_SEL>, 256, 0) != hipSuccess || nbSel < 1)) nbSel = 2;
-  if (nbPlain == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbPlain, qm_h2m_kernel<0>, 256, 0) != hipSuccess || nbPlain < 1)) nbPlain = 2;
-  const int nb = B.selscr ? nbSel : nbPlain;
-  const unsigned g = (unsigned)(grid < num_cu * nb ? grid : num_cu * nb);
-  if (B.selscr) hipLaunchKernelGGL(qm_h2m_kernel<QM_F_SEL>, dim3(g), dim3(256), 0, st, ix, B);
-  else hipLaunchKernelGGL(qm_h2m_kernel<0>, dim3(g), dim3(256), 0, st, ix, B);
+// the list kernels: persistent grids over the caller's blocks (qm_grid.h: what each of them gets)
+hipError_t qmk_h2m(const DevIndex& ix, const ReadBatch& B, int grid, int num_cu, hipStream_t st) {
+  if (B.selscr) hipLaunchKernelGGL(qm_h2m_kernel<QM_F_SEL>, dim3((unsigned)grid_clamp(grid, num_cu, resident_per_cu<qm_h2m_kernel<QM_F_SEL>, 256, 2, false>(), 1)), dim3(256), 0, st, ix, B);
+  else hipLaunchKernelGGL(qm_h2m_kernel<0>, dim3((unsigned)grid_clamp(grid, num_cu, resident_per_cu<qm_h2m_kernel<0>, 256, 2, false>(), 1)), dim3(256), 0, st, ix, B);
   return hipGetLastError();
 }
-hipError_t qmk_h2m_pack(const void* ixp, const void* bp, long long* todoq, int grid, int num_cu, hipStream_t st) {
-  const DevIndex& ix = *(const DevIndex*)ixp;
-  const ReadBatch& B = *(const ReadBatch*)bp;
-  static int nb = 0;
-  if (nb == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, qm_h2m_pack_kernel, 256, 0) != hipSuccess || nb < 1)) nb = 2;
-  const long long cap = (long long)num_cu * nb * qmk_grid_oversub();                 // contiguous ranges of reads per wave: more, smaller ranges balance better
-  const unsigned g = (unsigned)(grid < cap ? grid : cap);
-  hipLaunchKernelGGL(qm_h2m_pack_kernel, dim3(g), dim3(256), 0, st, ix, B, todoq);
+hipError_t qmk_h2m_pack(const DevIndex& ix, const ReadBatch& B, long long* todoq, int grid, int num_cu, hipStream_t st) {
+  const int g = grid_clamp(grid, num_cu, resident_per_cu<qm_h2m_pack_kernel, 256, 2, false>(), grid_oversub());   // contiguous ranges of reads per wave: more, smaller ranges balance better
+  hipLaunchKernelGGL(qm_h2m_pack_kernel, dim3((unsigned)g), dim3(256), 0, st, ix, B, todoq);
   return hipGetLastError();
 }
-hipError_t qmk_h2m_packw(const void* ixp, const void* bp, const long long* ids, const unsigned long long* nids, long long* todoq, int grid, int num_cu, hipStream_t st) {
-  const DevIndex& ix = *(const DevIndex*)ixp;
-  const ReadBatch& B = *(const ReadBatch*)bp;
-  static int nb = 0;
-  if (nb == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, qm_h2m_packw_kernel, 256, 0) != hipSuccess || nb < 1)) nb = 1;
-  const long long cap = (long long)num_cu * nb * qmk_grid_oversub();
-  const unsigned g = (unsigned)(grid < cap ? grid : cap);
-  hipLaunchKernelGGL(qm_h2m_packw_kernel, dim3(g), dim3(256), 0, st, ix, B, ids, (const u64*)nids, todoq);
+hipError_t qmk_h2m_packw(const DevIndex& ix, const ReadBatch& B, const long long* ids, const unsigned long long* nids, long long* todoq, int grid, int num_cu, hipStream_t st) {
+  const int g = grid_clamp(grid, num_cu, resident_per_cu<qm_h2m_packw_kernel, 256, 1, false>(), grid_oversub());
+  hipLaunchKernelGGL(qm_h2m_packw_kernel, dim3((unsigned)g), dim3(256), 0, st, ix, B, ids, (const u64*)nids, todoq);
   return hipGetLastError();
 }
-hipError_t qmk_sel_merge(const void* pp, const void* ap, hipStream_t st) {
-  const PairBatch& P = *(const PairBatch*)pp; const SelBatch& A = *(const SelBatch*)ap;
+hipError_t qmk_sel_merge(const PairBatch& P, const SelBatch& A, hipStream_t st) {
   if (P.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(qm_sel_merge_kernel, dim3((unsigned)((P.n + 255) / 256)), dim3(256), 0, st, P, A);
   return hipGetLastError();
 }
-size_t qmk_sel_scratch_bytes(void) { return sizeof(SelScratch); }
-size_t qmk_sel_dyn_struct_bytes(void) { return sizeof(SelScratchDyn); }
-unsigned long long qmk_sel_dyn_bytes(long long n) { return SelScratchDyn::bytes_for(n); }
-// host image of wave w's SelScratchDyn over device memory at `base`
-void qmk_sel_dyn_bind(void* host_struct, void* dev_base, long long n) { ((SelScratchDyn*)host_struct)->bind((unsigned char*)dev_base, n); }
 hipError_t qmk_collect_marked(const unsigned int* lcnt, long long nreads, unsigned int mark, long long* q, long long cap, unsigned long long* count, hipStream_t st) {
   if (nreads <= 0) return hipSuccess;
   hipLaunchKernelGGL(qm_collect_slow_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, st, lcnt, nreads, q, (u64*)count, (u32)mark, (unsigned long long)(cap > 0 ? cap : 0));
   return hipGetLastError();
 }
-hipError_t qmk_sel_slots(const void* pp, hipStream_t st) {
-  const PairBatch& P = *(const PairBatch*)pp;
+hipError_t qmk_sel_slots(const PairBatch& P, hipStream_t st) {
   hipLaunchKernelGGL(qm_sel_slots_kernel, dim3((unsigned)((P.n + 1 + 255) / 256)), dim3(256), 0, st, P);
   return hipGetLastError();
 }
 // the three steps of a chunk of units [A.u0, A.u1): plan (per unit) -> ksw2 (four alignments per wavefront) -> finish (per unit)
-hipError_t qmk_sel_plan(const void* pp, const void* ap, int num_cu, hipStream_t st) {
-  const PairBatch& P = *(const PairBatch*)pp; const SelBatch& A = *(const SelBatch*)ap;
+hipError_t qmk_sel_plan(const PairBatch& P, const SelBatch& A, int num_cu, hipStream_t st) {
   if (A.u1 <= A.u0) return hipSuccess;
   const long long nu = A.u1 - A.u0;
   hipLaunchKernelGGL(qm_sel_sides_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, st, P, A);
@@ -805,13 +742,11 @@ hipError_t qmk_sel_plan(const void* pp, const void* ap, int num_cu, hipStream_t 
   if (A.torder2) hipLaunchKernelGGL(qm_sel_strip_kernel, dim3((unsigned)(num_cu * 8)), dim3(256), 0, st, A);   // (17 KB of LDS per block: up to nine blocks per CU)
   return hipGetLastError();
 }
-size_t qmk_sel_side_bytes(void) { return sizeof(SelSide); }
-hipError_t qmk_sel_align_finish(const void* pp, const void* ap, int num_cu, hipStream_t st) {
-  const PairBatch& P = *(const PairBatch*)pp; const SelBatch& A = *(const SelBatch*)ap;
+hipError_t qmk_sel_align_finish(const PairBatch& P, const SelBatch& A, int num_cu, hipStream_t st) {
   if (A.u1 <= A.u0) return hipSuccess;
   const unsigned nb = (unsigned)((A.u1 - A.u0 + 255) / 256);
-  // the alignment kernels stride over the tasks like stage A over the reads: oversubscribed grids for the same reason (qmk_map_grid)
-  static const int ao = getenv("QM_ALIGN_OVERSUB") && atoi(getenv("QM_ALIGN_OVERSUB")) > 0 ? atoi(getenv("QM_ALIGN_OVERSUB")) : qmk_grid_oversub();
+  // the alignment kernels stride over the tasks like stage A over the reads: oversubscribed grids for the same reason (qm_grid.h)
+  static const int ao = getenv("QM_ALIGN_OVERSUB") && atoi(getenv("QM_ALIGN_OVERSUB")) > 0 ? atoi(getenv("QM_ALIGN_OVERSUB")) : grid_oversub();
   if (A.long_reads) {                                    // reads of 513 .. 2048 characters in the batch: two waves per block, long images
     switch (sel_ksw_ring_slots(A.bandwidth)) {
       case 32: hipLaunchKernelGGL((qm_sel_align_kernel<32, 2, QM_KSW_MAXLEN_LONG>), dim3((unsigned)(num_cu * 4 * ao)), dim3(128), 0, st, P, A); break;
@@ -837,24 +772,20 @@ hipError_t qmk_sel_align_finish(const void* pp, const void* ap, int num_cu, hipS
   hipLaunchKernelGGL(qm_sel_finish_kernel, dim3(nb), dim3(256), 0, st, P, A);
   return hipGetLastError();
 }
-size_t qmk_sel_task_bytes(void) { return sizeof(SelTask); }
 size_t qmk_sel_gmem_rows_bytes(int num_cu) { return (size_t)num_cu * QMK_GMEM_WAVES * 4 * sizeof(KswRowT<QM_KSW_RING_GMEM, QM_KSW_MAXLEN_LONG>); }
-hipError_t qmk_sel_compact(const void* pp, const void* tmp, const void* toff, hipStream_t st) {
-  const PairBatch& P = *(const PairBatch*)pp;
+hipError_t qmk_sel_compact(const PairBatch& P, const void* tmp, const void* toff, hipStream_t st) {
   if (P.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(qm_sel_compact_kernel, dim3((unsigned)((P.n + 255) / 256)), dim3(256), 0, st, P, (const qm_hit*)tmp, (const long long*)toff);
   return hipGetLastError();
 }
 
-hipError_t qmk_pair_count(const void* pp, hipStream_t st) {
-  const PairBatch& P = *(const PairBatch*)pp;
+hipError_t qmk_pair_count(const PairBatch& P, hipStream_t st) {
   if (P.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(qm_pair_count_kernel, dim3((unsigned)((P.n + 255) / 256)), dim3(256), 0, st, P);
   return hipGetLastError();
 }
 
-hipError_t qmk_pair_write(const void* pp, hipStream_t st) {
-  const PairBatch& P = *(const PairBatch*)pp;
+hipError_t qmk_pair_write(const PairBatch& P, hipStream_t st) {
   if (P.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(qm_pair_write_kernel, dim3((unsigned)((P.n + 255) / 256)), dim3(256), 0, st, P);
   return hipGetLastError();
@@ -895,5 +826,3 @@ hipError_t qmk_stage_gather(long long nreads, const u32* ivcnt, const long long*
                      (const qm_sa_interval_hit*)iv, ivcsr, (qm_sa_interval_hit*)iv_out, lcnt, loff, (const u64*)lists, lcsr, (u64*)words_out);
   return hipGetLastError();
 }
-
-}  // extern "C"

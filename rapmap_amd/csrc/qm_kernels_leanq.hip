@@ -6,18 +6,7 @@ using namespace qm;
 
 // The N-aware edition over a queue (B.slowq[0 .. B.nreads): reads of the batch the first pass left): reads whose characters outside A C G T
 // are all N are mapped here, the others marked again (qm_host.hip, run_stage_a).  Not for the wide edition.
-extern "C" hipError_t qmk_launch_lean_nq(const void* ixp, const void* bp, int num_cu, hipStream_t st) {
-  const DevIndex& ix = *(const DevIndex*)ixp; const ReadBatch& B = *(const ReadBatch*)bp;
+hipError_t qmk_launch_lean_nq(const DevIndex& ix, const ReadBatch& B, int num_cu, hipStream_t st) {
   if (B.lean_wide || !B.slowq) return hipErrorInvalidValue;
-  const int v = (B.seq2 ? 4 : 0) | (B.selscr ? 2 : 0) | (ix.ph ? 1 : 0);
-  switch (v) {
-    case 0: return launch_lean<false, false, false, false, true>(ix, B, num_cu, st);
-    case 1: return launch_lean<false, false, true, false, true>(ix, B, num_cu, st);
-    case 2: return launch_lean<false, true, false, false, true>(ix, B, num_cu, st);
-    case 3: return launch_lean<false, true, true, false, true>(ix, B, num_cu, st);
-    case 4: return launch_lean<true, false, false, false, true>(ix, B, num_cu, st);
-    case 5: return launch_lean<true, false, true, false, true>(ix, B, num_cu, st);
-    case 6: return launch_lean<true, true, false, false, true>(ix, B, num_cu, st);
-    default: return launch_lean<true, true, true, false, true>(ix, B, num_cu, st);
-  }
+  return launch_lean<false, true>(ix, B, num_cu, st);
 }

@@ -3,6 +3,6 @@
 // qm_read_kernel.inl and map_read (qm_mapper.inl).  Of -s its collector flavours (qm_read_kernel<32,.,SEL|COLLECT>): the long reads' intervals
 // for the list kernel.
 #include "qm_read_kernel.inl"
-extern "C" hipError_t qmk_launch_reads_ns32(const void* ixp, const void* bp, int collect, int grid, int num_cu, hipStream_t st) {
-  return qm::launch_reads_ns<32, 1, 1, 1, 1, 1, true>(*(const qm::DevIndex*)ixp, *(const qm::ReadBatch*)bp, collect != 0, grid, num_cu, st);
+hipError_t qmk_launch_reads_ns32(const qm::DevIndex& ix, const qm::ReadBatch& B, bool collect, int grid, int num_cu, hipStream_t st) {
+  return qm::launch_reads_ns<32, 1, 1, 1, 1, 1, true>(ix, B, collect, grid, num_cu, st);
 }

@@ -30,6 +30,7 @@
 // the two strands' images 16 words apart, MMP extensions through the 224-character table (SaExt2).  Reads of 129 .. 256 characters
 // take it (qm_host.hip, run_stage_a: leanWide).
 #pragma once
+#include <type_traits>
 #include "qm_mapper.inl"
 
 namespace qm {
@@ -1083,6 +1084,24 @@ QM_DEV void lean_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, Le
   for (int it = gw; it < nit; it += nw) {
     lean_iter<PAIRED, SEL, PH, WIDE, NQ>(ix, B, it, nit, nw, par, M, wa);
     par ^= 1;
+  }
+}
+
+// The runtime flags of a launch -> the instantiation: f(PAIRED, SEL, PH) with each a std::true_type / std::false_type.  The one place
+// that knows the mapping: the kernel's launchers (qm_lean_kernel.inl) and the lane emulation (tests/emu) both come through here;
+// WIDE and NQ stay with the caller, so a compile unit only instantiates its own editions.
+template <class Fn>
+inline auto lean_dispatch(bool paired, bool sel, bool ph, Fn&& f) {
+  typedef std::true_type Y; typedef std::false_type N;
+  switch ((paired ? 4 : 0) | (sel ? 2 : 0) | (ph ? 1 : 0)) {
+    case 0: return f(N(), N(), N());
+    case 1: return f(N(), N(), Y());
+    case 2: return f(N(), Y(), N());
+    case 3: return f(N(), Y(), Y());
+    case 4: return f(Y(), N(), N());
+    case 5: return f(Y(), N(), Y());
+    case 6: return f(Y(), Y(), N());
+    default: return f(Y(), Y(), Y());
   }
 }
 

@@ -200,6 +200,17 @@ struct ReadBatch {
   u32* pair_cnt; int max_num_hits, no_orphans, no_dovetail;
 };
 
+#ifndef QM_EMU
+// The two argument structs of a stage-A kernel (~70 dwords) are read through the kernarg segment where they are used -- scalar loads
+// from constant memory -- instead of being loaded into SGPRs at entry and kept there: at 8 waves/SIMD a wave has 78 SGPRs, and
+// half of the v_readlane / v_writelane spill traffic of qm_read_kernel was for these words.  For kernels declared (DevIndex, ReadBatch).
+struct StageArgs { DevIndex ix; ReadBatch B; };
+QM_DEV const StageArgs& stage_args() {
+  typedef const StageArgs __attribute__((address_space(4)))* AP4;
+  return *(const StageArgs*)(AP4)__builtin_amdgcn_kernarg_segment_ptr();
+}
+#endif
+
 // stage B launch arguments
 struct PairBatch {
   long long n;             // pairs (or single-end reads)

@@ -1,6 +1,7 @@
 // qm_read_kernel.inl -- the stage-A kernel template and its per-slot-count launch wrappers.  The 36 instantiations
 // (read-length class x index flavour x --noSensitive x -s, plus the collector-only stage entry) are spread over four
-// translation units -- qm_kernels_ns{2,3,4,8}.hip, each defining qmk_launch_reads_ns<N> -- so that they compile in parallel.
+// translation units -- qm_kernels_ns{2,3,4,8}.hip, each defining qmk_launch_reads_ns<N> -- so that they compile in parallel
+// (qm_kernels_ns32.hip: the long-read pass).  qmk_map_reads (qm_kernels.hip) picks the unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -16,13 +17,7 @@ template <int NS> struct WavesPerBlock { static constexpr int value = NS > 16 ? 
 template <int NS, int WPS, int F>
 __global__ __launch_bounds__(64 * WavesPerBlock<NS>::value, WPS) void qm_read_kernel(DevIndex ix_, ReadBatch B_) {
   constexpr int WB = WavesPerBlock<NS>::value;
-  // The two argument structs (~70 dwords) are read through the kernarg segment where they are used -- scalar loads from
-  // constant memory -- instead of being loaded into SGPRs at entry and kept there: at 8 waves/SIMD a wave has 78 SGPRs, and
-  // half of the v_readlane / v_writelane spill traffic of this kernel was for these words.
-  struct Args { DevIndex ix; ReadBatch B; };
-  typedef const Args __attribute__((address_space(4)))* AP4;
-  const Args* args = (const Args*)(AP4)__builtin_amdgcn_kernarg_segment_ptr();
-  const DevIndex& ix = args->ix; const ReadBatch& B = args->B;
+  const DevIndex& ix = stage_args().ix; const ReadBatch& B = stage_args().B;   // (through the kernarg segment, not ix_ / B_: see stage_args)
   // The collector-only kernels never reach finish_read, the one user of WaveMem::buf (its first member, 1.5 KB): their waves' slabs are laid
   // over each other by that much -- wave w's buf is the tail of wave w-1's slab, wave 0's a pad in front -- and four waves take 4.6 KB less:
   // 8 blocks per CU instead of 6 at three slots (-s on 2 x 150 bp), 6 instead of 5 at four (2 x 250 bp).
@@ -68,58 +63,54 @@ __global__ __launch_bounds__(64 * WavesPerBlock<NS>::value, WPS) void qm_read_ke
 }
 
 
+// one instantiation over a persistent grid (every wave strides over the reads): at most `grid` blocks, and at most the oversubscribed
+// resident ones -- the occupancy of this instantiation (VGPR / LDS dependent) decides the resident count (qm_grid.h)
+template <int NS, int WPS, int F>
+static hipError_t launch_read_kernel(const DevIndex& ix, const ReadBatch& B, int grid, int num_cu, hipStream_t st) {
+  constexpr int THREADS = 64 * WavesPerBlock<NS>::value;
+  const int g = grid_clamp(grid, num_cu, resident_per_cu<qm_read_kernel<NS, WPS, F>, THREADS, WPS, true>(), (F & QM_F_PH) ? grid_oversub_ph() : grid_oversub());
+  hipLaunchKernelGGL((qm_read_kernel<NS, WPS, F>), dim3((unsigned)g), dim3(THREADS), 0, st, ix, B);
+  return hipGetLastError();
+}
+
 // launch of one slot-count class; collect: the collector-only stage entry (QM_F_COLLECT)
 template <int NS, int W0, int WPH, int WNIP, int WPHNIP, int WSEL, bool WITH_COLLECT, int WCOLL = W0>     // WCOLL: the -s collector of the default index
 static hipError_t launch_reads_ns(const DevIndex& ix, const ReadBatch& B, bool collect, int grid, int num_cu, hipStream_t st) {
   const int F = (ix.ph ? QM_F_PH : 0) | (B.sensitive ? 0 : QM_F_NIP) | (B.selscr ? QM_F_SEL : 0);
-  // A persistent grid (every wave strides over the reads) of QM_GRID_OVERSUB times the blocks that are resident at once: see
-  // qmk_map_grid in qm_kernels.hip.  The occupancy of the chosen instantiation (VGPR/LDS dependent) decides the resident count.
-#define QM_LAUNCH(WPS_, F_) do {                                                                               \
-    static const int nb = [] { int v = 0;                                                                       \
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, qm_read_kernel<NS, WPS_, F_>, 64 * WavesPerBlock<NS>::value, 0) != hipSuccess || v < 1) v = WPS_; \
-      return v; }();                                                                                            \
-    static const char* ov = getenv("QM_BLOCKS_PER_CU");   /* tuning knob: fewer resident blocks than the occupancy allows */ \
-    long long g = (long long)num_cu * ((ov && atoi(ov) > 0 && atoi(ov) < nb) ? atoi(ov) : nb) * (((F_) & QM_F_PH) ? qmk_grid_oversub_ph() : qmk_grid_oversub());  \
-    if (g > grid) g = grid;                                                                                     \
-    hipLaunchKernelGGL((qm_read_kernel<NS, WPS_, F_>), dim3((unsigned)g), dim3(64 * WavesPerBlock<NS>::value), 0, st, ix, B); \
-  } while (0)
+#define QM_LAUNCH(WPS_, F_) return launch_read_kernel<NS, WPS_, F_>(ix, B, grid, num_cu, st)
   if constexpr (WITH_COLLECT) if (collect) {
     // collector-only kernels: the chain-scoring flavours for every slot count (first pass of a fused -s call: without the
     // chaining code they fit the register budget of the default kernel, so they are built for its occupancy), the others
     // only at eight slots (the stage entry qm_collect_reads, any read length)
     if constexpr (NS <= 8 || NS == 32) {                   // (32: the long-read pass of a -s call)
       switch (F) {
-        case QM_F_SEL: QM_LAUNCH(WCOLL, QM_F_SEL | QM_F_COLLECT); return hipGetLastError();
-        case QM_F_SEL | QM_F_PH: QM_LAUNCH(WPH, QM_F_SEL | QM_F_PH | QM_F_COLLECT); return hipGetLastError();
-        case QM_F_SEL | QM_F_NIP: QM_LAUNCH(WNIP, QM_F_SEL | QM_F_NIP | QM_F_COLLECT); return hipGetLastError();
-        case QM_F_SEL | QM_F_PH | QM_F_NIP: QM_LAUNCH(WPHNIP, QM_F_SEL | QM_F_PH | QM_F_NIP | QM_F_COLLECT); return hipGetLastError();
+        case QM_F_SEL: QM_LAUNCH(WCOLL, QM_F_SEL | QM_F_COLLECT);
+        case QM_F_SEL | QM_F_PH: QM_LAUNCH(WPH, QM_F_SEL | QM_F_PH | QM_F_COLLECT);
+        case QM_F_SEL | QM_F_NIP: QM_LAUNCH(WNIP, QM_F_SEL | QM_F_NIP | QM_F_COLLECT);
+        case QM_F_SEL | QM_F_PH | QM_F_NIP: QM_LAUNCH(WPHNIP, QM_F_SEL | QM_F_PH | QM_F_NIP | QM_F_COLLECT);
         default: break;
       }
     }
     if (F & QM_F_SEL) return hipErrorInvalidValue;
-    switch (F) {
-      default:
-        if constexpr (NS == 8 || NS == 32) {
-          switch (F) {
-            case 0: QM_LAUNCH(W0, QM_F_COLLECT); break;
-            case QM_F_PH: QM_LAUNCH(WPH, QM_F_PH | QM_F_COLLECT); break;
-            case QM_F_NIP: QM_LAUNCH(WNIP, QM_F_NIP | QM_F_COLLECT); break;
-            default: QM_LAUNCH(WPHNIP, QM_F_PH | QM_F_NIP | QM_F_COLLECT); break;
-          }
-        } else return hipErrorInvalidValue;
+    if constexpr (NS == 8 || NS == 32) {
+      switch (F) {
+        case 0: QM_LAUNCH(W0, QM_F_COLLECT);
+        case QM_F_PH: QM_LAUNCH(WPH, QM_F_PH | QM_F_COLLECT);
+        case QM_F_NIP: QM_LAUNCH(WNIP, QM_F_NIP | QM_F_COLLECT);
+        default: QM_LAUNCH(WPHNIP, QM_F_PH | QM_F_NIP | QM_F_COLLECT);
+      }
     }
-    return hipGetLastError();
+    return hipErrorInvalidValue;
   }
   switch (F) {
-    case 0: QM_LAUNCH(W0, 0); break;
-    case QM_F_PH: QM_LAUNCH(WPH, QM_F_PH); break;
-    case QM_F_NIP: QM_LAUNCH(WNIP, QM_F_NIP); break;
-    case QM_F_PH | QM_F_NIP: QM_LAUNCH(WPHNIP, QM_F_PH | QM_F_NIP); break;
+    case 0: QM_LAUNCH(W0, 0);
+    case QM_F_PH: QM_LAUNCH(WPH, QM_F_PH);
+    case QM_F_NIP: QM_LAUNCH(WNIP, QM_F_NIP);
+    case QM_F_PH | QM_F_NIP: QM_LAUNCH(WPHNIP, QM_F_PH | QM_F_NIP);
     // -s never runs as one fused kernel: the host launches the chain-scoring collector (above) and qm_h2m_kernel<QM_F_SEL>
     default: return hipErrorInvalidValue;
   }
 #undef QM_LAUNCH
-  return hipGetLastError();
 }
 
 }  // namespace qm

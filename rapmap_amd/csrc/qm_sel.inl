@@ -48,7 +48,7 @@ struct SelScratchDyn {
   QM_DEV int cap() const { return capN; } QM_DEV int outcap() const { return outN; } QM_DEV int gcap() const { return capN; }
   QM_DEV int tmp_bytes() const { return capN * (int)sizeof(SelRec); }
   QM_DEV SelGroup* grpp(int s) { return s == 0 ? grp0 : grp1; }
-  // bytes of device memory one wave's arrays take for `n` suffixes per strand (host: qmk_sel_dyn_bytes / qmk_sel_dyn_bind)
+  // bytes of device memory one wave's arrays take for `n` suffixes per strand (host: pass_sel_slow in qm_host.hip)
   static inline unsigned long long bytes_for(long long n) {
     return (unsigned long long)n * (2 * sizeof(SelRec) + sizeof(double) + 4 * sizeof(int) + 2 * sizeof(SelGroup) + 2 * sizeof(int) + 6 * sizeof(u64)) + 64;
   }

@@ -43,18 +43,12 @@ static void emu_read(int ns, int F, const ReadPass& p) {
   }
 }
 
-// qm_lean_kernel<PAIRED, SEL, PH, WIDE, NQ> as three waves; the runtime flags -> the instantiation, as qmk_launch_lean picks it
-template <bool PAIRED, bool SEL, bool PH, bool WIDE, bool NQ> static void emu_lean_waves(const DevIndex& ix, const ReadBatch& B) {
-  const int NW = 3;
-  for (int w = 0; w < NW; ++w) lean_wave<PAIRED, SEL, PH, WIDE, NQ>(ix, B, w, NW, garbage_slab<LeanMem>());
-}
+// qm_lean_kernel<PAIRED, SEL, PH, WIDE, NQ> as three waves; the runtime flags -> the instantiation by lean_dispatch, as the library's launchers pick it
 template <bool WIDE, bool NQ> static void emu_lean(bool paired, bool sel, const DevIndex& ix, const ReadBatch& B) {
-  switch ((paired ? 4 : 0) | (sel ? 2 : 0) | (ix.ph ? 1 : 0)) {
-    case 0: emu_lean_waves<false, false, false, WIDE, NQ>(ix, B); break; case 1: emu_lean_waves<false, false, true, WIDE, NQ>(ix, B); break;
-    case 2: emu_lean_waves<false, true, false, WIDE, NQ>(ix, B); break;  case 3: emu_lean_waves<false, true, true, WIDE, NQ>(ix, B); break;
-    case 4: emu_lean_waves<true, false, false, WIDE, NQ>(ix, B); break;  case 5: emu_lean_waves<true, false, true, WIDE, NQ>(ix, B); break;
-    case 6: emu_lean_waves<true, true, false, WIDE, NQ>(ix, B); break;   default: emu_lean_waves<true, true, true, WIDE, NQ>(ix, B); break;
-  }
+  lean_dispatch(paired, sel, ix.ph != nullptr, [&](auto P, auto S, auto H) {
+    const int NW = 3;
+    for (int w = 0; w < NW; ++w) lean_wave<decltype(P)::value, decltype(S)::value, decltype(H)::value, WIDE, NQ>(ix, B, w, NW, garbage_slab<LeanMem>());
+  });
 }
 // QM_EMU_LEAN_STATS=2: besides the counts, the reads each kernel left, by index (one line per kernel and pass)
 static bool lean_stats_list() { const char* e = getenv("QM_EMU_LEAN_STATS"); return e && e[0] == '2'; }
@@ -319,11 +313,9 @@ int qe_map(int k, const unsigned char* text, long long n, const u32* SA, long lo
       const unsigned long long prof1 = qm::qm_prof[1], prof3 = qm::qm_prof[3];
       struct ProfOut { unsigned long long a, b; long long n; ~ProfOut() { fprintf(stderr, "[qm emu prof] pair kernel: %.2f bucket loads, %.2f probe rounds per read\n", (double)(qm::qm_prof[1] - a) / n, (double)(qm::qm_prof[3] - b) / n); } } profOut{prof1, prof3, nreads};
 #endif
-      for (int w = 0; w < 3; ++w) {
-        DuoMem& M = garbage_slab<DuoMem>();
-        if (B.quasi_cov > 0.0) { if (ix.ph) duo_wave<true, true>(ix, Lb, w, 3, M); else duo_wave<false, true>(ix, Lb, w, 3, M); }
-        else { if (ix.ph) duo_wave<true, false>(ix, Lb, w, 3, M); else duo_wave<false, false>(ix, Lb, w, 3, M); }
-      }
+      duo_dispatch(ix.ph != nullptr, B.quasi_cov > 0.0, [&](auto H, auto C) {
+        for (int w = 0; w < 3; ++w) duo_wave<decltype(H)::value, decltype(C)::value>(ix, Lb, w, 3, garbage_slab<DuoMem>());
+      });
       PairBatch Pg; memset(&Pg, 0, sizeof(Pg));           // the general kernel's lists through stage B: what a merged pair must equal
       std::vector<u32> hcg(nunits + 1, 0);
       Pg.n = nunits; Pg.paired = 1; Pg.off1 = off1; Pg.off2 = off2; Pg.lcnt = lcnt.data(); Pg.loff = loff.data(); Pg.lists = lists.data(); Pg.cnt = hcg.data();
