@@ -20,6 +20,7 @@
 // (k1, k2) < (a1, a2) for the rank sorts' keys (k2 and a2 below 2^32: query end << 16 | lane), counted into cnt: the borrow of the
 // 96-bit subtraction (k1 : k2) - (a1 : a2), added with carry -- four full-rate instructions.  (Written as compares, or as __builtin_subc,
 // the compiler makes three 64-bit compares of it, which run at a fraction of the rate.)  A key of all ones is below nothing.
+// (The carry chain and the emulation's expression are held to each other on the device: tests/test_wave_primitives_gpu.py, op key_count.)
 QM_DEV void key_count(u64 c1, u64 c2, u64 a1, u64 a2, int& cnt) {
 #ifdef QM_EMU
   cnt += (int)(c1 < a1) | ((int)(c1 == a1) & (int)((u32)c2 < (u32)a2));

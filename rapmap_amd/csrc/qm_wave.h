@@ -8,6 +8,11 @@
 // never shipped in the product library) an LV<T> is a 64-entry array and
 // QM_LANES is a loop, so the *same source* runs lane-by-lane on a CPU and can
 // be checked against the oracle without a GPU.
+//
+// Every primitive below therefore exists twice, and the CPU suite is worth what the two editions' agreement is worth.  They are held to each
+// other, and to a numpy restatement of the comment above each primitive, bit for bit: tests/test_wave_primitives.py (the emulation edition) and
+// tests/test_wave_primitives_gpu.py (the device edition, through tests/device/qm_probe.hip); the probe body both run is
+// tests/device/qm_wave_probe.inl, the inputs and the restatements are in tests/wave_cases.py.  A new primitive gets an op there.
 #pragma once
 #include <stdint.h>
 
@@ -48,6 +53,7 @@ QM_DEV u64 ballot(const LV<bool>& b) {
   for (int l = 0; l < 64; ++l) m |= (u64)(b.v[l] ? 1 : 0) << l;
   return m;
 }
+// x of lane `lane`; `lane` is wave-uniform and in 0 .. 63 (the device reads it from the first active lane)
 template <typename T> QM_DEV T read_lane(const LV<T>& x, int lane) { return x.v[lane]; }
 QM_DEV int ctz64(u64 x) { return x ? __builtin_ctzll(x) : 64; }
 QM_DEV int popc64(u64 x) { return __builtin_popcountll(x); }
@@ -63,6 +69,7 @@ QM_DEV void atomic_min_u64(u64* p, u64 v) { if (v < *p) *p = v; }
 QM_DEV void atomic_max_u64(u64* p, u64 v) { if (v > *p) *p = v; }
 QM_DEV void atomic_or_u64(u64* p, u64 v) { *p |= v; }
 QM_DEV u64 atomic_add_u64(u64* p, u64 v) { u64 o = *p; *p = o + v; return o; }
+// x itself, which must hold one value in every active lane (the device hands back the first active lane's)
 template <typename T> QM_DEV T uniform(T x) { return x; }
 #else
 QM_DEV u64 ballot(const LV<bool>& b) { return __builtin_amdgcn_ballot_w64(b.v[0]); }
@@ -85,7 +92,7 @@ QM_DEV void atomic_min_u64(u64* p, u64 v) { atomicMin(p, v); }
 QM_DEV void atomic_max_u64(u64* p, u64 v) { atomicMax(p, v); }
 QM_DEV void atomic_or_u64(u64* p, u64 v) { atomicOr(p, v); }
 QM_DEV u64 atomic_add_u64(u64* p, u64 v) { return atomicAdd(p, v); }
-// tell the compiler a value is wave-uniform (keeps control flow on the scalar unit)
+// tell the compiler a value is wave-uniform (keeps control flow on the scalar unit); it must be: the first active lane's value is what comes back
 QM_DEV int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 QM_DEV u32 uniform(u32 x) { return (u32)__builtin_amdgcn_readfirstlane((int)x); }
 QM_DEV u64 uniform(u64 x) {
@@ -105,7 +112,8 @@ QM_DEV u64 mulhi64(u64 a, u64 b) { return __umul64hi(a, b); }
 
 #ifdef QM_EMU
 QM_DEV int wave_max(const LV<int>& x) { int m = x.v[0]; for (int l = 1; l < 64; ++l) m = x.v[l] > m ? x.v[l] : m; return m; }
-// inclusive scans over the lanes: x[l] = x[0] + ... + x[l]  /  max(x[0], ..., x[l]) (values >= 0)
+// inclusive scans over the lanes: x[l] = x[0] + ... + x[l]  /  max(x[0], ..., x[l]) (lane_scan_max: values >= 0 -- the device takes 0 as the
+// identity; all 64 lanes active)
 QM_DEV void lane_scan_add(LV<int>& x) { for (int l = 1; l < 64; ++l) x.v[l] += x.v[l - 1]; }
 QM_DEV void lane_scan_max(LV<int>& x) { for (int l = 1; l < 64; ++l) x.v[l] = x.v[l - 1] > x.v[l] ? x.v[l - 1] : x.v[l]; }
 // out[l] = in[(l - 1) & 63]: every lane reads its lower neighbour (wrapping)
@@ -132,7 +140,7 @@ QM_DEV void group_min(LV<int>& x, int G) {
 QM_DEV int clz64(u64 x) { return x ? __builtin_clzll(x) : 64; }
 QM_DEV u64 load_u64_unaligned(const unsigned char* p) { u64 v; __builtin_memcpy(&v, p, 8); return v; }
 QM_DEV u32 load_u32_unaligned(const unsigned char* p) { u32 v; __builtin_memcpy(&v, p, 4); return v; }
-// v_perm_b32 with selectors 0..7: byte j of the result = byte sel_j of the eight bytes {hi, lo} (0..3 from lo, 4..7 from hi)
+// v_perm_b32 with selectors 0..7 (and 0x0c; the instruction's other selectors are not emulated): byte j of the result = byte sel_j of the eight bytes {hi, lo} (0..3 from lo, 4..7 from hi)
 QM_DEV u32 perm8(u32 hi, u32 lo, u32 sel) {                 // (selector 0x0c: the constant byte 0x00)
   const u64 tab = ((u64)hi << 32) | lo; u32 r = 0;
   for (int j = 0; j < 4; ++j) { const u32 sj = (sel >> (8 * j)) & 0xff; if (sj != 0x0c) r |= (u32)((tab >> (8 * (sj & 7))) & 0xff) << (8 * j); }
@@ -171,7 +179,7 @@ template <int N> QM_DEV void load_8_16xN(const u64* const* B, const int* bit, u6
 // ---- half-wavefront helpers (qm_duo.inl: lanes 0-31 and lanes 32-63 each work on a read of their own)
 // every lane gets the 32 ballot bits of its own half
 QM_DEV void half_ballot(const LV<bool>& b, LV<u32>& out) { const u64 m = ballot(b); for (int l = 0; l < 64; ++l) out.v[l] = (u32)(m >> (l & 32)); }
-// out[l] = x[lane idx[l] of l's half]
+// out[l] = x[lane idx[l] & 31 of l's half]; wave_read: out[l] = x[lane idx[l] & 63]
 QM_DEV void half_read(const LV<u32>& x, const LV<int>& idx, LV<u32>& out) { LV<u32> t; for (int l = 0; l < 64; ++l) t.v[l] = x.v[(l & 32) + (idx.v[l] & 31)]; out = t; }
 QM_DEV void wave_read(const LV<u32>& x, const LV<int>& idx, LV<u32>& out) { LV<u32> t; for (int l = 0; l < 64; ++l) t.v[l] = x.v[idx.v[l] & 63]; out = t; }
 // every lane gets the OR over its aligned group of 8 lanes (lean_h2m: a row of an 8 x 8 tile)
@@ -432,6 +440,7 @@ QM_DEV void quarters_sum_f64(LV<double>& x) {
 }
 #endif
 
+// the lanes below l (0 .. 63) as a ballot mask
 QM_DEV u64 lanemask_lt(int l) { return l ? (~0ULL >> (64 - l)) : 0ULL; }
 
 // An N x 64-bit unsigned integer with just the operators the collector's per-position flag word needs (shifts, and / or / not,

@@ -15,15 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, os.path.join(HERE, "emu"))
 from oracle import oracle  # noqa: E402
 import emu  # noqa: E402
-from parity_cases import ksw_cases, ksw_mutate  # noqa: E402
-
-
-# (match, mismatch, gap open, gap extend, band): bands <= 15 run on the register edition of the row kernel ("32"), <= 33 on the
-# 64-slot ring, <= 97 on 128 slots, everything else (and the "whole matrix" band -1) on 1024
-SCHEMES = [(2, -4, 4, 2, 15), (2, -4, 4, 2, 5), (1, -1, 1, 1, 15), (2, -6, 5, 3, 33), (2, -4, 4, 2, 0), (4, -4, 6, 2, 20),
-           (2, -4, 4, 2, 1), (2, -6, 5, 3, 8), (1, 0, 25, 25, 15), (2, -4, 4, 2, 14), (2, -4, 4, 2, 16),
-           (2, -4, 4, 2, 34), (2, -4, 4, 2, 40), (2, -6, 5, 3, 64), (1, -1, 1, 1, 97), (2, -4, 4, 2, 98), (2, -4, 4, 2, 150),
-           (2, -4, 4, 2, 1000), (2, -4, 4, 2, -1)]
+import ksw_rows_cases as kc  # noqa: E402
 
 
 def _rows(el, grp, a, b, q_, e_, w, ring=-1):
@@ -37,141 +29,56 @@ def _rows(el, grp, a, b, q_, e_, w, ring=-1):
     return list(out)
 
 
-@pytest.mark.parametrize("scheme", SCHEMES)
+def rows(groups, scheme, ring=-1):
+    """the lane emulation's row kernel, a wavefront (group) at a time (tests/ksw_rows_cases.py)"""
+    el = emu._lib()
+    return [_rows(el, grp, *scheme, ring)[:len(grp)] for grp in groups]
+
+
+def rows8(groups, scheme):
+    """... eight alignments of one shape per wavefront"""
+    el = emu._lib()
+    outs = []
+    for grp in groups:
+        n = len(grp)
+        dummy = np.zeros(1, dtype=np.uint8)
+        qp = (C.c_void_p * 8)(*[g[0].ctypes.data for g in grp] + [dummy.ctypes.data] * (8 - n))
+        tp = (C.c_void_p * 8)(*[g[1].ctypes.data for g in grp] + [dummy.ctypes.data] * (8 - n))
+        out = (C.c_int * 8)()
+        el.qe_ksw_rows8(n, len(grp[0][0]), qp, len(grp[0][1]), tp, *scheme, out)
+        outs.append(list(out)[:n])
+    return outs
+
+
+# the bodies of the row-kernel tests live in tests/ksw_rows_cases.py; test_ksw_rows_gpu.py runs them on the device
+@pytest.mark.parametrize("scheme", kc.SCHEMES)
 def test_ksw_rows_kernel_four_at_a_time(scheme):
-    """the 16-lane-row kernel (four alignments of different shapes per wavefront, idle rows included) against the oracle"""
-    a, b, q_, e_, w = scheme
-    ol = oracle._lib(); el = emu._lib()
-    ol.qo_ksw_extz2.restype = C.c_int
-    cases = list(ksw_cases(4321 + w, 400))
-    rng = np.random.default_rng(5)
-    bad = []
-    for i in range(0, len(cases), 4):
-        grp = cases[i:i + 4]
-        if rng.random() < 0.2:
-            grp = grp[:int(rng.integers(1, 4))]            # a partly filled wavefront
-        out = _rows(el, grp, a, b, q_, e_, w)
-        for k, (qq, tt) in enumerate(grp):
-            ref = ol.qo_ksw_extz2(len(qq), qq.ctypes.data_as(C.c_void_p), len(tt), tt.ctypes.data_as(C.c_void_p), a, b, q_, e_, w)
-            if out[k] != ref:
-                bad.append((k, len(qq), len(tt), ref, out[k]))
-    assert not bad, "%d mismatches, first: %r" % (len(bad), bad[:5])
+    kc.four_at_a_time(rows, scheme)
 
 
-@pytest.mark.parametrize("ring", [32, 64, 128, 1024])
+@pytest.mark.parametrize("ring", kc.RINGS)
 def test_ksw_rows_every_ring_gives_the_same_scores(ring):
-    """a band that fits the smallest ring must score the same on the larger ones (the ring is storage, not arithmetic); 32: the
-    register edition, bands up to 15 only"""
-    ol = oracle._lib(); el = emu._lib()
-    ol.qo_ksw_extz2.restype = C.c_int
-    cases = list(ksw_cases(99, 200))
-    for w in ((15, 7) if ring == 32 else (15, 33)):
-        for i in range(0, len(cases), 4):
-            grp = cases[i:i + 4]
-            out = _rows(el, grp, 2, -4, 4, 2, w, ring)
-            for k, (qq, tt) in enumerate(grp):
-                ref = ol.qo_ksw_extz2(len(qq), qq.ctypes.data_as(C.c_void_p), len(tt), tt.ctypes.data_as(C.c_void_p), 2, -4, 4, 2, w)
-                assert out[k] == ref, (ring, w, len(qq), len(tt), ref, out[k])
+    kc.every_ring_gives_the_same_scores(rows, ring)
 
 
-@pytest.mark.parametrize("qmax", [256, 512])
+@pytest.mark.parametrize("qmax", kc.QMAX)
 def test_ksw_rows_longest_alignments(qmax):
-    """queries of up to 512 bases against targets 20 longer (the longest the -s path produces), narrow to full band"""
-    ol = oracle._lib(); el = emu._lib()
-    ol.qo_ksw_extz2.restype = C.c_int
-    rng = np.random.default_rng(31 + qmax)
-    for w in (15, 33, 60, 97, 200, -1):
-        grp = []
-        for _ in range(4):
-            q = rng.integers(0, 4, int(rng.integers(qmax - 26, qmax + 1))).astype(np.uint8)
-            t = ksw_mutate(rng, q, len(q) + 20, sub=0.03, indel=0.01)
-            grp.append((q, t))
-        out = _rows(el, grp, 2, -4, 4, 2, w)
-        for k, (qq, tt) in enumerate(grp):
-            ref = ol.qo_ksw_extz2(len(qq), qq.ctypes.data_as(C.c_void_p), len(tt), tt.ctypes.data_as(C.c_void_p), 2, -4, 4, 2, w)
-            assert out[k] == ref, (w, len(qq), len(tt), ref, out[k])
+    kc.longest_alignments(rows, qmax)
 
 
-@pytest.mark.parametrize("w", [15, 40, 120])
+@pytest.mark.parametrize("w", kc.BANDS_EVERY_TLEN)
 def test_ksw_rows_every_target_length(w):
-    """query 100, perfect and 1-error targets of every length 1..160: the rounds where the band has shrunk to its last cells
-    sit at a different place of the 16-byte vectors for every residue of tlen mod 16"""
-    ol = oracle._lib(); el = emu._lib()
-    ol.qo_ksw_extz2.restype = C.c_int
-    rng = np.random.default_rng(9)
-    for t0 in range(1, 161, 4):
-        grp = []
-        for tlen in range(t0, t0 + 4):
-            q = rng.integers(0, 4, 100).astype(np.uint8)
-            t = np.resize(q, tlen).copy()
-            if tlen > 3:
-                t[tlen // 2] ^= 1
-            grp.append((q, t))
-        out = _rows(el, grp, 2, -4, 4, 2, w)
-        for k in range(4):
-            qq, tt = grp[k]
-            ref = ol.qo_ksw_extz2(100, qq.ctypes.data_as(C.c_void_p), len(tt), tt.ctypes.data_as(C.c_void_p), 2, -4, 4, 2, w)
-            assert out[k] == ref, (w, t0 + k, ref, out[k])
+    kc.every_target_length(rows, w)
 
 
-@pytest.mark.parametrize("scheme", [(2, -4, 4, 2, 15), (2, -6, 5, 3, 8), (1, -1, 1, 1, 0), (2, -4, 4, 2, 5), (1, 0, 25, 25, 15)])
+@pytest.mark.parametrize("scheme", kc.SAME_SHAPE_SCHEMES)
 def test_ksw_rows_same_shape_wavefronts(scheme):
-    """four (or fewer: idle rows) alignments of ONE shape per wavefront -- the register edition then keeps the band's geometry on
-    the scalar unit (sel_ksw_extz2_rows_reg<.., UNI = true>): every query length class and target length residue, indels, N's"""
-    a, b, q_, e_, w = scheme
-    ol = oracle._lib(); el = emu._lib()
-    ol.qo_ksw_extz2.restype = C.c_int
-    rng = np.random.default_rng(77 + w)
-    bad = []
-    shapes = [(100, 120), (100, 100), (100, 87), (1, 1), (1, 21), (31, 51), (75, 95), (140, 160), (50, 1), (16, 16), (17, 33), (128, 148)]
-    shapes += [(int(rng.integers(1, 141)), int(rng.integers(1, 161))) for _ in range(60)]
-    for qlen, tlen in shapes:
-        for n in (4, 4, int(rng.integers(1, 4))):
-            grp = []
-            for _ in range(n):
-                q = rng.integers(0, 4, qlen).astype(np.uint8)
-                if rng.random() < 0.2:
-                    q[rng.integers(0, qlen)] = 4
-                t = ksw_mutate(rng, q, tlen) if rng.random() < 0.85 else rng.integers(0, 5, tlen).astype(np.uint8)
-                grp.append((q, t))
-            out = _rows(el, grp, a, b, q_, e_, w)
-            for k, (qq, tt) in enumerate(grp):
-                ref = ol.qo_ksw_extz2(len(qq), qq.ctypes.data_as(C.c_void_p), len(tt), tt.ctypes.data_as(C.c_void_p), a, b, q_, e_, w)
-                if out[k] != ref:
-                    bad.append((k, n, len(qq), len(tt), ref, out[k]))
-    assert not bad, "%d mismatches, first: %r" % (len(bad), bad[:5])
+    kc.same_shape_wavefronts(rows, scheme)
 
 
-@pytest.mark.parametrize("scheme", [(2, -4, 4, 2, 15), (2, -6, 5, 3, 8), (1, -1, 1, 1, 0), (2, -4, 4, 2, 5)])
+@pytest.mark.parametrize("scheme", kc.EIGHT_SCHEMES)
 def test_ksw_rows_eight_per_wavefront(scheme):
-    """eight alignments of one shape as two sets of state through the same rounds (sel_ksw_extz2_rows_reg<.., UNI, 2>, what
-    qm_sel_align2_kernel runs when a wavefront's eight tasks share their lengths), 5 .. 8 of them real"""
-    a, b, q_, e_, w = scheme
-    ol = oracle._lib(); el = emu._lib()
-    ol.qo_ksw_extz2.restype = C.c_int
-    rng = np.random.default_rng(177 + w)
-    bad = []
-    shapes = [(100, 120), (100, 100), (100, 87), (1, 1), (31, 51), (75, 95), (140, 160), (16, 16), (17, 33), (128, 148)]
-    shapes += [(int(rng.integers(1, 141)), int(rng.integers(1, 161))) for _ in range(40)]
-    for qlen, tlen in shapes:
-        for n in (8, int(rng.integers(5, 8))):
-            grp = []
-            for _ in range(n):
-                q = rng.integers(0, 4, qlen).astype(np.uint8)
-                if rng.random() < 0.2:
-                    q[rng.integers(0, qlen)] = 4
-                t = ksw_mutate(rng, q, tlen) if rng.random() < 0.85 else rng.integers(0, 5, tlen).astype(np.uint8)
-                grp.append((q, t))
-            dummy = np.zeros(1, dtype=np.uint8)
-            qp = (C.c_void_p * 8)(*[g[0].ctypes.data for g in grp] + [dummy.ctypes.data] * (8 - n))
-            tp = (C.c_void_p * 8)(*[g[1].ctypes.data for g in grp] + [dummy.ctypes.data] * (8 - n))
-            out = (C.c_int * 8)()
-            el.qe_ksw_rows8(n, qlen, qp, tlen, tp, a, b, q_, e_, w, out)
-            for k, (qq, tt) in enumerate(grp):
-                ref = ol.qo_ksw_extz2(len(qq), qq.ctypes.data_as(C.c_void_p), len(tt), tt.ctypes.data_as(C.c_void_p), a, b, q_, e_, w)
-                if out[k] != ref:
-                    bad.append((k, n, qlen, tlen, ref, out[k]))
-    assert not bad, "%d mismatches, first: %r" % (len(bad), bad[:5])
+    kc.eight_per_wavefront(rows8, scheme)
 
 
 @pytest.mark.parametrize("scheme", [(2, -4, 4, 2, 15), (2, -4, 4, 2, 1), (2, -4, 4, 2, 5), (1, -1, 1, 1, 15), (2, -6, 5, 3, 33), (4, -4, 6, 2, 20),

@@ -1,0 +1,420 @@
+"""Inputs and expected answers of the primitive tests (test_wave_primitives.py: the emulation edition of rapmap_amd/csrc/qm_wave.h,
+test_wave_primitives_gpu.py: the device edition).  Both editions run tests/device/qm_wave_probe.inl, one call of a primitive per wave:
+
+    run(op, prm[W], a / b / c / d [W, 64] uint64, mem[W, MEMB] uint8, atom[W] uint64) -> (out[W, NOUT, 64] uint64, atom[W] uint64)
+
+A case is a name ("group_min[8]": the op and, where there is one, the wave-uniform parameter), the inputs of its W waves -- stacked as the
+waves of one launch -- and `want`: per output row the [W, 64] array the comment above the primitive promises, restated in one line of numpy
+(`EXPECT`).  Rows an op does not write keep the 0xEE the runner fills them with.  Everything is compared bit for bit.
+
+The cross-lane inputs: the 64 one-hot vectors (positive in zeros, and negative in zeros for the minima), permutations of distinct values,
+all-equal vectors, 16 seeded random vectors and the integer extremes -- with one-hot and distinct-per-lane inputs every output lane names the
+source lanes it read, so a wrong pairing, row mask or fill cannot pass.  The inputs stay inside the preconditions of the primitives:
+lane_scan_max values >= 0 (the device's identity is 0), lane_scan_add sums that fit an int, perm8 selectors 0 .. 7 and 0x0c, align_bytes
+shifts 0 .. 3, read_lane and uniform wave-uniform arguments, group_min G a power of two, group_sum_f64 G 8 or 16."""
+import numpy as np
+
+MEMB = 4096          # bytes of read-only memory per wave (QP_MEMB)
+NOUT = 6             # output rows (QP_NOUT)
+FILL = np.uint64(0xEEEEEEEEEEEEEEEE)
+L = np.arange(64)
+M32 = np.uint64(0xffffffff)
+INT_MIN, INT_MAX = -(1 << 31), (1 << 31) - 1
+
+
+# ---- views
+def i32(x):
+    return (np.asarray(x, dtype=np.uint64) & M32).astype(np.uint32).view(np.int32)
+
+
+def u32(x):
+    return (np.asarray(x, dtype=np.uint64) & M32).astype(np.uint32)
+
+
+def as_u64(x):
+    """an int32 / uint32 / uint64 result as the probe stores it: (u64)(u32)x"""
+    x = np.asarray(x)
+    if x.dtype == np.int32:
+        x = x.view(np.uint32)
+    return x.astype(np.uint64)
+
+
+def f64(x):
+    return np.ascontiguousarray(x, dtype=np.uint64).view(np.float64)
+
+
+def bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+def lanes(v):
+    """a per-wave value in all 64 lanes"""
+    return np.repeat(np.asarray(v)[:, None], 64, axis=1)
+
+
+def groups(x, g, f):
+    """f over every aligned group of g lanes (last axis), the result in every lane of the group"""
+    w = x.shape[0]
+    return np.repeat(f(x.reshape(w, 64 // g, g)), g, axis=1).reshape(w, 64)
+
+
+def pyints(f, *xs):
+    """f over Python ints, element by element -> uint64"""
+    flat = [np.asarray(x, dtype=np.uint64).ravel() for x in xs]
+    out = np.array([f(*(int(v) for v in t)) & 0xffffffffffffffff for t in zip(*flat)], dtype=np.uint64)
+    return out.reshape(np.asarray(xs[0]).shape)
+
+
+# ---- input sets ([W, 64] uint64)
+def ints_xlane(seed, extremes=True):
+    """cross-lane int inputs (the 32-bit pattern in the low half)"""
+    rng = np.random.default_rng(seed)
+    rows = []
+    rows += [np.where(L == i, 0x40000000 + 64 * i + 1, 0) for i in range(64)]                    # one-hot, positive in zeros
+    rows += [np.where(L == i, -(i + 1), 0) for i in range(64)]                                    # one-hot, negative in zeros
+    rows += [rng.permutation(64) * 1000 + 7, rng.permutation(64) - 32, (rng.permutation(64) - 31) * 30000001, 63 - L, L.copy()]
+    rows += [np.full(64, v) for v in (0, -1, 12345)]
+    rows += [rng.integers(INT_MIN, INT_MAX + 1, 64) for _ in range(16)]
+    if extremes:
+        rows += [np.where(L == i, INT_MAX, INT_MIN) for i in (0, 15, 16, 31, 32, 63)] + [np.where(L == i, INT_MIN, INT_MAX) for i in (0, 15, 16, 31, 32, 63)]
+        rows += [np.where(L % 2 == 0, INT_MIN, INT_MAX), np.full(64, INT_MIN), np.full(64, INT_MAX)]
+    return (np.array(rows, dtype=np.int64) & 0xffffffff).astype(np.uint64)
+
+
+def u64_xlane(seed):
+    """cross-lane 64-bit inputs: both dwords differ from lane to lane"""
+    rng = np.random.default_rng(seed)
+    rows = [np.where(L == i, np.uint64(0x8000000100000000 + (i << 40) + i + 1), np.uint64(0)) for i in range(64)]
+    p, q = rng.permutation(64).astype(np.uint64), rng.permutation(64).astype(np.uint64)
+    rows += [(p << np.uint64(32)) | q, (q << np.uint64(56)) | (p << np.uint64(8)) | np.uint64(0x00a5000000c30000)]
+    rows += [np.full(64, v, dtype=np.uint64) for v in (0, 0xffffffffffffffff, 0x0123456789abcdef)]
+    rows += [rng.integers(0, 1 << 64, 64, dtype=np.uint64) for _ in range(16)]
+    return np.array(rows, dtype=np.uint64)
+
+
+def doubles_xlane(seed):
+    """magnitudes from 2^-40 to 2^60 with mixed signs (the order of the additions shows in the bits), signed zeros, one-hot"""
+    rng = np.random.default_rng(seed)
+    rows = [np.where(L == i, 1.5 + i, 0.0) for i in range(64)]
+    rows += [np.where(L == i, -0.0, 0.0) for i in (0, 7, 8, 15, 16, 32, 63)] + [np.full(64, -0.0), np.full(64, 0.0), np.where(L % 2 == 0, -0.0, 0.0)]
+    for _ in range(24):
+        rows.append(rng.choice([-1.0, 1.0], 64) * (1.0 + rng.random(64)) * np.exp2(rng.integers(-40, 61, 64).astype(np.float64)))
+    rows += [rng.permutation(64) + 0.1, np.full(64, 0.1), (1.0 + rng.random(64)) * 2.0 ** 60, np.where(L % 2 == 0, 2.0 ** 60, -(2.0 ** 60)) + L * 2.0 ** 8]
+    return bits(np.array(rows, dtype=np.float64))
+
+
+def scalars64(seed, n=8):
+    """per-lane 64-bit operands: single bits, their complements, runs of ones, extremes, random"""
+    rng = np.random.default_rng(seed)
+    one = np.uint64(1)
+    rows = [one << L.astype(np.uint64), ~(one << L.astype(np.uint64)), (one << L.astype(np.uint64)) - one, ~((one << L.astype(np.uint64)) - one)]
+    ext = np.array([0, 1, 2, 0xffffffffffffffff, 0x8000000000000000, 0x7fffffffffffffff, 0xffffffff, 0x100000000, 0x80000000, 0x7fffffff,
+                    0xffff, 0x10000, 0x8000, 0x7fff, 0xffffffff00000000, 0x00000000ffffffff], dtype=np.uint64)
+    rows.append(np.resize(ext, 64))
+    rows += [rng.integers(0, 1 << 64, 64, dtype=np.uint64) for _ in range(n)]
+    rows += [rng.integers(0, 1 << 64, 64, dtype=np.uint64) >> rng.integers(0, 64, 64).astype(np.uint64) for _ in range(n)]
+    return np.array(rows, dtype=np.uint64)
+
+
+def halves(seed):
+    """pairs of dwords whose 16-bit halves are every pair of 0, 1, 0x7fff, 0x8000, 0xffff and random ones"""
+    rng = np.random.default_rng(seed)
+    h = np.array([0, 1, 0x7fff, 0x8000, 0xffff, 0x8001, 0xfffe, 0x1234], dtype=np.uint64)
+    lo_a, lo_b = [x.ravel() for x in np.meshgrid(h, h)]                                           # 64 pairs: the low halves
+    A, B = [], []
+    for s in range(8):                                                                            # ... against each high-half pair, rotated
+        A.append(lo_a | (np.roll(lo_a, 8 * s + 1) << np.uint64(16))); B.append(lo_b | (np.roll(lo_b, 8 * s + 3) << np.uint64(16)))
+    for _ in range(8):
+        A.append(rng.integers(0, 1 << 32, 64, dtype=np.uint64)); B.append(rng.integers(0, 1 << 32, 64, dtype=np.uint64))
+    return np.array(A, dtype=np.uint64), np.array(B, dtype=np.uint64)
+
+
+class Case:
+    def __init__(self, name, a, b=None, c=None, d=None, prm=None, mem_seed=None, atom=None):
+        self.name = name
+        self.op = name.split("[")[0]
+        self.a = np.ascontiguousarray(a, dtype=np.uint64)
+        w = self.a.shape[0]
+        z = np.zeros((w, 64), dtype=np.uint64)
+        self.b, self.c, self.d = [z if x is None else np.ascontiguousarray(x, dtype=np.uint64) for x in (b, c, d)]
+        self.prm = np.ascontiguousarray(np.zeros(w) if prm is None else np.broadcast_to(prm, (w,)), dtype=np.int32)
+        self.mem = np.random.default_rng(mem_seed if mem_seed is not None else 1).integers(0, 256, (w, MEMB), dtype=np.uint8)
+        self.atom = np.ascontiguousarray(np.zeros(w) if atom is None else atom, dtype=np.uint64)
+        assert self.b.shape == self.a.shape == self.c.shape == self.d.shape == (w, 64)
+        self.w = w
+
+    def args(self):
+        return self.prm, self.a, self.b, self.c, self.d, self.mem, self.atom
+
+    def want(self):
+        """({output row: [W, 64] uint64}, atom[W] afterwards)"""
+        r = EXPECT[self.op](self)
+        if isinstance(r, tuple):
+            return {}, r[1]
+        if not isinstance(r, dict):
+            r = {0: r}
+        return {k: np.asarray(v, dtype=np.uint64) for k, v in r.items()}, self.atom
+
+
+# ---- the restatements: what the comment above each primitive promises
+def _ballot(k):
+    return ((k.a & np.uint64(1)) << L.astype(np.uint64)).sum(axis=1, dtype=np.uint64)
+
+
+def _mem_dwords(k, byte_off, n):
+    """n consecutive dwords of each lane's memory from its byte offset -> [W, 64, n]"""
+    idx = np.asarray(byte_off, dtype=np.int64)[:, :, None] + np.arange(4 * n)[None, None, :]
+    by = k.mem[np.arange(k.w)[:, None, None], idx].astype(np.uint64).reshape(k.w, 64, n, 4)
+    return by[..., 0] | (by[..., 1] << np.uint64(8)) | (by[..., 2] << np.uint64(16)) | (by[..., 3] << np.uint64(24))
+
+
+def _pairs(dw):
+    """[W, 64, 2n] dwords -> n output rows of u64"""
+    return [dw[..., 2 * i] | (dw[..., 2 * i + 1] << np.uint64(32)) for i in range(dw.shape[-1] // 2)]
+
+
+def _rows(lst, first=0):
+    return {first + i: v for i, v in enumerate(lst)}
+
+
+def _pick(x, lane):
+    """x[w, lane[w, l]]"""
+    return np.take_along_axis(x, np.asarray(lane, dtype=np.int64), axis=1)
+
+
+def _sum8(x):
+    """((x0 + x1) + (x2 + x3)) + ((x4 + x5) + (x6 + x7)) over the last axis, eight at a time"""
+    p = x[..., 0::2] + x[..., 1::2]; q = p[..., 0::2] + p[..., 1::2]
+    return q[..., 0::2] + q[..., 1::2]
+
+
+def _sum16(x):
+    r = _sum8(x)
+    return r[..., 0::2] + r[..., 1::2]
+
+
+def _perm8(hi, lo, sel):
+    tab = (hi << 32) | lo
+    return sum((0 if ((sel >> (8 * j)) & 0xff) == 0x0c else ((tab >> (8 * ((sel >> (8 * j)) & 7))) & 0xff)) << (8 * j) for j in range(4))
+
+
+def _pk(a, b, f):
+    a, b = u32(a).astype(np.int64), u32(b).astype(np.int64)
+    return ((f(a & 0xffff, b & 0xffff) & 0xffff) | ((f(a >> 16, b >> 16) & 0xffff) << 16)).astype(np.uint64)
+
+
+def _s16(x):
+    return np.where(x >= 0x8000, x - 0x10000, x)
+
+
+def _row16(k, f):
+    return as_u64(f(i32(k.a).reshape(k.w, 4, 16), k.prm.astype(np.int32)[:, None, None]).reshape(k.w, 64).astype(np.int32))
+
+
+def _scan_excl(x, fill):
+    return np.maximum.accumulate(np.concatenate([np.broadcast_to(fill, x[..., :1].shape), x[..., :15]], axis=2), axis=2)
+
+
+def _shl1(x, fill):
+    return np.concatenate([x[..., 1:], np.broadcast_to(fill, x[..., :1].shape)], axis=2)
+
+
+def _wide(k, n, lane):
+    return _rows([_pick(x, lane) for x in (k.a, k.b, k.c, k.d)[:n]])
+
+
+EXPECT = {
+    "ballot": lambda k: lanes(_ballot(k)),
+    "half_ballot": lambda k: np.where(L < 32, lanes(_ballot(k) & M32), lanes(_ballot(k) >> np.uint64(32))),
+    "read_lane_i32": lambda k: as_u64(_pick(i32(k.a), lanes(k.prm & 63))),
+    "read_lane_u32": lambda k: as_u64(_pick(u32(k.a), lanes(k.prm & 63))),
+    "read_lane_u64": lambda k: _pick(k.a, lanes(k.prm & 63)),
+    "read_lane_f64": lambda k: _pick(k.a, lanes(k.prm & 63)),
+    "read_lane_w2": lambda k: _wide(k, 2, lanes(k.prm & 63)),
+    "read_lane_w4": lambda k: _wide(k, 4, lanes(k.prm & 63)),
+    "uniform_i32": lambda k: as_u64(i32(k.a)),
+    "uniform_u32": lambda k: as_u64(u32(k.a)),
+    "uniform_u64": lambda k: k.a,
+    "uniform_i64": lambda k: k.a,
+    "uniform_bool": lambda k: k.a & np.uint64(1),
+    "wave_max": lambda k: as_u64(lanes(i32(k.a).max(axis=1))),
+    "lane_scan_add": lambda k: as_u64(np.cumsum(i32(k.a), axis=1, dtype=np.int64).astype(np.int32)),
+    "lane_scan_max": lambda k: as_u64(np.maximum.accumulate(i32(k.a & np.uint64(0x7fffffff)), axis=1)),
+    "lane_rotate_up": lambda k: as_u64(i32(k.a)[:, (L - 1) & 63]),
+    "row_rotate_up": lambda k: as_u64(i32(k.a)[:, (L & ~15) | ((L - 1) & 15)]),
+    "row_last": lambda k: as_u64(i32(k.a)[:, L | 15]),
+    "row16_shl1": lambda k: _row16(k, _shl1),
+    "row16_scan_max_excl": lambda k: _row16(k, _scan_excl),
+    "row16_max_all": lambda k: as_u64(groups(i32(k.a), 16, lambda x: x.max(axis=2))),
+    "group_min": lambda k: as_u64(groups(i32(k.a), int(k.prm[0]), lambda x: x.min(axis=2))),
+    "lane_xor1": lambda k: as_u64(u32(k.a)[:, L ^ 1]),
+    "swap32_u32": lambda k: as_u64(u32(k.a)[:, L ^ 32]),
+    "swap32_u64": lambda k: k.a[:, L ^ 32],
+    "swap32_w2": lambda k: _wide(k, 2, np.broadcast_to(L ^ 32, k.a.shape)),
+    "swap32_w4": lambda k: _wide(k, 4, np.broadcast_to(L ^ 32, k.a.shape)),
+    "half_read": lambda k: as_u64(_pick(u32(k.a), (L & 32) + (i32(k.b) & 31))),
+    "wave_read": lambda k: as_u64(_pick(u32(k.a), i32(k.b) & 63)),
+    "row8_or": lambda k: as_u64(groups(u32(k.a), 8, lambda x: np.bitwise_or.reduce(x, axis=2))),
+    "half_max": lambda k: as_u64(groups(i32(k.a), 32, lambda x: x.max(axis=2))),
+    "group_sum_f64": lambda k: bits(np.repeat((_sum8 if k.prm[0] == 8 else _sum16)(f64(k.a)), int(k.prm[0]), axis=1)),
+    "wave_sum_f64": lambda k: bits(lanes((lambda r: (r[:, 0] + r[:, 1]) + (r[:, 2] + r[:, 3]))(_sum16(f64(k.a))))),
+    "quarters_sum_f64": lambda k: bits(np.tile((lambda q: (q[:, 0] + q[:, 1]) + (q[:, 2] + q[:, 3]))(f64(k.a).reshape(k.w, 4, 16)), (1, 4))),
+    "ctz64": lambda k: pyints(lambda x: (x & -x).bit_length() - 1 if x else 64, k.a),
+    "clz64": lambda k: pyints(lambda x: 64 - x.bit_length(), k.a),
+    "popc64": lambda k: pyints(lambda x: bin(x).count("1"), k.a),
+    "brev64": lambda k: pyints(lambda x: int(format(x, "064b")[::-1], 2), k.a),
+    "brev32": lambda k: pyints(lambda x: int(format(x & 0xffffffff, "032b")[::-1], 2), k.a),
+    "mulhi64": lambda k: pyints(lambda x, y: (x * y) >> 64, k.a, k.b),
+    "lanemask_lt": lambda k: pyints(lambda x: (1 << (x & 63)) - 1, k.a),
+    "perm8": lambda k: pyints(lambda hi, lo, sel: _perm8(hi & 0xffffffff, lo & 0xffffffff, sel), k.a, k.b, k.c),
+    "align_bytes": lambda k: pyints(lambda hi, lo, s: ((((hi & 0xffffffff) << 32) | (lo & 0xffffffff)) >> (8 * (s & 3))) & 0xffffffff, k.a, k.b, k.c),
+    "pk_add": lambda k: _pk(k.a, k.b, lambda x, y: x + y),
+    "pk_sub": lambda k: _pk(k.a, k.b, lambda x, y: x - y),
+    "pk_max_i": lambda k: _pk(k.a, k.b, lambda x, y: np.maximum(_s16(x), _s16(y))),
+    "pk_max_u": lambda k: _pk(k.a, k.b, np.maximum),
+    "pk_min_u": lambda k: _pk(k.a, k.b, np.minimum),
+    "load_u32_unaligned": lambda k: _mem_dwords(k, k.a % np.uint64(MEMB - 8), 1)[..., 0],
+    "load_u64_unaligned": lambda k: _pairs(_mem_dwords(k, k.a % np.uint64(MEMB - 8), 2))[0],
+    "load_16": lambda k: _rows(_pairs(_mem_dwords(k, 16 * (k.a % np.uint64(MEMB // 16)), 4))),
+    "load_32": lambda k: _rows(_pairs(_mem_dwords(k, 16 * (k.a % np.uint64(MEMB // 16 - 1)), 8))),
+    "load_16x2": lambda k: _rows(_pairs(_mem_dwords(k, 16 * (k.a % np.uint64(MEMB // 16)), 4)) + _pairs(_mem_dwords(k, 16 * (k.b % np.uint64(MEMB // 16)), 4))),
+    "load_8_16": lambda k: _rows(_pairs(_mem_dwords(k, 8 * (k.a % np.uint64(MEMB // 8)), 2)) + _pairs(_mem_dwords(k, 16 * (k.b % np.uint64(MEMB // 16)), 4))),
+    "load_48": lambda k: _rows(_pairs(_mem_dwords(k, 16 * (k.a % np.uint64(MEMB // 16 - 2)), 12))),
+    "load_uniform_i64": lambda k: _pairs(_mem_dwords(k, lanes(8 * (k.prm.view(np.uint32).astype(np.int64) % (MEMB // 8))), 2))[0],
+    "lds_dma_u32": lambda k: _mem_dwords(k, 4 * (k.a % np.uint64(MEMB // 4)), 1)[..., 0],
+    "lds_dma_u128": lambda k: _rows(_pairs(_mem_dwords(k, 16 * (k.a % np.uint64(MEMB // 16)), 4))),
+    "atomic_min_u64": lambda k: (None, np.minimum(k.atom, k.a.min(axis=1))),
+    "atomic_max_u64": lambda k: (None, np.maximum(k.atom, k.a.max(axis=1))),
+    "atomic_or_u64": lambda k: (None, k.atom | np.bitwise_or.reduce(k.a, axis=1)),
+    "atomic_add_u64": lambda k: (None, k.atom + k.a.sum(axis=1, dtype=np.uint64)),
+    "key_count": lambda k: as_u64((k.prm[:, None] + pyints(lambda c1, c2, a1, a2: (c1, c2 & 0xffffffff) < (a1, a2 & 0xffffffff), k.a, k.b, k.c, k.d).astype(np.int64)).astype(np.int32)),
+}
+
+
+# ---- the cases
+def _every_lane(x):
+    """every lane 0 .. 63 as the index, on distinct-per-lane inputs first, then on the whole input set"""
+    w = x.shape[0]
+    return (np.arange(w) * 7 + 3) % 64 if w < 64 else np.concatenate([np.arange(64), (np.arange(w - 64) * 7 + 3) % 64])
+
+
+def _scan_add_inputs():
+    x = i32(ints_xlane(21, extremes=False)).astype(np.int64)
+    x = np.where(np.abs(x) > (1 << 24), x >> 7, x)                                                # 64 of them fit an int
+    ext = [np.where(L == i, INT_MAX, -(L % 5)) for i in (0, 15, 16, 63)] + [np.where(L == i, INT_MIN, L % 7) for i in (0, 15, 16, 63)]
+    return (np.concatenate([x, np.array(ext, dtype=np.int64)]) & 0xffffffff).astype(np.uint64)
+
+
+def _fills(x):
+    """fill values below, inside and above the data, wave by wave"""
+    v = i32(x).astype(np.int64)
+    lo, hi, mid = v.min(axis=1), v.max(axis=1), np.median(v, axis=1).astype(np.int64)
+    pick = np.arange(len(v)) % 5
+    f = np.choose(pick, [np.maximum(lo - 1, INT_MIN), mid, np.minimum(hi + 1, INT_MAX), np.full(len(v), INT_MIN), np.full(len(v), INT_MAX)])
+    return f.astype(np.int32)
+
+
+def _key_count_case():
+    rng = np.random.default_rng(77)
+    F, H = 0xffffffffffffffff, 0xffffffff
+    named = [  # (c1, c2, a1, a2)
+        (5, 9, 5, 9), (0, 0, 0, 0), (F, H, F, H),                                                 # equal keys, the all-ones key among them
+        (5, 8, 5, 9), (5, 9, 5, 8), (7, 0, 7, H), (7, H, 7, 0),                                   # only the low word of c2 differs
+        (0x100000004, 9, 0x100000005, 9), (0x100000005, 9, 0x100000004, 9),                       # only the low dword of c1
+        (0x400000005, 9, 0x500000005, 9), (0x500000005, 9, 0x400000005, 9),                       # only its high dword
+        (0x100000000, 0, 0x0ffffffff, H), (0x0ffffffff, H, 0x100000000, 0),                       # a borrow rippling from c2 through c1's low dword into its high dword
+        (5, 0, 4, H), (4, H, 5, 0), (0x100000000, 0, 0x100000000, 1), (0x100000000, 1, 0x100000000, 0),
+        (0x700000000, 5, 0x6ffffffff, 6), (0x6ffffffff, 6, 0x700000000, 5),                       # ... across the boundary inside c1
+        (F, H, 0, 0), (0, 0, F, H), (F, H - 1, F, H), (F - 1, H, F, H), (F, H, F - 1, H), (F, H, F, H - 1),   # a key of all ones is below nothing
+        (0x8000000000000000, 0, 0x7fffffffffffffff, H), (0x7fffffffffffffff, H, 0x8000000000000000, 0),
+        (5, 0x100000009, 5, 0x200000009), (5, 0x100000008, 5, 9),                                 # bits of c2 / a2 beyond 2^32 are not part of the key
+    ]
+    rows = [np.resize(np.array([r[j] for r in named], dtype=np.uint64), 64) for j in range(4)]
+    A = [[np.roll(rows[j], s) if j < 2 else rows[j] for s in range(0, 64, 4)] for j in range(4)]  # every named key against every other
+    for j in range(4):
+        A[j] = [np.roll(rows[j], 5 * s) for s in range(4)] + A[j]                                 # ... and against itself, at four places of the wavefront
+        for _ in range(8):
+            r = rng.integers(0, 1 << 64, 64, dtype=np.uint64)
+            A[j].append(r >> np.uint64(40 * (j & 1)) if j & 1 else r)
+    a, b, c, d = [np.array(x, dtype=np.uint64) for x in A]
+    same = np.random.default_rng(78).random(a.shape) < 0.4                                        # random keys that agree in c1: the low words decide
+    c = np.where(same & (np.arange(a.shape[0])[:, None] >= 20), a, c)
+    return Case("key_count", a, b, c, d, prm=(np.arange(a.shape[0]) * 1000003) % 50 - 3)
+
+
+def _build():
+    I, U, D, S = ints_xlane(11), u64_xlane(12), doubles_xlane(13), scalars64(14)
+    rng = np.random.default_rng(15)
+    cs = []
+    onehot_bits = np.concatenate([np.eye(64, dtype=np.uint64), 1 - np.eye(64, dtype=np.uint64), np.zeros((1, 64), np.uint64), np.ones((1, 64), np.uint64),
+                                  rng.integers(0, 2, (16, 64)).astype(np.uint64)])
+    cs += [Case("ballot", onehot_bits), Case("half_ballot", onehot_bits)]
+    U2 = [u64_xlane(30 + j) for j in range(3)]
+    for t, x in (("i32", I), ("u32", I), ("u64", U), ("f64", D)):
+        cs.append(Case("read_lane_" + t, x, prm=_every_lane(x)))
+    cs.append(Case("read_lane_w2", U, U2[0], prm=_every_lane(U)))
+    cs.append(Case("read_lane_w4", U, U2[0], U2[1], U2[2], prm=_every_lane(U)))
+    uni = np.concatenate([S.ravel()[:256], I.ravel()[::37][:64]])                                 # one value per wave, in all its lanes
+    for t in ("i32", "u32", "u64", "i64", "bool"):
+        cs.append(Case("uniform_" + t, lanes(uni)))
+    cs += [Case("wave_max", I), Case("lane_scan_add", _scan_add_inputs()), Case("lane_scan_max", I), Case("lane_rotate_up", I),
+           Case("row_rotate_up", I), Case("row_last", I), Case("row16_max_all", I), Case("half_max", I)]
+    cs += [Case("row16_shl1", I, prm=_fills(I)), Case("row16_scan_max_excl", I, prm=_fills(I))]
+    cs += [Case("group_min[%d]" % g, I, prm=g) for g in (1, 2, 4, 8, 16, 32, 64)]
+    cs += [Case("lane_xor1", I), Case("swap32_u32", I), Case("swap32_u64", U), Case("swap32_w2", U, U2[0]), Case("swap32_w4", U, U2[0], U2[1], U2[2])]
+    idx = np.array([rng.permutation(64) for _ in range(I.shape[0] // 2)] + [rng.integers(INT_MIN, INT_MAX + 1, 64) for _ in range(I.shape[0] - I.shape[0] // 2)])
+    idx[0], idx[1], idx[2] = L, 63 - L, L ^ 32
+    cs += [Case("half_read", I, (idx & 0xffffffff).astype(np.uint64)), Case("wave_read", I, (idx & 0xffffffff).astype(np.uint64))]
+    orbits = np.concatenate([np.where(L[None, :] == np.arange(64)[:, None], np.uint64(1) << (np.arange(64)[:, None] % 32).astype(np.uint64), np.uint64(0)),
+                             (np.uint64(1) << (L % 32).astype(np.uint64))[None, :], I])
+    cs.append(Case("row8_or", orbits))
+    cs += [Case("group_sum_f64[%d]" % g, D, prm=g) for g in (8, 16)] + [Case("wave_sum_f64", D), Case("quarters_sum_f64", D)]
+    S2 = scalars64(16)[::-1]
+    cs += [Case(n, S) for n in ("ctz64", "clz64", "popc64", "brev64", "brev32")] + [Case("mulhi64", S, S2)]
+    cs.append(Case("lanemask_lt", np.array([L, 63 - L, (L * 5) % 64, L ^ 32] + [rng.permutation(64) for _ in range(4)], dtype=np.uint64)))
+    sel = np.array([[int(rng.choice([0, 1, 2, 3, 4, 5, 6, 7, 0x0c])) for _ in range(4)] for _ in range(S.shape[0] * 64)])
+    sel[:8], sel[8] = np.arange(8)[:, None], [0, 1, 2, 3]
+    sel[9], sel[10], sel[11] = [4, 5, 6, 7], [0x0c] * 4, [3, 2, 1, 0]
+    selw = (sel[:, 0] | (sel[:, 1] << 8) | (sel[:, 2] << 16) | (sel[:, 3] << 24)).astype(np.uint64).reshape(S.shape)
+    cs.append(Case("perm8", S, S2, selw))
+    cs.append(Case("align_bytes", S, S2, np.broadcast_to((L % 4).astype(np.uint64), S.shape)))
+    HA, HB = halves(17)
+    cs += [Case(n, HA, HB) for n in ("pk_add", "pk_sub", "pk_max_i", "pk_max_u", "pk_min_u")]
+    offs = np.array([L, L * 9 + 1, MEMB - 8 - L, rng.integers(0, 1 << 40, 64), rng.integers(0, MEMB, 64), (L % 8) + 8 * rng.integers(0, 500, 64)], dtype=np.uint64)
+    offs = np.concatenate([offs, rng.integers(0, 1 << 63, (10, 64), dtype=np.uint64)])           # (every offset mod 8 occurs in every wave)
+    offs2 = offs[::-1, ::-1]
+    cs += [Case("load_u32_unaligned", offs, mem_seed=2), Case("load_u64_unaligned", offs, mem_seed=3)]
+    cs += [Case(n, offs, offs2, mem_seed=4 + i) for i, n in enumerate(("load_16", "load_32", "load_16x2", "load_8_16", "load_48", "lds_dma_u32", "lds_dma_u128"))]
+    cs.append(Case("load_uniform_i64", np.zeros((80, 64), np.uint64), prm=np.concatenate([np.arange(16), [MEMB // 8 - 1, MEMB // 8, -1, INT_MAX], rng.integers(INT_MIN, INT_MAX + 1, 60)]), mem_seed=12))
+    at = np.concatenate([U, S])
+    a0 = np.resize(np.array([0, 0xffffffffffffffff, 0x8000000000000000, 0x00000001ffffffff, 12345], dtype=np.uint64), at.shape[0])
+    a0[5:] = np.where(np.arange(at.shape[0] - 5) % 3 == 0, np.sort(at[5:], axis=1)[:, 32], a0[5:])
+    cs += [Case(n, at, atom=a0) for n in ("atomic_min_u64", "atomic_max_u64", "atomic_or_u64", "atomic_add_u64")]
+    cs.append(_key_count_case())
+    return {k.name: k for k in cs}
+
+
+CASES = _build()
+NAMES = list(CASES)
+
+
+def check(run, name):
+    """run the case through `run` and hold every output row, and the atomics' words, to the restatement; returns what run gave"""
+    k = CASES[name]
+    out, atom = run(k.op, *k.args())
+    want, want_atom = k.want()
+    assert out.shape == (k.w, NOUT, 64) and atom.shape == (k.w,)
+    for r in range(NOUT):
+        w = want.get(r, np.broadcast_to(FILL, (k.w, 64)))
+        bad = np.argwhere(out[:, r, :] != w)
+        assert not len(bad), "%s: output row %d differs from the restatement in %d places, first at wave %d lane %d: got %#x, want %#x (prm %d)" % (
+            name, r, len(bad), bad[0][0], bad[0][1], int(out[bad[0][0], r, bad[0][1]]), int(w[bad[0][0], bad[0][1]]), int(k.prm[bad[0][0]]))
+    bad = np.argwhere(atom != want_atom)
+    assert not len(bad), "%s: the atomics' word of wave %d: got %#x, want %#x" % (name, bad[0][0], int(atom[bad[0][0]]), int(want_atom[bad[0][0]]))
+    return out, atom
+
+
+def same_bits_in_a_group(out, g):
+    """every lane of an aligned group of g holds the same bits (the double sums)"""
+    x = out[:, 0, :].reshape(out.shape[0], 64 // g, g)
+    return bool((x == x[:, :, :1]).all())
