@@ -515,6 +515,70 @@ int qm_fld_eff_lens_from_counts(int32_t max_len, const uint64_t* counts /*[max_l
 /* no counterpart in the reference; consumer of the hit records.  qm_fld_fetch + qm_fld_eff_lens_from_counts. */
 int qm_fld_eff_lens(qm_fld* f, int64_t n_txps, const uint32_t* lens, double* eff /*[n_txps]*/);
 
+/* ---- library type: hit orientations tallied, compatible hits kept ------------------------------------------------------------
+ * (No counterpart in the reference; consumer of the hit records.  The names follow Salmon's -l / --libType and its
+ * lib_format_counts.json; parity with Salmon is NOT claimed: none was at hand to compare with.  The model is this project's own,
+ * exactly defined, integers only.)  Every hit record has a CODE; a byte counts as forward when it is not 0:
+ *     mate_status 3 (PE_PAIRED)   fwd != mate_is_fwd, not outward:  fwd 0 ISF, !fwd 1 ISR
+ *                                 fwd != mate_is_fwd, outward:      fwd 2 OSF, !fwd 3 OSR
+ *                                 both forward 4 MSF, both reverse 5 MSR
+ *     mate_status 1 (PE_LEFT)     fwd 6 LF, !fwd 7 LR
+ *     mate_status 2 (PE_RIGHT)    fwd 8 RF, !fwd 9 RR
+ *     mate_status 0 (SINGLE_END)  fwd 10 SF, !fwd 11 SR
+ *     mate_status > 3             no code: tallied as `other`, never kept
+ * Outward is the reference's own dovetail predicate, (fwd && pos > mate_pos) || (mate_is_fwd && mate_pos > pos), compared as signed
+ * numbers (src/RapMapSAMapper.cpp:539-551 as the oracle restates it): a DOVETAILING pair counts as outward.
+ * A library type is a 12-bit mask over the codes (qm_lib_type_mask): IU = ISF ISR LF LR RF RR, ISF = ISF LF RR, ISR = ISR LR RF;
+ * OU / OSF / OSR and MU the same with the O / M codes, MSF = MSF LF RF, MSR = MSR LR RR; U = SF SR, SF, SR; A = all twelve
+ * (nothing is dropped, the run only reports).  A qm_lib holds one mask and 32 unsigned 64-bit tallies in device memory:
+ *     [0..11] hits by code   [12..23] units with exactly one hit, by that hit's code   [24] units   [25] units without hits
+ *     [26] kept units: at least one hit whose code is in the mask   [27] dropped units: hits, but none in the mask
+ *     [28] hits   [29] kept hits   [30] `other` hits   [31] 0
+ * so that sum [0..11] + [30] == [28], [25] + [26] + [27] == [24], and [29] is the sum of [0..11] over the mask's codes.
+ * A unit's FILTERED hit list is its hit list without the hits outside the mask, order kept; its class label is defined on that
+ * list as above (equivalence classes); a dropped unit contributes nothing, like a unit without hits.  Integer adds only: a tally
+ * does not depend on the grid.  Not thread-safe (one per context / host thread; merge with qm_lib_add_counts). */
+typedef struct qm_lib qm_lib;
+#define QM_LIB_ALL_CODES 0xfffu
+/* no counterpart in the reference; consumer of the hit records.  mask: the codes kept, 1 .. 0xfff (0, or a bit above 11: QM_E_ARG).
+ * flags & 0xffff: at most that many workgroups per sweep (0 = as many as are resident; tests, tuning); other bits must be 0. */
+int qm_lib_create(qm_ctx* ctx, uint32_t mask, uint32_t flags, qm_lib** out);
+/* no counterpart in the reference; consumer of the hit records */
+int qm_lib_destroy(qm_lib* lib);
+/* no counterpart in the reference; consumer of the hit records.  The tallies back to zero. */
+int qm_lib_clear(qm_lib* lib);
+/* no counterpart in the reference; consumer of the hit records.  Tallies the result of ctx's last map call (what qm_result_device
+ * names) where it lies, on ctx's stream, before anything can overwrite it.  QM_E_STATE without a result, QM_E_ARG when object and
+ * context are on different devices. */
+int qm_lib_add(qm_lib* lib, qm_ctx* ctx);
+/* no counterpart in the reference; consumer of the hit records.  The same sweep over arrays in HOST memory, uploaded in parts.
+ * hits may be NULL (or empty) when no unit has a hit. */
+int qm_lib_add_hits(qm_lib* lib, int64_t n_units, const int64_t* hit_offsets, const qm_hit* hits);
+/* no counterpart in the reference; consumer of the hit records.  qm_lib_add_hits, and the filtered lists brought back:
+ * new_offsets[n_units + 1] (new_offsets[0] = 0) and the kept hits' tids[new_offsets[n_units]] (room for as many as there are hits). */
+int qm_lib_compact_hits(qm_lib* lib, int64_t n_units, const int64_t* hit_offsets, const qm_hit* hits, int64_t* new_offsets, uint32_t* tids);
+/* no counterpart in the reference; consumer of the hit records.  tally[i] += counts[i], i < 31: the merge primitive (contexts,
+ * devices, ranks).  counts[31] != 0: QM_E_ARG. */
+int qm_lib_add_counts(qm_lib* lib, const uint64_t counts[32]);
+/* no counterpart in the reference; consumer of the hit records */
+int qm_lib_fetch(qm_lib* lib, uint64_t counts[32]);
+/* no counterpart in the reference; consumer of the hit records.  Since creation / the last clear: the sweeps; the last sweep from
+ * its first launch to its last, in microseconds, by HIP events on its stream; the mask */
+enum { QM_LIB_STAT_SWEEPS = 0, QM_LIB_STAT_LAST_SWEEP_US = 1, QM_LIB_STAT_MASK = 2 };
+int qm_lib_stat(const qm_lib* lib, int which, int64_t* value);
+/* no counterpart in the reference; consumer of the hit records and of qm_eqc.  qm_eqc_add over the FILTERED hit lists of ctx's last
+ * map call: sweep and tally (into lib), compact the kept hits' tids, fold those.  Under the all-codes mask nothing is compacted: it
+ * tallies and runs qm_eqc_add's fold.  QM_E_STATE without a result, QM_E_ARG unless all three are on one device. */
+int qm_eqc_add_lib(qm_eqc* t, qm_ctx* ctx, qm_lib* lib);
+/* no counterpart in the reference.  Pure host functions: no device, no context.  The mask of a type name (IU ISF ISR OU OSF OSR MU
+ * MSF MSR U SF SR A, upper case); an unknown name is QM_E_ARG. */
+int qm_lib_type_mask(const char* name, uint32_t* mask);
+/* no counterpart in the reference.  The expected type from the single-hit words [12..23], 64-bit integer arithmetic only: with
+ * I = ISF + ISR, O = OSF + OSR, M = MSF + MSR, S = SF + SR the orientation is the largest (ties: the earlier in that order; all
+ * zero: ""); within it, a the forward-sense and b the reverse-sense count, 10 a > 7 (a + b) gives ..SF, 10 a < 3 (a + b) gives
+ * ..SR, anything else ..U (for S: SF, SR, U).  A count of 2^59 or more: QM_E_UNSUPPORTED. */
+int qm_lib_infer(const uint64_t counts[32], char out[4]);
+
 /* ---- host-side callers of the path -------------------------------------------
  * Read ingest: replaces fastx_parser::FastxParser<ReadPair|ReadSeq> (include/FastxParser.hpp:62-66,
  * src/FastxParser.cpp:229-328: one kseq producer thread, per-record std::strings).  FASTA/FASTQ, plain or
@@ -564,6 +628,12 @@ int qm_stream_open(const qm_index* ix, int device_id, uint32_t ctx_flags, const 
  * context's stream, before the batch's buffers are reused; with or without QM_STREAM_EQ_CLASSES (QM_STREAM_NO_HITS keeps its rule:
  * only together with QM_STREAM_EQ_CLASSES).  qm_stream_fld_fetch sums the contexts' histograms. */
 #define QM_STREAM_FLD 8u
+/* QM_STREAM_LIB -- every map context owns a qm_lib whose mask is bits 16..27 of stream_flags (0 there: all codes).  Together with
+ * QM_STREAM_EQ_CLASSES each batch is folded through qm_eqc_add_lib (the classes hold compatible hits only), without it each batch
+ * is tallied by qm_lib_add; qm_stream_lib_fetch sums the contexts' tallies.  A stream without the flag creates no qm_lib and
+ * launches nothing of it. */
+#define QM_STREAM_LIB 16u
+#define QM_STREAM_LIB_MASK_SHIFT 16
 int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devices, uint32_t ctx_flags, const qm_opts* opts,
                       const char* path1, const char* path2, int64_t batch_units, int32_t reader_threads, uint32_t stream_flags,
                       qm_stream** out);
@@ -582,6 +652,9 @@ int qm_stream_eqc_fetch(qm_stream* s, int64_t* label_offsets, uint32_t* tids, ui
  * qm_stream_eqc_finish is valid; QM_E_STATE otherwise, and for a stream opened without QM_STREAM_FLD): the contexts' histograms and
  * counters summed, across devices.  stats7: the units, then used, unmapped, multi, not_paired, same_strand, out_of_range. */
 int qm_stream_fld_fetch(qm_stream* s, uint64_t* counts /*[QM_FLD_DEFAULT_MAX_LEN+1]*/, int64_t* stats7);
+/* No counterpart in the reference; consumer of the hit records.  Once qm_stream_next has returned the end of the input (QM_E_STATE
+ * before that, and for a stream opened without QM_STREAM_LIB): the contexts' tallies summed, across devices. */
+int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]);
 void qm_stream_close(qm_stream* s);
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result

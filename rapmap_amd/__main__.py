@@ -93,6 +93,10 @@ def _quasimap(argv):
                     "class counts resampled, the EM run again per replicate, 64 replicates at a time), written to FILE.bootstraps.gz in the "
                     "layout of Salmon's bootstraps.gz: B x transcripts little-endian float64")
     ap.add_argument("--bootstrapSeed", type=int, default=0, metavar="S", help="[only with numBootstraps]: seed of the resampling")
+    ap.add_argument("--libType", default="", metavar="T", help="the library type, named as Salmon's -l names it (IU ISF ISR OU OSF OSR MU MSF MSR for "
+                    "paired-end reads, U SF SR for single-end reads, A for any): every hit's orientation is tallied on the GPU, and with "
+                    "--eqClasses / --quant only the hits that are compatible with T go into the classes; the tallies are written to "
+                    "FILE.lib_format_counts.json next to the first of those files.  A drops nothing and reports the type the run points to")
     ap.add_argument("--chunk", type=int, default=1 << 18, help="read pairs per GPU batch")
     a = ap.parse_args(argv)
     if a.numBootstraps and not a.quant:
@@ -109,6 +113,13 @@ def _quasimap(argv):
         ap.error("--quantFLD learns the fragment lengths from the run: not together with --quantFragLenMean")
     if a.quantFLD and not (a.leftMates and a.rightMates):
         ap.error("--quantFLD needs paired-end reads (-1 and -2)")
+    lib_types = ("IU", "ISF", "ISR", "OU", "OSF", "OSR", "MU", "MSF", "MSR", "U", "SF", "SR", "A")       # rapmap_amd.LIB_TYPES
+    if a.libType and a.libType not in lib_types:
+        ap.error("--libType must be one of " + " ".join(lib_types))
+    if a.libType in ("U", "SF", "SR") and a.leftMates and a.rightMates:
+        ap.error("--libType %s is a single-end type: not with paired-end reads (-1 and -2)" % a.libType)
+    if a.libType and a.libType not in ("U", "SF", "SR", "A") and not (a.leftMates and a.rightMates):
+        ap.error("--libType %s is a paired-end type: it needs paired-end reads (-1 and -2)" % a.libType)
 
     paired = bool(a.leftMates and a.rightMates)
     single = bool(a.unmatedReads)
@@ -211,10 +222,13 @@ def _quasimap(argv):
     # --quantFLD: every stream folds its batches into fragment-length histograms as well; their sums (one per file) meet here
     fld_counts = np.zeros(ra.FLD_DEFAULT_MAX_LEN + 1, dtype=np.uint64) if a.quantFLD else None
     fld_stats = dict.fromkeys(ra.FLD_STATS, 0); fld_s = 0.0
+    # --libType: every stream tallies its batches by orientation code and folds the compatible hits only; the tallies (one per file) meet here
+    lib_counts = np.zeros(32, dtype=np.uint64) if a.libType else None
     for f1, f2 in pairs:
         os.environ.setdefault("QM_INGEST_PIN", "1")   # a whole-machine job with one ingest engine: its workers on the NUMA node that holds the files' pages
         st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None,
-                             eq_classes=classes is not None, hits=out is not None or classes is None, frag_len_dist=a.quantFLD)
+                             eq_classes=classes is not None, hits=out is not None or classes is None, frag_len_dist=a.quantFLD,
+                             lib_type=a.libType or None)
         for b in st:
             gpu_ms += b.gpu_ms
             for kk in tot:
@@ -229,6 +243,8 @@ def _quasimap(argv):
                     tot["numReads"], tot["peHits"] / max(1, tot["numReads"]), tot["seHits"] / max(1, tot["numReads"])))
         if classes is not None:
             classes.add_labels(*st.eq_classes())
+        if a.libType:
+            lib_counts += st.lib_counts()
         if a.quantFLD:
             c_, s_ = st.frag_len_dist()
             fld_counts += c_; fld_s += st.stats()["fld_fold_s"]
@@ -236,6 +252,14 @@ def _quasimap(argv):
                 fld_stats[kk] += s_[kk]
         log("stream: " + ", ".join("%s %.3f" % kv for kv in st.stats().items()))
         st.close()
+    if a.libType:
+        d = ra.lib_format_counts(lib_counts, a.libType)
+        log("library type %s: %d hits (%s), %d units: %d without hits, %d compatible, %d dropped; the single-hit units point to %s" % (
+            a.libType, d["hits"], ", ".join("%s %d" % kv for kv in d["hits_by_code"].items() if kv[1]), d["units"], d["unmapped_units"],
+            d["kept_units"], d["dropped_units"], d["inferred_format"] or "no type"))
+        if a.eqClasses or a.quant:
+            ra.write_lib_format_counts((a.eqClasses or a.quant) + ".lib_format_counts.json", lib_counts, a.libType)
+            log("wrote %s.lib_format_counts.json" % (a.eqClasses or a.quant))
     if classes is not None:
         if a.eqClasses:
             classes.write(a.eqClasses, qi.txp_names)

@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "qm_boot_stat", "qm_boot_destroy",
     "qm_fld_create", "qm_fld_destroy", "qm_fld_clear", "qm_fld_add", "qm_fld_add_hits", "qm_fld_add_counts", "qm_fld_fetch", "qm_fld_stat",
     "qm_fld_eff_lens_from_counts", "qm_fld_eff_lens", "qm_stream_fld_fetch",
+    "qm_lib_create", "qm_lib_destroy", "qm_lib_clear", "qm_lib_add", "qm_lib_add_hits", "qm_lib_compact_hits", "qm_lib_add_counts", "qm_lib_fetch",
+    "qm_lib_stat", "qm_eqc_add_lib", "qm_lib_type_mask", "qm_lib_infer", "qm_stream_lib_fetch",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
 ]
 
@@ -225,8 +227,26 @@ def lib():
     L.qm_fld_eff_lens_from_counts.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.qm_fld_eff_lens.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.qm_stream_fld_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_lib_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.qm_lib_destroy.argtypes = [C.c_void_p]
+    L.qm_lib_clear.argtypes = [C.c_void_p]
+    L.qm_lib_add.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_lib_add_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_lib_compact_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_lib_add_counts.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_lib_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_lib_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_eqc_add_lib.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_lib_type_mask.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
+    L.qm_lib_infer.argtypes = [C.c_void_p, C.c_char_p]
+    L.qm_stream_lib_fetch.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
+
+
+def lib_():
+    """lib(), for a method whose own parameter is called lib"""
+    return lib()
 
 
 def _check(rc):
@@ -622,9 +642,13 @@ class EqClasses:
         _check(lib().qm_eqc_create(mapper._h, int(expected), int(hash_bits) << 8, C.byref(self._h)))
         self.device = mapper.device
 
-    def add(self, mapper):
-        """fold the result of the mapper's last map call"""
-        _check(lib().qm_eqc_add(self._h, mapper._h))
+    def add(self, mapper, lib=None):
+        """fold the result of the mapper's last map call; lib (a LibFormat): only the hits its library type keeps are folded, and the
+        batch is tallied into it (qm_eqc_add_lib)"""
+        if lib is None:
+            _check(lib_().qm_eqc_add(self._h, mapper._h))
+        else:
+            _check(lib_().qm_eqc_add_lib(self._h, mapper._h, lib._h))
 
     def add_labels(self, offsets, tids, weights=None):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64); tids = np.ascontiguousarray(tids, dtype=np.uint32)
@@ -1056,6 +1080,148 @@ class FragLenDist:
             pass
 
 
+LIB_TYPES = ("IU", "ISF", "ISR", "OU", "OSF", "OSR", "MU", "MSF", "MSR", "U", "SF", "SR", "A")
+LIB_CODES = ("ISF", "ISR", "OSF", "OSR", "MSF", "MSR", "LF", "LR", "RF", "RR", "SF", "SR")    # a hit's code: words 0 .. 11 of a tally
+LIB_TOTALS = ("units", "unmapped_units", "kept_units", "dropped_units", "hits", "kept_hits")  # words 24 .. 29; word 30: other_hits
+LIB_ALL_CODES = 0xfff
+
+
+def lib_type_mask(name):
+    """qm_lib_type_mask, a pure host function: the 12-bit mask over the codes of a library type name (LIB_TYPES)"""
+    m = C.c_uint32()
+    _check(lib().qm_lib_type_mask(str(name).encode(), C.byref(m)))
+    return m.value
+
+
+def _lib_counts(counts):
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if c.size != 32:
+        raise ValueError("a tally has 32 words")
+    return c
+
+
+def infer_lib_type(counts):
+    """qm_lib_infer, a pure host function: the type the single-hit units of a tally (words 12 .. 23) point to -- the orientation with
+    the most of them, stranded when more than 70 % agree -- or "" without any"""
+    c = _lib_counts(counts)
+    out = C.create_string_buffer(4)
+    _check(lib().qm_lib_infer(c.ctypes.data, out))
+    return out.value.decode()
+
+
+def lib_format_counts(counts, lib_type):
+    """the dictionary write_lib_format_counts writes"""
+    c = [int(x) for x in _lib_counts(counts)]
+    inferred = infer_lib_type(counts)
+    kept, dropped = c[26], c[27]
+    d = {"expected_format": inferred if lib_type == "A" else str(lib_type), "inferred_format": inferred,
+         "compatible_fragment_ratio": kept / (kept + dropped) if kept + dropped else 0.0}
+    d.update(zip(LIB_TOTALS, c[24:30]))
+    d["other_hits"] = c[30]
+    d["hits_by_code"] = dict(zip(LIB_CODES, c[:12]))
+    d["single_hit_units_by_code"] = dict(zip(LIB_CODES, c[12:24]))
+    return d
+
+
+def write_lib_format_counts(path, counts, lib_type):
+    """FILE.lib_format_counts.json: the twelve hit counts and the twelve single-hit counts by code name, the totals, expected_format
+    (the given type; under A the inferred one), inferred_format and compatible_fragment_ratio = kept / (kept + dropped) units"""
+    import json
+    with open(path, "w") as f:
+        json.dump(lib_format_counts(counts, lib_type), f, indent=2)
+        f.write("\n")
+
+
+def read_lib_format_counts(path):
+    """the inverse of write_lib_format_counts: (counts uint64[32], the dictionary)"""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    c = np.zeros(32, dtype=np.uint64)
+    c[:12] = [d["hits_by_code"][k] for k in LIB_CODES]; c[12:24] = [d["single_hit_units_by_code"][k] for k in LIB_CODES]
+    c[24:30] = [d[k] for k in LIB_TOTALS]; c[30] = d["other_hits"]
+    return c, d
+
+
+class LibFormat:
+    """qm_lib_*: the tallies of a library type in the device memory of a mapper's GPU.  Every hit record has an orientation code
+    (LIB_CODES; include/qmap_mi355.h has the table); lib_type names the codes that are compatible (LIB_TYPES, or a 12-bit mask; "A":
+    all of them, nothing is dropped).  add(mapper) tallies the mapper's last result where it lies, add_hits arrays held on the host
+    through the same sweep, compact_hits also brings the filtered lists back, add_counts adds another tally (the merge primitive);
+    EqClasses.add(mapper, lib=...) folds the compatible hits only.  max_blocks: at most that many workgroups per sweep (0: as many
+    as are resident)."""
+
+    STATS = ("sweeps", "last_sweep_us", "mask")
+
+    def __init__(self, mapper, lib_type="A", max_blocks=0):
+        self._h = C.c_void_p()
+        if not 0 <= int(max_blocks) <= 0xffff:
+            raise ValueError("max_blocks must be 0 .. 65535")
+        self.mask = lib_type_mask(lib_type) if isinstance(lib_type, str) else int(lib_type)
+        self.lib_type = lib_type
+        _check(lib().qm_lib_create(mapper._h, self.mask & 0xffffffff, int(max_blocks), C.byref(self._h)))
+        self.device = mapper.device
+
+    def add(self, mapper):
+        """tally the result of the mapper's last map call"""
+        _check(lib().qm_lib_add(self._h, mapper._h))
+
+    @staticmethod
+    def _host(hit_offsets, hits):
+        hit_offsets = np.ascontiguousarray(hit_offsets, dtype=np.int64)
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE) if hits is not None else np.zeros(0, dtype=HIT_DTYPE)
+        n = len(hit_offsets) - 1
+        if n < 0:
+            raise ValueError("hit_offsets needs n + 1 entries")
+        if n and int(hit_offsets[-1]) > hits.size:
+            raise ValueError("hit_offsets point beyond hits")
+        return n, hit_offsets, hits
+
+    def add_hits(self, hit_offsets, hits):
+        n, hit_offsets, hits = self._host(hit_offsets, hits)
+        _check(lib().qm_lib_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
+
+    def compact_hits(self, hit_offsets, hits):
+        """add_hits, and the filtered lists: (new_offsets int64[n + 1], tids uint32[]) -- every unit's kept hits, in their order"""
+        n, hit_offsets, hits = self._host(hit_offsets, hits)
+        new_off = np.zeros(n + 1, dtype=np.int64); tids = np.zeros((int(hit_offsets[-1] - hit_offsets[0]) if n else 0) + 1, dtype=np.uint32)
+        _check(lib().qm_lib_compact_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None, new_off.ctypes.data, tids.ctypes.data))
+        return new_off, tids[:int(new_off[-1])].copy()
+
+    def add_counts(self, counts):
+        c = _lib_counts(counts)
+        _check(lib().qm_lib_add_counts(self._h, c.ctypes.data))
+
+    def counts(self):
+        """uint64[32]: hits by code, single-hit units by code, then units, unmapped, kept, dropped, hits, kept hits, other hits, 0"""
+        c = np.zeros(32, dtype=np.uint64)
+        _check(lib().qm_lib_fetch(self._h, c.ctypes.data))
+        return c
+
+    def stat(self):
+        """qm_lib_stat: a dictionary of STATS (last_sweep_us: the last sweep by HIP events)"""
+        d = {}
+        for i, k in enumerate(self.STATS):
+            v = C.c_int64()
+            _check(lib().qm_lib_stat(self._h, i, C.byref(v)))
+            d[k] = v.value
+        return d
+
+    def clear(self):
+        _check(lib().qm_lib_clear(self._h))
+
+    def close(self):
+        if self._h:
+            lib().qm_lib_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 PACK_EXC_DTYPE = np.dtype([("pos", "<u4"), ("ch", "<u4")])
 
 
@@ -1182,10 +1348,12 @@ class MappedStream:
     the next batch is taken.  names=False: read names are not kept (hits-only callers).  eq_classes=True: every batch is folded
     into equivalence classes on its device (eq_classes() after the last batch); with hits=False on top the hits stay on the
     device -- hit_offsets / hits of a batch are None, n_hits and counters as ever.  frag_len_dist=True: every batch is folded into a
-    fragment-length histogram on its device as well (frag_len_dist() after the last batch)."""
+    fragment-length histogram on its device as well (frag_len_dist() after the last batch).  lib_type (a name of LIB_TYPES or a
+    12-bit mask): every batch is tallied by orientation code on its device (lib_counts() after the last batch), and with
+    eq_classes=True the classes hold only the hits that type keeps."""
 
     def __init__(self, index: QuasiIndex, path1, path2=None, opts=None, device=0, batch_units=1 << 20, threads=None, ph_compact=False,
-                 names=True, eq_classes=False, hits=True, frag_len_dist=False):
+                 names=True, eq_classes=False, hits=True, frag_len_dist=False, lib_type=None):
         self._h = C.c_void_p()
         self.paired = path2 is not None
         self.names = bool(names)
@@ -1200,7 +1368,8 @@ class MappedStream:
         rc = lib().qm_stream_open_ex(index._h, darr, len(devs), 1 if ph_compact else 0, C.byref(opts), os.fsencode(path1),
                                      os.fsencode(path2) if path2 else None, int(batch_units),
                                      int(threads or min(32, os.cpu_count() or 1)),
-                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0), C.byref(self._h))
+                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0) |
+                                     (0 if lib_type is None else 16 | (lib_type_mask(lib_type) if isinstance(lib_type, str) else int(lib_type)) << 16), C.byref(self._h))
         if rc != 0:
             raise QmError("qm_stream_open failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
         self._index = index
@@ -1256,6 +1425,15 @@ class MappedStream:
         if rc != 0:
             raise QmError("qm_stream_fld_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
         return c, dict(zip(FLD_STATS, (int(x) for x in st)))
+
+    def lib_counts(self):
+        """after the last batch of a stream opened with lib_type: the tallies uint64[32] (LibFormat.counts) summed over the stream's
+        contexts and devices"""
+        c = np.zeros(32, dtype=np.uint64)
+        rc = lib().qm_stream_lib_fetch(self._h, c.ctypes.data)
+        if rc != 0:
+            raise QmError("qm_stream_lib_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        return c
 
     def stats(self):
         """seconds: read_s = open to the last batch packed (wall), map_s / fetch_s = upload + kernels / download summed over the

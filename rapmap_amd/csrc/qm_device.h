@@ -91,7 +91,7 @@ hipError_t qmk_stage_gather(long long nreads, const unsigned int* ivcnt, const l
                             const unsigned int* lcnt, const long long* loff, const unsigned long long* lists, const long long* lcsr,
                             unsigned long long* words_out, hipStream_t st);
 
-extern "C" {   // (the estimation objects' launchers: the lane emulation defines them a second time, qm_eqc_host.inl / qm_fld_host.inl)
+extern "C" {   // (the estimation objects' launchers: the lane emulation defines them a second time, qm_eqc_host.inl / qm_fld_host.inl / qm_lib_host.inl)
 // the kernels of the equivalence-class table that are no plain wave body (src: EqcSrc by address)
 hipError_t qmk_eqc_label_queued(const void* src, long long nq, hipStream_t st);
 hipError_t qmk_eqc_reset_probes(unsigned long long* q, long long n, hipStream_t st);
@@ -100,4 +100,9 @@ hipError_t qmk_eqc_sum(const unsigned long long* count, const unsigned long long
 // (qmk_fld_grid: as many as are resident on num_cu compute units and have work, at most max_blocks when that is not 0)
 int qmk_fld_grid(long long n_units, int num_cu, int max_blocks);
 hipError_t qmk_fld_fold(const void* src, const void* acc, int blocks, hipStream_t st);
+// the library-type sweep (qm_lib.inl; src / acc: LibSrc, LibAcc by address): its two persistent kernels.  blocks: qmk_lib_grid over
+// the hits (classify) or the units -- the workgroups resident on num_cu compute units that have work, at most max_blocks when not 0
+int qmk_lib_grid(long long lanes, int num_cu, int max_blocks);
+hipError_t qmk_lib_classify(const void* src, const void* acc, int blocks, hipStream_t st);
+hipError_t qmk_lib_units(const void* src, const void* acc, int blocks, hipStream_t st);
 }

@@ -2078,3 +2078,4 @@ int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
 #include "qm_quant_host.inl"
 #include "qm_boot_host.inl"
 #include "qm_fld_host.inl"
+#include "qm_lib_host.inl"

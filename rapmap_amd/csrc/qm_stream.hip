@@ -113,6 +113,8 @@ struct qm_stream {
   std::vector<qm_fld*> fld;                // QM_STREAM_FLD: one fragment-length histogram per context, summed by qm_stream_fld_fetch
   bool fldOn = false;
   double tFld = 0;                         // seconds in qm_fld_add (summed over the contexts)
+  std::vector<qm_lib*> lib;                // QM_STREAM_LIB: one library-type tally per context, summed by qm_stream_lib_fetch
+  bool libOn = false;
   std::vector<OutSlot> slots;
   std::mutex mu; std::condition_variable cv;
   int64_t nextOut = 0;
@@ -156,7 +158,9 @@ static void map_loop(qm_stream* s, int which) {
     else rc = qm_map_reads(c, &s->opts, n, in->seq[0], in->off[0], &S.nHits, &S.ctr);
     t1 = now_s();
     double tf = 0;
-    if (!rc && s->eqClasses) { rc = qm_eqc_add(s->eqc[(size_t)which], c); tf = now_s() - t1; t1 += tf; }   // folded where it lies, before the next call overwrites it
+    // folded where it lies, before the next call overwrites it; QM_STREAM_LIB: the compatible hits only, tallied on the way
+    if (!rc && s->eqClasses) { rc = s->libOn ? qm_eqc_add_lib(s->eqc[(size_t)which], c, s->lib[(size_t)which]) : qm_eqc_add(s->eqc[(size_t)which], c); tf = now_s() - t1; t1 += tf; }
+    else if (!rc && s->libOn) { rc = qm_lib_add(s->lib[(size_t)which], c); tf = now_s() - t1; t1 += tf; }
     double tl = 0;
     if (!rc && s->fldOn) { rc = qm_fld_add(s->fld[(size_t)which], c); tl = now_s() - t1; t1 += tl; }          // ... and so is the histogram
     if (!rc && s->noHits) {
@@ -198,6 +202,7 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
   s->ix = ix; s->opts = *opts; s->paired = path2 != nullptr;
   s->eqClasses = (stream_flags & QM_STREAM_EQ_CLASSES) != 0; s->noHits = (stream_flags & QM_STREAM_NO_HITS) != 0;
   s->fldOn = (stream_flags & QM_STREAM_FLD) != 0;
+  s->libOn = (stream_flags & QM_STREAM_LIB) != 0;
   { const char* np = getenv("QM_STREAM_NO_PACK"); s->packed = !(np && atoi(np) != 0); }
   const char* cpd = getenv("QM_STREAM_CTX_PER_DEVICE");
   // contexts (map threads) per device: each uploads, maps and downloads its batch in turn, so several of them keep the link and
@@ -252,6 +257,20 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
     if (rc) {
       sfail(rc, qm_last_error());
       qm_ingest_cancel(s->g);
+      for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
+      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
+      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
+      qm_ingest_close(s->g); delete s; return rc;
+    }
+  }
+  if (s->libOn) {
+    const uint32_t m = (stream_flags >> QM_STREAM_LIB_MASK_SHIFT) & QM_LIB_ALL_CODES;
+    s->lib.assign((size_t)nctx, nullptr);
+    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_lib_create(s->ctx[(size_t)i], m ? m : QM_LIB_ALL_CODES, 0, &s->lib[(size_t)i]); }
+    if (rc) {
+      sfail(rc, qm_last_error());
+      qm_ingest_cancel(s->g);
+      for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
       for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
       for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
       for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
@@ -373,6 +392,21 @@ int qm_stream_fld_fetch(qm_stream* s, uint64_t* counts, int64_t* stats7) {
   return QM_OK;
 }
 
+/* The contexts' library-type tallies summed on the host: 256 bytes per context. */
+int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]) {
+  if (!s || !counts) return sfail(QM_E_ARG, "qm_stream_lib_fetch: bad argument");
+  if (!s->libOn) return sfail(QM_E_STATE, "qm_stream_lib_fetch: the stream was opened without QM_STREAM_LIB");
+  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_lib_fetch: the input has not ended"); }
+  uint64_t part[32];
+  for (int i = 0; i < 32; ++i) counts[i] = 0;
+  for (qm_lib* l : s->lib) {
+    const int rc = qm_lib_fetch(l, part);
+    if (rc) return sfail(rc, qm_last_error());
+    for (int i = 0; i < 32; ++i) counts[i] += part[i];
+  }
+  return QM_OK;
+}
+
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
  * buffers; qm_stream_stats_ex adds [6] open to the first batch packed, [7] parse tasks (summed over the workers), [8] copy tasks
@@ -402,6 +436,7 @@ void qm_stream_close(qm_stream* s) {
   for (OutSlot& S : s->slots) { pin_free(S.hitOff); pin_free(S.hits); }
   for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
   for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
+  for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
   for (qm_ctx* c : s->ctx) if (c) qm_ctx_destroy(c);
   qm_ingest_close(s->g);
   delete s;
