@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 FIELDS = ("TotalSGPRs", "VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
-WANT = re.compile(r"(eqc|quant|boot|fld)_\w+")
+WANT = re.compile(r"(eqc|quant|boot|fld|lib)_\w+")
 
 
 def main(path):

@@ -13,7 +13,7 @@
 #include "qm_boot.inl"
 #include "qm_exec.h"
 
-struct qm_boot {
+struct qm_boot : qx::Base {      // (opened on its quant's stream: it owns the two events only)
   qm_quant* q = nullptr;
   int32_t nReps = 0; int64_t Bp = 0, nqCls = 0, nqTxp = 0;
   uint64_t N = 0; int64_t draws = 0;
@@ -22,7 +22,7 @@ struct qm_boot {
   DevBuf<double> d_single, d_w, d_r, d_alpha, d_alphaT, d_lastRel;
   DevBuf<u32> d_done; DevBuf<int> d_iters; DevBuf<long long> d_qCls, d_qTxp;
   DevBuf<unsigned char> d_tmp; PinBuf<u64> h_word;
-  qx::Event ev0{}, ev1{}; int64_t lastResampleUs = 0, lastRunUs = 0, lastLaunches = 0;
+  int64_t lastResampleUs = 0, lastRunUs = 0, lastLaunches = 0;
   int aggregate = 0;                                                  // equal classes meet within a wavefront before the atomic (QM_BOOT_AGGREGATE=1)
 };
 
@@ -220,8 +220,7 @@ int qm_boot_create(qm_quant* q, int32_t n_reps, qm_boot** out) {
   b->q = q;
   const char* ag = getenv("QM_BOOT_AGGREGATE");
   if (ag && *ag) b->aggregate = atoi(ag) != 0;
-  int rc = QM_OK;
-  if (hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_boot_create: events");
+  int rc = b->open("qm_boot_create", q->device, q->numCU, &q->stream);     // the quant's stream, borrowed
   if (!rc) rc = boot_open(b, q, n_reps);
   if (rc) { qm_boot_destroy(b); return rc; }
   *out = b;
@@ -230,10 +229,7 @@ int qm_boot_create(qm_quant* q, int32_t n_reps, qm_boot** out) {
 
 int qm_boot_destroy(qm_boot* b) {
   if (!b) return QM_OK;
-  hipSetDevice(b->q->device);
-  hipStreamSynchronize(b->q->stream);
-  if (b->ev0) hipEventDestroy(b->ev0);
-  if (b->ev1) hipEventDestroy(b->ev1);
+  b->close();                  // (waits for the borrowed stream and leaves it to the quant object)
   boot_close(b);
   delete b;                    // (the buffers free themselves)
   return QM_OK;

@@ -14,23 +14,23 @@ struct EqcStore {              // the six arrays of a table; EqcTable is a view 
   DevBuf<u64> key, claim, count; DevBuf<long long> loff; DevBuf<u32> llen, pool;
   void swap(EqcStore& o) { key.swap(o.key); claim.swap(o.claim); count.swap(o.count); loff.swap(o.loff); llen.swap(o.llen); pool.swap(o.pool); }
 };
-struct qm_eqc {
-  int device = 0; qx::Stream stream{}; u64 keyMask = ~0ULL; int aggregate = 1;
+struct qm_eqc : qx::Base {
+  u64 keyMask = ~0ULL; int aggregate = 1;
   EqcStore store; EqcTable T{}; DevBuf<u64> d_scal; u64 h[EQC_SC_WORDS] = {0};
   // a fold's scratch
   DevBuf<u32> d_lab, d_len; DevBuf<u64> d_key, d_q[2]; DevBuf<long long> d_longq;
   int64_t longMin = 1024;                                             // the long-unit queue's least capacity (the emulation starts smaller: the regrow is tested)
   DevBuf<u64> d_gq[2];                                                // the queues of a rebuild
-  DevBuf<long long> d_inOff; DevBuf<u32> d_inTids; DevBuf<u64> d_inW; // qm_eqc_add_labels
+  qx::FeedBuf in;                                                     // qm_eqc_add_labels
   int64_t growths = 0, longUnits = 0, rounds = 0;
-  qx::Event ev0{}, ev1{}; int64_t lastFoldUs = 0;                    // around the last fold on its stream (QM_EQC_STAT_LAST_FOLD_US)
+  int64_t lastFoldUs = 0;                                             // the events: around the last fold on its stream (QM_EQC_STAT_LAST_FOLD_US)
 };
 
 // the kernels that are no plain wave body (qm_kernels_eqc.hip, declared in qm_device.h), as the emulation runs them
 #ifdef QM_EMU
-static int qmk_eqc_label_queued(const void* src, long long nq, qx::Stream) {
+static int qmk_eqc_label_queued(const EqcSrc& S, long long nq, qx::Stream) {
   std::vector<u32> slab(EQC_SLAB);
-  for (long long w = 0; w < nq; ++w) eqc_label_queued(*(const EqcSrc*)src, w, slab.data());
+  for (long long w = 0; w < nq; ++w) eqc_label_queued(S, w, slab.data());
   return 0;
 }
 static int qmk_eqc_reset_probes(u64* q, long long n, qx::Stream) {
@@ -136,7 +136,7 @@ static int eqc_fold(qm_eqc* t, EqcSrc S, int64_t nTids, const u64* d_w, qx::Stre
     if (pass) return fail(QM_E_STATE, "long-unit queue overflowed twice");
     if ((rc = t->d_longq.ensure(nl))) return rc;       // counted, not written: a larger queue and the launch again
   }
-  HIPCHK(qmk_eqc_label_queued(&S, nl, st));
+  HIPCHK(qmk_eqc_label_queued(S, nl, st));
   t->longUnits += nl;
   const EqcSet set{S.lab, S.off, S.len, S.key, d_w, S.n};
   u64* q[2] = {t->d_q[0], t->d_q[1]};
@@ -158,6 +158,44 @@ static int eqc_size(qm_eqc* t, int64_t* n_classes, int64_t* n_tids, uint64_t* to
   return QM_OK;
 }
 
+// qm_eqc_add_labels: the host lists in parts (at most maxUnits lists and maxTids tids each) through the fold
+static int eqc_add_labels(qm_eqc* t, int64_t n, const int64_t* offsets, const uint32_t* tids, const uint64_t* weights, int64_t maxUnits, int64_t maxTids) {
+  return qx::feed(t->stream, t->in, "qm_eqc_add_labels", "list", "tids", n, offsets, tids, 4, weights, maxUnits, maxTids,
+                  [&](const long long* off, const unsigned char* d_tids, const u64* d_w, int64_t, int64_t nu, int64_t nt) {
+                    EqcSrc S{};
+                    S.tids = d_tids; S.stride = 4; S.off = off; S.n = nu;
+                    return eqc_fold(t, S, nt, d_w, t->stream);
+                  });
+}
+
+// The table in canonical order as CSR arrays (label_offsets: classes + 1 entries; tids, counts: may be null): the published slots,
+// labels ascending, compared as sequences of unsigned 32-bit numbers (a proper prefix comes first).  t->h holds the scalars afterwards.
+static int eqc_fetch(qm_eqc* t, int64_t* label_offsets, uint32_t* tids, uint64_t* counts) {
+  int rc;
+  if ((rc = eqc_read_scalars(t, t->stream))) return rc;
+  const size_t cap = (size_t)(t->T.mask + 1), used = (size_t)t->h[EQC_SC_POOL];
+  std::vector<u64> key(cap), cnt(cap); std::vector<long long> loff(cap); std::vector<u32> llen(cap), pool(used + 1);
+  if ((rc = qx::read(t->stream, key.data(), t->T.key, cap * 8)) || (rc = qx::read(t->stream, cnt.data(), t->T.count, cap * 8)) ||
+      (rc = qx::read(t->stream, loff.data(), t->T.loff, cap * 8)) || (rc = qx::read(t->stream, llen.data(), t->T.llen, cap * 4)) ||
+      (used && (rc = qx::read(t->stream, pool.data(), t->T.pool, used * 4)))) return rc;
+  std::vector<size_t> order;
+  for (size_t s = 0; s < cap; ++s) if (key[s]) order.push_back(s);
+  if (order.size() != (size_t)t->h[EQC_SC_CLASSES]) return fail(QM_E_STATE, "equivalence-class table: %zu published slots, %llu counted", order.size(), (unsigned long long)t->h[EQC_SC_CLASSES]);
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return std::lexicographical_compare(pool.begin() + loff[a], pool.begin() + loff[a] + llen[a], pool.begin() + loff[b], pool.begin() + loff[b] + llen[b]);
+  });
+  int64_t o = 0;
+  for (size_t i = 0; i < order.size(); ++i) {
+    const size_t s = order[i];
+    label_offsets[i] = o;
+    if (tids) memcpy(tids + o, pool.data() + loff[s], (size_t)llen[s] * 4);
+    if (counts) counts[i] = cnt[s];
+    o += llen[s];
+  }
+  label_offsets[order.size()] = o;
+  return QM_OK;
+}
+
 #ifndef QM_EMU
 extern "C" {
 
@@ -167,12 +205,10 @@ int qm_eqc_create(qm_ctx* c, int64_t expected_classes, uint32_t flags, qm_eqc** 
   if (bits > 63) return fail(QM_E_ARG, "qm_eqc_create: at most 63 key bits");
   HIPCHK(hipSetDevice(c->device));
   qm_eqc* t = new qm_eqc();
-  t->device = c->device; t->keyMask = bits ? ((1ULL << bits) - 1) : ~0ULL;
+  t->keyMask = bits ? ((1ULL << bits) - 1) : ~0ULL;
   { const char* e = getenv("QM_EQC_NO_AGGREGATE"); t->aggregate = !(e && atoi(e) != 0); }   // (A/B timing of the per-wavefront aggregation: INTEGRATION.md, environment)
   u64 cap = 16; while (cap < 2 * (u64)expected_classes && cap < (1ULL << 31)) cap <<= 1;
-  int rc = QM_OK;
-  if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_eqc_create: stream");
-  if (!rc && (hipEventCreate(&t->ev0) != hipSuccess || hipEventCreate(&t->ev1) != hipSuccess)) rc = fail(QM_E_NOGPU, "qm_eqc_create: events");
+  int rc = t->open("qm_eqc_create", c->device, c->numCU);
   if (!rc) rc = eqc_open(t, cap, std::max<u64>(64, 8 * (u64)expected_classes));
   if (rc) { qm_eqc_destroy(t); return rc; }
   *out = t;
@@ -181,11 +217,7 @@ int qm_eqc_create(qm_ctx* c, int64_t expected_classes, uint32_t flags, qm_eqc** 
 
 int qm_eqc_destroy(qm_eqc* t) {
   if (!t) return QM_OK;
-  hipSetDevice(t->device);
-  if (t->stream) hipStreamSynchronize(t->stream);
-  if (t->ev0) hipEventDestroy(t->ev0);
-  if (t->ev1) hipEventDestroy(t->ev1);
-  if (t->stream) hipStreamDestroy(t->stream);
+  t->close();
   delete t;                    // (the table and the scratch buffers free themselves)
   return QM_OK;
 }
@@ -207,30 +239,9 @@ int qm_eqc_add(qm_eqc* t, qm_ctx* c) {
 }
 
 int qm_eqc_add_labels(qm_eqc* t, int64_t n, const int64_t* offsets, const uint32_t* tids, const uint64_t* weights) {
-  if (!t || n < 0 || (n > 0 && !offsets)) return fail(QM_E_ARG, "qm_eqc_add_labels: bad argument");
-  for (int64_t i = 0; i < n; ++i) if (offsets[i + 1] < offsets[i]) return fail(QM_E_ARG, "qm_eqc_add_labels: offsets decrease at list %lld", (long long)i);
-  if (n > 0 && offsets[n] > offsets[0] && !tids) return fail(QM_E_ARG, "qm_eqc_add_labels: null tids");
+  if (!t) return fail(QM_E_ARG, "qm_eqc_add_labels: bad argument");
   HIPCHK(hipSetDevice(t->device));
-  const int64_t maxUnits = 1 << 22, maxTids = 1 << 25;          // a part: what is uploaded and folded in one go
-  std::vector<long long> off;
-  int rc;
-  for (int64_t u0 = 0; u0 < n;) {
-    int64_t u1 = u0 + 1;
-    while (u1 < n && u1 - u0 < maxUnits && offsets[u1 + 1] - offsets[u0] <= maxTids) ++u1;
-    const int64_t nu = u1 - u0, nt = offsets[u1] - offsets[u0];
-    off.resize((size_t)nu + 1);
-    for (int64_t i = 0; i <= nu; ++i) off[(size_t)i] = offsets[u0 + i] - offsets[u0];
-    if ((rc = t->d_inOff.ensure(nu + 1)) || (rc = t->d_inTids.ensure(std::max<int64_t>(nt, 1))) || (weights && (rc = t->d_inW.ensure(nu)))) return rc;
-    HIPCHK(hipMemcpyAsync(t->d_inOff, off.data(), (size_t)(nu + 1) * 8, hipMemcpyHostToDevice, t->stream));
-    if (nt > 0) HIPCHK(hipMemcpyAsync(t->d_inTids, tids + offsets[u0], (size_t)nt * 4, hipMemcpyHostToDevice, t->stream));
-    if (weights) HIPCHK(hipMemcpyAsync(t->d_inW, weights + u0, (size_t)nu * 8, hipMemcpyHostToDevice, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));                    // (the host vector is reused)
-    EqcSrc S{};
-    S.tids = (const unsigned char*)t->d_inTids.p; S.stride = 4; S.off = t->d_inOff; S.n = nu;
-    if ((rc = eqc_fold(t, S, nt, weights ? t->d_inW : nullptr, t->stream))) return rc;
-    u0 = u1;
-  }
-  return QM_OK;
+  return eqc_add_labels(t, n, offsets, tids, weights, 1 << 22, 1 << 25);   // a part: what is uploaded and folded in one go
 }
 
 int qm_eqc_size(qm_eqc* t, int64_t* n_classes, int64_t* n_tids, uint64_t* total_count) {
@@ -242,33 +253,7 @@ int qm_eqc_size(qm_eqc* t, int64_t* n_classes, int64_t* n_tids, uint64_t* total_
 int qm_eqc_fetch(qm_eqc* t, int64_t* label_offsets, uint32_t* tids, uint64_t* counts) {
   if (!t || !label_offsets) return fail(QM_E_ARG, "qm_eqc_fetch: bad argument");
   HIPCHK(hipSetDevice(t->device));
-  int rc;
-  if ((rc = eqc_read_scalars(t, t->stream))) return rc;
-  const size_t cap = (size_t)(t->T.mask + 1), used = (size_t)t->h[EQC_SC_POOL];
-  std::vector<u64> key(cap), cnt(cap); std::vector<long long> loff(cap); std::vector<u32> llen(cap), pool(used + 1);
-  HIPCHK(hipMemcpyAsync(key.data(), t->T.key, cap * 8, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipMemcpyAsync(cnt.data(), t->T.count, cap * 8, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipMemcpyAsync(loff.data(), t->T.loff, cap * 8, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipMemcpyAsync(llen.data(), t->T.llen, cap * 4, hipMemcpyDeviceToHost, t->stream));
-  if (used) HIPCHK(hipMemcpyAsync(pool.data(), t->T.pool, used * 4, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  std::vector<size_t> order;
-  for (size_t s = 0; s < cap; ++s) if (key[s]) order.push_back(s);
-  if (order.size() != (size_t)t->h[EQC_SC_CLASSES]) return fail(QM_E_STATE, "equivalence-class table: %zu published slots, %llu counted", order.size(), (unsigned long long)t->h[EQC_SC_CLASSES]);
-  // canonical order: labels ascending, compared as sequences of unsigned 32-bit numbers (a proper prefix comes first)
-  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-    return std::lexicographical_compare(pool.begin() + loff[a], pool.begin() + loff[a] + llen[a], pool.begin() + loff[b], pool.begin() + loff[b] + llen[b]);
-  });
-  int64_t o = 0;
-  for (size_t i = 0; i < order.size(); ++i) {
-    const size_t s = order[i];
-    label_offsets[i] = o;
-    if (tids) memcpy(tids + o, pool.data() + loff[s], (size_t)llen[s] * 4);
-    if (counts) counts[i] = cnt[s];
-    o += llen[s];
-  }
-  label_offsets[order.size()] = o;
-  return QM_OK;
+  return eqc_fetch(t, label_offsets, tids, counts);
 }
 
 int qm_eqc_stat(const qm_eqc* t, int which, int64_t* value) {

@@ -1,5 +1,7 @@
-// qm_exec.h -- what the drivers of the estimation objects (qm_eqc_host.inl, qm_quant_host.inl, qm_boot_host.inl) run on: a buffer
-// type, the launch of a wave body over a number of wavefronts, two scans and a sort, and five host operations.  Like qm_wave.h it
+// qm_exec.h -- what the five drivers of the estimation objects (qm_eqc_host.inl, qm_quant_host.inl, qm_boot_host.inl, qm_fld_host.inl,
+// qm_lib_host.inl) run on: a buffer type, the launch of a wave body over a number of wavefronts, two scans and a sort, the host
+// operations, and two things every object needs: Base -- device, stream and the two timer events, opened and closed in one place --
+// and feed -- host arrays in CSR form cut into parts, uploaded and handed to the caller's function part by part.  Like qm_wave.h it
 // has two definitions.  In the library (included by qm_host.hip, after DevBuf, PinBuf, fail and HIPCHK) a launch is a kernel on a
 // stream, the scans and the sort are rocPRIM's, and the host operations are HIP's.  With -DQM_EMU (tests/emu only) a buffer is a
 // vector, a launch is a loop over the wavefronts, one after the other, and the rest is serial host code: the drivers are the same
@@ -84,6 +86,7 @@ inline int upload(Stream, void* dst, const void* src, size_t bytes) { if (bytes)
 inline int read(Stream, void* dst, const void* src, size_t bytes) { if (bytes) memcpy(dst, src, bytes); return QM_OK; }
 inline int sync(Stream) { return QM_OK; }
 inline int tick(Event, Stream) { return QM_OK; }
+inline void elapsed(Event, Event, int64_t* us) { *us = 0; }
 inline int tock(Event, Event, Stream, int64_t* us) { *us = 0; return QM_OK; }
 
 #else
@@ -155,16 +158,77 @@ inline int read(Stream st, void* dst, const void* src, size_t bytes) {
   return QM_OK;
 }
 inline int sync(Stream st) { HIPCHK(hipStreamSynchronize(st)); return QM_OK; }
-// the timer pair: tick before the work, tock after it (waits for the stream); microseconds, left as they are when the events fail
-inline int tick(Event e0, Stream st) { HIPCHK(hipEventRecord(e0, st)); return QM_OK; }
+// the timer pair: tick before the work, tock after it (waits for the stream); microseconds, left as they are when the events fail.
+// A driver that waits for a read-back anyway ticks both events itself and asks for `elapsed` after the read: no second wait.
+inline int tick(Event e, Stream st) { HIPCHK(hipEventRecord(e, st)); return QM_OK; }
+inline void elapsed(Event e0, Event e1, int64_t* us) {
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *us = (int64_t)(ms * 1000.0f + 0.5f);
+}
 inline int tock(Event e0, Event e1, Stream st, int64_t* us) {
   HIPCHK(hipEventRecord(e1, st));
   HIPCHK(hipEventSynchronize(e1));
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *us = (int64_t)(ms * 1000.0f + 0.5f);
+  elapsed(e0, e1, us);
   return QM_OK;
 }
 #endif
+
+// What every estimation object owns: its device, a stream and the two events of its timer.  open: `who` names the object's create
+// function in the messages; with `borrowed` the stream is another object's (a qm_boot runs on its quant's) and only the events are
+// made.  close gives back what open made -- a borrowed stream is waited for and left alone.  The emulation has nothing to make.
+struct Base {
+  int device = 0, numCU = 256;
+  Stream stream{}; Event ev0{}, ev1{};
+  bool ownsStream = true;
+  int open(const char* who, int dev, int cus, const Stream* borrowed = nullptr) {
+    device = dev; numCU = cus; ownsStream = !borrowed;
+    if (borrowed) stream = *borrowed;
+#ifndef QM_EMU
+    if (ownsStream && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return fail(QM_E_NOGPU, "%s: stream", who);
+    if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) return fail(QM_E_NOGPU, "%s: events", who);
+#endif
+    return QM_OK;
+  }
+  void close() {
+#ifndef QM_EMU
+    hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    if (stream && ownsStream) hipStreamDestroy(stream);
+#endif
+  }
+};
+
+// Host arrays in parts.  The n units' items lie in `items` (itemBytes each) from offsets[u] to offsets[u + 1]; perUnit (optional)
+// has one word per unit.  A part always takes one unit and is extended while it has fewer than maxUnits units and the next unit
+// still fits into maxItems items.  Per part the offsets are rebased to 0 and go up with the part's items and words into the
+// buffers of `in`; the stream is waited for (the host vector is reused), and part(off, items, perUnit, u0, nu, nItems) gets the
+// device pointers -- items null for a part without items, perUnit null when there is none.  who / unit / item: for the messages.
+struct FeedBuf { DevBuf<long long> off; DevBuf<unsigned char> items; DevBuf<u64> perUnit; std::vector<long long> h_off; };
+template <class Part>
+int feed(Stream st, FeedBuf& in, const char* who, const char* unit, const char* item, int64_t n, const int64_t* offsets, const void* items, size_t itemBytes,
+         const uint64_t* perUnit, int64_t maxUnits, int64_t maxItems, Part&& part) {
+  if (n < 0 || (n > 0 && !offsets)) return fail(QM_E_ARG, "%s: bad argument", who);
+  for (int64_t i = 0; i < n; ++i) if (offsets[i + 1] < offsets[i]) return fail(QM_E_ARG, "%s: offsets decrease at %s %lld", who, unit, (long long)i);
+  if (n > 0 && offsets[n] > offsets[0] && !items) return fail(QM_E_ARG, "%s: null %s", who, item);
+  int rc;
+  for (int64_t u0 = 0; u0 < n;) {
+    int64_t u1 = u0 + 1;
+    while (u1 < n && u1 - u0 < maxUnits && offsets[u1 + 1] - offsets[u0] <= maxItems) ++u1;
+    const int64_t nu = u1 - u0, ni = offsets[u1] - offsets[u0];
+    in.h_off.resize((size_t)nu + 1);
+    for (int64_t i = 0; i <= nu; ++i) in.h_off[(size_t)i] = offsets[u0 + i] - offsets[u0];
+    if ((rc = in.off.ensure(nu + 1)) || (ni > 0 && (rc = in.items.ensure(ni * (int64_t)itemBytes))) || (perUnit && (rc = in.perUnit.ensure(nu)))) return rc;
+    QXCHK(upload(st, in.off, in.h_off.data(), (size_t)(nu + 1) * 8));
+    if (ni > 0) QXCHK(upload(st, in.items, (const unsigned char*)items + (size_t)offsets[u0] * itemBytes, (size_t)ni * itemBytes));
+    if (perUnit) QXCHK(upload(st, in.perUnit, perUnit + u0, (size_t)nu * 8));
+    QXCHK(sync(st));
+    if ((rc = part((const long long*)in.off.p, ni > 0 ? (const unsigned char*)in.items.p : nullptr, perUnit ? (const u64*)in.perUnit.p : nullptr, u0, nu, ni))) return rc;
+    u0 = u1;
+  }
+  return QM_OK;
+}
 
 }  // namespace qx
 }  // namespace qm

@@ -26,6 +26,8 @@ static_assert(sizeof(qm_hit) == 32 && offsetof(qm_hit, frag_len) == 12 && offset
 #define FLD_SLAB 1024        // words of a wavefront's LDS slab: max_len + 1 <= 1024 bins of 4 bytes, 4 KB
 enum { FLD_C_USED = 0, FLD_C_UNMAPPED = 1, FLD_C_MULTI = 2, FLD_C_NOT_PAIRED = 3, FLD_C_SAME_STRAND = 4, FLD_C_OUT_OF_RANGE = 5, FLD_C_WORDS = 8 };
 #define FLD_ACC_WORDS (FLD_SLAB + FLD_C_WORDS)   // the object's device memory: the 64-bit bins, then the counters
+// workgroups resident per compute unit: 8 waves per SIMD = 32 per CU = 8 workgroups (16 KB of LDS each: 128 of the CU's 160 KB)
+#define FLD_BLOCKS_PER_CU 8
 
 struct FldSrc {              // the units of a fold
   const unsigned char* hits; int stride;   // hit j's record: hits + j * stride (32: qm_hit); may be null when no unit has a hit

@@ -26,9 +26,7 @@ __global__ void __launch_bounds__(EQC_BLOCK) qm_eqc_sum_kernel(const u64* count,
   if (s) atomicAdd(out, s);
 }
 
-extern "C" {
-hipError_t qmk_eqc_label_queued(const void* src, long long nq, hipStream_t st) {
-  const EqcSrc& S = *(const EqcSrc*)src;
+hipError_t qmk_eqc_label_queued(const EqcSrc& S, long long nq, hipStream_t st) {
   if (nq <= 0) return hipSuccess;
   hipLaunchKernelGGL(qm_eqc_label_queued_kernel, dim3(eqc_blocks(nq)), dim3(EQC_BLOCK), 0, st, S, nq);
   return hipGetLastError();
@@ -43,5 +41,4 @@ hipError_t qmk_eqc_sum(const unsigned long long* count, const unsigned long long
   long long blocks = (cap + EQC_BLOCK - 1) / EQC_BLOCK; if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL(qm_eqc_sum_kernel, dim3((unsigned)blocks), dim3(EQC_BLOCK), 0, st, (const u64*)count, (const u64*)key, cap, (u64*)out);
   return hipGetLastError();
-}
 }

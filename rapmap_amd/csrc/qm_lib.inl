@@ -35,6 +35,8 @@ enum { LIB_ISF = 0, LIB_ISR = 1, LIB_OSF = 2, LIB_OSR = 3, LIB_MSF = 4, LIB_MSR 
 enum { LIB_W_HITS_BY_CODE = 0, LIB_W_SINGLE_BY_CODE = 12, LIB_W_UNITS = 24, LIB_W_UNMAPPED = 25, LIB_W_KEPT_UNITS = 26, LIB_W_DROPPED_UNITS = 27,
        LIB_W_HITS = 28, LIB_W_KEPT_HITS = 29, LIB_W_OTHER_HITS = 30, LIB_WORDS = 32 };
 #define LIB_ALL_CODES 0xfffu
+// workgroups of the two persistent kernels resident per compute unit: 8 waves per SIMD = 32 per CU = 8 workgroups
+#define LIB_BLOCKS_PER_CU 8
 
 struct LibSrc {              // the units of a sweep
   const unsigned char* hits; int stride;   // hit j's record: hits + j * stride (32: qm_hit); may be null when no unit has a hit

@@ -11,31 +11,27 @@
 #include "qm_exec.h"
 #include "qm_grid.h"
 
-struct qm_lib {
-  int device = 0, numCU = 256, maxBlocks = 0; u32 mask = LIB_ALL_CODES;
-  qx::Stream stream{};
+struct qm_lib : qx::Base {
+  int maxBlocks = 0; u32 mask = LIB_ALL_CODES;
   DevBuf<u64> d_ctr;                                                  // LIB_WORDS
   DevBuf<u64> d_keepMask; DevBuf<u32> d_keepCnt; DevBuf<long long> d_waveBase; DevBuf<unsigned char> d_tmp;   // a sweep's scratch
   DevBuf<u32> d_outTids; DevBuf<long long> d_newOff;                  // the filtered lists of the last compacting sweep
-  DevBuf<long long> d_inOff; DevBuf<qm_hit> d_inHits;                 // qm_lib_add_hits
-  int64_t sweeps = 0, lastSweepUs = 0;
-  qx::Event ev0{}, ev1{};                                             // around the last sweep on its stream
+  qx::FeedBuf in;                                                     // qm_lib_add_hits, qm_lib_compact_hits
+  int64_t sweeps = 0, lastSweepUs = 0;                                // (the events: around the last sweep on its stream)
 };
 
-// the persistent kernels (qm_kernels_lib.hip, declared in qm_device.h), as the emulation runs them: 256 compute units
+// the grid of the two persistent kernels over `lanes` hits or units (sweep_grid of qm_grid.h at this sweep's resident blocks)
+static int qmk_lib_grid(long long lanes, int num_cu, int max_blocks) { return sweep_grid(lanes, num_cu, LIB_BLOCKS_PER_CU, max_blocks); }
+// the persistent kernels (qm_kernels_lib.hip, declared in qm_device.h), as the emulation runs them: four wavefronts per workgroup
 #ifdef QM_EMU
-static int qmk_lib_grid(long long lanes, int num_cu, int max_blocks) {
-  const int g = qm::grid_blocks((lanes + 63) / 64, num_cu > 0 ? num_cu : 1, 8, 1);
-  return max_blocks > 0 && g > max_blocks ? max_blocks : g;
-}
-static int qmk_lib_classify(const void* src, const void* acc, int blocks, qx::Stream) {
-  if (((const LibSrc*)src)->nh <= 0) return 0;
-  for (long long w = 0; w < 4LL * blocks; ++w) lib_classify_wave(*(const LibSrc*)src, *(const LibAcc*)acc, w, 4LL * blocks);
+static int qmk_lib_classify(const LibSrc& S, const LibAcc& A, int blocks, qx::Stream) {
+  if (S.nh <= 0) return 0;
+  for (long long w = 0; w < 4LL * blocks; ++w) lib_classify_wave(S, A, w, 4LL * blocks);
   return 0;
 }
-static int qmk_lib_units(const void* src, const void* acc, int blocks, qx::Stream) {
-  if (((const LibSrc*)src)->n <= 0) return 0;
-  for (long long w = 0; w < 4LL * blocks; ++w) lib_units_wave(*(const LibSrc*)src, *(const LibAcc*)acc, w, 4LL * blocks);
+static int qmk_lib_units(const LibSrc& S, const LibAcc& A, int blocks, qx::Stream) {
+  if (S.n <= 0) return 0;
+  for (long long w = 0; w < 4LL * blocks; ++w) lib_units_wave(S, A, w, 4LL * blocks);
   return 0;
 }
 #endif
@@ -64,10 +60,10 @@ static int lib_sweep(qm_lib* L, const LibSrc& S, bool lists, qx::Stream st) {
   const LibAcc A{L->d_ctr, L->mask, L->d_keepMask, L->d_keepCnt, L->d_waveBase, lists ? L->d_outTids.p : nullptr, lists ? L->d_newOff.p : nullptr};
   if ((rc = qx::tick(L->ev0, st))) return rc;
   QXCHK(qx::fill(st, L->d_keepCnt + hw, 0, sizeof(u32)));            // (the scan's last input: read, never used)
-  HIPCHK(qmk_lib_classify(&S, &A, qmk_lib_grid(S.nh, L->numCU, L->maxBlocks), st));
+  HIPCHK(qmk_lib_classify(S, A, qmk_lib_grid(S.nh, L->numCU, L->maxBlocks), st));
   QXCHK(qx::scan_u32(st, L->d_tmp, L->d_keepCnt, L->d_waveBase, hw + 1));
   if (lists) HIPCHK(qx::launch<lib_compact_wave>(st, hw, S, A));
-  HIPCHK(qmk_lib_units(&S, &A, qmk_lib_grid(S.n, L->numCU, L->maxBlocks), st));
+  HIPCHK(qmk_lib_units(S, A, qmk_lib_grid(S.n, L->numCU, L->maxBlocks), st));
   if ((rc = qx::tock(L->ev0, L->ev1, st, &L->lastSweepUs))) return rc;
   L->sweeps++;
   return QM_OK;
@@ -91,52 +87,34 @@ static int lib_eqc_fold(qm_lib* L, qm_eqc* t, const LibSrc& S, qx::Stream st) {
   return eqc_fold(t, E, kept, nullptr, st);
 }
 
-#ifndef QM_EMU
-// a part of host arrays uploaded into the object's input buffers: units [u0, u1) -> S
-static int lib_upload_part(qm_lib* L, const int64_t* offsets, const qm_hit* hits, int64_t u0, int64_t u1, std::vector<long long>& off, LibSrc& S) {
-  const int64_t nu = u1 - u0, nh = offsets[u1] - offsets[u0];
-  int rc;
-  off.resize((size_t)nu + 1);
-  for (int64_t i = 0; i <= nu; ++i) off[(size_t)i] = offsets[u0 + i] - offsets[u0];
-  if ((rc = L->d_inOff.ensure(nu + 1)) || (nh > 0 && (rc = L->d_inHits.ensure(nh)))) return rc;
-  HIPCHK(hipMemcpyAsync(L->d_inOff, off.data(), (size_t)(nu + 1) * 8, hipMemcpyHostToDevice, L->stream));
-  if (nh > 0) HIPCHK(hipMemcpyAsync(L->d_inHits, hits + offsets[u0], (size_t)nh * sizeof(qm_hit), hipMemcpyHostToDevice, L->stream));
-  HIPCHK(hipStreamSynchronize(L->stream));                      // (the host vector is reused)
-  S = LibSrc{nh > 0 ? (const unsigned char*)L->d_inHits.p : nullptr, (int)sizeof(qm_hit), L->d_inOff, nu, nh};
-  return QM_OK;
-}
-// qm_lib_add_hits / qm_lib_compact_hits: the host arrays in parts through the sweep
-static int lib_add_host(qm_lib* L, const char* who, int64_t n, const int64_t* offsets, const qm_hit* hits, int64_t* new_offsets, uint32_t* tids) {
-  if (!L || n < 0 || (n > 0 && !offsets)) return fail(QM_E_ARG, "%s: bad argument", who);
-  for (int64_t i = 0; i < n; ++i) if (offsets[i + 1] < offsets[i]) return fail(QM_E_ARG, "%s: offsets decrease at unit %lld", who, (long long)i);
-  if (n > 0 && offsets[n] > offsets[0] && !hits) return fail(QM_E_ARG, "%s: null hits", who);
-  HIPCHK(hipSetDevice(L->device));
-  const int64_t maxUnits = 1 << 22, maxHits = 1 << 21;           // a part: what is uploaded and swept in one go
-  std::vector<long long> off;
+// qm_lib_add_hits / qm_lib_compact_hits: the host arrays in parts (at most maxUnits units and maxHits hits each) through the sweep;
+// with new_offsets every part's filtered lists are appended to new_offsets / tids
+static int lib_add_host(qm_lib* L, const char* who, int64_t n, const int64_t* offsets, const qm_hit* hits, int64_t* new_offsets, uint32_t* tids,
+                        int64_t maxUnits, int64_t maxHits) {
   int64_t outBase = 0;
-  int rc;
-  if (new_offsets) new_offsets[0] = 0;
-  for (int64_t u0 = 0; u0 < n;) {
-    int64_t u1 = u0 + 1;
-    while (u1 < n && u1 - u0 < maxUnits && offsets[u1 + 1] - offsets[u0] <= maxHits) ++u1;
-    LibSrc S{};
-    if ((rc = lib_upload_part(L, offsets, hits, u0, u1, off, S)) || (rc = lib_sweep(L, S, new_offsets != nullptr, L->stream))) return rc;
-    if (new_offsets) {
-      HIPCHK(hipMemcpyAsync(off.data(), L->d_newOff, (size_t)(S.n + 1) * 8, hipMemcpyDeviceToHost, L->stream));
-      HIPCHK(hipStreamSynchronize(L->stream));
-      const long long kept = off[(size_t)S.n];
-      for (int64_t i = 1; i <= S.n; ++i) new_offsets[u0 + i] = outBase + off[(size_t)i];
-      if (kept > 0) {
-        if (!tids) return fail(QM_E_ARG, "%s: null tids", who);
-        HIPCHK(hipMemcpyAsync(tids + outBase, L->d_outTids, (size_t)kept * 4, hipMemcpyDeviceToHost, L->stream));
-        HIPCHK(hipStreamSynchronize(L->stream));
-      }
-      outBase += kept;
+  std::vector<long long> off;
+  const int rc = qx::feed(L->stream, L->in, who, "unit", "hits", n, offsets, hits, sizeof(qm_hit), nullptr, maxUnits, maxHits,
+                          [&](const long long* d_off, const unsigned char* d_hits, const u64*, int64_t u0, int64_t nu, int64_t nh) {
+    QXCHK(lib_sweep(L, LibSrc{d_hits, (int)sizeof(qm_hit), d_off, nu, nh}, new_offsets != nullptr, L->stream));
+    if (!new_offsets) return (int)QM_OK;
+    off.resize((size_t)nu + 1);
+    QXCHK(qx::read(L->stream, off.data(), L->d_newOff, (size_t)(nu + 1) * 8));
+    const long long kept = off[(size_t)nu];
+    for (int64_t i = 1; i <= nu; ++i) new_offsets[u0 + i] = outBase + off[(size_t)i];
+    if (kept > 0) {
+      if (!tids) return fail(QM_E_ARG, "%s: null tids", who);
+      QXCHK(qx::read(L->stream, tids + outBase, L->d_outTids, (size_t)kept * 4));
     }
-    u0 = u1;
-  }
-  return QM_OK;
+    outBase += kept;
+    return (int)QM_OK;
+  });
+  if (!rc && new_offsets) new_offsets[0] = 0;
+  return rc;
 }
+
+#ifndef QM_EMU
+#define LIB_PART_UNITS (1 << 22)   // a part of host arrays: what is uploaded and swept in one go
+#define LIB_PART_HITS (1 << 21)
 
 extern "C" {
 
@@ -174,10 +152,8 @@ int qm_lib_create(qm_ctx* c, uint32_t mask, uint32_t flags, qm_lib** out) {
   if (!mask || (mask & ~LIB_ALL_CODES)) return fail(QM_E_ARG, "qm_lib_create: mask 0x%x", (unsigned)mask);
   HIPCHK(hipSetDevice(c->device));
   qm_lib* L = new qm_lib();
-  L->device = c->device; L->numCU = c->numCU; L->mask = mask; L->maxBlocks = (int)(flags & 0xffffu);
-  int rc = QM_OK;
-  if (hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_lib_create: stream");
-  if (!rc && (hipEventCreate(&L->ev0) != hipSuccess || hipEventCreate(&L->ev1) != hipSuccess)) rc = fail(QM_E_NOGPU, "qm_lib_create: events");
+  L->mask = mask; L->maxBlocks = (int)(flags & 0xffffu);
+  int rc = L->open("qm_lib_create", c->device, c->numCU);
   if (!rc) rc = lib_open(L);
   if (rc) { qm_lib_destroy(L); return rc; }
   *out = L;
@@ -186,11 +162,7 @@ int qm_lib_create(qm_ctx* c, uint32_t mask, uint32_t flags, qm_lib** out) {
 
 int qm_lib_destroy(qm_lib* L) {
   if (!L) return QM_OK;
-  hipSetDevice(L->device);
-  if (L->stream) hipStreamSynchronize(L->stream);
-  if (L->ev0) hipEventDestroy(L->ev0);
-  if (L->ev1) hipEventDestroy(L->ev1);
-  if (L->stream) hipStreamDestroy(L->stream);
+  L->close();
   delete L;                    // (the buffers free themselves)
   return QM_OK;
 }
@@ -210,11 +182,17 @@ int qm_lib_add(qm_lib* L, qm_ctx* c) {
   return lib_sweep(L, S, false, c->stream);
 }
 
-int qm_lib_add_hits(qm_lib* L, int64_t n, const int64_t* offsets, const qm_hit* hits) { return lib_add_host(L, "qm_lib_add_hits", n, offsets, hits, nullptr, nullptr); }
+int qm_lib_add_hits(qm_lib* L, int64_t n, const int64_t* offsets, const qm_hit* hits) {
+  if (!L) return fail(QM_E_ARG, "qm_lib_add_hits: bad argument");
+  HIPCHK(hipSetDevice(L->device));
+  return lib_add_host(L, "qm_lib_add_hits", n, offsets, hits, nullptr, nullptr, LIB_PART_UNITS, LIB_PART_HITS);
+}
 
 int qm_lib_compact_hits(qm_lib* L, int64_t n, const int64_t* offsets, const qm_hit* hits, int64_t* new_offsets, uint32_t* tids) {
   if (!new_offsets) return fail(QM_E_ARG, "qm_lib_compact_hits: null new_offsets");
-  return lib_add_host(L, "qm_lib_compact_hits", n, offsets, hits, new_offsets, tids);
+  if (!L) return fail(QM_E_ARG, "qm_lib_compact_hits: bad argument");
+  HIPCHK(hipSetDevice(L->device));
+  return lib_add_host(L, "qm_lib_compact_hits", n, offsets, hits, new_offsets, tids, LIB_PART_UNITS, LIB_PART_HITS);
 }
 
 int qm_lib_fetch(qm_lib* L, uint64_t counts[32]) {

@@ -13,8 +13,7 @@
 #include "qm_quant.inl"
 #include "qm_exec.h"
 
-struct qm_quant {
-  int device = 0; qx::Stream stream{};
+struct qm_quant : qx::Base {
   int64_t nTxps = 0, nClasses = 0, nEntries = 0, present = 0, maxLabel = 0, maxList = 0, nqCls = 0, nqTxp = 0;
   uint64_t total = 0;                                                 // the sum of the snapshot's counts
   DevBuf<long long> d_coff, d_toff, d_qCls, d_qTxp; DevBuf<u32> d_clab, d_tcls;
@@ -23,7 +22,7 @@ struct qm_quant {
   DevBuf<unsigned char> d_tmp;                                        // the scans' and the sort's scratch (structure build)
   int method = QM_QUANT_METHOD_EM; DevBuf<double> d_prior;           // the weight of a transcript (quant_weight); the prior: [n_txps], made by the first set_method
   int boots = 0;                                                      // live qm_boot objects that borrow the graph and the stream (qm_boot_host.inl)
-  qx::Event ev0{}, ev1{}; int64_t lastRunUs = 0, buildUs = 0;        // around the last run / the structure build on its stream (QM_QUANT_STAT_LAST_RUN_US, _BUILD_US)
+  int64_t lastRunUs = 0, buildUs = 0;                                 // the events: around the last run / the structure build on its stream (QM_QUANT_STAT_LAST_RUN_US, _BUILD_US)
 };
 
 // one side's queue: the rows of more than QNT_GROUP items, ascending (flag, pos: n + 1 entries of scratch)
@@ -193,9 +192,7 @@ int qm_quant_create(qm_eqc* t, int64_t n_txps, const double* eff_len, qm_quant**
   if ((rc = quant_check(n_txps, eff_len))) return rc;
   HIPCHK(hipSetDevice(t->device));
   qm_quant* q = new qm_quant();
-  q->device = t->device;
-  if (hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(QM_E_NOGPU, "qm_quant_create: stream");
-  if (!rc && (hipEventCreate(&q->ev0) != hipSuccess || hipEventCreate(&q->ev1) != hipSuccess)) rc = fail(QM_E_NOGPU, "qm_quant_create: events");
+  rc = q->open("qm_quant_create", t->device, t->numCU);
   if (!rc) rc = quant_open(q, t, n_txps, eff_len);
   if (rc) { qm_quant_destroy(q); return rc; }
   *out = q;
@@ -205,11 +202,7 @@ int qm_quant_create(qm_eqc* t, int64_t n_txps, const double* eff_len, qm_quant**
 int qm_quant_destroy(qm_quant* q) {
   if (!q) return QM_OK;
   if (int rc = quant_may_close(q)) return rc;
-  hipSetDevice(q->device);
-  if (q->stream) hipStreamSynchronize(q->stream);
-  if (q->ev0) hipEventDestroy(q->ev0);
-  if (q->ev1) hipEventDestroy(q->ev1);
-  if (q->stream) hipStreamDestroy(q->stream);
+  q->close();
   delete q;                    // (the buffers free themselves)
   return QM_OK;
 }

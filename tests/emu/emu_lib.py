@@ -27,13 +27,17 @@ def _lib():
     if not os.path.exists(_LIB) or any(os.path.getmtime(_LIB) < os.path.getmtime(s) for s in _SRC):
         build()
     lib = C.CDLL(_LIB)
-    lib.qe_lib_sweep.restype = C.c_int
+    lib.qe_lib_add.restype = C.c_int
     lib.qe_lib_grid.restype = C.c_int
     lib.qe_lib_eqc.restype = C.c_longlong
     return lib
 
 
+PART_UNITS, PART_HITS = 1 << 22, 1 << 21                             # a part of host arrays, as qm_lib_add_hits cuts them
+
+
 def _arrays(hit_offsets, hits):
+    """offsets rebased to 0 and the bytes of the hits they cover, as a sweep is handed them on the device"""
     off = np.ascontiguousarray(hit_offsets, dtype=np.int64)
     n = len(off) - 1
     raw = None
@@ -46,28 +50,40 @@ def _arrays(hit_offsets, hits):
 
 
 class EmuLib:
-    """the emulated sweep behind the interface of rapmap_amd.LibFormat (what tests/lib_cases.py drives)"""
+    """the emulated driver behind the interface of rapmap_amd.LibFormat (what tests/lib_cases.py drives); max_units / max_hits: the
+    caps of a part of the host arrays (the library's by default)"""
 
-    def __init__(self, lib_type="A", max_blocks=0):
+    def __init__(self, lib_type="A", max_blocks=0, max_units=PART_UNITS, max_hits=PART_HITS):
         self.mask = mask_of(lib_type)
         if not 0 < self.mask <= 0xfff:
             raise ArgError("mask -1")
-        self.max_blocks = int(max_blocks)
+        self.max_blocks, self.max_units, self.max_hits = int(max_blocks), int(max_units), int(max_hits)
         self.clear()
 
     def clear(self):
         self._ctr = np.zeros(32, dtype=np.uint64); self._sweeps = 0
 
     def _sweep(self, hit_offsets, hits, lists):
-        off, n, raw = _arrays(hit_offsets, hits)
-        new_off = np.zeros(max(n, 0) + 1, dtype=np.int64); tids = np.zeros(int(off[-1]) + 1 if n > 0 else 1, dtype=np.uint32)
-        rc = _lib().qe_lib_sweep(C.c_longlong(n), C.c_void_p(off.ctypes.data), C.c_void_p(raw.ctypes.data if raw is not None else None), C.c_int(32),
-                                 C.c_uint32(self.mask), C.c_int(self.max_blocks), C.c_void_p(self._ctr.ctypes.data),
-                                 C.c_void_p(new_off.ctypes.data if lists else None), C.c_void_p(tids.ctypes.data if lists else None))
+        # the arrays as the caller has them: the driver rebases the offsets part by part
+        off = np.ascontiguousarray(hit_offsets, dtype=np.int64)
+        n = len(off) - 1
+        raw = None
+        if hits is not None and len(hits):
+            assert hits.dtype.itemsize == 32 and int(off[-1]) <= len(hits)
+            raw = np.ascontiguousarray(hits).view(np.uint8)
+        elif n > 0:
+            assert int(off[-1]) == int(off[0])
+        new_off = np.zeros(max(n, 0) + 1, dtype=np.int64); tids = np.zeros(max(int(off[-1] - off[0]), 0) + 1 if n > 0 else 1, dtype=np.uint32)
+        sweeps = C.c_longlong(0)
+        rc = _lib().qe_lib_add(C.c_longlong(n), C.c_void_p(off.ctypes.data), C.c_void_p(raw.ctypes.data if raw is not None else None),
+                               C.c_uint32(self.mask), C.c_int(self.max_blocks), C.c_longlong(self.max_units), C.c_longlong(self.max_hits),
+                               C.c_void_p(self._ctr.ctypes.data), C.c_void_p(new_off.ctypes.data if lists else None),
+                               C.c_void_p(tids.ctypes.data if lists else None), C.byref(sweeps))
+        self._sweeps += sweeps.value
+        if rc == -1:
+            raise ArgError("qe_lib_add -1")
         if rc:
-            raise RuntimeError("qe_lib_sweep failed (%d)" % rc)
-        if n > 0:
-            self._sweeps += 1
+            raise RuntimeError("qe_lib_add failed (%d)" % rc)
         return new_off, tids[:int(new_off[-1])].copy()
 
     def add_hits(self, hit_offsets, hits):

@@ -2,7 +2,7 @@
 // of qm_eqc_host.inl, which it hands its lists to) and the device code of qm_lib.inl, compiled with -DQM_EMU (an LV<T> is a 64-entry
 // array, QM_LANES a loop, a launch a loop over the wavefronts: qm_exec.h).  What is here is a C face over the driver's object.  One
 // wavefront after the other, one lane after the other: this checks the driver and the logic of the sweep -- codes, ballots, the
-// scan's use, the compaction, the unit offsets, the grid's cap --, not the atomics.  A sweep's scratch and its lists are handed over
+// scan's use, the compaction, the unit offsets, the parts of host arrays, the grid's cap --, not the atomics.  A sweep's scratch and its lists are handed over
 // filled with 0xA5: the sweep must write what it reads.
 #define QM_EMU
 #include "../../rapmap_amd/csrc/qm_wave.h"
@@ -26,29 +26,25 @@ extern "C" {
 
 int qe_lib_grid(long long lanes, int max_blocks) { return qmk_lib_grid(lanes, 256, max_blocks); }
 
-// Sweeps n units (off[0] = 0) into ctr[32] (added to).  new_off (n + 1 entries) / out_tids (room for off[n]) not null: the filtered
-// lists as well.  hits may be null when no unit has a hit.  Returns a QM_* code.
-int qe_lib_sweep(long long n, const long long* off, const unsigned char* hits, int stride, u32 mask, int max_blocks, u64* ctr, long long* new_off, u32* out_tids) {
+// qm_lib_add_hits (new_off null) / qm_lib_compact_hits over the host arrays, in parts of at most max_units units and max_hits hits, into
+// ctr[32] (added to; written back whatever the outcome).  new_off: n + 1 entries, out_tids: room for every hit.  hits may be null when no
+// unit has a hit.  *sweeps: the sweeps it took.  Returns a QM_* code.
+int qe_lib_add(long long n, const int64_t* off, const qm_hit* hits, u32 mask, int max_blocks, long long max_units, long long max_hits, u64* ctr,
+               int64_t* new_off, u32* out_tids, long long* sweeps) {
   if (!mask || (mask & ~LIB_ALL_CODES)) return QM_E_ARG;
-  if (n <= 0) return QM_OK;
-  const LibSrc S{hits, stride, off, n, off[n]};
+  const long long nh = n > 0 && off && off[n] > off[0] ? off[n] - off[0] : 0;
   qm_lib L;
-  int rc = emu_lib_open(L, mask, max_blocks, ctr, S);
-  if (!rc) rc = lib_sweep(&L, S, new_off != nullptr, L.stream);
-  if (rc) return rc;
+  int rc = emu_lib_open(L, mask, max_blocks, ctr, LibSrc{nullptr, 0, nullptr, n > 0 ? n : 0, nh});
+  if (!rc) rc = lib_add_host(&L, "qe_lib_add", n, off, hits, new_off, out_tids, max_units, max_hits);
   memcpy(ctr, L.d_ctr.p, LIB_WORDS * sizeof(u64));
-  if (new_off) {
-    memcpy(new_off, L.d_newOff.p, (size_t)(n + 1) * 8);
-    if (new_off[n] < 0 || new_off[n] > off[n]) return QM_E_STATE;
-    memcpy(out_tids, L.d_outTids.p, (size_t)new_off[n] * 4);
-  }
-  return QM_OK;
+  *sweeps = L.sweeps;
+  return rc;
 }
 
 // qm_eqc_add_lib's fold of n units into a fresh table; the tallies into ctr[32].  out_off needs room for n + 2 entries, out_tids for
 // off[n] + 1 words, out_counts for n + 1.  Returns the number of classes, or a QM_* code (negative).
 long long qe_lib_eqc(long long n, const long long* off, const unsigned char* hits, int stride, u32 mask, int max_blocks, u64* ctr,
-                     long long* out_off, u32* out_tids, u64* out_counts) {
+                     int64_t* out_off, u32* out_tids, uint64_t* out_counts) {
   if (!mask || (mask & ~LIB_ALL_CODES)) return QM_E_ARG;
   const LibSrc S{hits, stride, off, n, n > 0 ? off[n] : 0};
   qm_lib L; qm_eqc t;
@@ -58,19 +54,8 @@ long long qe_lib_eqc(long long n, const long long* off, const unsigned char* hit
   if (!rc) rc = lib_eqc_fold(&L, &t, S, t.stream);
   if (rc) return rc;
   memcpy(ctr, L.d_ctr.p, LIB_WORDS * sizeof(u64));
-  const EqcTable& T = t.T;
-  std::vector<size_t> order;
-  for (size_t s = 0; s <= T.mask; ++s) if (T.key[s]) order.push_back(s);
-  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-    return std::lexicographical_compare(T.pool + T.loff[a], T.pool + T.loff[a] + T.llen[a], T.pool + T.loff[b], T.pool + T.loff[b] + T.llen[b]);
-  });
-  long long o = 0;
-  for (size_t i = 0; i < order.size(); ++i) {
-    const size_t s = order[i];
-    out_off[i] = o; memcpy(out_tids + o, T.pool + T.loff[s], (size_t)T.llen[s] * 4); out_counts[i] = T.count[s]; o += T.llen[s];
-  }
-  out_off[order.size()] = o;
-  return (long long)order.size();
+  if ((rc = eqc_fetch(&t, out_off, out_tids, out_counts))) return rc;
+  return (long long)t.h[EQC_SC_CLASSES];
 }
 
 }  // extern "C"

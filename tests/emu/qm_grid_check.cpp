@@ -16,6 +16,7 @@ int main(int argc, char** argv) {
     if (!strcmp(fn, "blocks")) r = qm::grid_blocks(a[0], (int)a[1], (int)a[2], (int)a[3]);
     else if (!strcmp(fn, "clamp")) r = qm::grid_clamp(a[0], (int)a[1], (int)a[2], (int)a[3]);
     else if (!strcmp(fn, "resident")) r = qm::resident_grid(a[0], (int)a[1]);
+    else if (!strcmp(fn, "sweep")) r = qm::sweep_grid(a[0], (int)a[1], (int)a[2], (int)a[3]);
     else if (!strcmp(fn, "map")) r = qm::map_grid(a[0], (int)a[1], a[2] != 0);
     else if (!strcmp(fn, "lean")) r = qm::lean_iters(a[0], a[1] != 0);
     else if (!strcmp(fn, "pair")) r = qm::pair_iters(a[0]);

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import eqc_cases as ec
+import part_cases as pc
 from conftest import ROOT
 
 
@@ -67,6 +68,36 @@ def test_emulated_growth_and_accumulation(emu, crafted):
     o, t, c, st = emu.run(off2, tids2, weights=w, cap=16, pool_cap=64)
     ec.assert_table((o, t, c), ec.expected(L2, w), "crafted lists from a table of 16 slots")
     assert st["growths"] > 0
+
+
+@pytest.mark.parametrize("shape", sorted(pc.SHAPES))
+def test_emulated_host_lists_in_parts(emu, shape):
+    """qm_eqc_add_labels' driver, with weights, at MAX_UNITS lists and MAX_ITEMS tids to a part: the same table as in one part and as
+    the restatement.  The table keeps no count of its folds; every part with a tid costs a round at least"""
+    off = pc.offsets_of(shape)
+    rng = np.random.default_rng(len(shape))
+    n = len(off) - 1
+    tids = None if shape == "null" else rng.integers(0, 4, int(off[-1])).astype(np.uint32)      # few transcripts: lists of different parts meet in a class
+    w = rng.integers(1, 1 << 40, n).astype(np.uint64)
+    lists = [[] if tids is None else tids[off[i]:off[i + 1]] for i in range(n)]
+    small = emu.run(off, tids, weights=w, max_units=pc.MAX_UNITS, max_tids=pc.MAX_ITEMS)
+    whole = emu.run(off, tids, weights=w, max_units=pc.ONE_PART, max_tids=pc.ONE_PART)
+    ec.assert_table(small[:3], ec.expected(lists, w), shape); ec.assert_table(whole[:3], ec.expected(lists, w), shape + ", one part")
+    for x, y in zip(small[:3], whole[:3]):
+        assert x.tobytes() == y.tobytes()
+    with_tids = sum(1 for a, b in pc.parts(off) if off[b] > off[a])
+    assert small[3]["rounds"] >= with_tids and (small[3]["rounds"] == 0) == (with_tids == 0)
+    if shape != "null" and off[0] == 0 and n:                        # the same lists folded where they lie (no host arrays, no parts)
+        direct = emu.run(off, tids, weights=w)
+        for x, y in zip(small[:3], direct[:3]):
+            assert x.tobytes() == y.tobytes()
+
+
+def test_emulated_decreasing_list_offsets(emu):
+    with pytest.raises(emu.ArgError):
+        emu.run(pc.decreasing(), np.arange(6, dtype=np.uint32), weights=np.ones(4, dtype=np.uint64), max_units=pc.MAX_UNITS, max_tids=pc.MAX_ITEMS)
+    with pytest.raises(emu.ArgError):                                # tids that the offsets ask for are missing
+        emu.run(np.array([0, 2], dtype=np.int64), None, max_units=pc.MAX_UNITS, max_tids=pc.MAX_ITEMS)
 
 
 def test_write_parse_round_trip(tmp_path):

@@ -1,8 +1,10 @@
-"""The fragment-length distribution without a GPU: the sweep (rapmap_amd/csrc/qm_fld.inl) under the lane emulation, the arithmetic from
-histogram to effective lengths through the built library (a pure host function), the file format, the all-reduce, the CLI's checks.
+"""The fragment-length distribution without a GPU: the sweep and its driver (rapmap_amd/csrc/qm_fld.inl, qm_fld_host.inl) under the lane
+emulation, the arithmetic from histogram to effective lengths through the built library (a pure host function), the file format, the
+all-reduce, the CLI's checks.
 
 The emulation (tests/emu/qm_emu_fld.cpp) runs one wavefront after the other and one lane after the other, each on a slab filled with
-0xA5: it proves the LOGIC of the sweep -- offsets, categories, the slab, the flush, the grid's cap -- not the atomics; what contention
+0xA5: it proves the LOGIC of the sweep -- offsets, categories, the slab, the flush, the grid's cap -- and the driver's text (folds,
+add_counts, clear, the parts of host arrays), not the atomics; what contention
 does to them is the GPU tests' part (test_fld_gpu.py).  Every comparison is exact."""
 import os
 import socket
@@ -13,6 +15,7 @@ import numpy as np
 import pytest
 
 import fld_cases as fc
+import part_cases as pc
 from conftest import ROOT, load_oracle
 from util import pack
 
@@ -33,6 +36,42 @@ def test_emulated_grid_cap(emu):
     L = emu._lib()
     assert L.qe_fld_grid(70001, 1) == 1 and L.qe_fld_grid(70001, 2) == 2 and L.qe_fld_grid(70001, 0) == 274 and L.qe_fld_grid(10 ** 7, 0) == 2048
     assert L.qe_fld_grid(1, 0) == 1 and L.qe_fld_grid(257, 0) == 2
+
+
+def _part_hits(off, rng):
+    """records for offsets that may start above 0 (what lies in front is random and must not be looked at); every third: not paired"""
+    off_, h = fc.build(np.full(int(off[-1]), fc.U), 1000, rng)
+    h["mate_status"][::3] = 1
+    return h
+
+
+@pytest.mark.parametrize("shape", sorted(pc.SHAPES))
+def test_emulated_host_arrays_in_parts(emu, shape):
+    """qm_fld_add_hits' driver at MAX_UNITS units and MAX_ITEMS hits to a part: the same bins and counters as in one part and as the
+    restatement; one fold per part"""
+    off = pc.offsets_of(shape)
+    hits = None if shape == "null" else _part_hits(off, np.random.default_rng(len(shape)))
+    small = lambda max_len, max_blocks: emu.EmuFld(max_len, max_blocks, pc.MAX_UNITS, pc.MAX_ITEMS)
+    whole = lambda max_len, max_blocks: emu.EmuFld(max_len, max_blocks, pc.ONE_PART, pc.ONE_PART)
+    c1, s1 = fc.fold_once(whole, off, hits)
+    c, s = fc.fold_once(small, off, hits)
+    ec, es = fc.classify(off, hits, 1000)
+    fc.assert_same(c, s, ec, es, shape); fc.assert_same(c1, s1, ec, es, shape + ", one part")
+    assert s["folds"] == len(pc.parts(off)) and s1["folds"] == min(len(off) - 1, 1)
+    assert s["last_fold_us"] == 0
+
+
+def test_emulated_decreasing_offsets_leave_the_object_alone(emu):
+    off, h = fc.random_batch(300, 1000, seed=3)
+    f = emu.EmuFld(1000, 0, pc.MAX_UNITS, pc.MAX_ITEMS)
+    try:
+        f.add_hits(off, h)
+        before = (f.counts(), f.stat())
+        with pytest.raises(emu.ArgError):
+            f.add_hits(pc.decreasing(), h)
+        assert np.array_equal(f.counts(), before[0]) and f.stat() == before[1]
+    finally:
+        f.close()
 
 
 SMALL_VARIANTS = {"default": {}, "fuzzy": {"fuzzy": 1}, "no_dovetail": {"noDovetail": 1}, "sel_aln": {"selAln": 1}}

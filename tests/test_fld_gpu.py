@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import fld_cases as fc
+import part_cases as pc
 from conftest import GOLD, ROOT, load_oracle
 from util import pack
 
@@ -46,6 +47,21 @@ def _new(mp):
 @pytest.mark.parametrize("check", sorted(fc.CHECKS))
 def test_crafted(small, check):
     fc.CHECKS[check](_new(small["mp"]))
+
+
+def test_host_arrays_beyond_one_part(small):
+    """(1 << 21) + 65 hits through add_hits: one more than a part of host arrays takes, so the driver uploads and folds twice.  (The
+    cap of qm_eqc_add_labels, 1 << 25 tids, is crossed under the emulation only, at a cap of 5: test_eq_classes.py.)"""
+    off, h = pc.big_batch()
+    f = _new(small["mp"])(1000, 0)
+    try:
+        f.add_hits(off, h)
+        c, s = f.counts(), f.stat()
+    finally:
+        f.close()
+    ec, es = fc.classify(off, h, 1000)
+    fc.assert_same(c, s, ec, es, "2 097 217 hits")
+    assert s["folds"] == 2 and es["used"] > 10000 and es["out_of_range"] > 1000
 
 
 SMALL_VARIANTS = {"default": ({}, {}), "fuzzy": ({"fuzzy": 1}, {"fuzzy": 1}), "no_dovetail": ({"noDovetail": 1}, {"no_dovetail": 1}),

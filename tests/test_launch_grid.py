@@ -59,6 +59,18 @@ def test_resident_grid(ask):
     assert ask(q, QM_GRID_OVERSUB="2", QM_GRID_OVERSUB_PH="6") == [1, 2, 2047, 2048, 2048, 2048]
 
 
+def test_sweep_grid(ask):
+    # the fragment-length fold and the library-type sweep: one lane per unit or hit, 256 to a block, 8 resident per CU, no
+    # oversubscription, then the caller's max_blocks (the last argument; 0: none).  The values test_fld.py and test_lib_format.py hold
+    # the emulated grids to, asked of the shared function
+    q = ["sweep:70001,256,8,1", "sweep:70001,256,8,2", "sweep:70001,256,8,0", "sweep:10000000,256,8,0", "sweep:1,256,8,0", "sweep:257,256,8,0"]
+    assert ask(q) == [1, 2, 274, 2048, 1, 2]
+    # no lanes: one block; exactly one block's lanes and one more; the cap's edges; a cap above what the work wants; no compute units known
+    assert ask(["sweep:0,256,8,0", "sweep:256,256,8,0", "sweep:524288,256,8,0", "sweep:524032,256,8,0", "sweep:524289,256,8,0"]) == [1, 1, 2048, 2047, 2048]
+    assert ask(["sweep:70001,256,8,274", "sweep:70001,256,8,273", "sweep:70001,256,8,5000", "sweep:1000,0,8,0", "sweep:10000,0,8,0"]) == [274, 273, 274, 4, 8]
+    assert ask(q, QM_GRID_OVERSUB="2", QM_GRID_OVERSUB_PH="6") == [1, 2, 274, 2048, 1, 2]
+
+
 def test_lean_and_pair_iterations(ask):
     # narrow lean kernel: two reads per trip, (nreads + 1) >> 1; wide: one read per trip; pair kernel: nreads >> 1
     assert ask(["lean:0,0", "lean:1,0", "lean:2,0", "lean:3,0", "lean:7,0", "lean:20000000,0"]) == [0, 1, 1, 2, 4, 10000000]

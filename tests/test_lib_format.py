@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import lib_cases as lc
+import part_cases as pc
 from conftest import ROOT, load_oracle
 from util import pack
 
@@ -33,6 +34,36 @@ def test_emulated_grid_cap(emu):
     L = emu._lib()
     assert L.qe_lib_grid(70001, 1) == 1 and L.qe_lib_grid(70001, 2) == 2 and L.qe_lib_grid(70001, 0) == 274 and L.qe_lib_grid(10 ** 7, 0) == 2048
     assert L.qe_lib_grid(0, 0) == 1 and L.qe_lib_grid(1, 0) == 1 and L.qe_lib_grid(257, 0) == 2
+
+
+@pytest.mark.parametrize("shape", sorted(pc.SHAPES))
+def test_emulated_host_arrays_in_parts(emu, shape):
+    """qm_lib_add_hits' and qm_lib_compact_hits' driver at MAX_UNITS units and MAX_ITEMS hits to a part: the same tallies as in one
+    part and as the restatement, the parts' filtered lists joined into the restatement's; one sweep per part"""
+    off = pc.offsets_of(shape)
+    rng = np.random.default_rng(len(shape))
+    hits = None if shape == "null" else lc.records(lc.random_codes(int(off[-1]), rng, every_wave=False), rng)
+    small = lambda t, mb: emu.EmuLib(t, mb, pc.MAX_UNITS, pc.MAX_ITEMS)
+    whole = lambda t, mb: emu.EmuLib(t, mb, pc.ONE_PART, pc.ONE_PART)
+    for t in ("ISF", "IU", "A"):
+        ew, eo, et = lc.check_against_restatement(small, off, hits, t, what=shape)
+        lc.check_against_restatement(whole, off, hits, t, what=shape + ", one part")
+        a = small(t, 0); b = small(t, 0); w = whole(t, 0)
+        a.add_hits(off, hits); no, tids = b.compact_hits(off, hits); no1, tids1 = w.compact_hits(off, hits)
+        assert a.stat()["sweeps"] == b.stat()["sweeps"] == len(pc.parts(off)) and w.stat()["sweeps"] == min(len(off) - 1, 1)
+        assert np.array_equal(no, no1) and np.array_equal(tids, tids1) and np.array_equal(a.counts(), w.counts()) and np.array_equal(b.counts(), w.counts())
+        assert no[0] == 0 and len(no) == len(off) and int(no[-1]) == tids.size == int(ew[lc.W_KEPT_HITS])
+
+
+def test_emulated_decreasing_offsets_leave_the_object_alone(emu):
+    off, h = lc.random_batch(300, seed=3)
+    for compact in (False, True):
+        f = emu.EmuLib("ISF", 0, pc.MAX_UNITS, pc.MAX_ITEMS)
+        f.add_hits(off, h)
+        before = (f.counts(), f.stat())
+        with pytest.raises(emu.ArgError):
+            (f.compact_hits if compact else f.add_hits)(pc.decreasing(), h)
+        assert np.array_equal(f.counts(), before[0]) and f.stat() == before[1]
 
 
 def test_emulated_bad_mask(emu):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import lib_cases as lc
+import part_cases as pc
 from conftest import GOLD, ROOT, load_oracle
 from util import pack
 
@@ -50,6 +51,24 @@ def _new(mp):
 @pytest.mark.parametrize("check", sorted(lc.CHECKS))
 def test_crafted(small, check):
     lc.CHECKS[check](_new(small["mp"]))
+
+
+def test_host_arrays_beyond_one_part(small):
+    """(1 << 21) + 65 hits through add_hits and compact_hits ("ISF"): one more than a part of host arrays takes, so the driver uploads
+    and sweeps twice and joins the two parts' filtered lists.  (The cap of qm_eqc_add_labels, 1 << 25 tids, is crossed under the
+    emulation only, at a cap of 5: test_eq_classes.py.)"""
+    off, h = pc.big_batch()
+    ew, eo, et = lc.tally(off, h, "ISF")
+    a = _new(small["mp"])("ISF", 0); b = _new(small["mp"])("ISF", 0)
+    try:
+        a.add_hits(off, h)
+        no, t = b.compact_hits(off, h)
+        lc.assert_same(a.counts(), ew, "ISF", "2 097 217 hits (add_hits)"); lc.assert_same(b.counts(), ew, "ISF", "2 097 217 hits (compact_hits)")
+        assert np.array_equal(no, eo) and np.array_equal(t, et)
+        assert a.stat()["sweeps"] == 2 and b.stat()["sweeps"] == 2
+        assert int(ew[lc.W_KEPT_HITS]) > 100000 and int(ew[lc.W_DROPPED]) > 1000
+    finally:
+        a.close(); b.close()
 
 
 def _fold(mp, lib_type, max_blocks=0):
