@@ -515,6 +515,73 @@ int qm_fld_eff_lens_from_counts(int32_t max_len, const uint64_t* counts /*[max_l
 /* no counterpart in the reference; consumer of the hit records.  qm_fld_fetch + qm_fld_eff_lens_from_counts. */
 int qm_fld_eff_lens(qm_fld* f, int64_t n_txps, const uint32_t* lens, double* eff /*[n_txps]*/);
 
+/* ---- fragment GC bias: observed and expected fragment GC, effective lengths -------------------------------------------------
+ * (No counterpart in the reference; consumer of the hit records and of the transcript text.  The names follow Salmon's --gcBias;
+ * parity with Salmon is NOT claimed: none was at hand to compare with.  QM_GCB_BINS and the ratio clamp of 1000 are constants of
+ * this model.)  Integers only, except the closing host arithmetic.
+ *   GC of a character: 1 for G, C, g, c, else 0.  GC_t(s, e): the sum over characters s .. e - 1 of transcript t.
+ *   Bin of a window of n >= 1 characters holding g GC characters: min(QM_GCB_BINS - 1, (g * QM_GCB_BINS) / n), integer division.
+ * OBSERVED: obs[QM_GCB_BINS], unsigned 64-bit.  Every unit of a batch falls into exactly one of seven categories -- the first
+ * condition that holds --, each with a 64-bit counter; the seven always add up to the units swept.  The first five are qm_fld's,
+ * with the same conditions (unmapped, multi, not_paired, same_strand, out_of_range: frag_len == 0 or > max_len).  Then, with
+ * s = min(max(pos, 0), max(mate_pos, 0)) (the start mergeLeftRightHits uses for fragLen, include/RapMapUtils.hpp:1135-1141) and
+ * e = s + frag_len:
+ *     overhang      tid >= n_txps or e > txpLen[tid]
+ *     used          otherwise: obs[bin(GC_tid(s, e), frag_len)] += 1
+ * EXPECTED: H[n_txps][QM_GCB_BINS], unsigned 64-bit, from a fragment-length histogram counts[0 .. max_len] (qm_fld's shape,
+ * counts[0] == 0): with n_t(l, b) = #{ s in [0, L_t - l] : bin(GC_t(s, s + l), l) == b },
+ *     H[t][b] = sum over l = 1 .. min(L_t, max_len) of counts[l] * n_t(l, b)
+ * exact and order-free; sum over b of H[t][b] == (L_t + 1) * P[m] - Q[m], m = min(L_t, max_len), P and Q as in qm_fld above.
+ * EFFECTIVE LENGTHS, float64, every operation on its own (nothing fused), sums in ascending order of their index:
+ *     S_t      = sum over b of H[t][b] (integer);   M_t = P[min(L_t, max_len)]
+ *     exp[b]   = sum over t with alpha_t > 0 and S_t > 0 of alpha_t * ((double)H[t][b] / (double)S_t)
+ *     O        = sum over b of obs[b] (integer);   E = sum over b of exp[b]
+ *     ratio[b] = 1.0 when O == 0, E == 0 or exp[b] == 0; else ((double)obs[b] / (double)O) / (exp[b] / E), clamped to [1e-3, 1e3]
+ *     e'_t     = (double)L_t when M_t == 0; else (sum over b of ratio[b] * (double)H[t][b]) / (double)M_t
+ * With ratio == 1 this is S_t / M_t, qm_fld's effective length as one quotient.
+ * The GC rank structure (a 64-bit mask per 64 text characters and the GC characters in front of each block, 12 bytes per 64
+ * characters) lives in the index replica of the device and is built by the first qm_gcb_create of any context on it.
+ * Not thread-safe (one per context / host thread; merge with qm_gcb_add_counts). */
+typedef struct qm_gcb qm_gcb;
+#define QM_GCB_BINS 25
+/* no counterpart in the reference.  1 <= max_len <= 1023: 0 or negative is QM_E_ARG, above 1023 QM_E_UNSUPPORTED.
+ * flags & 0xffff: at most that many workgroups per launch (0 = as many as are resident; tests, tuning); other bits must be 0. */
+int qm_gcb_create(qm_ctx* ctx, int32_t max_len, uint32_t flags, qm_gcb** out);
+/* no counterpart in the reference */
+int qm_gcb_destroy(qm_gcb* g);
+/* no counterpart in the reference.  Bins and counters back to zero. */
+int qm_gcb_clear(qm_gcb* g);
+/* no counterpart in the reference.  Sweeps the result of ctx's last map call where it lies, on ctx's stream, before anything can
+ * overwrite it.  QM_E_STATE without a result, QM_E_ARG when object and context are on different devices or indexes. */
+int qm_gcb_add(qm_gcb* g, qm_ctx* ctx);
+/* no counterpart in the reference.  The same kernel over arrays in HOST memory, uploaded in parts.  hits may be NULL when no
+ * unit has a hit. */
+int qm_gcb_add_hits(qm_gcb* g, int64_t n_units, const int64_t* hit_offsets, const qm_hit* hits);
+/* no counterpart in the reference.  obs[b] += counts[b]: the merge primitive (contexts, devices, ranks).  Their sum is added to
+ * `used` and to the units. */
+int qm_gcb_add_counts(qm_gcb* g, const uint64_t* obs /*[QM_GCB_BINS]*/);
+/* no counterpart in the reference */
+int qm_gcb_fetch(qm_gcb* g, uint64_t* obs /*[QM_GCB_BINS]*/);
+/* no counterpart in the reference.  Since creation / the last clear: the units swept, the seven categories, max_len, the folds,
+ * the last fold's kernel and the last qm_gcb_expect's kernel in microseconds (HIP events), and the microseconds this object spent
+ * building the replica's rank structure (0 when it was there already; not cleared) */
+enum { QM_GCB_STAT_UNITS = 0, QM_GCB_STAT_USED = 1, QM_GCB_STAT_UNMAPPED = 2, QM_GCB_STAT_MULTI = 3, QM_GCB_STAT_NOT_PAIRED = 4, QM_GCB_STAT_SAME_STRAND = 5,
+       QM_GCB_STAT_OUT_OF_RANGE = 6, QM_GCB_STAT_OVERHANG = 7, QM_GCB_STAT_MAX_LEN = 8, QM_GCB_STAT_FOLDS = 9, QM_GCB_STAT_LAST_FOLD_US = 10,
+       QM_GCB_STAT_LAST_EXPECT_US = 11, QM_GCB_STAT_RANK_BUILD_US = 12 };
+int qm_gcb_stat(const qm_gcb* g, int which, int64_t* value);
+/* no counterpart in the reference.  The expected matrix H[n_txps][QM_GCB_BINS] of counts[0 .. max_len] over every transcript of
+ * the index (n_txps must be the index's).  counts[0] != 0: QM_E_ARG; P[max_len] * (the longest transcript) >= 2^63:
+ * QM_E_UNSUPPORTED. */
+int qm_gcb_expect(qm_gcb* g, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, uint64_t* H /*[n_txps*QM_GCB_BINS]*/);
+/* no counterpart in the reference.  The arithmetic above as a pure host function: no device, no context.  exp_out and ratio_out
+ * (QM_GCB_BINS doubles each) may be NULL.  lens[i] == 0, counts[0] != 0, max_len < 1: QM_E_ARG; max_len > 1023: QM_E_UNSUPPORTED. */
+int qm_gcb_eff_lens_from_counts(int32_t max_len, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, const uint32_t* lens,
+                                const uint64_t* H /*[n_txps*QM_GCB_BINS]*/, const double* alpha /*[n_txps]*/, const uint64_t* obs /*[QM_GCB_BINS]*/,
+                                double* eff /*[n_txps]*/, double* exp_out, double* ratio_out);
+/* no counterpart in the reference.  A probe of the rank structure: out[i] = GC_tids[i](starts[i], starts[i] + lens[i]), or -1
+ * where the window is empty or does not lie on the transcript. */
+int qm_gcb_window_gc(qm_gcb* g, int64_t n, const uint32_t* tids, const int32_t* starts, const int32_t* lens, int32_t* out /*[n]*/);
+
 /* ---- library type: hit orientations tallied, compatible hits kept ------------------------------------------------------------
  * (No counterpart in the reference; consumer of the hit records.  The names follow Salmon's -l / --libType and its
  * lib_format_counts.json; parity with Salmon is NOT claimed: none was at hand to compare with.  The model is this project's own,
@@ -634,6 +701,11 @@ int qm_stream_open(const qm_index* ix, int device_id, uint32_t ctx_flags, const 
  * launches nothing of it. */
 #define QM_STREAM_LIB 16u
 #define QM_STREAM_LIB_MASK_SHIFT 16
+/* QM_STREAM_GCB -- every map context owns a qm_gcb of QM_FLD_DEFAULT_MAX_LEN and sweeps each batch into it after mapping (after the
+ * QM_STREAM_FLD fold, when there is one), on the context's stream, before the batch's buffers are reused; with or without the other
+ * flags.  qm_stream_gcb_fetch sums the contexts' observed counts.  A stream without the flag creates no qm_gcb, builds no rank
+ * structure and launches nothing of it. */
+#define QM_STREAM_GCB 32u
 int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devices, uint32_t ctx_flags, const qm_opts* opts,
                       const char* path1, const char* path2, int64_t batch_units, int32_t reader_threads, uint32_t stream_flags,
                       qm_stream** out);
@@ -655,13 +727,18 @@ int qm_stream_fld_fetch(qm_stream* s, uint64_t* counts /*[QM_FLD_DEFAULT_MAX_LEN
 /* No counterpart in the reference; consumer of the hit records.  Once qm_stream_next has returned the end of the input (QM_E_STATE
  * before that, and for a stream opened without QM_STREAM_LIB): the contexts' tallies summed, across devices. */
 int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]);
+/* No counterpart in the reference; consumer of the hit records.  Once qm_stream_next has returned the end of the input (QM_E_STATE
+ * before that, and for a stream opened without QM_STREAM_GCB): the contexts' observed GC counts and counters summed, across devices.
+ * stats8: the units, then used, unmapped, multi, not_paired, same_strand, out_of_range, overhang. */
+int qm_stream_gcb_fetch(qm_stream* s, uint64_t* obs /*[QM_GCB_BINS]*/, int64_t* stats8);
 void qm_stream_close(qm_stream* s);
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
- * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 16) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
+ * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 17) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
  * [8] copy tasks, [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that went
  * to the device 2-bit packed, [13] qm_eqc_add of the batches (summed over the contexts), [14] contexts that folded at least one batch,
- * [15] qm_fld_add of the batches of a QM_STREAM_FLD stream (seconds, summed over the contexts; not part of [1], [2] or [13]) */
+ * [15] qm_fld_add of the batches of a QM_STREAM_FLD stream (seconds, summed over the contexts; not part of [1], [2] or [13]),
+ * [16] qm_gcb_add of the batches of a QM_STREAM_GCB stream (seconds, summed over the contexts; not part of [1], [2], [13] or [15]) */
 int qm_stream_stats(qm_stream* s, double* out6);
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n);
 const char* qm_stream_last_error(void);

@@ -84,6 +84,11 @@ def _quasimap(argv):
     ap.add_argument("--quantFLD", action="store_true", help="[only with quant, paired-end reads]: learn the fragment-length distribution from the "
                     "run's uniquely and properly paired fragments on the GPU; effective length = Length + 1 - (mean of the fragment lengths "
                     "that fit the transcript); the distribution is written to FILE.flenDist.txt.  Not together with --quantFragLenMean")
+    ap.add_argument("--quantGCBias", action="store_true", help="[only with quantFLD]: one round of fragment GC bias correction: the run's uniquely and "
+                    "properly paired fragments are counted by the GC fraction of their window on the transcript (observed), the same count "
+                    "over every window of every transcript under the run's fragment-length distribution is computed on the GPU (expected), "
+                    "and a second estimate, started from the first, runs on effective lengths weighted by observed / expected; bins, "
+                    "counts and ratios are written to FILE.gcBias.txt")
     ap.add_argument("--quantVB", action="store_true", help="[only with quant]: the variational Bayes EM in place of the EM: a transcript's weight is "
                     "exp(digamma(abundance + prior)) / effective length; the bootstrap replicates of --numBootstraps use it as well")
     ap.add_argument("--quantVBPrior", type=float, default=1e-2, metavar="P", help="[only with quantVB]: the prior, per nucleotide: P x effective length "
@@ -105,6 +110,8 @@ def _quasimap(argv):
         ap.error("--numBootstraps must not be negative")
     if a.quantFLD and not a.quant:
         ap.error("--quantFLD needs --quant")
+    if a.quantGCBias and not a.quantFLD:
+        ap.error("--quantGCBias needs --quantFLD")
     if a.quantVB and not a.quant:
         ap.error("--quantVB needs --quant")
     if not (a.quantVBPrior >= 0 and a.quantVBPrior < float("inf")):
@@ -224,11 +231,14 @@ def _quasimap(argv):
     fld_stats = dict.fromkeys(ra.FLD_STATS, 0); fld_s = 0.0
     # --libType: every stream tallies its batches by orientation code and folds the compatible hits only; the tallies (one per file) meet here
     lib_counts = np.zeros(32, dtype=np.uint64) if a.libType else None
+    # --quantGCBias: ... and sweeps them into observed GC counts; their sums (one per file) meet here
+    gcb_obs = np.zeros(ra.GCB_BINS, dtype=np.uint64) if a.quantGCBias else None
+    gcb_stats = dict.fromkeys(ra.GCB_STATS, 0); gcb_s = 0.0
     for f1, f2 in pairs:
         os.environ.setdefault("QM_INGEST_PIN", "1")   # a whole-machine job with one ingest engine: its workers on the NUMA node that holds the files' pages
         st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None,
                              eq_classes=classes is not None, hits=out is not None or classes is None, frag_len_dist=a.quantFLD,
-                             lib_type=a.libType or None)
+                             lib_type=a.libType or None, gc_bias=a.quantGCBias)
         for b in st:
             gpu_ms += b.gpu_ms
             for kk in tot:
@@ -250,6 +260,11 @@ def _quasimap(argv):
             fld_counts += c_; fld_s += st.stats()["fld_fold_s"]
             for kk in fld_stats:
                 fld_stats[kk] += s_[kk]
+        if a.quantGCBias:
+            c_, s_ = st.gc_bias()
+            gcb_obs += c_; gcb_s += st.stats()["gcb_sweep_s"]
+            for kk in gcb_stats:
+                gcb_stats[kk] += s_[kk]
         log("stream: " + ", ".join("%s %.3f" % kv for kv in st.stats().items()))
         st.close()
     if a.libType:
@@ -281,6 +296,26 @@ def _quasimap(argv):
                 # --quantVB: the prior is built from the effective lengths that Quant was given
                 qn.set_method("vbem", prior=a.quantVBPrior, per_transcript=a.quantPerTranscriptPrior)
             iters, rel = qn.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
+            if a.quantGCBias:
+                # --quantGCBias: the expected matrix once on device 0, the effective lengths on the host, a second estimate over the
+                # same table started from the first; what follows (quant.sf, the bootstrap) takes the second
+                first = qn.fetch()
+                gb = ra.GCBias(keep[0])
+                H = gb.expect(fld_counts, qi.n_txps)
+                expect_us = gb.stat()["last_expect_us"]; rank_us = gb.stat()["rank_build_us"]
+                gb.close()
+                eff, gc_exp, gc_ratio = ra.gc_eff_lens_from_counts(fld_counts, lens, H, first, gcb_obs)
+                ra.write_gc_bias(a.quant + ".gcBias.txt", gcb_obs, gc_exp, gc_ratio)
+                log("fragment GC: %s, swept in %.3f ms; expected counts in %.3f ms on the GPU (rank structure %.3f ms); ratios %g .. %g; wrote %s.gcBias.txt" % (
+                    ", ".join("%s %d" % (kk, gcb_stats[kk]) for kk in ra.GCB_STATS), gcb_s * 1e3, expect_us / 1e3, rank_us / 1e3,
+                    float(gc_ratio.min()), float(gc_ratio.max()), a.quant))
+                qn.close()
+                qn = ra.Quant(classes, qi.n_txps, eff)
+                if a.quantVB:
+                    qn.set_method("vbem", prior=a.quantVBPrior, per_transcript=a.quantPerTranscriptPrior)
+                qn.set_start(first)
+                it2, rel = qn.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
+                iters += it2
             ra.write_quant(a.quant, qi.txp_names, lens, eff, qn.fetch())
             what = "VBEM iterations, prior %g per %s" % (a.quantVBPrior, "transcript" if a.quantPerTranscriptPrior else "nucleotide") if a.quantVB else "EM iterations"
             log("wrote abundances of %d transcripts to %s (%d %s, %.3f ms on the GPU, last relative change %g)" % (

@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "qm_boot_stat", "qm_boot_destroy",
     "qm_fld_create", "qm_fld_destroy", "qm_fld_clear", "qm_fld_add", "qm_fld_add_hits", "qm_fld_add_counts", "qm_fld_fetch", "qm_fld_stat",
     "qm_fld_eff_lens_from_counts", "qm_fld_eff_lens", "qm_stream_fld_fetch",
+    "qm_gcb_create", "qm_gcb_destroy", "qm_gcb_clear", "qm_gcb_add", "qm_gcb_add_hits", "qm_gcb_add_counts", "qm_gcb_fetch", "qm_gcb_stat",
+    "qm_gcb_expect", "qm_gcb_eff_lens_from_counts", "qm_gcb_window_gc", "qm_stream_gcb_fetch",
     "qm_lib_create", "qm_lib_destroy", "qm_lib_clear", "qm_lib_add", "qm_lib_add_hits", "qm_lib_compact_hits", "qm_lib_add_counts", "qm_lib_fetch",
     "qm_lib_stat", "qm_eqc_add_lib", "qm_lib_type_mask", "qm_lib_infer", "qm_stream_lib_fetch",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
@@ -227,6 +229,18 @@ def lib():
     L.qm_fld_eff_lens_from_counts.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.qm_fld_eff_lens.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.qm_stream_fld_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_gcb_create.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.qm_gcb_destroy.argtypes = [C.c_void_p]
+    L.qm_gcb_clear.argtypes = [C.c_void_p]
+    L.qm_gcb_add.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_gcb_add_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_gcb_add_counts.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_gcb_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_gcb_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_gcb_expect.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.qm_gcb_eff_lens_from_counts.argtypes = [C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 7
+    L.qm_gcb_window_gc.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_stream_gcb_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.qm_lib_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.qm_lib_destroy.argtypes = [C.c_void_p]
     L.qm_lib_clear.argtypes = [C.c_void_p]
@@ -1080,6 +1094,137 @@ class FragLenDist:
             pass
 
 
+GCB_BINS = 25                                                         # QM_GCB_BINS
+GCB_STATS = ("units", "used", "unmapped", "multi", "not_paired", "same_strand", "out_of_range", "overhang")
+
+
+def gc_eff_lens_from_counts(counts, lens, H, alpha, obs):
+    """qm_gcb_eff_lens_from_counts, a pure host function: (eff float64[T], exp float64[25], ratio float64[25]) from the
+    fragment-length histogram counts uint64[max_len + 1], the expected matrix H uint64[T][25], a first estimate alpha float64[T]
+    and the observed histogram obs uint64[25] -- the arithmetic of include/qmap_mi355.h, nothing fused"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64); lens = _fld_lens(lens)
+    H = np.ascontiguousarray(H, dtype=np.uint64); alpha = np.ascontiguousarray(alpha, dtype=np.float64); obs = np.ascontiguousarray(obs, dtype=np.uint64)
+    if H.size != lens.size * GCB_BINS or alpha.size != lens.size or obs.size != GCB_BINS:
+        raise ValueError("H must be [len(lens)][%d], alpha [len(lens)], obs [%d]" % (GCB_BINS, GCB_BINS))
+    eff = np.zeros(lens.size, dtype=np.float64); ex = np.zeros(GCB_BINS, dtype=np.float64); ratio = np.zeros(GCB_BINS, dtype=np.float64)
+    some = lens.size > 0
+    _check(lib().qm_gcb_eff_lens_from_counts(int(counts.size) - 1, counts.ctypes.data if counts.size else None, int(lens.size),
+                                             lens.ctypes.data if some else None, H.ctypes.data if some else None, alpha.ctypes.data if some else None,
+                                             obs.ctypes.data, eff.ctypes.data if some else None, ex.ctypes.data, ratio.ctypes.data))
+    return eff, ex, ratio
+
+
+class GCBias:
+    """qm_gcb_*: the fragment GC bias model in the device memory of a mapper's GPU.  add(mapper) sweeps the mapper's last result where
+    it lies, add_hits sweeps arrays held on the host through the same kernel, add_counts adds another object's observed counts (the
+    merge primitive): a unit with exactly one hit that is properly paired, on opposite strands, of 1 .. max_len bases and lying on
+    its transcript counts in the bin of its window's GC fraction; stat() tells where the others went.  expect(counts) is the same
+    count over every window of every transcript, weighted by a fragment-length histogram; window_gc probes the rank structure.
+    max_blocks: at most that many workgroups per launch (0: as many as are resident)."""
+
+    STATS = GCB_STATS + ("max_len", "folds", "last_fold_us", "last_expect_us", "rank_build_us")
+
+    def __init__(self, mapper, max_len=FLD_DEFAULT_MAX_LEN, max_blocks=0):
+        self._h = C.c_void_p()
+        if not 0 <= int(max_blocks) <= 0xffff:
+            raise ValueError("max_blocks must be 0 .. 65535")
+        _check(lib().qm_gcb_create(mapper._h, int(max_len), int(max_blocks), C.byref(self._h)))
+        self.device = mapper.device
+        self.max_len = int(max_len)
+
+    def add(self, mapper):
+        """sweep the result of the mapper's last map call"""
+        _check(lib().qm_gcb_add(self._h, mapper._h))
+
+    def add_hits(self, hit_offsets, hits):
+        hit_offsets = np.ascontiguousarray(hit_offsets, dtype=np.int64)
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE) if hits is not None else np.zeros(0, dtype=HIT_DTYPE)
+        n = len(hit_offsets) - 1
+        if n < 0:
+            raise ValueError("hit_offsets needs n + 1 entries")
+        if n and int(hit_offsets[-1]) > hits.size:
+            raise ValueError("hit_offsets point beyond hits")
+        _check(lib().qm_gcb_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
+
+    def add_counts(self, obs):
+        obs = np.ascontiguousarray(obs, dtype=np.uint64)
+        if obs.size != GCB_BINS:
+            raise ValueError("%d counts" % GCB_BINS)
+        _check(lib().qm_gcb_add_counts(self._h, obs.ctypes.data))
+
+    def counts(self):
+        """the observed histogram, uint64[25]"""
+        c = np.zeros(GCB_BINS, dtype=np.uint64)
+        _check(lib().qm_gcb_fetch(self._h, c.ctypes.data))
+        return c
+
+    def stat(self):
+        """qm_gcb_stat: a dictionary of STATS (the seven categories add up to units; the times by HIP events)"""
+        d = {}
+        for i, k in enumerate(self.STATS):
+            v = C.c_int64()
+            _check(lib().qm_gcb_stat(self._h, i, C.byref(v)))
+            d[k] = v.value
+        return d
+
+    def expect(self, counts, n_txps):
+        """qm_gcb_expect: the expected matrix uint64[n_txps][25] of a fragment-length histogram counts uint64[max_len + 1]"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if counts.size != self.max_len + 1:
+            raise ValueError("max_len + 1 counts")
+        H = np.zeros((int(n_txps), GCB_BINS), dtype=np.uint64)
+        _check(lib().qm_gcb_expect(self._h, counts.ctypes.data, int(n_txps), H.ctypes.data if H.size else None))
+        return H
+
+    def window_gc(self, tids, starts, lens):
+        """qm_gcb_window_gc: int32[n], the G / C characters of transcript tids[i] in [starts[i], starts[i] + lens[i]); -1 where the
+        window is empty or does not lie on the transcript"""
+        tids = np.ascontiguousarray(tids, dtype=np.uint32); starts = np.ascontiguousarray(starts, dtype=np.int32); lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if not tids.size == starts.size == lens.size:
+            raise ValueError("tids, starts and lens must be of one length")
+        out = np.zeros(tids.size, dtype=np.int32)
+        if tids.size:
+            _check(lib().qm_gcb_window_gc(self._h, int(tids.size), tids.ctypes.data, starts.ctypes.data, lens.ctypes.data, out.ctypes.data))
+        return out
+
+    def clear(self):
+        _check(lib().qm_gcb_clear(self._h))
+
+    def close(self):
+        if self._h:
+            lib().qm_gcb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_gc_bias(path, obs, exp, ratio):
+    """FILE.gcBias.txt: a header line, then per bin `bin<TAB>obs<TAB>exp<TAB>ratio` -- obs an integer, exp and ratio %.17g (every double
+    comes back bit for bit)"""
+    with open(path, "w") as f:
+        f.write("bin\tobs\texp\tratio\n")
+        for b in range(GCB_BINS):
+            f.write("%d\t%d\t%.17g\t%.17g\n" % (b, int(obs[b]), float(exp[b]), float(ratio[b])))
+
+
+def read_gc_bias(path):
+    """the inverse of write_gc_bias: (obs uint64[25], exp float64[25], ratio float64[25])"""
+    obs = np.zeros(GCB_BINS, dtype=np.uint64); ex = np.zeros(GCB_BINS, dtype=np.float64); ratio = np.zeros(GCB_BINS, dtype=np.float64)
+    with open(path) as f:
+        if f.readline().rstrip("\n").split("\t") != ["bin", "obs", "exp", "ratio"]:
+            raise ValueError("%s: not a gcBias file" % path)
+        for b in range(GCB_BINS):
+            w = f.readline().rstrip("\n").split("\t")
+            if len(w) != 4 or int(w[0]) != b:
+                raise ValueError("%s: line %d" % (path, b + 2))
+            obs[b] = int(w[1]); ex[b] = float(w[2]); ratio[b] = float(w[3])
+    return obs, ex, ratio
+
+
 LIB_TYPES = ("IU", "ISF", "ISR", "OU", "OSF", "OSR", "MU", "MSF", "MSR", "U", "SF", "SR", "A")
 LIB_CODES = ("ISF", "ISR", "OSF", "OSR", "MSF", "MSR", "LF", "LR", "RF", "RR", "SF", "SR")    # a hit's code: words 0 .. 11 of a tally
 LIB_TOTALS = ("units", "unmapped_units", "kept_units", "dropped_units", "hits", "kept_hits")  # words 24 .. 29; word 30: other_hits
@@ -1348,12 +1493,13 @@ class MappedStream:
     the next batch is taken.  names=False: read names are not kept (hits-only callers).  eq_classes=True: every batch is folded
     into equivalence classes on its device (eq_classes() after the last batch); with hits=False on top the hits stay on the
     device -- hit_offsets / hits of a batch are None, n_hits and counters as ever.  frag_len_dist=True: every batch is folded into a
-    fragment-length histogram on its device as well (frag_len_dist() after the last batch).  lib_type (a name of LIB_TYPES or a
+    fragment-length histogram on its device as well (frag_len_dist() after the last batch).  gc_bias=True: every batch is swept into
+    the observed counts of the fragment GC bias model as well (gc_bias() after the last batch).  lib_type (a name of LIB_TYPES or a
     12-bit mask): every batch is tallied by orientation code on its device (lib_counts() after the last batch), and with
     eq_classes=True the classes hold only the hits that type keeps."""
 
     def __init__(self, index: QuasiIndex, path1, path2=None, opts=None, device=0, batch_units=1 << 20, threads=None, ph_compact=False,
-                 names=True, eq_classes=False, hits=True, frag_len_dist=False, lib_type=None):
+                 names=True, eq_classes=False, hits=True, frag_len_dist=False, lib_type=None, gc_bias=False):
         self._h = C.c_void_p()
         self.paired = path2 is not None
         self.names = bool(names)
@@ -1368,7 +1514,7 @@ class MappedStream:
         rc = lib().qm_stream_open_ex(index._h, darr, len(devs), 1 if ph_compact else 0, C.byref(opts), os.fsencode(path1),
                                      os.fsencode(path2) if path2 else None, int(batch_units),
                                      int(threads or min(32, os.cpu_count() or 1)),
-                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0) |
+                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0) | (32 if gc_bias else 0) |
                                      (0 if lib_type is None else 16 | (lib_type_mask(lib_type) if isinstance(lib_type, str) else int(lib_type)) << 16), C.byref(self._h))
         if rc != 0:
             raise QmError("qm_stream_open failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
@@ -1426,6 +1572,15 @@ class MappedStream:
             raise QmError("qm_stream_fld_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
         return c, dict(zip(FLD_STATS, (int(x) for x in st)))
 
+    def gc_bias(self):
+        """after the last batch of a stream opened with gc_bias=True: (obs uint64[25], stats) summed over the stream's contexts and
+        devices -- stats: a dictionary of units and the seven categories (GCB_STATS)"""
+        c = np.zeros(GCB_BINS, dtype=np.uint64); st = np.zeros(8, dtype=np.int64)
+        rc = lib().qm_stream_gcb_fetch(self._h, c.ctypes.data, st.ctypes.data)
+        if rc != 0:
+            raise QmError("qm_stream_gcb_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        return c, dict(zip(GCB_STATS, (int(x) for x in st)))
+
     def lib_counts(self):
         """after the last batch of a stream opened with lib_type: the tallies uint64[32] (LibFormat.counts) summed over the stream's
         contexts and devices"""
@@ -1438,10 +1593,10 @@ class MappedStream:
     def stats(self):
         """seconds: read_s = open to the last batch packed (wall), map_s / fetch_s = upload + kernels / download summed over the
         contexts, parse_cpu_s / copy_cpu_s = the ingest workers' task time summed over the workers"""
-        a = (C.c_double * 16)()
-        _check(lib().qm_stream_stats_ex(self._h, a, 16))
+        a = (C.c_double * 17)()
+        _check(lib().qm_stream_stats_ex(self._h, a, 17))
         return dict(zip(("read_s", "map_s", "fetch_s", "caller_wait_s", "open_s", "alloc_s", "first_batch_s", "parse_cpu_s", "copy_cpu_s",
-                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts", "fld_fold_s"), [float(x) for x in a]))
+                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts", "fld_fold_s", "gcb_sweep_s"), [float(x) for x in a]))
 
     def close(self):
         if self._h:

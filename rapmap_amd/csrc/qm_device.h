@@ -15,7 +15,7 @@
 
 namespace qm {
 struct DevIndex; struct ReadBatch; struct PairBatch; struct SelBatch;   // the launch arguments (qm_mapper.inl, qm_sel.inl)
-struct EqcSrc; struct FldSrc; struct FldAcc; struct LibSrc; struct LibAcc;   // ... of the estimation objects (qm_eqc.inl, qm_fld.inl, qm_lib.inl)
+struct EqcSrc; struct FldSrc; struct FldAcc; struct LibSrc; struct LibAcc; struct GcbIdx; struct GcbAcc; // ... of the estimation objects (qm_eqc.inl, qm_fld.inl, qm_lib.inl)
 
 // Resident blocks per CU of kernel K launched with THREADS threads: the occupancy query, once per instantiation (FALLBACK where it
 // fails); KNOB: QM_BLOCKS_PER_CU -- a tuning knob, fewer resident blocks than the occupancy allows -- may lower it.  See qm_grid.h.
@@ -102,3 +102,5 @@ hipError_t qmk_eqc_sum(const unsigned long long* count, const unsigned long long
 hipError_t qmk_fld_fold(const qm::FldSrc& src, const qm::FldAcc& acc, int blocks, hipStream_t st);
 hipError_t qmk_lib_classify(const qm::LibSrc& src, const qm::LibAcc& acc, int blocks, hipStream_t st);
 hipError_t qmk_lib_units(const qm::LibSrc& src, const qm::LibAcc& acc, int blocks, hipStream_t st);
+// the observed sweep of the GC bias model (qm_gcb.inl)
+hipError_t qmk_gcb_obs(const qm::FldSrc& src, const qm::GcbIdx& idx, const qm::GcbAcc& acc, int blocks, hipStream_t st);

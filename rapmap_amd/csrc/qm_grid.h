@@ -23,6 +23,8 @@
 //   qm_fld_fold_kernel          sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
 //   qm_lib_classify_kernel      sweep_grid: hits / 64         8 (fixed)  no    1, then at most the caller's max_blocks
 //   qm_lib_units_kernel         sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
+//   qm_gcb_obs_kernel           sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
+//   gcb_expect_wave (qx)        sweep_grid: tiles of 64       8 (fixed)  no    1, then at most the caller's max_blocks
 //
 // map_grid is the host's plan for the general kernels (the "caller's grid" above, and what their scratch and the bump allocators' slack
 // are sized by); resident_grid the one it falls back to when that scratch does not fit, and the size of the list kernels' -s scratch.
@@ -66,7 +68,7 @@ inline long long pair_iters(long long nreads) { return nreads >> 1; }
 inline int map_grid(long long nreads, int num_cu, bool ph_compact) { return grid_blocks(nreads, num_cu, GRID_NOMINAL_PER_CU, ph_compact ? grid_oversub_ph() : grid_oversub()); }
 inline int resident_grid(long long nreads, int num_cu) { return grid_blocks(nreads, num_cu, GRID_NOMINAL_PER_CU, 1); }
 
-// the two sweeps of the estimation objects (qm_fld.inl, qm_lib.inl), one lane per unit or hit: the workgroups that are resident at
+// the sweeps of the estimation objects (qm_fld.inl, qm_lib.inl, qm_gcb.inl), one lane per unit, hit or window start: the workgroups that are resident at
 // once (FLD_ / LIB_BLOCKS_PER_CU, no query), fewer when the lanes do not fill them, at most max_blocks when that is not 0
 inline int sweep_grid(long long lanes, int num_cu, int resident_per_cu, int max_blocks) {
   const int g = grid_blocks((lanes + 63) / 64, num_cu > 0 ? num_cu : 1, resident_per_cu, 1);

@@ -134,6 +134,7 @@ struct Replica {
   std::mutex sanextMu; DevBuf<unsigned int> sanext;        // -s: built by the first -s call of any context of this replica
   DevBuf<unsigned char> saext;                              // the packed characters behind every suffix's k-mer (SaExt), or empty
   DevBuf<unsigned char> saext2; bool saext2Tried = false;   // ... the wide edition (SaExt2), built when reads of 129 .. 256 characters first ask (sanextMu)
+  DevBuf<u64> gcMask; DevBuf<uint32_t> gcRank; bool gcBuilt = false;   // the GC rank structure over the text, built by the first qm_gcb (sanextMu; qm_gcb_host.inl)
   ~Replica() { hipSetDevice(device); }                      // (then the members free themselves)
 };
 static std::mutex g_repMu;
@@ -2079,3 +2080,4 @@ int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
 #include "qm_boot_host.inl"
 #include "qm_fld_host.inl"
 #include "qm_lib_host.inl"
+#include "qm_gcb_host.inl"

@@ -113,6 +113,9 @@ struct qm_stream {
   std::vector<qm_fld*> fld;                // QM_STREAM_FLD: one fragment-length histogram per context, summed by qm_stream_fld_fetch
   bool fldOn = false;
   double tFld = 0;                         // seconds in qm_fld_add (summed over the contexts)
+  std::vector<qm_gcb*> gcb;                // QM_STREAM_GCB: one set of observed GC counts per context, summed by qm_stream_gcb_fetch
+  bool gcbOn = false;
+  double tGcb = 0;                         // seconds in qm_gcb_add (summed over the contexts)
   std::vector<qm_lib*> lib;                // QM_STREAM_LIB: one library-type tally per context, summed by qm_stream_lib_fetch
   bool libOn = false;
   std::vector<OutSlot> slots;
@@ -163,6 +166,8 @@ static void map_loop(qm_stream* s, int which) {
     else if (!rc && s->libOn) { rc = qm_lib_add(s->lib[(size_t)which], c); tf = now_s() - t1; t1 += tf; }
     double tl = 0;
     if (!rc && s->fldOn) { rc = qm_fld_add(s->fld[(size_t)which], c); tl = now_s() - t1; t1 += tl; }          // ... and so is the histogram
+    double tg = 0;
+    if (!rc && s->gcbOn) { rc = qm_gcb_add(s->gcb[(size_t)which], c); tg = now_s() - t1; t1 += tg; }          // ... and the observed GC counts, before the buffers are reused
     if (!rc && s->noHits) {
       t2 = now_s();
       double a = 0, b = 0;
@@ -181,7 +186,7 @@ static void map_loop(qm_stream* s, int which) {
     std::unique_lock<std::mutex> lk(s->mu);
     if (rc) { if (!s->failed) { s->failed = rc; snprintf(s->err, sizeof(s->err), "%s", rc == QM_E_NOMEM ? "out of pinned memory" : qm_last_error()); } break; }
     S.state = 2;
-    s->tMap += t1 - t0 - tf - tl; s->tFold += tf; s->tFld += tl; if (s->eqClasses) s->eqcFolds[(size_t)which]++; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
+    s->tMap += t1 - t0 - tf - tl - tg; s->tFold += tf; s->tFld += tl; s->tGcb += tg; if (s->eqClasses) s->eqcFolds[(size_t)which]++; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
     s->cv.notify_all();
   }
   std::unique_lock<std::mutex> lk(s->mu);
@@ -203,6 +208,7 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
   s->eqClasses = (stream_flags & QM_STREAM_EQ_CLASSES) != 0; s->noHits = (stream_flags & QM_STREAM_NO_HITS) != 0;
   s->fldOn = (stream_flags & QM_STREAM_FLD) != 0;
   s->libOn = (stream_flags & QM_STREAM_LIB) != 0;
+  s->gcbOn = (stream_flags & QM_STREAM_GCB) != 0;
   { const char* np = getenv("QM_STREAM_NO_PACK"); s->packed = !(np && atoi(np) != 0); }
   const char* cpd = getenv("QM_STREAM_CTX_PER_DEVICE");
   // contexts (map threads) per device: each uploads, maps and downloads its batch in turn, so several of them keep the link and
@@ -270,6 +276,20 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
     if (rc) {
       sfail(rc, qm_last_error());
       qm_ingest_cancel(s->g);
+      for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
+      for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
+      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
+      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
+      qm_ingest_close(s->g); delete s; return rc;
+    }
+  }
+  if (s->gcbOn) {
+    s->gcb.assign((size_t)nctx, nullptr);
+    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_gcb_create(s->ctx[(size_t)i], QM_FLD_DEFAULT_MAX_LEN, 0, &s->gcb[(size_t)i]); }
+    if (rc) {
+      sfail(rc, qm_last_error());
+      qm_ingest_cancel(s->g);
+      for (qm_gcb* g : s->gcb) if (g) qm_gcb_destroy(g);
       for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
       for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
       for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
@@ -392,6 +412,23 @@ int qm_stream_fld_fetch(qm_stream* s, uint64_t* counts, int64_t* stats7) {
   return QM_OK;
 }
 
+/* The contexts' observed GC counts and counters summed on the host: 200 bytes and eight numbers per context. */
+int qm_stream_gcb_fetch(qm_stream* s, uint64_t* obs, int64_t* stats8) {
+  if (!s || !obs || !stats8) return sfail(QM_E_ARG, "qm_stream_gcb_fetch: bad argument");
+  if (!s->gcbOn) return sfail(QM_E_STATE, "qm_stream_gcb_fetch: the stream was opened without QM_STREAM_GCB");
+  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_gcb_fetch: the input has not ended"); }
+  uint64_t part[QM_GCB_BINS];
+  for (int b = 0; b < QM_GCB_BINS; ++b) obs[b] = 0;
+  for (int i = 0; i < 8; ++i) stats8[i] = 0;
+  for (qm_gcb* g : s->gcb) {
+    int rc = qm_gcb_fetch(g, part);
+    for (int i = 0; i < 8 && !rc; ++i) { int64_t v = 0; rc = qm_gcb_stat(g, QM_GCB_STAT_UNITS + i, &v); if (!rc) stats8[i] += v; }
+    if (rc) return sfail(rc, qm_last_error());
+    for (int b = 0; b < QM_GCB_BINS; ++b) obs[b] += part[b];
+  }
+  return QM_OK;
+}
+
 /* The contexts' library-type tallies summed on the host: 256 bytes per context. */
 int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]) {
   if (!s || !counts) return sfail(QM_E_ARG, "qm_stream_lib_fetch: bad argument");
@@ -412,18 +449,19 @@ int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]) {
  * buffers; qm_stream_stats_ex adds [6] open to the first batch packed, [7] parse tasks (summed over the workers), [8] copy tasks
  * (summed), [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that
  * went to the device 2-bit packed, [13] qm_eqc_add of the batches (QM_STREAM_EQ_CLASSES; not part of [1] or [2]), [14] contexts that
- * folded at least one batch, [15] qm_fld_add of the batches (QM_STREAM_FLD; not part of [1], [2] or [13]) */
+ * folded at least one batch, [15] qm_fld_add of the batches (QM_STREAM_FLD; not part of [1], [2] or [13]), [16] qm_gcb_add of the
+ * batches (QM_STREAM_GCB; not part of [1], [2], [13] or [15]) */
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n) {
   if (!s || !out || n < 0) return sfail(QM_E_ARG, "qm_stream_stats: bad argument");
-  double v[16] = {0}; double ing[8] = {0};
+  double v[17] = {0}; double ing[8] = {0};
   qm_ingest_stats(s->g, ing);
   std::unique_lock<std::mutex> lk(s->mu);
   v[0] = ing[6]; v[1] = s->tMap; v[2] = s->tFetch; v[3] = s->tWait; v[4] = s->tOpen; v[5] = s->tAlloc;
   v[6] = ing[0]; v[7] = ing[1]; v[8] = ing[2]; v[9] = ing[3]; v[10] = ing[4]; v[11] = s->tLastMapped;
   v[12] = (double)__atomic_load_n(&s->nPacked, __ATOMIC_RELAXED);
   v[13] = s->tFold; for (int64_t f : s->eqcFolds) v[14] += f > 0 ? 1 : 0;
-  v[15] = s->tFld;
-  for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
+  v[15] = s->tFld; v[16] = s->tGcb;
+  for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
   return QM_OK;
 }
 int qm_stream_stats(qm_stream* s, double* out6) { return qm_stream_stats_ex(s, out6, 6); }
@@ -437,6 +475,7 @@ void qm_stream_close(qm_stream* s) {
   for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
   for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
   for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
+  for (qm_gcb* g : s->gcb) if (g) qm_gcb_destroy(g);
   for (qm_ctx* c : s->ctx) if (c) qm_ctx_destroy(c);
   qm_ingest_close(s->g);
   delete s;
