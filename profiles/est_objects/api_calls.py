@@ -1,5 +1,5 @@
-"""profiles/est_objects/api_calls.py -- HIP API calls per fold of qm_fld_add and per sweep of qm_lib_add.
-  run TREE fld|lib N    one small mapped batch, then N calls, with rapmap_amd imported from TREE: the run a HIP trace wraps
+"""profiles/est_objects/api_calls.py -- HIP API calls per fold of qm_fld_add and per sweep of qm_lib_add and qm_gcb_add.
+  run TREE fld|lib|gcb N   one small mapped batch, then N calls, with rapmap_amd imported from TREE: the run a HIP trace wraps
                         (rocprofv3 --hip-trace --stats -d DIR/<what>_<N>_<parent|branch> -o t --output-format csv -- python ... run ...)
   table DIR             the table from those runs' t_hip_api_stats.csv at N = 1 and N = 11, parent and branch
 profiles/est_objects/run.sh does both."""
@@ -20,7 +20,7 @@ def run(root, what, n):
         idx = os.path.join(td, "idx"); ra.build_index(fa, idx, threads=4)
         qi = ra.QuasiIndex(idx); mp = ra.QuasiMapper(qi, 0)
         mp.map_pairs(s1, off, s2, off)
-        obj = ra.FragLenDist(mp) if what == "fld" else ra.LibFormat(mp, "IU")
+        obj = ra.FragLenDist(mp) if what == "fld" else ra.GCBias(mp) if what == "gcb" else ra.LibFormat(mp, "IU")
         for _ in range(n):
             obj.add(mp)
         print(what, n, obj.stat())
@@ -31,8 +31,10 @@ def table(d):
     def load(p):
         return {r["Name"]: int(r["Calls"]) for r in csv.DictReader(open(os.path.join(d, p, "t_hip_api_stats.csv")))}
     print("# rocprofv3 --hip-trace --stats (no counters), runs of their own: one small mapped batch, then N = 1 and N = 11 calls of qm_fld_add")
-    print("# (FragLenDist.add) or qm_lib_add (LibFormat(\"IU\").add).  Per call = (calls at N = 11 - calls at N = 1) / 10; APIs that do not grow with N are left out.")
-    for what, name in (("fld", "qm_fld_add, per fold"), ("lib", "qm_lib_add, per sweep")):
+    print("# (FragLenDist.add), qm_lib_add (LibFormat(\"IU\").add) or qm_gcb_add (GCBias.add).  Per call = (calls at N = 11 - calls at N = 1) / 10; APIs that do not grow with N are left out.")
+    for what, name in (("fld", "qm_fld_add, per fold"), ("lib", "qm_lib_add, per sweep"), ("gcb", "qm_gcb_add, per sweep")):
+        if not os.path.isdir(os.path.join(d, "%s_1_parent" % what)):
+            continue
         print("## %-31s %8s %8s" % (name, "parent", "branch"))
         per = {}
         for t in ("parent", "branch"):

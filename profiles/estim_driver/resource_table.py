@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 FIELDS = ("TotalSGPRs", "VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
-WANT = re.compile(r"(eqc|quant|boot|fld|lib)_\w+")
+WANT = re.compile(r"(eqc|quant|boot|fld|lib|gcb)_\w+")
 
 
 def main(path):
@@ -26,12 +26,12 @@ def main(path):
     for mangled, name in zip(names, plain):
         if "rocprim" in name or not WANT.search(name):
             continue
-        body = re.search(r"wave2?_kernelITnDaXadL_Z(?:NS_)?(\d+)", mangled)          # (the body's name, read from the mangled one)
+        body = re.search(r"(?:wave2?|sweep)_kernelITnDaXadL_Z(?:NS_)?(\d+)", mangled)          # (the body's name, read from the mangled one)
         if body:
             key = mangled[body.end():body.end() + int(body.group(1))]
             agg = re.match(r"ILi(\d)E", mangled[body.end() + int(body.group(1)):])
             key += "<%s>" % agg.group(1) if agg else ""
-            key += "  (wave2_kernel)" if "wave2_kernel" in mangled else "  (wave_kernel)"
+            key += "  (wave2_kernel)" if "wave2_kernel" in mangled else "  (sweep_kernel)" if "sweep_kernel" in mangled else "  (wave_kernel)"
         else:
             key = re.sub(r"\(.*", "", name).replace("void ", "")
         out[key] = rows[mangled]

@@ -641,13 +641,56 @@ def read_eq_classes(path):
     return names, off, np.array(tids, dtype=np.uint32), counts
 
 
-class EqClasses:
+def _host_hits(hit_offsets, hits):
+    """(n, hit_offsets int64[n + 1], hits HIT_DTYPE[]) of host arrays in CSR form, checked"""
+    hit_offsets = np.ascontiguousarray(hit_offsets, dtype=np.int64)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE) if hits is not None else np.zeros(0, dtype=HIT_DTYPE)
+    n = len(hit_offsets) - 1
+    if n < 0:
+        raise ValueError("hit_offsets needs n + 1 entries")
+    if n and int(hit_offsets[-1]) > hits.size:
+        raise ValueError("hit_offsets point beyond hits")
+    return n, hit_offsets, hits
+
+
+class _Object:
+    """what the estimation classes share: the ABI handle self._h; close() through the class's destroy function (DESTROY), whose
+    answer is looked at only where CLOSE_RAISES; __del__; and stat(), a dictionary of STATS from the class's stat function (STAT)"""
+
+    DESTROY = STAT = None
+    STATS = ()
+    CLOSE_RAISES = False
+
+    def _stat(self, which):
+        v = C.c_int64()
+        _check(getattr(lib(), self.STAT)(self._h, int(which), C.byref(v)))
+        return v.value
+
+    def stat(self):
+        return {k: self._stat(i) for i, k in enumerate(self.STATS)}
+
+    def close(self):
+        if self._h:
+            rc = getattr(lib(), self.DESTROY)(self._h)
+            if self.CLOSE_RAISES:
+                _check(rc)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EqClasses(_Object):
     """qm_eqc_*: a label -> count table in the device memory of a mapper's GPU.  A unit's label is the ascending list of the
     distinct transcripts of its hit list; add(mapper) folds the mapper's last result where it lies (no hit crosses PCIe),
     add_labels folds lists held on the host (the merge primitive: another table's fetch() with its counts as weights).
     expected: classes to size the table for (it grows by itself); hash_bits: keep only that many bits of the 64-bit key (tests)."""
 
     GROWTHS, COLLISION_PROBES, LONG_UNITS, ROUNDS, LAST_FOLD_US = 0, 1, 2, 3, 4
+    DESTROY, STAT = "qm_eqc_destroy", "qm_eqc_stat"
 
     def __init__(self, mapper, expected=1 << 16, hash_bits=0):
         self._h = C.c_void_p()
@@ -702,9 +745,7 @@ class EqClasses:
     def stat(self, which):
         """qm_eqc_stat; which is one of this module's QM_EQC_STAT_*: GROWTHS, COLLISION_PROBES, LONG_UNITS, ROUNDS, LAST_FOLD_US (the last fold by
         HIP events on its stream)"""
-        v = C.c_int64()
-        _check(lib().qm_eqc_stat(self._h, int(which), C.byref(v)))
-        return v.value
+        return self._stat(which)
 
     def clear(self):
         _check(lib().qm_eqc_clear(self._h))
@@ -725,19 +766,8 @@ class EqClasses:
         finally:
             q.close()
 
-    def close(self):
-        if self._h:
-            lib().qm_eqc_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Quant:
+class Quant(_Object):
     """qm_quant_*: abundance estimation on the device, the EM over a snapshot of an EqClasses table (later folds into the table do
     not alter it).  One iteration, all in float64: w = alpha / eff; d_c = sum of w over the class's label; r_c = n_c / d_c;
     alpha'_t = w_t * sum of r_c over the classes that contain t.  eff_lens: n_txps positive numbers (None: 1.0 each).  The start is
@@ -745,6 +775,15 @@ class Quant:
     chooses the variational Bayes EM instead, which differs in w alone."""
 
     STATS = ("classes", "entries", "present", "longest_label", "longest_list", "queued_labels", "queued_txps", "last_run_us", "build_us")
+    DESTROY, STAT, CLOSE_RAISES = "qm_quant_destroy", "qm_quant_stat", True
+
+    def stat(self):
+        """qm_quant_stat: a dictionary of STATS (last_run_us, build_us: the last run / the structure build by HIP events on its stream)"""
+        return super().stat()
+
+    def close(self):
+        """qm_quant_destroy; raises while a Bootstrap of this object lives (nothing is destroyed then)"""
+        super().close()
     DEFAULTS = dict(max_iter=10000, check_every=10, rel_tol=1e-2, min_alpha=1e-8)     # Salmon's offline EM
 
     def __init__(self, eq_classes, n_txps, eff_lens=None):
@@ -801,15 +840,6 @@ class Quant:
         _check(lib().qm_quant_fetch(self._h, a.ctypes.data if a.size else None))
         return a
 
-    def stat(self):
-        """qm_quant_stat: a dictionary of STATS (last_run_us, build_us: the last run / the structure build by HIP events on its stream)"""
-        d = {}
-        for i, k in enumerate(self.STATS):
-            v = C.c_int64()
-            _check(lib().qm_quant_stat(self._h, i, C.byref(v)))
-            d[k] = v.value
-        return d
-
     def classes(self):
         """qm_quant_fetch_classes: the snapshot's class side in the snapshot's own order, which is what a bootstrap draw is defined
         against (NOT the sorted order of EqClasses.fetch): (label_offsets int64[classes + 1], tids uint32[], counts uint64[classes])"""
@@ -829,18 +859,6 @@ class Quant:
         finally:
             b.close()
 
-    def close(self):
-        """qm_quant_destroy; raises while a Bootstrap of this object lives (nothing is destroyed then)"""
-        if self._h:
-            _check(lib().qm_quant_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def exp_digamma(x, device=0):
     """qm_quant_exp_digamma: E(x) = exp(digamma(x)), 0 below 1e-10, as the variational method computes it on the device -> float64
@@ -851,7 +869,7 @@ def exp_digamma(x, device=0):
     return out
 
 
-class Bootstrap:
+class Bootstrap(_Object):
     """qm_boot_*: bootstrap replicates of a Quant's estimate on the device (Salmon's --numBootstraps).  A replicate resamples the
     snapshot's class counts -- N draws, a multinomial over the classes -- and runs Quant's method (the EM, or what set_method chose
     before this object was made) on them; n_reps replicates are iterated
@@ -860,6 +878,11 @@ class Bootstrap:
     stream: close this before the Quant."""
 
     STATS = ("replicates", "draws", "last_resample_us", "last_run_us", "launches", "queued_labels", "queued_txps")
+    DESTROY, STAT = "qm_boot_destroy", "qm_boot_stat"
+
+    def stat(self):
+        """qm_boot_stat: a dictionary of STATS (last_resample_us, last_run_us: by HIP events on the stream)"""
+        return super().stat()
 
     def __init__(self, quant, n_reps):
         self._h = C.c_void_p()
@@ -899,26 +922,10 @@ class Bootstrap:
         _check(lib().qm_boot_fetch(self._h, a.ctypes.data if a.size else None))
         return a
 
-    def stat(self):
-        """qm_boot_stat: a dictionary of STATS (last_resample_us, last_run_us: by HIP events on the stream)"""
-        d = {}
-        for i, k in enumerate(self.STATS):
-            v = C.c_int64()
-            _check(lib().qm_boot_stat(self._h, i, C.byref(v)))
-            d[k] = v.value
-        return d
-
     def close(self):
         if self._h:
-            lib().qm_boot_destroy(self._h)
-            self._h = C.c_void_p()
+            super().close()
             self._quant = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def write_bootstraps(path, alphas):
@@ -1017,7 +1024,7 @@ def read_flen_dist(path):
         return np.array([float(x) for x in f.readline().rstrip("\n").split("\t")], dtype=np.float64)
 
 
-class FragLenDist:
+class FragLenDist(_Object):
     """qm_fld_*: a histogram fragment length -> fragments in the device memory of a mapper's GPU.  add(mapper) folds the mapper's
     last result where it lies; add_hits folds arrays held on the host through the same kernel; add_counts adds another histogram's
     counts (the merge primitive, and the way to a prior).  Only a unit with exactly one hit that is properly paired, on opposite
@@ -1025,6 +1032,11 @@ class FragLenDist:
     fold (0: as many as are resident)."""
 
     STATS = FLD_STATS + ("max_len", "folds", "last_fold_us")
+    DESTROY, STAT = "qm_fld_destroy", "qm_fld_stat"
+
+    def stat(self):
+        """qm_fld_stat: a dictionary of STATS (the six categories add up to units; last_fold_us: the last fold's kernel by HIP events)"""
+        return super().stat()
 
     def __init__(self, mapper, max_len=FLD_DEFAULT_MAX_LEN, max_blocks=0):
         self._h = C.c_void_p()
@@ -1039,13 +1051,7 @@ class FragLenDist:
         _check(lib().qm_fld_add(self._h, mapper._h))
 
     def add_hits(self, hit_offsets, hits):
-        hit_offsets = np.ascontiguousarray(hit_offsets, dtype=np.int64)
-        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE) if hits is not None else np.zeros(0, dtype=HIT_DTYPE)
-        n = len(hit_offsets) - 1
-        if n < 0:
-            raise ValueError("hit_offsets needs n + 1 entries")
-        if n and int(hit_offsets[-1]) > hits.size:
-            raise ValueError("hit_offsets point beyond hits")
+        n, hit_offsets, hits = _host_hits(hit_offsets, hits)
         _check(lib().qm_fld_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
 
     def add_counts(self, counts):
@@ -1060,15 +1066,6 @@ class FragLenDist:
         _check(lib().qm_fld_fetch(self._h, c.ctypes.data))
         return c
 
-    def stat(self):
-        """qm_fld_stat: a dictionary of STATS (the six categories add up to units; last_fold_us: the last fold's kernel by HIP events)"""
-        d = {}
-        for i, k in enumerate(self.STATS):
-            v = C.c_int64()
-            _check(lib().qm_fld_stat(self._h, i, C.byref(v)))
-            d[k] = v.value
-        return d
-
     def eff_lens(self, lens):
         """qm_fld_eff_lens: effective lengths float64[len(lens)] from the histogram as it stands"""
         lens = _fld_lens(lens)
@@ -1081,17 +1078,6 @@ class FragLenDist:
 
     def clear(self):
         _check(lib().qm_fld_clear(self._h))
-
-    def close(self):
-        if self._h:
-            lib().qm_fld_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 GCB_BINS = 25                                                         # QM_GCB_BINS
@@ -1114,7 +1100,7 @@ def gc_eff_lens_from_counts(counts, lens, H, alpha, obs):
     return eff, ex, ratio
 
 
-class GCBias:
+class GCBias(_Object):
     """qm_gcb_*: the fragment GC bias model in the device memory of a mapper's GPU.  add(mapper) sweeps the mapper's last result where
     it lies, add_hits sweeps arrays held on the host through the same kernel, add_counts adds another object's observed counts (the
     merge primitive): a unit with exactly one hit that is properly paired, on opposite strands, of 1 .. max_len bases and lying on
@@ -1123,6 +1109,11 @@ class GCBias:
     max_blocks: at most that many workgroups per launch (0: as many as are resident)."""
 
     STATS = GCB_STATS + ("max_len", "folds", "last_fold_us", "last_expect_us", "rank_build_us")
+    DESTROY, STAT = "qm_gcb_destroy", "qm_gcb_stat"
+
+    def stat(self):
+        """qm_gcb_stat: a dictionary of STATS (the seven categories add up to units; the times by HIP events)"""
+        return super().stat()
 
     def __init__(self, mapper, max_len=FLD_DEFAULT_MAX_LEN, max_blocks=0):
         self._h = C.c_void_p()
@@ -1137,13 +1128,7 @@ class GCBias:
         _check(lib().qm_gcb_add(self._h, mapper._h))
 
     def add_hits(self, hit_offsets, hits):
-        hit_offsets = np.ascontiguousarray(hit_offsets, dtype=np.int64)
-        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE) if hits is not None else np.zeros(0, dtype=HIT_DTYPE)
-        n = len(hit_offsets) - 1
-        if n < 0:
-            raise ValueError("hit_offsets needs n + 1 entries")
-        if n and int(hit_offsets[-1]) > hits.size:
-            raise ValueError("hit_offsets point beyond hits")
+        n, hit_offsets, hits = _host_hits(hit_offsets, hits)
         _check(lib().qm_gcb_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
 
     def add_counts(self, obs):
@@ -1157,15 +1142,6 @@ class GCBias:
         c = np.zeros(GCB_BINS, dtype=np.uint64)
         _check(lib().qm_gcb_fetch(self._h, c.ctypes.data))
         return c
-
-    def stat(self):
-        """qm_gcb_stat: a dictionary of STATS (the seven categories add up to units; the times by HIP events)"""
-        d = {}
-        for i, k in enumerate(self.STATS):
-            v = C.c_int64()
-            _check(lib().qm_gcb_stat(self._h, i, C.byref(v)))
-            d[k] = v.value
-        return d
 
     def expect(self, counts, n_txps):
         """qm_gcb_expect: the expected matrix uint64[n_txps][25] of a fragment-length histogram counts uint64[max_len + 1]"""
@@ -1189,17 +1165,6 @@ class GCBias:
 
     def clear(self):
         _check(lib().qm_gcb_clear(self._h))
-
-    def close(self):
-        if self._h:
-            lib().qm_gcb_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def write_gc_bias(path, obs, exp, ratio):
@@ -1288,7 +1253,7 @@ def read_lib_format_counts(path):
     return c, d
 
 
-class LibFormat:
+class LibFormat(_Object):
     """qm_lib_*: the tallies of a library type in the device memory of a mapper's GPU.  Every hit record has an orientation code
     (LIB_CODES; include/qmap_mi355.h has the table); lib_type names the codes that are compatible (LIB_TYPES, or a 12-bit mask; "A":
     all of them, nothing is dropped).  add(mapper) tallies the mapper's last result where it lies, add_hits arrays held on the host
@@ -1297,6 +1262,11 @@ class LibFormat:
     as are resident)."""
 
     STATS = ("sweeps", "last_sweep_us", "mask")
+    DESTROY, STAT = "qm_lib_destroy", "qm_lib_stat"
+
+    def stat(self):
+        """qm_lib_stat: a dictionary of STATS (last_sweep_us: the last sweep by HIP events)"""
+        return super().stat()
 
     def __init__(self, mapper, lib_type="A", max_blocks=0):
         self._h = C.c_void_p()
@@ -1311,24 +1281,13 @@ class LibFormat:
         """tally the result of the mapper's last map call"""
         _check(lib().qm_lib_add(self._h, mapper._h))
 
-    @staticmethod
-    def _host(hit_offsets, hits):
-        hit_offsets = np.ascontiguousarray(hit_offsets, dtype=np.int64)
-        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE) if hits is not None else np.zeros(0, dtype=HIT_DTYPE)
-        n = len(hit_offsets) - 1
-        if n < 0:
-            raise ValueError("hit_offsets needs n + 1 entries")
-        if n and int(hit_offsets[-1]) > hits.size:
-            raise ValueError("hit_offsets point beyond hits")
-        return n, hit_offsets, hits
-
     def add_hits(self, hit_offsets, hits):
-        n, hit_offsets, hits = self._host(hit_offsets, hits)
+        n, hit_offsets, hits = _host_hits(hit_offsets, hits)
         _check(lib().qm_lib_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
 
     def compact_hits(self, hit_offsets, hits):
         """add_hits, and the filtered lists: (new_offsets int64[n + 1], tids uint32[]) -- every unit's kept hits, in their order"""
-        n, hit_offsets, hits = self._host(hit_offsets, hits)
+        n, hit_offsets, hits = _host_hits(hit_offsets, hits)
         new_off = np.zeros(n + 1, dtype=np.int64); tids = np.zeros((int(hit_offsets[-1] - hit_offsets[0]) if n else 0) + 1, dtype=np.uint32)
         _check(lib().qm_lib_compact_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None, new_off.ctypes.data, tids.ctypes.data))
         return new_off, tids[:int(new_off[-1])].copy()
@@ -1343,28 +1302,8 @@ class LibFormat:
         _check(lib().qm_lib_fetch(self._h, c.ctypes.data))
         return c
 
-    def stat(self):
-        """qm_lib_stat: a dictionary of STATS (last_sweep_us: the last sweep by HIP events)"""
-        d = {}
-        for i, k in enumerate(self.STATS):
-            v = C.c_int64()
-            _check(lib().qm_lib_stat(self._h, i, C.byref(v)))
-            d[k] = v.value
-        return d
-
     def clear(self):
         _check(lib().qm_lib_clear(self._h))
-
-    def close(self):
-        if self._h:
-            lib().qm_lib_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 PACK_EXC_DTYPE = np.dtype([("pos", "<u4"), ("ch", "<u4")])
@@ -1520,15 +1459,18 @@ class MappedStream:
             raise QmError("qm_stream_open failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
         self._index = index
 
+    def _call(self, name, *args):
+        """lib().<name>(the stream, args...); QmError with qm_stream_last_error when it fails"""
+        rc = getattr(lib(), name)(self._h, *args)
+        if rc != 0:
+            raise QmError("%s failed (%d): %s" % (name, rc, lib().qm_stream_last_error().decode(errors="replace")))
+
     def __iter__(self):
-        L = lib()
         sb = QmStreamBatch()
 
         arr = _view
         while True:
-            rc = L.qm_stream_next(self._h, C.byref(sb))
-            if rc != 0:
-                raise QmError("qm_stream_next failed (%d): %s" % (rc, L.qm_stream_last_error().decode(errors="replace")))
+            self._call("qm_stream_next", C.byref(sb))
             if sb.n_units == 0:
                 return
             b = ReadBatch(); b.n = n = sb.n_units
@@ -1554,40 +1496,30 @@ class MappedStream:
         """after the last batch: the classes of the whole input, merged over the stream's contexts and devices --
         (label_offsets, tids, counts) as EqClasses.fetch gives them"""
         nc, nt = C.c_int64(), C.c_int64()
-        rc = lib().qm_stream_eqc_finish(self._h, C.byref(nc), C.byref(nt))
-        if rc != 0:
-            raise QmError("qm_stream_eqc_finish failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        self._call("qm_stream_eqc_finish", C.byref(nc), C.byref(nt))
         off = np.zeros(nc.value + 1, dtype=np.int64); tids = np.zeros(nt.value + 1, dtype=np.uint32); cnt = np.zeros(nc.value + 1, dtype=np.uint64)
-        rc = lib().qm_stream_eqc_fetch(self._h, off.ctypes.data, tids.ctypes.data, cnt.ctypes.data)
-        if rc != 0:
-            raise QmError("qm_stream_eqc_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        self._call("qm_stream_eqc_fetch", off.ctypes.data, tids.ctypes.data, cnt.ctypes.data)
         return off, tids[:nt.value], cnt[:nc.value]
 
     def frag_len_dist(self):
         """after the last batch of a stream opened with frag_len_dist=True: (counts uint64[1001], stats) summed over the stream's
         contexts and devices -- stats: a dictionary of units and the six categories (FLD_STATS)"""
         c = np.zeros(FLD_DEFAULT_MAX_LEN + 1, dtype=np.uint64); st = np.zeros(7, dtype=np.int64)
-        rc = lib().qm_stream_fld_fetch(self._h, c.ctypes.data, st.ctypes.data)
-        if rc != 0:
-            raise QmError("qm_stream_fld_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        self._call("qm_stream_fld_fetch", c.ctypes.data, st.ctypes.data)
         return c, dict(zip(FLD_STATS, (int(x) for x in st)))
 
     def gc_bias(self):
         """after the last batch of a stream opened with gc_bias=True: (obs uint64[25], stats) summed over the stream's contexts and
         devices -- stats: a dictionary of units and the seven categories (GCB_STATS)"""
         c = np.zeros(GCB_BINS, dtype=np.uint64); st = np.zeros(8, dtype=np.int64)
-        rc = lib().qm_stream_gcb_fetch(self._h, c.ctypes.data, st.ctypes.data)
-        if rc != 0:
-            raise QmError("qm_stream_gcb_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        self._call("qm_stream_gcb_fetch", c.ctypes.data, st.ctypes.data)
         return c, dict(zip(GCB_STATS, (int(x) for x in st)))
 
     def lib_counts(self):
         """after the last batch of a stream opened with lib_type: the tallies uint64[32] (LibFormat.counts) summed over the stream's
         contexts and devices"""
         c = np.zeros(32, dtype=np.uint64)
-        rc = lib().qm_stream_lib_fetch(self._h, c.ctypes.data)
-        if rc != 0:
-            raise QmError("qm_stream_lib_fetch failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
+        self._call("qm_stream_lib_fetch", c.ctypes.data)
         return c
 
     def stats(self):

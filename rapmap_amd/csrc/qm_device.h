@@ -15,7 +15,7 @@
 
 namespace qm {
 struct DevIndex; struct ReadBatch; struct PairBatch; struct SelBatch;   // the launch arguments (qm_mapper.inl, qm_sel.inl)
-struct EqcSrc; struct FldSrc; struct FldAcc; struct LibSrc; struct LibAcc; struct GcbIdx; struct GcbAcc; // ... of the estimation objects (qm_eqc.inl, qm_fld.inl, qm_lib.inl)
+struct EqcSrc;              // ... of the equivalence-class table (qm_eqc.inl)
 
 // Resident blocks per CU of kernel K launched with THREADS threads: the occupancy query, once per instantiation (FALLBACK where it
 // fails); KNOB: QM_BLOCKS_PER_CU -- a tuning knob, fewer resident blocks than the occupancy allows -- may lower it.  See qm_grid.h.
@@ -92,15 +92,9 @@ hipError_t qmk_stage_gather(long long nreads, const unsigned int* ivcnt, const l
                             const unsigned int* lcnt, const long long* loff, const unsigned long long* lists, const long long* lcsr,
                             unsigned long long* words_out, hipStream_t st);
 
-// The estimation objects' kernels that are no plain wave body (the lane emulation defines these launchers a second time, static, next
-// to the drivers: qm_eqc_host.inl, qm_fld_host.inl, qm_lib_host.inl).  The equivalence-class table:
+// The estimation objects' kernels that are neither a plain wave body nor a persistent sweep (those two kinds are launched through
+// qm_exec.h where their driver is compiled): the equivalence-class table's.  The lane emulation defines these launchers a second time,
+// static, next to the driver (qm_eqc_host.inl).
 hipError_t qmk_eqc_label_queued(const qm::EqcSrc& src, long long nq, hipStream_t st);
 hipError_t qmk_eqc_reset_probes(unsigned long long* q, long long n, hipStream_t st);
 hipError_t qmk_eqc_sum(const unsigned long long* count, const unsigned long long* key, long long cap, unsigned long long* out, hipStream_t st);
-// the fragment-length histogram (qm_fld.inl) and the two persistent kernels of the library-type sweep (qm_lib.inl: classify over the
-// hits, units over the units).  blocks: workgroups of the persistent grid, sweep_grid of qm_grid.h
-hipError_t qmk_fld_fold(const qm::FldSrc& src, const qm::FldAcc& acc, int blocks, hipStream_t st);
-hipError_t qmk_lib_classify(const qm::LibSrc& src, const qm::LibAcc& acc, int blocks, hipStream_t st);
-hipError_t qmk_lib_units(const qm::LibSrc& src, const qm::LibAcc& acc, int blocks, hipStream_t st);
-// the observed sweep of the GC bias model (qm_gcb.inl)
-hipError_t qmk_gcb_obs(const qm::FldSrc& src, const qm::GcbIdx& idx, const qm::GcbAcc& acc, int blocks, hipStream_t st);

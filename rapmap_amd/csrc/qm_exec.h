@@ -6,8 +6,11 @@
 // stream, the scans and the sort are rocPRIM's, and the host operations are HIP's.  With -DQM_EMU (tests/emu only) a buffer is a
 // vector, a launch is a loop over the wavefronts, one after the other, and the rest is serial host code: the drivers are the same
 // text in both builds, so the CPU suite runs the drivers and not a transcription of them.
-// A kernel that is not a plain wave body (an LDS slab per wavefront, a persistent grid) is not launched through here: it keeps its
-// own kernel and a named launch function with two definitions next to its driver.
+// There are two kinds of launch.  launch / launch2: a plain wave body, one wavefront per piece of work.  sweep: a persistent grid of
+// `blocks` workgroups whose wavefronts stride over the work themselves (Body gets its index and their number), each with an LDS
+// slab of its own when the body wants one; the emulation hands every wavefront a slab filled with 0xA5, so a body must zero what it
+// uses.  A kernel that is neither (qm_eqc_host.inl has three) keeps its own kernel and a named launch function with two
+// definitions next to its driver.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -58,6 +61,19 @@ int launch(Stream, long long waves, const A&... a) {
 template <auto Body, class... A>
 int launch2(Stream, long long waves, long long ny, const A&... a) {
   for (long long y = 0; y < ny; ++y) for (long long w = 0; w < waves; ++w) Body(a..., w, y);
+  return 0;
+}
+
+// the persistent grid: Body(args..., wave, 4 * blocks[, slab]) for every wavefront, one after the other, each on SLAB_WORDS words
+// refilled with 0xA5A5A5A5
+template <auto Body, int SLAB_WORDS = 0, class... A>
+int sweep(Stream, int blocks, const A&... a) {
+  const long long nWaves = 4LL * blocks;
+  std::vector<u32> slab((size_t)SLAB_WORDS);
+  for (long long w = 0; w < nWaves; ++w) {
+    if constexpr (SLAB_WORDS > 0) { slab.assign((size_t)SLAB_WORDS, 0xA5A5A5A5u); Body(a..., w, nWaves, slab.data()); }
+    else Body(a..., w, nWaves);
+  }
   return 0;
 }
 
@@ -119,6 +135,24 @@ template <auto Body, class... A>
 hipError_t launch2(Stream st, long long waves, long long ny, A... a) {
   if (waves <= 0 || ny <= 0) return hipSuccess;
   hipLaunchKernelGGL((wave2_kernel<Body, A...>), dim3(wave_blocks(waves), (unsigned)ny), dim3(QX_BLOCK), 0, st, waves, a...);
+  return hipGetLastError();
+}
+
+// The one kernel of every persistent grid: every wavefront of the `blocks` workgroups runs Body(args..., wave, waves in the grid
+// [, slab]), slab: SLAB_WORDS words of LDS of its own.  blocks <= 0 launches nothing.
+template <auto Body, int SLAB_WORDS, class... A>
+__global__ void __launch_bounds__(QX_BLOCK) sweep_kernel(A... a) {
+  const long long w = uniform(((long long)blockIdx.x * QX_BLOCK + threadIdx.x) >> 6), nWaves = (long long)gridDim.x * (QX_BLOCK / 64);
+  if constexpr (SLAB_WORDS > 0) {
+    __shared__ u32 slab[QX_BLOCK / 64][SLAB_WORDS];
+    Body(a..., w, nWaves, (QM_LDS(u32)*)&slab[threadIdx.x >> 6][0]);
+  }
+  else Body(a..., w, nWaves);
+}
+template <auto Body, int SLAB_WORDS = 0, class... A>
+hipError_t sweep(Stream st, int blocks, A... a) {
+  if (blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL((sweep_kernel<Body, SLAB_WORDS, A...>), dim3((unsigned)blocks), dim3(QX_BLOCK), 0, st, a...);
   return hipGetLastError();
 }
 

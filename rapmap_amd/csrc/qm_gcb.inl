@@ -14,13 +14,12 @@
 //   gcb_mask_wave    64 blocks per wavefront: a ballot per block, lane j keeps block j's, then one coalesced store of masks and counts
 //   gcb_rank_wave    the exclusive scan of the counts (64-bit, qx::scan_u32) narrowed to 32 bits
 //   gcb_probe_wave   qm_gcb_window_gc: one lane per question
-//   gcb_obs_wave     the observed sweep, fld_wave's shape (below)
+//   gcb_obs_wave     the observed sweep, on the frame of qm_sweep.h (below)
 //   gcb_tiles_wave   tiles (GCB_TILE consecutive starts) per transcript, for the scan that gives the tile table
-//   gcb_expect_wave  the expected matrix (below)
+//   gcb_expect_wave  the expected matrix: a persistent grid, launched by qx::sweep like the observed sweep (below)
 #pragma once
 #include <stddef.h>
-#include "qm_wave.h"
-#include "qm_fld.inl"        // FldSrc: the units of a fold; the first five categories are the fragment-length histogram's
+#include "qm_sweep.h"
 
 namespace qm {
 
@@ -31,8 +30,6 @@ static_assert(sizeof(qm_hit) == 32 && offsetof(qm_hit, tid) == 0 && offsetof(qm_
 
 #define GCB_BINS QM_GCB_BINS
 #define GCB_SLAB 32          // words of a wavefront's LDS tally, and of the object's 64-bit bins in device memory
-enum { GCB_C_USED = 0, GCB_C_UNMAPPED = 1, GCB_C_MULTI = 2, GCB_C_NOT_PAIRED = 3, GCB_C_SAME_STRAND = 4, GCB_C_OUT_OF_RANGE = 5, GCB_C_OVERHANG = 6, GCB_C_WORDS = 8 };
-#define GCB_ACC_WORDS (GCB_SLAB + GCB_C_WORDS)   // the object's device memory: the 64-bit bins, then the counters
 #define GCB_BLOCKS_PER_CU 8  // workgroups of four wavefronts resident per compute unit (both sweeps)
 #define GCB_TILE 64          // consecutive start positions of one transcript: one lane each
 #define GCB_MAX_LEN 1023     // the longest fragment: g * 2 * GCB_BINS < 2^16 and the reciprocal rule below hold up to here
@@ -92,16 +89,12 @@ QM_DEV void gcb_probe_wave(const GcbIdx& I, long long nq, const u32* tid, const 
   }
 }
 
-// ---- the observed sweep.  fld_wave's shape: off[u + 1] from one coalesced 8-byte load per lane, off[u] from the lane below; only a
-// lane whose unit has exactly one hit loads from that hit's record -- 16 bytes at 0 (tid, pos, mate_pos, frag_len) and the dword at
-// byte 24 (fwd, mate_is_fwd, is_paired, mate_status), one 32-byte sector; a lane that passes the five categories of the
-// fragment-length histogram gathers txpOff and txpLen and, where the window lies on the transcript, the two rank lookups.  The
-// categories are ballots and popcounts; a used lane adds one to its bin in the wavefront's LDS tally, flushed once at the end.
-struct GcbAcc {
-  u64* bins;                 // [GCB_BINS]
-  u64* ctr;                  // [GCB_C_WORDS]
-  int maxLen;
-};
+// ---- the observed sweep, on the frame of qm_sweep.h.  Only a lane whose unit has exactly one hit loads from that hit's record -- 16
+// bytes at 0 (tid, pos, mate_pos, frag_len) and the dword at byte 24 (fwd, mate_is_fwd, is_paired, mate_status), one 32-byte sector; a
+// lane that passes the categories of the fragment-length histogram (frag_gate) gathers txpOff and txpLen and, where the window lies
+// on the transcript, the two rank lookups; where it does not, the unit is the one category this sweep adds: overhang.  A used lane
+// adds one to its bin in the wavefront's LDS tally, flushed once at the end.
+enum { GCB_C_OVERHANG = SW_C_GATE, GCB_C_N = SW_C_GATE + 1, GCB_C_WORDS = SW_C_WORDS };   // (GCB_C_WORDS: the object's counter words behind its bins)
 
 #ifdef QM_EMU
 QM_DEV void gcb_load_rec(const unsigned char* r, U4& a, u32& w) { a = load_16(r); w = *(const u32*)(r + 24); }
@@ -116,59 +109,38 @@ QM_DEV void gcb_load_rec(const unsigned char* r, U4& a, u32& w) {
 #endif
 
 // wavefront `wave` of `nWaves` (both wave-uniform); slab: GCB_SLAB words of its own
-QM_DEV void gcb_obs_wave(const FldSrc& S, const GcbIdx& I, const GcbAcc& A, long long wave, long long nWaves, QM_LDS(u32)* slab) {
-  QM_LANES(l) if (l < GCB_SLAB) slab[l] = 0;
-  wave_fence();
-  u64 ctr[7] = {0, 0, 0, 0, 0, 0, 0};
+QM_DEV void gcb_obs_wave(const UnitSrc& S, const GcbIdx& I, const SweepAcc& A, long long wave, long long nWaves, QM_LDS(u32)* slab) {
+  slab_zero(slab, GCB_SLAB);
+  u64 ctr[GCB_C_N] = {0, 0, 0, 0, 0, 0, 0};
   for (long long base = wave * 64; base < S.n; base += nWaves * 64) {
-    LV<int> hiLo, hiHi, loLo, loHi;                             // off[u + 1] as two dwords, and the lane below's
+    LV<long long> o0, o1;
+    unit_bounds(S, base, o0, o1);
+    LV<int> cat; LV<u32> bin;
     QM_LANES(l) {
-      const long long u = base + l;
-      const long long e = u < S.n ? S.off[u + 1] : 0;
-      hiLo[l] = (int)(u32)(u64)e; hiHi[l] = (int)(u32)((u64)e >> 32);
-    }
-    lane_rotate_up(hiLo, loLo); lane_rotate_up(hiHi, loHi);
-    const long long first = load_uniform_i64(S.off + base);     // off[base]: lane 0 has no lane below
-    LV<bool> unm, multi, np, ss, oor, ovh, used; LV<u32> bin;
-    QM_LANES(l) {
-      unm[l] = multi[l] = np[l] = ss[l] = oor[l] = ovh[l] = used[l] = false; bin[l] = 0;
-      const long long u = base + l;
-      if (u >= S.n) continue;
-      const long long o1 = (long long)(((u64)(u32)hiHi[l] << 32) | (u32)hiLo[l]);
-      const long long o0 = l ? (long long)(((u64)(u32)loHi[l] << 32) | (u32)loLo[l]) : first;
-      const long long c = o1 - o0;
-      if (c == 0) unm[l] = true;
-      else if (c != 1) multi[l] = true;
-      else {
-        U4 a; u32 w;
-        gcb_load_rec(S.hits + o0 * (long long)S.stride, a, w);
-        const u32 f = a.w;
-        if ((w >> 24) != 3u) np[l] = true;                      // mate_status != PE_PAIRED
-        else if ((w & 0xffu) == ((w >> 8) & 0xffu)) ss[l] = true;   // fwd == mate_is_fwd
-        else if (f == 0 || f > (u32)A.maxLen) oor[l] = true;
-        else if ((long long)a.x >= I.nTxp) ovh[l] = true;
-        else {
+      cat[l] = -1; bin[l] = 0;
+      if (base + l >= S.n) continue;
+      const long long c = o1[l] - o0[l];
+      U4 a{0, 0, 0, 0}; u32 w = 0;
+      if (c == 1) gcb_load_rec(S.hits + o0[l] * (long long)S.stride, a, w);
+      const u32 f = a.w;
+      int k = frag_gate(c, f, w, A.maxLen);
+      if (k == SW_C_USED) {
+        k = GCB_C_OVERHANG;
+        if ((long long)a.x < I.nTxp) {
           const int p = (int)a.y, mp = (int)a.z;
           const long long s = (p > 0 ? p : 0) < (mp > 0 ? mp : 0) ? (p > 0 ? p : 0) : (mp > 0 ? mp : 0), e = s + (long long)f;
           const long long o = I.txpOff[a.x], L = I.txpLen[a.x];
-          if (e > L) ovh[l] = true;
-          else { used[l] = true; bin[l] = gcb_bin(gcb_rank_at(I, o + e) - gcb_rank_at(I, o + s), f); }
+          if (e <= L) { k = SW_C_USED; bin[l] = gcb_bin(gcb_rank_at(I, o + e) - gcb_rank_at(I, o + s), f); }
         }
       }
+      cat[l] = k;
     }
-    ctr[GCB_C_UNMAPPED] += (u64)popc64(ballot(unm)); ctr[GCB_C_MULTI] += (u64)popc64(ballot(multi)); ctr[GCB_C_NOT_PAIRED] += (u64)popc64(ballot(np));
-    ctr[GCB_C_SAME_STRAND] += (u64)popc64(ballot(ss)); ctr[GCB_C_OUT_OF_RANGE] += (u64)popc64(ballot(oor)); ctr[GCB_C_OVERHANG] += (u64)popc64(ballot(ovh));
-    ctr[GCB_C_USED] += (u64)popc64(ballot(used));
-    QM_LANES(l) if (used[l]) fld_slab_inc(slab + bin[l]);
+    tally<GCB_C_N>(cat, ctr);
+    QM_LANES(l) if (cat[l] == SW_C_USED) slab_inc(slab + bin[l]);
   }
-  wave_fence();
-  QM_LANES(l) if (l < GCB_BINS) { const u32 v = slab[l]; if (v) atomic_add_u64(&A.bins[l], (u64)v); }
-  // the counter flush: lane i holds counter i
-  QM_LANES(l) {
-    if (l >= 7) continue;
-    const u64 v = l == 0 ? ctr[0] : l == 1 ? ctr[1] : l == 2 ? ctr[2] : l == 3 ? ctr[3] : l == 4 ? ctr[4] : l == 5 ? ctr[5] : ctr[6];
-    if (v) atomic_add_u64(&A.ctr[l], v);
-  }
+  slab_flush(slab, GCB_BINS, A.bins);
+  const int word[GCB_C_N] = {SW_C_USED, SW_C_UNMAPPED, SW_C_MULTI, SW_C_NOT_PAIRED, SW_C_SAME_STRAND, SW_C_OUT_OF_RANGE, GCB_C_OVERHANG};
+  flush_counters(A.ctr, ctr, word);
 }
 
 // ---- the expected matrix: H[t][b] = sum over l of counts[l] * #{ starts s in [0, L_t - l] whose window [s, s + l) falls in bin b }.
@@ -197,7 +169,7 @@ struct GcbExp {
   const long long* tileOff;  // [nTxp + 1]
   const u64* tab;            // [2 * (maxLen + 1)]: counts[l], then ceil(2^31 / l)
   u64* H;                    // [nTxp * GCB_BINS]
-  long long nTxp, nTiles, nWaves;
+  long long nTxp, nTiles;
   int maxLen;
 };
 
@@ -221,8 +193,9 @@ QM_DEV void gcb_expect_flush(const GcbExp& E, long long t, LV<u64>& acc) {
   QM_LANES(l) { if (l < GCB_BINS && acc[l]) atomic_add_u64(&E.H[t * GCB_BINS + l], acc[l]); acc[l] = 0; }
 }
 
-QM_DEV void gcb_expect_wave(const GcbExp& E, long long wave) {
-  const long long per = (E.nTiles + E.nWaves - 1) / E.nWaves;
+// wavefront `wave` of `nWaves` (both wave-uniform)
+QM_DEV void gcb_expect_wave(const GcbExp& E, long long wave, long long nWaves) {
+  const long long per = (E.nTiles + nWaves - 1) / nWaves;
   const long long k0 = wave * per, k1 = k0 + per < E.nTiles ? k0 + per : E.nTiles;
   if (k0 >= k1) return;
   long long lo = 0, hi = E.nTxp;                                 // tileOff[lo] <= k0 < tileOff[hi]

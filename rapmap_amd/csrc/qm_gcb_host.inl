@@ -1,5 +1,5 @@
-// qm_gcb_host.inl -- host driver of the fragment GC bias model (device code: qm_gcb.inl, the observed sweep's kernel:
-// qm_kernels_gcb.hip) and the arithmetic from the two sets of counts to effective lengths.  Included at the end of qm_host.hip:
+// qm_gcb_host.inl -- host driver of the fragment GC bias model (device code: qm_gcb.inl; the tally half of the object:
+// qm_tally_host.inl) and the arithmetic from the two sets of counts to effective lengths.  Included at the end of qm_host.hip:
 // qm_gcb_add reads the context's last result where it lies in device memory, and the rank structure lives in the context's
 // replica.  Everything above the extern "C" block is written against qm_exec.h and compiled twice: here, and with -DQM_EMU by
 // tests/emu.
@@ -9,38 +9,19 @@
 // object's first qm_gcb_expect.
 #include <algorithm>
 #include "qm_gcb.inl"
-#include "qm_exec.h"
-#include "qm_grid.h"
+#include "qm_tally_host.inl"
 
-struct qm_gcb : qx::Base {
+struct qm_gcb : qx::Tally<GCB_SLAB> {
 #ifndef QM_EMU
-  std::shared_ptr<Replica> rep;                                       // (first: the last member to go)
+  std::shared_ptr<Replica> rep;                                       // (held while the object lives; the base's buffers are freed after it is released and need nothing from it)
 #endif
-  int maxLen = QM_FLD_DEFAULT_MAX_LEN, maxBlocks = 0;
   GcbIdx I{};                                                         // the replica's (the emulation: the object's own) rank structure and transcripts
   long long maxTxpLen = 0;                                            // the longest transcript: the overflow refusal of expect
-  DevBuf<u64> d_acc;                                                  // GCB_ACC_WORDS: the bins, then the counters
-  u64 h[GCB_C_WORDS] = {0};                                           // the counters as last read
-  qx::FeedBuf in;                                                     // qm_gcb_add_hits
   DevBuf<u32> d_tileCnt; DevBuf<long long> d_tileOff; long long nTiles = -1;   // the tile table (-1: not made yet)
   DevBuf<u64> d_tab, d_H; DevBuf<unsigned char> d_tmp;                // expect: (count, reciprocal) per length, the matrix, the scan's scratch
   DevBuf<u32> d_qTid; DevBuf<int> d_qStart, d_qLen, d_qOut;           // qm_gcb_window_gc
-  int64_t units = 0, folds = 0, lastFoldUs = 0, lastExpectUs = 0, rankBuildUs = 0;
+  int64_t lastExpectUs = 0, rankBuildUs = 0;
 };
-
-// the sweep's kernel (qm_kernels_gcb.hip, declared in qm_device.h) as the emulation runs it: four wavefronts per workgroup, one
-// after the other, each on a tally filled with 0xA5 -- the body must zero what it uses
-#ifdef QM_EMU
-static int qmk_gcb_obs(const FldSrc& S, const GcbIdx& I, const GcbAcc& A, int blocks, qx::Stream) {
-  if (S.n <= 0 || blocks <= 0) return 0;
-  u32 slab[GCB_SLAB];
-  for (long long w = 0; w < 4LL * blocks; ++w) {
-    for (int i = 0; i < GCB_SLAB; ++i) slab[i] = 0xA5A5A5A5u;
-    gcb_obs_wave(S, I, A, w, 4LL * blocks, slab);
-  }
-  return 0;
-}
-#endif
 
 // The rank structure over text[0 .. n) into mask and rank (gcb_blocks(n) words each); tmp: scratch.  The stream is idle when this returns.
 static int gcb_build_rank(qx::Stream st, const unsigned char* text, long long n, DevBuf<u64>& mask, DevBuf<u32>& rank, DevBuf<unsigned char>& tmp) {
@@ -54,64 +35,31 @@ static int gcb_build_rank(qx::Stream st, const unsigned char* text, long long n,
   return qx::sync(st);                                                // (cnt and scan go out of scope)
 }
 
+// (the driver's functions are what the extern "C" shells below and the emulation's face call)
 static int gcb_clear(qm_gcb* g) {
-  int rc;
-  if ((rc = qx::fill(g->stream, g->d_acc, 0, GCB_ACC_WORDS * sizeof(u64))) || (rc = qx::sync(g->stream))) return rc;
-  memset(g->h, 0, sizeof(g->h));
-  g->units = g->folds = g->lastFoldUs = g->lastExpectUs = 0;
-  return QM_OK;
+  const int rc = g->clear();
+  if (!rc) g->lastExpectUs = 0;
+  return rc;
 }
-static int gcb_open(qm_gcb* g) {
-  const int rc = g->d_acc.ensure(GCB_ACC_WORDS);
-  return rc ? rc : gcb_clear(g);
+static int gcb_open(qm_gcb* g) { return g->open_bins(); }
+static int gcb_add_counts(qm_gcb* g, const uint64_t* obs) { return g->add_counts(obs, GCB_BINS); }
+static int gcb_fold(qm_gcb* g, const UnitSrc& S, qx::Stream st) {
+  return g->fold(S, st, GCB_BLOCKS_PER_CU, [&](const SweepAcc& A, int blocks) { return qx::sweep<gcb_obs_wave, GCB_SLAB>(st, blocks, S, g->I, A); });
 }
-
-static int gcb_fold(qm_gcb* g, const FldSrc& S, qx::Stream st) {
-  if (S.n <= 0) return QM_OK;
-  if (S.n >= (1LL << 32)) return fail(QM_E_ARG, "more than 2^32 - 1 units in one fold");   // (a wavefront's 32-bit tally cannot overflow)
-  const GcbAcc A{g->d_acc, g->d_acc + GCB_SLAB, g->maxLen};
-  QXCHK(qx::tick(g->ev0, st));
-  HIPCHK(qmk_gcb_obs(S, g->I, A, sweep_grid(S.n, g->numCU, GCB_BLOCKS_PER_CU, g->maxBlocks), st));
-  QXCHK(qx::tick(g->ev1, st));
-  QXCHK(qx::read(st, g->h, g->d_acc + GCB_SLAB, sizeof(g->h)));       // (the one wait of a fold: both events have passed)
-  qx::elapsed(g->ev0, g->ev1, &g->lastFoldUs);
-  g->units += S.n; g->folds++;
-  return QM_OK;
-}
-
 // qm_gcb_add_hits: the host arrays in parts (at most maxUnits units and maxHits hits each) through the fold
 static int gcb_add_hits(qm_gcb* g, int64_t n, const int64_t* offsets, const qm_hit* hits, int64_t maxUnits, int64_t maxHits) {
-  return qx::feed(g->stream, g->in, "qm_gcb_add_hits", "unit", "hits", n, offsets, hits, sizeof(qm_hit), nullptr, maxUnits, maxHits,
-                  [&](const long long* off, const unsigned char* h, const u64*, int64_t, int64_t nu, int64_t) {
-                    return gcb_fold(g, FldSrc{h, (int)sizeof(qm_hit), off, nu}, g->stream);
-                  });
-}
-
-static int gcb_fetch(qm_gcb* g, uint64_t* obs) { return qx::read(g->stream, obs, g->d_acc, GCB_BINS * sizeof(u64)); }
-
-static int gcb_add_counts(qm_gcb* g, const uint64_t* obs) {
-  // off the per-batch path: the bins and the `used` counter come to the host, are added to and go back
-  u64 acc[GCB_ACC_WORDS];
-  QXCHK(qx::read(g->stream, acc, g->d_acc, sizeof(acc)));
-  u64 sum = 0;
-  for (int b = 0; b < GCB_BINS; ++b) { acc[b] += obs[b]; sum += obs[b]; }
-  acc[GCB_SLAB + GCB_C_USED] += sum;
-  QXCHK(qx::upload(g->stream, g->d_acc, acc, sizeof(acc)));
-  QXCHK(qx::sync(g->stream));
-  memcpy(g->h, acc + GCB_SLAB, sizeof(g->h));
-  g->units += (int64_t)sum;
-  return QM_OK;
+  return g->add_hits("qm_gcb_add_hits", n, offsets, hits, maxUnits, maxHits, [&](const UnitSrc& S) { return gcb_fold(g, S, g->stream); });
 }
 
 static int gcb_stat(const qm_gcb* g, int which, int64_t* value) {
   switch (which) {
     case QM_GCB_STAT_UNITS: *value = g->units; break;
-    case QM_GCB_STAT_USED: *value = (int64_t)g->h[GCB_C_USED]; break;
-    case QM_GCB_STAT_UNMAPPED: *value = (int64_t)g->h[GCB_C_UNMAPPED]; break;
-    case QM_GCB_STAT_MULTI: *value = (int64_t)g->h[GCB_C_MULTI]; break;
-    case QM_GCB_STAT_NOT_PAIRED: *value = (int64_t)g->h[GCB_C_NOT_PAIRED]; break;
-    case QM_GCB_STAT_SAME_STRAND: *value = (int64_t)g->h[GCB_C_SAME_STRAND]; break;
-    case QM_GCB_STAT_OUT_OF_RANGE: *value = (int64_t)g->h[GCB_C_OUT_OF_RANGE]; break;
+    case QM_GCB_STAT_USED: *value = (int64_t)g->h[SW_C_USED]; break;
+    case QM_GCB_STAT_UNMAPPED: *value = (int64_t)g->h[SW_C_UNMAPPED]; break;
+    case QM_GCB_STAT_MULTI: *value = (int64_t)g->h[SW_C_MULTI]; break;
+    case QM_GCB_STAT_NOT_PAIRED: *value = (int64_t)g->h[SW_C_NOT_PAIRED]; break;
+    case QM_GCB_STAT_SAME_STRAND: *value = (int64_t)g->h[SW_C_SAME_STRAND]; break;
+    case QM_GCB_STAT_OUT_OF_RANGE: *value = (int64_t)g->h[SW_C_OUT_OF_RANGE]; break;
     case QM_GCB_STAT_OVERHANG: *value = (int64_t)g->h[GCB_C_OVERHANG]; break;
     case QM_GCB_STAT_MAX_LEN: *value = g->maxLen; break;
     case QM_GCB_STAT_FOLDS: *value = g->folds; break;
@@ -150,10 +98,9 @@ static int gcb_expect(qm_gcb* g, const uint64_t* counts, int64_t nTxps, uint64_t
   if ((rc = g->d_tab.ensure((int64_t)tab.size())) || (rc = g->d_H.ensure(nTxps * GCB_BINS))) return rc;
   QXCHK(qx::upload(st, g->d_tab, tab.data(), tab.size() * sizeof(u64)));
   QXCHK(qx::fill(st, g->d_H, 0, (size_t)nTxps * GCB_BINS * sizeof(u64)));
-  GcbExp E{g->I.mask, g->I.txpOff, g->I.txpLen, g->d_tileOff, g->d_tab, g->d_H, g->I.nTxp, g->nTiles, 0, g->maxLen};
-  E.nWaves = 4LL * sweep_grid(g->nTiles * 64, g->numCU, GCB_BLOCKS_PER_CU, g->maxBlocks);
+  const GcbExp E{g->I.mask, g->I.txpOff, g->I.txpLen, g->d_tileOff, g->d_tab, g->d_H, g->I.nTxp, g->nTiles, g->maxLen};
   QXCHK(qx::tick(g->ev0, st));
-  if (P && g->nTiles > 0) HIPCHK((qx::launch<gcb_expect_wave>(st, E.nWaves, E)));
+  if (P && g->nTiles > 0) HIPCHK((qx::sweep<gcb_expect_wave>(st, sweep_grid(g->nTiles * 64, g->numCU, GCB_BLOCKS_PER_CU, g->maxBlocks), E)));
   QXCHK(qx::tick(g->ev1, st));
   QXCHK(qx::read(st, H, g->d_H, (size_t)nTxps * GCB_BINS * sizeof(u64)));   // (waits; the table on the host may go)
   qx::elapsed(g->ev0, g->ev1, &g->lastExpectUs);
@@ -265,36 +212,28 @@ int qm_gcb_destroy(qm_gcb* g) {
 }
 
 int qm_gcb_clear(qm_gcb* g) {
-  if (!g) return fail(QM_E_ARG, "null object");
-  HIPCHK(hipSetDevice(g->device));
+  QXCHK(qx::enter(g, true, "null object"));
   return gcb_clear(g);
 }
 
 int qm_gcb_add(qm_gcb* g, qm_ctx* c) {
-  if (!g || !c) return fail(QM_E_ARG, "qm_gcb_add: null argument");
-  if (c->last.units < 0) return fail(QM_E_STATE, "no mapping result to fold");
-  if (c->device != g->device) return fail(QM_E_ARG, "GC counts on device %d, context on device %d", g->device, c->device);
+  QXCHK(qx::enter_add(g, c, "qm_gcb_add", "GC counts", "fold"));
   if (c->rep.get() != g->rep.get()) return fail(QM_E_ARG, "qm_gcb_add: the context maps to another index");
-  HIPCHK(hipSetDevice(g->device));
-  const FldSrc S{(const unsigned char*)c->d_hits.p, (int)sizeof(qm_hit), c->d_offs, c->last.units};
-  return gcb_fold(g, S, c->stream);
+  return gcb_fold(g, qx::last_units(c), c->stream);
 }
 
 int qm_gcb_add_hits(qm_gcb* g, int64_t n, const int64_t* offsets, const qm_hit* hits) {
-  if (!g) return fail(QM_E_ARG, "qm_gcb_add_hits: bad argument");
-  HIPCHK(hipSetDevice(g->device));
+  QXCHK(qx::enter(g, true, "qm_gcb_add_hits: bad argument"));
   return gcb_add_hits(g, n, offsets, hits, 1 << 22, 1 << 21);       // a part: what is uploaded and folded in one go
 }
 
 int qm_gcb_fetch(qm_gcb* g, uint64_t* obs) {
-  if (!g || !obs) return fail(QM_E_ARG, "qm_gcb_fetch: bad argument");
-  HIPCHK(hipSetDevice(g->device));
-  return gcb_fetch(g, obs);
+  QXCHK(qx::enter(g, obs != nullptr, "qm_gcb_fetch: bad argument"));
+  return g->fetch(obs, GCB_BINS);
 }
 
 int qm_gcb_add_counts(qm_gcb* g, const uint64_t* obs) {
-  if (!g || !obs) return fail(QM_E_ARG, "qm_gcb_add_counts: bad argument");
-  HIPCHK(hipSetDevice(g->device));
+  QXCHK(qx::enter(g, obs != nullptr, "qm_gcb_add_counts: bad argument"));
   return gcb_add_counts(g, obs);
 }
 
@@ -304,14 +243,12 @@ int qm_gcb_stat(const qm_gcb* g, int which, int64_t* value) {
 }
 
 int qm_gcb_expect(qm_gcb* g, const uint64_t* counts, int64_t n_txps, uint64_t* H) {
-  if (!g || !counts || n_txps < 0 || (n_txps > 0 && !H)) return fail(QM_E_ARG, "qm_gcb_expect: bad argument");
-  HIPCHK(hipSetDevice(g->device));
+  QXCHK(qx::enter(g, counts && n_txps >= 0 && (n_txps == 0 || H), "qm_gcb_expect: bad argument"));
   return gcb_expect(g, counts, n_txps, H);
 }
 
 int qm_gcb_window_gc(qm_gcb* g, int64_t n, const uint32_t* tids, const int32_t* starts, const int32_t* lens, int32_t* out) {
-  if (!g || n < 0 || (n > 0 && (!tids || !starts || !lens || !out))) return fail(QM_E_ARG, "qm_gcb_window_gc: bad argument");
-  HIPCHK(hipSetDevice(g->device));
+  QXCHK(qx::enter(g, n >= 0 && (n == 0 || (tids && starts && lens && out)), "qm_gcb_window_gc: bad argument"));
   return gcb_window_gc(g, n, tids, starts, lens, out);
 }
 

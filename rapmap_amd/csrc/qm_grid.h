@@ -20,11 +20,11 @@
 //   qm_h2m_packw_kernel         the caller's grid (blocks)    1          no    G
 //   map_grid                    reads                         nominal 8  no    the compact -p image ? P : G
 //   resident_grid               reads                         nominal 8  no    1
-//   qm_fld_fold_kernel          sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
-//   qm_lib_classify_kernel      sweep_grid: hits / 64         8 (fixed)  no    1, then at most the caller's max_blocks
-//   qm_lib_units_kernel         sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
-//   qm_gcb_obs_kernel           sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
-//   gcb_expect_wave (qx)        sweep_grid: tiles of 64       8 (fixed)  no    1, then at most the caller's max_blocks
+//   fld_wave (qx::sweep)        sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
+//   lib_classify_wave (sweep)   sweep_grid: hits / 64         8 (fixed)  no    1, then at most the caller's max_blocks
+//   lib_units_wave (sweep)      sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
+//   gcb_obs_wave (sweep)        sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
+//   gcb_expect_wave (sweep)     sweep_grid: tiles of 64       8 (fixed)  no    1, then at most the caller's max_blocks
 //
 // map_grid is the host's plan for the general kernels (the "caller's grid" above, and what their scratch and the bump allocators' slack
 // are sized by); resident_grid the one it falls back to when that scratch does not fit, and the size of the list kernels' -s scratch.
@@ -69,7 +69,7 @@ inline int map_grid(long long nreads, int num_cu, bool ph_compact) { return grid
 inline int resident_grid(long long nreads, int num_cu) { return grid_blocks(nreads, num_cu, GRID_NOMINAL_PER_CU, 1); }
 
 // the sweeps of the estimation objects (qm_fld.inl, qm_lib.inl, qm_gcb.inl), one lane per unit, hit or window start: the workgroups that are resident at
-// once (FLD_ / LIB_BLOCKS_PER_CU, no query), fewer when the lanes do not fill them, at most max_blocks when that is not 0
+// once (FLD_ / LIB_ / GCB_BLOCKS_PER_CU, no query), fewer when the lanes do not fill them, at most max_blocks when that is not 0
 inline int sweep_grid(long long lanes, int num_cu, int resident_per_cu, int max_blocks) {
   const int g = grid_blocks((lanes + 63) / 64, num_cu > 0 ? num_cu : 1, resident_per_cu, 1);
   return max_blocks > 0 && g > max_blocks ? max_blocks : g;

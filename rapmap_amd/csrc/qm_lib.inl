@@ -15,14 +15,15 @@
 //   (the host scans keepCnt into waveBase)
 //   lib_compact_wave    lane l of hit wavefront w writes its tid to outTids[waveBase[w] + popc(keepMask[w] & lanemask_lt(l))]
 //                       when its bit is set: the kept hits in their order
-//   lib_units_wave      a persistent grid, one lane per unit: with P(h) = waveBase[h >> 6] + popc(keepMask[h >> 6] & bits below
-//                       h & 63), newOff[u] = P(off[u]); off[u + 1] is loaded once, off[u] comes from the lane below (as fld_wave
-//                       does).  Units, unmapped, kept and dropped are ballots; a unit of exactly one hit derives that hit's code
-//                       again for the single-hit words.
+//   lib_units_wave      a persistent grid, one lane per unit, on the frame of qm_sweep.h: with P(h) = waveBase[h >> 6] +
+//                       popc(keepMask[h >> 6] & bits below h & 63), newOff[u] = P(off[u]); off[u + 1] is loaded once and P of it
+//                       computed once, off[u] and its P come from the lane below (unit_bounds, lane_below_i64).  Units, unmapped,
+//                       kept and dropped are ballots; a unit of exactly one hit derives that hit's code again for the single-hit
+//                       words.
+// Both persistent grids are launched by qx::sweep (qm_exec.h).  The classify pass is a sweep over HITS and has no sibling: of the
+// frame it shares the tails (tally, flush_counters).
 #pragma once
-#include <stddef.h>
-#include "qm_wave.h"
-#include "../../include/qmap_mi355.h"
+#include "qm_sweep.h"
 
 namespace qm {
 
@@ -38,11 +39,7 @@ enum { LIB_W_HITS_BY_CODE = 0, LIB_W_SINGLE_BY_CODE = 12, LIB_W_UNITS = 24, LIB_
 // workgroups of the two persistent kernels resident per compute unit: 8 waves per SIMD = 32 per CU = 8 workgroups
 #define LIB_BLOCKS_PER_CU 8
 
-struct LibSrc {              // the units of a sweep
-  const unsigned char* hits; int stride;   // hit j's record: hits + j * stride (32: qm_hit); may be null when no unit has a hit
-  const long long* off;      // [n + 1], off[0] = 0
-  long long n, nh;           // units, hits (= off[n])
-};
+typedef UnitSrc LibSrc;      // the units of a sweep, under the name the sweep's callers give them
 struct LibAcc {
   u64* ctr;                  // [LIB_WORDS]
   u32 mask;                  // the codes kept
@@ -75,20 +72,14 @@ QM_DEV void lib_load_rec(const unsigned char* r, int& pos, int& matePos, u32& w)
 }
 #endif
 
-// lane i (< N) adds acc[i] to its word of the tally when it is not 0: at most one atomic per counter and wavefront.  The word of
-// accumulator i is i + shift below `mirror` and 42 - i from there on (the classify sweep's other, kept hits, hits: words 30, 29, 28)
-template <int N>
-QM_DEV void lib_flush(u64* ctr, const u64* acc, int shift, int mirror) {
-  QM_LANES(l) {
-    u64 v = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) if (l == i) v = acc[i];
-    if (l < N && v) atomic_add_u64(&ctr[l < mirror ? l + shift : 42 - l], v);
-  }
-}
+// the words of the classify sweep's fifteen accumulators (the twelve codes, other, kept hits, hits) and of the unit sweep's sixteen
+// (the twelve single-hit codes, units, unmapped, kept, dropped)
+#define LIB_CLASSIFY_WORDS {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, LIB_W_OTHER_HITS, LIB_W_KEPT_HITS, LIB_W_HITS}
+#define LIB_UNITS_WORDS {12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, LIB_W_UNITS, LIB_W_UNMAPPED, LIB_W_KEPT_UNITS, LIB_W_DROPPED_UNITS}
+static_assert(LIB_W_HITS_BY_CODE == 0 && LIB_W_SINGLE_BY_CODE == 12 && LIB_CODES == 12, "the first twelve words of both maps");
 
 // wavefront `wave` of `nWaves` (both wave-uniform) over the hit wavefronts
-QM_DEV void lib_classify_wave(const LibSrc& S, const LibAcc& A, long long wave, long long nWaves) {
+QM_DEV void lib_classify_wave(const UnitSrc& S, const LibAcc& A, long long wave, long long nWaves) {
   u64 acc[15];               // the twelve codes, other, kept hits, hits
 #pragma unroll
   for (int i = 0; i < 15; ++i) acc[i] = 0;
@@ -104,23 +95,19 @@ QM_DEV void lib_classify_wave(const LibSrc& S, const LibAcc& A, long long wave, 
         code[l] = lib_hit_code(pos, matePos, wd);
       }
     }
-#pragma unroll
-    for (int i = 0; i <= LIB_OTHER; ++i) {
-      QM_LANES(l) b[l] = code[l] == i;
-      acc[i] += (u64)popc64(ballot(b));
-    }
+    tally<LIB_OTHER + 1>(code, acc);
     QM_LANES(l) b[l] = code[l] >= 0 && code[l] < LIB_CODES && ((A.mask >> code[l]) & 1u);
     const u64 keep = ballot(b);
     QM_LANES(l) b[l] = code[l] >= 0;
     acc[13] += (u64)popc64(keep); acc[14] += (u64)popc64(ballot(b));
     QM_LANES(l) if (l == 0) { A.keepMask[w] = keep; A.keepCnt[w] = (u32)popc64(keep); }
   }
-  static_assert(42 - 12 == LIB_W_OTHER_HITS && 42 - 13 == LIB_W_KEPT_HITS && 42 - 14 == LIB_W_HITS, "lib_flush's mirror");
-  lib_flush<15>(A.ctr, acc, LIB_W_HITS_BY_CODE, 12);
+  const int word[15] = LIB_CLASSIFY_WORDS;
+  flush_counters(A.ctr, acc, word);
 }
 
 // hit wavefront `wave`: the kept hits' tids, in their order
-QM_DEV void lib_compact_wave(const LibSrc& S, const LibAcc& A, long long wave) {
+QM_DEV void lib_compact_wave(const UnitSrc& S, const LibAcc& A, long long wave) {
   const u64 keep = uniform(A.keepMask[wave]);
   if (!keep) return;
   const long long base = load_uniform_i64(A.waveBase + wave);
@@ -137,51 +124,36 @@ QM_DEV long long lib_kept_before(const LibAcc& A, long long h) {
 }
 
 // wavefront `wave` of `nWaves` (both wave-uniform) over the units, one lane per unit
-QM_DEV void lib_units_wave(const LibSrc& S, const LibAcc& A, long long wave, long long nWaves) {
+QM_DEV void lib_units_wave(const UnitSrc& S, const LibAcc& A, long long wave, long long nWaves) {
   u64 acc[16];               // the twelve single-hit codes, units, unmapped, kept, dropped
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0;
   for (long long base = wave * 64; base < S.n; base += nWaves * 64) {
-    LV<int> hiLo, hiHi, loLo, loHi, pLo, pHi, qLo, qHi;         // off[u + 1] and the kept hits in front of it as two dwords each, and the lane below's
+    LV<long long> o0, o1, p0, p1;                               // the unit's bounds and the kept hits in front of each
+    const long long first = unit_bounds(S, base, o0, o1);
+    QM_LANES(l) p1[l] = base + l < S.n ? lib_kept_before(A, o1[l]) : 0;
+    lane_below_i64(p1, lib_kept_before(A, first), p0);
+    LV<int> code, what; LV<bool> valid;                         // what: 0 unmapped, 1 a unit with kept hits, 2 dropped
     QM_LANES(l) {
+      code[l] = what[l] = -1;
       const long long u = base + l;
-      const long long e = u < S.n ? S.off[u + 1] : 0;
-      const long long p = u < S.n ? lib_kept_before(A, e) : 0;
-      hiLo[l] = (int)(u32)(u64)e; hiHi[l] = (int)(u32)((u64)e >> 32);
-      pLo[l] = (int)(u32)(u64)p; pHi[l] = (int)(u32)((u64)p >> 32);
-    }
-    lane_rotate_up(hiLo, loLo); lane_rotate_up(hiHi, loHi); lane_rotate_up(pLo, qLo); lane_rotate_up(pHi, qHi);
-    const long long first = load_uniform_i64(S.off + base);     // off[base]: lane 0 has no lane below
-    const long long pFirst = lib_kept_before(A, first);
-    LV<int> code; LV<bool> valid, unm, kept, drop, b;
-    QM_LANES(l) {
-      valid[l] = unm[l] = kept[l] = drop[l] = false; code[l] = -1;
-      const long long u = base + l;
-      if (u >= S.n) continue;
-      valid[l] = true;
-      const long long o1 = (long long)(((u64)(u32)hiHi[l] << 32) | (u32)hiLo[l]), p1 = (long long)(((u64)(u32)pHi[l] << 32) | (u32)pLo[l]);
-      const long long o0 = l ? (long long)(((u64)(u32)loHi[l] << 32) | (u32)loLo[l]) : first;
-      const long long p0 = l ? (long long)(((u64)(u32)qHi[l] << 32) | (u32)qLo[l]) : pFirst;
-      if (A.newOff) { A.newOff[u + 1] = p1; if (u == 0) A.newOff[0] = p0; }
-      const long long c = o1 - o0;
-      if (c == 0) unm[l] = true;
-      else if (p1 > p0) kept[l] = true;
-      else drop[l] = true;
+      valid[l] = u < S.n;
+      if (!valid[l]) continue;
+      if (A.newOff) { A.newOff[u + 1] = p1[l]; if (u == 0) A.newOff[0] = p0[l]; }
+      const long long c = o1[l] - o0[l];
+      what[l] = c == 0 ? 0 : p1[l] > p0[l] ? 1 : 2;
       if (c == 1) {
         int pos, matePos; u32 wd;
-        lib_load_rec(S.hits + o0 * (long long)S.stride, pos, matePos, wd);
+        lib_load_rec(S.hits + o0[l] * (long long)S.stride, pos, matePos, wd);
         code[l] = lib_hit_code(pos, matePos, wd);
       }
     }
-#pragma unroll
-    for (int i = 0; i < LIB_CODES; ++i) {
-      QM_LANES(l) b[l] = code[l] == i;
-      acc[i] += (u64)popc64(ballot(b));
-    }
-    acc[12] += (u64)popc64(ballot(valid)); acc[13] += (u64)popc64(ballot(unm)); acc[14] += (u64)popc64(ballot(kept)); acc[15] += (u64)popc64(ballot(drop));
+    tally<LIB_CODES>(code, acc);
+    acc[12] += (u64)popc64(ballot(valid));
+    tally<3>(what, acc + 13);
   }
-  static_assert(LIB_W_UNITS == 24 && LIB_W_UNMAPPED == 25 && LIB_W_KEPT_UNITS == 26 && LIB_W_DROPPED_UNITS == 27, "accumulators 12 .. 15");
-  lib_flush<16>(A.ctr, acc, LIB_W_SINGLE_BY_CODE, 16);
+  const int word[16] = LIB_UNITS_WORDS;
+  flush_counters(A.ctr, acc, word);
 }
 
 }  // namespace qm

@@ -1,4 +1,4 @@
-// qm_lib_host.inl -- host driver of the library-type sweep (device code: qm_lib.inl; its two persistent kernels: qm_kernels_lib.hip).
+// qm_lib_host.inl -- host driver of the library-type sweep (device code: qm_lib.inl; the shells' preambles: qm_tally_host.inl).
 // Included at the end of qm_host.hip, after qm_eqc_host.inl: qm_lib_add reads the context's last result where it lies in device
 // memory, qm_eqc_add_lib hands the compacted lists to eqc_fold.  Everything above the extern "C" block is written against
 // qm_exec.h and compiled twice: here, and with -DQM_EMU by tests/emu.
@@ -8,8 +8,7 @@
 // 64 hits.  Nothing is read back but what the caller asks for.
 #include <algorithm>
 #include "qm_lib.inl"
-#include "qm_exec.h"
-#include "qm_grid.h"
+#include "qm_tally_host.inl"
 
 struct qm_lib : qx::Base {
   int maxBlocks = 0; u32 mask = LIB_ALL_CODES;
@@ -22,20 +21,6 @@ struct qm_lib : qx::Base {
 
 // the grid of the two persistent kernels over `lanes` hits or units (sweep_grid of qm_grid.h at this sweep's resident blocks)
 static int qmk_lib_grid(long long lanes, int num_cu, int max_blocks) { return sweep_grid(lanes, num_cu, LIB_BLOCKS_PER_CU, max_blocks); }
-// the persistent kernels (qm_kernels_lib.hip, declared in qm_device.h), as the emulation runs them: four wavefronts per workgroup
-#ifdef QM_EMU
-static int qmk_lib_classify(const LibSrc& S, const LibAcc& A, int blocks, qx::Stream) {
-  if (S.nh <= 0) return 0;
-  for (long long w = 0; w < 4LL * blocks; ++w) lib_classify_wave(S, A, w, 4LL * blocks);
-  return 0;
-}
-static int qmk_lib_units(const LibSrc& S, const LibAcc& A, int blocks, qx::Stream) {
-  if (S.n <= 0) return 0;
-  for (long long w = 0; w < 4LL * blocks; ++w) lib_units_wave(S, A, w, 4LL * blocks);
-  return 0;
-}
-#endif
-
 static int lib_open(qm_lib* L) {
   int rc;
   if ((rc = L->d_ctr.ensure(LIB_WORDS)) || (rc = qx::fill(L->stream, L->d_ctr, 0, LIB_WORDS * sizeof(u64)))) return rc;
@@ -50,7 +35,7 @@ static int lib_clear(qm_lib* L) {
 
 // S: hits, stride, off, n, nh filled in.  lists: the kept hits' tids go to d_outTids and the units' offsets to d_newOff.  The stream
 // is idle when this returns.
-static int lib_sweep(qm_lib* L, const LibSrc& S, bool lists, qx::Stream st) {
+static int lib_sweep(qm_lib* L, const UnitSrc& S, bool lists, qx::Stream st) {
   if (S.n <= 0) return QM_OK;
   if (S.n >= (1LL << 32)) return fail(QM_E_ARG, "more than 2^32 - 1 units in one sweep");
   const long long hw = qx::waves_of(S.nh);
@@ -60,10 +45,10 @@ static int lib_sweep(qm_lib* L, const LibSrc& S, bool lists, qx::Stream st) {
   const LibAcc A{L->d_ctr, L->mask, L->d_keepMask, L->d_keepCnt, L->d_waveBase, lists ? L->d_outTids.p : nullptr, lists ? L->d_newOff.p : nullptr};
   if ((rc = qx::tick(L->ev0, st))) return rc;
   QXCHK(qx::fill(st, L->d_keepCnt + hw, 0, sizeof(u32)));            // (the scan's last input: read, never used)
-  HIPCHK(qmk_lib_classify(S, A, qmk_lib_grid(S.nh, L->numCU, L->maxBlocks), st));
+  if (S.nh > 0) HIPCHK((qx::sweep<lib_classify_wave>(st, qmk_lib_grid(S.nh, L->numCU, L->maxBlocks), S, A)));
   QXCHK(qx::scan_u32(st, L->d_tmp, L->d_keepCnt, L->d_waveBase, hw + 1));
   if (lists) HIPCHK(qx::launch<lib_compact_wave>(st, hw, S, A));
-  HIPCHK(qmk_lib_units(S, A, qmk_lib_grid(S.n, L->numCU, L->maxBlocks), st));
+  HIPCHK((qx::sweep<lib_units_wave>(st, qmk_lib_grid(S.n, L->numCU, L->maxBlocks), S, A)));
   if ((rc = qx::tock(L->ev0, L->ev1, st, &L->lastSweepUs))) return rc;
   L->sweeps++;
   return QM_OK;
@@ -71,7 +56,7 @@ static int lib_sweep(qm_lib* L, const LibSrc& S, bool lists, qx::Stream st) {
 
 // the fold of qm_eqc_add_lib: sweep, then eqc_fold over the filtered lists (the all-codes mask: nothing is compacted, the fold is
 // qm_eqc_add's over the hits as they are)
-static int lib_eqc_fold(qm_lib* L, qm_eqc* t, const LibSrc& S, qx::Stream st) {
+static int lib_eqc_fold(qm_lib* L, qm_eqc* t, const UnitSrc& S, qx::Stream st) {
   int rc;
   if ((rc = lib_sweep(L, S, L->mask != LIB_ALL_CODES, st))) return rc;
   EqcSrc E{};
@@ -95,7 +80,7 @@ static int lib_add_host(qm_lib* L, const char* who, int64_t n, const int64_t* of
   std::vector<long long> off;
   const int rc = qx::feed(L->stream, L->in, who, "unit", "hits", n, offsets, hits, sizeof(qm_hit), nullptr, maxUnits, maxHits,
                           [&](const long long* d_off, const unsigned char* d_hits, const u64*, int64_t u0, int64_t nu, int64_t nh) {
-    QXCHK(lib_sweep(L, LibSrc{d_hits, (int)sizeof(qm_hit), d_off, nu, nh}, new_offsets != nullptr, L->stream));
+    QXCHK(lib_sweep(L, UnitSrc{d_hits, (int)sizeof(qm_hit), d_off, nu, nh}, new_offsets != nullptr, L->stream));
     if (!new_offsets) return (int)QM_OK;
     off.resize((size_t)nu + 1);
     QXCHK(qx::read(L->stream, off.data(), L->d_newOff, (size_t)(nu + 1) * 8));
@@ -168,36 +153,28 @@ int qm_lib_destroy(qm_lib* L) {
 }
 
 int qm_lib_clear(qm_lib* L) {
-  if (!L) return fail(QM_E_ARG, "null library-type object");
-  HIPCHK(hipSetDevice(L->device));
+  QXCHK(qx::enter(L, true, "null library-type object"));
   return lib_clear(L);
 }
 
 int qm_lib_add(qm_lib* L, qm_ctx* c) {
-  if (!L || !c) return fail(QM_E_ARG, "qm_lib_add: null argument");
-  if (c->last.units < 0) return fail(QM_E_STATE, "no mapping result to tally");
-  if (c->device != L->device) return fail(QM_E_ARG, "library-type object on device %d, context on device %d", L->device, c->device);
-  HIPCHK(hipSetDevice(L->device));
-  const LibSrc S{(const unsigned char*)c->d_hits.p, (int)sizeof(qm_hit), c->d_offs, c->last.units, c->last.hits};
-  return lib_sweep(L, S, false, c->stream);
+  QXCHK(qx::enter_add(L, c, "qm_lib_add", "library-type object", "tally"));
+  return lib_sweep(L, qx::last_units(c), false, c->stream);
 }
 
 int qm_lib_add_hits(qm_lib* L, int64_t n, const int64_t* offsets, const qm_hit* hits) {
-  if (!L) return fail(QM_E_ARG, "qm_lib_add_hits: bad argument");
-  HIPCHK(hipSetDevice(L->device));
+  QXCHK(qx::enter(L, true, "qm_lib_add_hits: bad argument"));
   return lib_add_host(L, "qm_lib_add_hits", n, offsets, hits, nullptr, nullptr, LIB_PART_UNITS, LIB_PART_HITS);
 }
 
 int qm_lib_compact_hits(qm_lib* L, int64_t n, const int64_t* offsets, const qm_hit* hits, int64_t* new_offsets, uint32_t* tids) {
   if (!new_offsets) return fail(QM_E_ARG, "qm_lib_compact_hits: null new_offsets");
-  if (!L) return fail(QM_E_ARG, "qm_lib_compact_hits: bad argument");
-  HIPCHK(hipSetDevice(L->device));
+  QXCHK(qx::enter(L, true, "qm_lib_compact_hits: bad argument"));
   return lib_add_host(L, "qm_lib_compact_hits", n, offsets, hits, new_offsets, tids, LIB_PART_UNITS, LIB_PART_HITS);
 }
 
 int qm_lib_fetch(qm_lib* L, uint64_t counts[32]) {
-  if (!L || !counts) return fail(QM_E_ARG, "qm_lib_fetch: bad argument");
-  HIPCHK(hipSetDevice(L->device));
+  QXCHK(qx::enter(L, counts != nullptr, "qm_lib_fetch: bad argument"));
   return qx::read(L->stream, counts, L->d_ctr, LIB_WORDS * sizeof(u64));
 }
 
@@ -230,8 +207,7 @@ int qm_eqc_add_lib(qm_eqc* t, qm_ctx* c, qm_lib* L) {
   if (c->last.units < 0) return fail(QM_E_STATE, "no mapping result to fold");
   if (c->device != t->device || c->device != L->device) return fail(QM_E_ARG, "table on device %d, library-type object on device %d, context on device %d", t->device, L->device, c->device);
   HIPCHK(hipSetDevice(t->device));
-  const LibSrc S{(const unsigned char*)c->d_hits.p, (int)sizeof(qm_hit), c->d_offs, c->last.units, c->last.hits};
-  return lib_eqc_fold(L, t, S, c->stream);
+  return lib_eqc_fold(L, t, qx::last_units(c), c->stream);
 }
 
 }  // extern "C"

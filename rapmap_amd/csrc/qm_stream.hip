@@ -96,6 +96,33 @@ struct OutSlot {                 // the result side of ingest slot i
   int state = 0;                 // 0 idle, 1 being mapped, 2 mapped, 3 with the caller
 };
 
+// The per-context tallies of a stream: what a map context folds each batch into where it lies in device memory, one object per
+// context and kind.  The table is in the order the kinds run on a batch; a new kind is a row here, a flag and its fetch function.
+enum { K_EQC = 0, K_LIB = 1, K_FLD = 2, K_GCB = 3, K_N = 4 };
+struct TallyKind {
+  uint32_t flag; const char* flagName;                     // the stream flag that turns it on
+  int (*create)(qm_ctx* c, uint32_t stream_flags, void** out);
+  void (*destroy)(void* o);
+  int (*add)(void* o, qm_ctx* c);                          // the context's last result into the object
+  int (*fetch)(void* o, uint64_t* part);                   // the object's words (null: the kind has a fetch of its own) ...
+  int (*counter)(void* o, int which, int64_t* value);      // ... and its counters, which = 0 .. (null: none)
+};
+static_assert(QM_FLD_STAT_UNITS == 0 && QM_GCB_STAT_UNITS == 0, "the counters a stream sums start at 0");
+const TallyKind KINDS[K_N] = {
+  {QM_STREAM_EQ_CLASSES, "QM_STREAM_EQ_CLASSES", [](qm_ctx* c, uint32_t, void** o) { return qm_eqc_create(c, 1 << 16, 0, (qm_eqc**)o); },
+   [](void* o) { qm_eqc_destroy((qm_eqc*)o); }, [](void* o, qm_ctx* c) { return qm_eqc_add((qm_eqc*)o, c); }, nullptr, nullptr},
+  {QM_STREAM_LIB, "QM_STREAM_LIB",
+   [](qm_ctx* c, uint32_t f, void** o) { const uint32_t m = (f >> QM_STREAM_LIB_MASK_SHIFT) & QM_LIB_ALL_CODES; return qm_lib_create(c, m ? m : QM_LIB_ALL_CODES, 0, (qm_lib**)o); },
+   [](void* o) { qm_lib_destroy((qm_lib*)o); }, [](void* o, qm_ctx* c) { return qm_lib_add((qm_lib*)o, c); },
+   [](void* o, uint64_t* part) { return qm_lib_fetch((qm_lib*)o, part); }, nullptr},
+  {QM_STREAM_FLD, "QM_STREAM_FLD", [](qm_ctx* c, uint32_t, void** o) { return qm_fld_create(c, QM_FLD_DEFAULT_MAX_LEN, 0, (qm_fld**)o); },
+   [](void* o) { qm_fld_destroy((qm_fld*)o); }, [](void* o, qm_ctx* c) { return qm_fld_add((qm_fld*)o, c); },
+   [](void* o, uint64_t* part) { return qm_fld_fetch((qm_fld*)o, part); }, [](void* o, int w, int64_t* v) { return qm_fld_stat((qm_fld*)o, w, v); }},
+  {QM_STREAM_GCB, "QM_STREAM_GCB", [](qm_ctx* c, uint32_t, void** o) { return qm_gcb_create(c, QM_FLD_DEFAULT_MAX_LEN, 0, (qm_gcb**)o); },
+   [](void* o) { qm_gcb_destroy((qm_gcb*)o); }, [](void* o, qm_ctx* c) { return qm_gcb_add((qm_gcb*)o, c); },
+   [](void* o, uint64_t* part) { return qm_gcb_fetch((qm_gcb*)o, part); }, [](void* o, int w, int64_t* v) { return qm_gcb_stat((qm_gcb*)o, w, v); }},
+};
+
 }  // namespace
 
 struct qm_stream {
@@ -106,18 +133,10 @@ struct qm_stream {
   int64_t nPacked = 0;                     // batches that did
   qm_ingest* g = nullptr;
   std::vector<qm_ctx*> ctx; std::vector<int> ctxDev;
-  std::vector<qm_eqc*> eqc;                // QM_STREAM_EQ_CLASSES: one table per context, merged into eqc[0] by qm_stream_eqc_finish
-  bool eqClasses = false, noHits = false, eqcMerged = false, ended = false;
+  struct { bool on = false; std::vector<void*> obj; } tally[K_N];   // KINDS[k]'s objects, one per context (eqc: merged into the first by qm_stream_eqc_finish)
+  bool noHits = false, eqcMerged = false, ended = false;
   std::vector<int64_t> eqcFolds;           // batches every context folded
-  double tFold = 0;                        // seconds in qm_eqc_add (summed over the contexts)
-  std::vector<qm_fld*> fld;                // QM_STREAM_FLD: one fragment-length histogram per context, summed by qm_stream_fld_fetch
-  bool fldOn = false;
-  double tFld = 0;                         // seconds in qm_fld_add (summed over the contexts)
-  std::vector<qm_gcb*> gcb;                // QM_STREAM_GCB: one set of observed GC counts per context, summed by qm_stream_gcb_fetch
-  bool gcbOn = false;
-  double tGcb = 0;                         // seconds in qm_gcb_add (summed over the contexts)
-  std::vector<qm_lib*> lib;                // QM_STREAM_LIB: one library-type tally per context, summed by qm_stream_lib_fetch
-  bool libOn = false;
+  double seconds[K_N] = {0};               // in the kinds' add functions, summed over the contexts (qm_stream_stats_ex [13], [15], [16])
   std::vector<OutSlot> slots;
   std::mutex mu; std::condition_variable cv;
   int64_t nextOut = 0;
@@ -160,14 +179,17 @@ static void map_loop(qm_stream* s, int which) {
     else if (s->paired) rc = qm_map_pairs(c, &s->opts, n, in->seq[0], in->off[0], in->seq[1], in->off[1], &S.nHits, &S.ctr);
     else rc = qm_map_reads(c, &s->opts, n, in->seq[0], in->off[0], &S.nHits, &S.ctr);
     t1 = now_s();
-    double tf = 0;
-    // folded where it lies, before the next call overwrites it; QM_STREAM_LIB: the compatible hits only, tallied on the way
-    if (!rc && s->eqClasses) { rc = s->libOn ? qm_eqc_add_lib(s->eqc[(size_t)which], c, s->lib[(size_t)which]) : qm_eqc_add(s->eqc[(size_t)which], c); tf = now_s() - t1; t1 += tf; }
-    else if (!rc && s->libOn) { rc = qm_lib_add(s->lib[(size_t)which], c); tf = now_s() - t1; t1 += tf; }
-    double tl = 0;
-    if (!rc && s->fldOn) { rc = qm_fld_add(s->fld[(size_t)which], c); tl = now_s() - t1; t1 += tl; }          // ... and so is the histogram
-    double tg = 0;
-    if (!rc && s->gcbOn) { rc = qm_gcb_add(s->gcb[(size_t)which], c); tg = now_s() - t1; t1 += tg; }          // ... and the observed GC counts, before the buffers are reused
+    const double tMapped = t1 - t0;
+    // folded where it lies, before the next call overwrites it, kind by kind.  With QM_STREAM_LIB the classes take the compatible hits
+    // only and the library type is tallied on the way: one call for both kinds
+    double tk[K_N] = {0};
+    const bool eqcLib = s->tally[K_EQC].on && s->tally[K_LIB].on;
+    for (int k = 0; k < K_N && !rc; ++k) {
+      if (!s->tally[k].on || (k == K_LIB && eqcLib)) continue;
+      void* o = s->tally[k].obj[(size_t)which];
+      rc = k == K_EQC && eqcLib ? qm_eqc_add_lib((qm_eqc*)o, c, (qm_lib*)s->tally[K_LIB].obj[(size_t)which]) : KINDS[k].add(o, c);
+      tk[k] = now_s() - t1; t1 += tk[k];
+    }
     if (!rc && s->noHits) {
       t2 = now_s();
       double a = 0, b = 0;
@@ -186,12 +208,49 @@ static void map_loop(qm_stream* s, int which) {
     std::unique_lock<std::mutex> lk(s->mu);
     if (rc) { if (!s->failed) { s->failed = rc; snprintf(s->err, sizeof(s->err), "%s", rc == QM_E_NOMEM ? "out of pinned memory" : qm_last_error()); } break; }
     S.state = 2;
-    s->tMap += t1 - t0 - tf - tl - tg; s->tFold += tf; s->tFld += tl; s->tGcb += tg; if (s->eqClasses) s->eqcFolds[(size_t)which]++; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
+    s->tMap += tMapped; for (int k = 0; k < K_N; ++k) s->seconds[k] += tk[k]; if (s->tally[K_EQC].on) s->eqcFolds[(size_t)which]++; s->tFetch += t2 - t1 - ta; s->tAlloc += ta; s->tLastMapped = t2 - s->t0;
     s->cv.notify_all();
   }
   std::unique_lock<std::mutex> lk(s->mu);
   s->mapDone++;
   s->cv.notify_all();
+}
+
+// Everything a stream owns given back: what qm_stream_close ends with, and every failure path of qm_stream_open_ex once the ingest
+// engine exists (the map threads: none yet, or told to stop by the caller)
+static void stream_free(qm_stream* s) {
+  qm_ingest_cancel(s->g);                                   // wakes map threads that wait for a batch
+  for (auto& t : s->mapThreads) if (t.joinable()) t.join();
+  for (OutSlot& S : s->slots) { pin_free(S.hitOff); pin_free(S.hits); }
+  for (int k = K_N - 1; k >= 0; --k) for (void* o : s->tally[k].obj) if (o) KINDS[k].destroy(o);
+  for (qm_ctx* c : s->ctx) if (c) qm_ctx_destroy(c);
+  qm_ingest_close(s->g);
+  delete s;
+}
+
+// the preamble of the fetch functions: the stream was opened with the kind, has not failed, and its input has ended
+static int fetch_ready(qm_stream* s, int k, const char* who) {
+  char m[160];
+  if (!s->tally[k].on) { snprintf(m, sizeof(m), "%s: the stream was opened without %s", who, KINDS[k].flagName); return sfail(QM_E_STATE, m); }
+  std::unique_lock<std::mutex> lk(s->mu);
+  if (s->failed) return sfail(s->failed, s->err);
+  if (!s->ended) { snprintf(m, sizeof(m), "%s: the input has not ended", who); return sfail(QM_E_STATE, m); }
+  return QM_OK;
+}
+// out[0 .. nWords) and stats[0 .. nStats): the contexts' words and counters of kind k summed on the host
+static int fetch_sum(qm_stream* s, int k, const char* who, uint64_t* out, int nWords, int64_t* stats, int nStats) {
+  const int rc0 = fetch_ready(s, k, who);
+  if (rc0) return rc0;
+  std::vector<uint64_t> part((size_t)nWords);
+  for (int i = 0; i < nWords; ++i) out[i] = 0;
+  for (int i = 0; i < nStats; ++i) stats[i] = 0;
+  for (void* o : s->tally[k].obj) {
+    int rc = KINDS[k].fetch(o, part.data());
+    for (int i = 0; i < nStats && !rc; ++i) { int64_t v = 0; rc = KINDS[k].counter(o, i, &v); if (!rc) stats[i] += v; }
+    if (rc) return sfail(rc, qm_last_error());
+    for (int i = 0; i < nWords; ++i) out[i] += part[(size_t)i];
+  }
+  return QM_OK;
 }
 
 extern "C" {
@@ -205,10 +264,8 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
   qm_stream* s = new qm_stream();
   s->t0 = now_s();
   s->ix = ix; s->opts = *opts; s->paired = path2 != nullptr;
-  s->eqClasses = (stream_flags & QM_STREAM_EQ_CLASSES) != 0; s->noHits = (stream_flags & QM_STREAM_NO_HITS) != 0;
-  s->fldOn = (stream_flags & QM_STREAM_FLD) != 0;
-  s->libOn = (stream_flags & QM_STREAM_LIB) != 0;
-  s->gcbOn = (stream_flags & QM_STREAM_GCB) != 0;
+  s->noHits = (stream_flags & QM_STREAM_NO_HITS) != 0;
+  for (int k = 0; k < K_N; ++k) s->tally[k].on = (stream_flags & KINDS[k].flag) != 0;
   { const char* np = getenv("QM_STREAM_NO_PACK"); s->packed = !(np && atoi(np) != 0); }
   const char* cpd = getenv("QM_STREAM_CTX_PER_DEVICE");
   // contexts (map threads) per device: each uploads, maps and downloads its batch in turn, so several of them keep the link and
@@ -240,62 +297,13 @@ int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devi
     for (auto& t : th) t.join();
   }
   for (int d = 0; d < n_devices; ++d)
-    if (rcs[(size_t)d]) {
-      rc = rcs[(size_t)d]; sfail(rc, errs[(size_t)d].c_str());
-      qm_ingest_cancel(s->g);
-      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
-      qm_ingest_close(s->g); delete s; return rc;
-    }
-  if (s->eqClasses) {
-    s->eqc.assign((size_t)nctx, nullptr); s->eqcFolds.assign((size_t)nctx, 0);
-    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_eqc_create(s->ctx[(size_t)i], 1 << 16, 0, &s->eqc[(size_t)i]); }
-    if (rc) {
-      sfail(rc, qm_last_error());
-      qm_ingest_cancel(s->g);
-      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
-      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
-      qm_ingest_close(s->g); delete s; return rc;
-    }
-  }
-  if (s->fldOn) {
-    s->fld.assign((size_t)nctx, nullptr);
-    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_fld_create(s->ctx[(size_t)i], QM_FLD_DEFAULT_MAX_LEN, 0, &s->fld[(size_t)i]); }
-    if (rc) {
-      sfail(rc, qm_last_error());
-      qm_ingest_cancel(s->g);
-      for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
-      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
-      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
-      qm_ingest_close(s->g); delete s; return rc;
-    }
-  }
-  if (s->libOn) {
-    const uint32_t m = (stream_flags >> QM_STREAM_LIB_MASK_SHIFT) & QM_LIB_ALL_CODES;
-    s->lib.assign((size_t)nctx, nullptr);
-    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_lib_create(s->ctx[(size_t)i], m ? m : QM_LIB_ALL_CODES, 0, &s->lib[(size_t)i]); }
-    if (rc) {
-      sfail(rc, qm_last_error());
-      qm_ingest_cancel(s->g);
-      for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
-      for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
-      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
-      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
-      qm_ingest_close(s->g); delete s; return rc;
-    }
-  }
-  if (s->gcbOn) {
-    s->gcb.assign((size_t)nctx, nullptr);
-    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = qm_gcb_create(s->ctx[(size_t)i], QM_FLD_DEFAULT_MAX_LEN, 0, &s->gcb[(size_t)i]); }
-    if (rc) {
-      sfail(rc, qm_last_error());
-      qm_ingest_cancel(s->g);
-      for (qm_gcb* g : s->gcb) if (g) qm_gcb_destroy(g);
-      for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
-      for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
-      for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
-      for (qm_ctx* x : s->ctx) if (x) qm_ctx_destroy(x);
-      qm_ingest_close(s->g); delete s; return rc;
-    }
+    if (rcs[(size_t)d]) { rc = rcs[(size_t)d]; sfail(rc, errs[(size_t)d].c_str()); stream_free(s); return rc; }
+  s->eqcFolds.assign((size_t)nctx, 0);
+  for (int k = 0; k < K_N; ++k) {
+    if (!s->tally[k].on) continue;
+    s->tally[k].obj.assign((size_t)nctx, nullptr);
+    for (int i = 0; i < nctx && !rc; ++i) { hipSetDevice(s->ctxDev[(size_t)i]); rc = KINDS[k].create(s->ctx[(size_t)i], stream_flags, &s->tally[k].obj[(size_t)i]); }
+    if (rc) { sfail(rc, qm_last_error()); stream_free(s); return rc; }
   }
   for (int i = 0; i < nctx; ++i) s->mapThreads.emplace_back(map_loop, s, i);
   s->tOpen = now_s() - s->t0;
@@ -371,77 +379,46 @@ int qm_stream_next(qm_stream* s, qm_stream_batch* b) {
  * other devices travel the same way). */
 int qm_stream_eqc_finish(qm_stream* s, int64_t* n_classes, int64_t* n_tids) {
   if (!s) return sfail(QM_E_ARG, "qm_stream_eqc_finish: null stream");
-  if (!s->eqClasses) return sfail(QM_E_STATE, "qm_stream_eqc_finish: the stream was opened without QM_STREAM_EQ_CLASSES");
-  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_eqc_finish: the input has not ended"); }
-  int rc = QM_OK;
+  int rc = fetch_ready(s, K_EQC, "qm_stream_eqc_finish");
+  if (rc) return rc;
+  const std::vector<void*>& eqc = s->tally[K_EQC].obj;
   if (!s->eqcMerged) {
     std::vector<int64_t> off; std::vector<uint32_t> tids; std::vector<uint64_t> cnt;
-    for (size_t i = 1; i < s->eqc.size() && !rc; ++i) {
+    for (size_t i = 1; i < eqc.size() && !rc; ++i) {
       int64_t nc = 0, nt = 0;
-      if ((rc = qm_eqc_size(s->eqc[i], &nc, &nt, nullptr))) break;
+      if ((rc = qm_eqc_size((qm_eqc*)eqc[i], &nc, &nt, nullptr))) break;
       off.assign((size_t)nc + 1, 0); tids.resize((size_t)nt + 1); cnt.resize((size_t)nc + 1);
-      if ((rc = qm_eqc_fetch(s->eqc[i], off.data(), tids.data(), cnt.data()))) break;
-      rc = qm_eqc_add_labels(s->eqc[0], nc, off.data(), tids.data(), cnt.data());
+      if ((rc = qm_eqc_fetch((qm_eqc*)eqc[i], off.data(), tids.data(), cnt.data()))) break;
+      rc = qm_eqc_add_labels((qm_eqc*)eqc[0], nc, off.data(), tids.data(), cnt.data());
     }
     if (rc) return sfail(rc, qm_last_error());
     s->eqcMerged = true;
   }
-  if ((rc = qm_eqc_size(s->eqc[0], n_classes, n_tids, nullptr))) return sfail(rc, qm_last_error());
+  if ((rc = qm_eqc_size((qm_eqc*)eqc[0], n_classes, n_tids, nullptr))) return sfail(rc, qm_last_error());
   return QM_OK;
 }
 int qm_stream_eqc_fetch(qm_stream* s, int64_t* label_offsets, uint32_t* tids, uint64_t* counts) {
-  if (!s || !s->eqClasses || !s->eqcMerged) return sfail(QM_E_STATE, "qm_stream_eqc_fetch: call qm_stream_eqc_finish first");
-  const int rc = qm_eqc_fetch(s->eqc[0], label_offsets, tids, counts);
+  if (!s || !s->tally[K_EQC].on || !s->eqcMerged) return sfail(QM_E_STATE, "qm_stream_eqc_fetch: call qm_stream_eqc_finish first");
+  const int rc = qm_eqc_fetch((qm_eqc*)s->tally[K_EQC].obj[0], label_offsets, tids, counts);
   return rc ? sfail(rc, qm_last_error()) : QM_OK;
 }
 
 /* The contexts' fragment-length histograms and counters summed on the host: 8 KB and seven numbers per context. */
 int qm_stream_fld_fetch(qm_stream* s, uint64_t* counts, int64_t* stats7) {
   if (!s || !counts || !stats7) return sfail(QM_E_ARG, "qm_stream_fld_fetch: bad argument");
-  if (!s->fldOn) return sfail(QM_E_STATE, "qm_stream_fld_fetch: the stream was opened without QM_STREAM_FLD");
-  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_fld_fetch: the input has not ended"); }
-  std::vector<uint64_t> part((size_t)QM_FLD_DEFAULT_MAX_LEN + 1);
-  for (int l = 0; l <= QM_FLD_DEFAULT_MAX_LEN; ++l) counts[l] = 0;
-  for (int i = 0; i < 7; ++i) stats7[i] = 0;
-  for (qm_fld* f : s->fld) {
-    int rc = qm_fld_fetch(f, part.data());
-    for (int i = 0; i < 7 && !rc; ++i) { int64_t v = 0; rc = qm_fld_stat(f, QM_FLD_STAT_UNITS + i, &v); stats7[i] += v; }
-    if (rc) return sfail(rc, qm_last_error());
-    for (int l = 0; l <= QM_FLD_DEFAULT_MAX_LEN; ++l) counts[l] += part[(size_t)l];
-  }
-  return QM_OK;
+  return fetch_sum(s, K_FLD, "qm_stream_fld_fetch", counts, QM_FLD_DEFAULT_MAX_LEN + 1, stats7, 7);
 }
 
 /* The contexts' observed GC counts and counters summed on the host: 200 bytes and eight numbers per context. */
 int qm_stream_gcb_fetch(qm_stream* s, uint64_t* obs, int64_t* stats8) {
   if (!s || !obs || !stats8) return sfail(QM_E_ARG, "qm_stream_gcb_fetch: bad argument");
-  if (!s->gcbOn) return sfail(QM_E_STATE, "qm_stream_gcb_fetch: the stream was opened without QM_STREAM_GCB");
-  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_gcb_fetch: the input has not ended"); }
-  uint64_t part[QM_GCB_BINS];
-  for (int b = 0; b < QM_GCB_BINS; ++b) obs[b] = 0;
-  for (int i = 0; i < 8; ++i) stats8[i] = 0;
-  for (qm_gcb* g : s->gcb) {
-    int rc = qm_gcb_fetch(g, part);
-    for (int i = 0; i < 8 && !rc; ++i) { int64_t v = 0; rc = qm_gcb_stat(g, QM_GCB_STAT_UNITS + i, &v); if (!rc) stats8[i] += v; }
-    if (rc) return sfail(rc, qm_last_error());
-    for (int b = 0; b < QM_GCB_BINS; ++b) obs[b] += part[b];
-  }
-  return QM_OK;
+  return fetch_sum(s, K_GCB, "qm_stream_gcb_fetch", obs, QM_GCB_BINS, stats8, 8);
 }
 
 /* The contexts' library-type tallies summed on the host: 256 bytes per context. */
 int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]) {
   if (!s || !counts) return sfail(QM_E_ARG, "qm_stream_lib_fetch: bad argument");
-  if (!s->libOn) return sfail(QM_E_STATE, "qm_stream_lib_fetch: the stream was opened without QM_STREAM_LIB");
-  { std::unique_lock<std::mutex> lk(s->mu); if (s->failed) return sfail(s->failed, s->err); if (!s->ended) return sfail(QM_E_STATE, "qm_stream_lib_fetch: the input has not ended"); }
-  uint64_t part[32];
-  for (int i = 0; i < 32; ++i) counts[i] = 0;
-  for (qm_lib* l : s->lib) {
-    const int rc = qm_lib_fetch(l, part);
-    if (rc) return sfail(rc, qm_last_error());
-    for (int i = 0; i < 32; ++i) counts[i] += part[i];
-  }
-  return QM_OK;
+  return fetch_sum(s, K_LIB, "qm_stream_lib_fetch", counts, 32, nullptr, 0);
 }
 
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
@@ -459,8 +436,8 @@ int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n) {
   v[0] = ing[6]; v[1] = s->tMap; v[2] = s->tFetch; v[3] = s->tWait; v[4] = s->tOpen; v[5] = s->tAlloc;
   v[6] = ing[0]; v[7] = ing[1]; v[8] = ing[2]; v[9] = ing[3]; v[10] = ing[4]; v[11] = s->tLastMapped;
   v[12] = (double)__atomic_load_n(&s->nPacked, __ATOMIC_RELAXED);
-  v[13] = s->tFold; for (int64_t f : s->eqcFolds) v[14] += f > 0 ? 1 : 0;
-  v[15] = s->tFld; v[16] = s->tGcb;
+  v[13] = s->seconds[K_EQC] + s->seconds[K_LIB]; for (int64_t f : s->eqcFolds) v[14] += f > 0 ? 1 : 0;
+  v[15] = s->seconds[K_FLD]; v[16] = s->seconds[K_GCB];
   for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
   return QM_OK;
 }
@@ -469,16 +446,7 @@ int qm_stream_stats(qm_stream* s, double* out6) { return qm_stream_stats_ex(s, o
 void qm_stream_close(qm_stream* s) {
   if (!s) return;
   { std::unique_lock<std::mutex> lk(s->mu); s->stop = true; s->cv.notify_all(); }
-  qm_ingest_cancel(s->g);                                   // wakes map threads that wait for a batch
-  for (auto& t : s->mapThreads) if (t.joinable()) t.join();
-  for (OutSlot& S : s->slots) { pin_free(S.hitOff); pin_free(S.hits); }
-  for (qm_eqc* t : s->eqc) if (t) qm_eqc_destroy(t);
-  for (qm_fld* f : s->fld) if (f) qm_fld_destroy(f);
-  for (qm_lib* l : s->lib) if (l) qm_lib_destroy(l);
-  for (qm_gcb* g : s->gcb) if (g) qm_gcb_destroy(g);
-  for (qm_ctx* c : s->ctx) if (c) qm_ctx_destroy(c);
-  qm_ingest_close(s->g);
-  delete s;
+  stream_free(s);
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ import emu_wave  # noqa: E402
 _LIB = os.path.join(_HERE, "libqm_probe.so")
 _CSRC = os.path.join(_HERE, "../../rapmap_amd/csrc")
 _SRC = [os.path.join(_HERE, f) for f in ("qm_probe.hip", "qm_wave_probe.inl", "Makefile")] + \
-       [os.path.join(_CSRC, f) for f in ("qm_wave.h", "qm_mapper.inl", "qm_sel.inl", "qm_selpack.inl", "qm_lean.inl")] + \
+       [os.path.join(_CSRC, f) for f in ("qm_wave.h", "qm_mapper.inl", "qm_sel.inl", "qm_selpack.inl", "qm_lean.inl", "qm_sweep.h", "qm_lib.inl")] + \
        [os.path.join(_HERE, "../../include/qmap_mi355.h")]
 DISPATCH, LOOP, TILES, ONE_TILE = 0, 1, 2, 3                      # `which` of qp_h2m (emu_h2m's numbers)
 RING_GMEM = 4096                                                  # the ring whose blocks live in device memory

@@ -1,7 +1,7 @@
 // tests/device/qm_probe.hip -- TEST-ONLY device probes (libqm_probe.so; nothing of it is linked into libqmap_mi355.so).  Each entry point
 // runs one wave body of the product's source by itself on the GPU, on inputs the caller chooses, so that the device edition of the body can
 // be held to its lane emulation (tests/emu) unit by unit:
-//   qp_wave       the primitives of qm_wave.h and key_count (qm_wave_probe.inl, the body tests/emu/qm_emu_wave.cpp compiles with -DQM_EMU)
+//   qp_wave       the primitives of qm_wave.h, key_count and the pieces of qm_sweep.h (qm_wave_probe.inl, the body tests/emu/qm_emu_wave.cpp compiles with -DQM_EMU)
 //   qp_h2m        lean_h2m, lean_h2m_loop, lean_h2m_tiles<false / true> of qm_lean.inl on a stash in LDS          (tests/emu/qm_emu_h2m.cpp)
 //   qp_ksw_rows   sel_ksw_extz2_rows<RING> of qm_sel.inl, four alignments per wavefront                           (tests/emu/qm_emu.cpp)
 //   qp_ksw_rows8  sel_ksw_extz2_rows_reg<.., true, 2>, eight alignments of one shape per wavefront
@@ -194,6 +194,8 @@ int qp_wave(int op, int nw, const int* prm, const u64* a, const u64* b, const u6
   for (int w = 0; w < nw; ++w) {
     if (op == QP_group_min && !(prm[w] == 1 || prm[w] == 2 || prm[w] == 4 || prm[w] == 8 || prm[w] == 16 || prm[w] == 32 || prm[w] == 64)) return (int)hipErrorInvalidValue;
     if (op == QP_group_sum_f64 && prm[w] != 8 && prm[w] != 16) return (int)hipErrorInvalidValue;
+    if (op == QP_unit_bounds && !QP_UNIT_BOUNDS_OK(prm[w], a[(size_t)w * 64], b[(size_t)w * 64])) return (int)hipErrorInvalidValue;
+    if (op == QP_slab_flush && (prm[w] < 1 || prm[w] > QP_LDSB / 4)) return (int)hipErrorInvalidValue;
   }
   hipError_t e = hipSetDevice(0);
   if (e != hipSuccess) return (int)e;

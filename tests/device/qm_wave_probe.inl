@@ -1,5 +1,5 @@
 // tests/device/qm_wave_probe.inl -- TEST-ONLY: one wave body that calls every primitive of rapmap_amd/csrc/qm_wave.h (and key_count of
-// qm_selpack.inl) once, written against LV / QM_LANES like every wave body of the product.  It is compiled twice: with -DQM_EMU by
+// qm_selpack.inl, and the pieces of the sweep frame of qm_sweep.h) once, written against LV / QM_LANES like every wave body of the product.  It is compiled twice: with -DQM_EMU by
 // tests/emu/qm_emu_wave.cpp (a loop over waves on the CPU) and as a kernel by tests/device/qm_probe.hip (one wavefront per wave, four
 // wavefronts per block, all 64 lanes active), so the two editions of a primitive see the same input and can be compared bit for bit.
 //
@@ -8,10 +8,11 @@
 // write stays as the caller filled it.  Every address into mem is reduced modulo the room here, whatever the caller passes.
 #pragma once
 #include "../../rapmap_amd/csrc/qm_mapper.inl"
+#include "../../rapmap_amd/csrc/qm_lib.inl"     // (qm_sweep.h, and the word maps of the library-type sweep's counter flush)
 
 #define QP_MEMB 4096               // bytes of read-only memory per wave
-#define QP_LDSB 1024               // bytes of LDS per wave (lds_dma_u128: 16 bytes per lane)
-#define QP_NOUT 6                  // u64 per lane of output (load_48: twelve dwords)
+#define QP_LDSB 4096               // bytes of LDS per wave (slab_flush: the 1024 words of the largest slab)
+#define QP_NOUT 16                 // u64 per lane of output (slab_flush: 1024 bins)
 
 #define QP_OPS(X) \
   X(ballot) X(half_ballot) \
@@ -25,7 +26,8 @@
   X(pk_add) X(pk_sub) X(pk_max_i) X(pk_max_u) X(pk_min_u) X(load_u32_unaligned) X(load_u64_unaligned) \
   X(load_16) X(load_32) X(load_16x2) X(load_8_16) X(load_48) X(load_uniform_i64) X(lds_dma_u32) X(lds_dma_u128) \
   X(atomic_min_u64) X(atomic_max_u64) X(atomic_or_u64) X(atomic_add_u64) \
-  X(key_count)
+  X(key_count) \
+  X(unit_bounds) X(flush_counters_1) X(flush_counters_7) X(flush_counters_16) X(flush_counters_lib) X(slab_flush)
 
 namespace qm {
 
@@ -41,6 +43,17 @@ QM_DEV u64 qp_pair(u32 lo, u32 hi) { return ((u64)hi << 32) | lo; }
 #define QP_LV(T, x, expr) LV<T> x; QM_LANES(l) { x[l] = (T)(expr); }
 #define QP_OUT(k, expr) QM_LANES(l) { out[(k) * 64 + l] = (u64)(expr); }
 #define QP_OUT_U4(k, v) QM_LANES(l) { out[(k) * 64 + l] = qp_pair(v[l].x, v[l].y); out[((k) + 1) * 64 + l] = qp_pair(v[l].z, v[l].w); }
+
+// flush_counters onto the output's first row as the counter words: accumulator i = a[i] (wave-uniform)
+template <int N>
+QM_DEV void probe_flush(const u64* a, u64* out, const int (&word)[N]) {
+  u64 acc[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) acc[i] = uniform(a[i]);
+  flush_counters(out, acc, word);
+}
+// the arguments unit_bounds is probed with: n = prm units whose n + 1 offsets fit mem, wavefront a[0] of b[0]
+#define QP_UNIT_BOUNDS_OK(prm, wave, nWaves) ((prm) >= 1 && (prm) <= QP_MEMB / 8 - 1 && (u64)(nWaves) >= 1 && (u64)(nWaves) <= 64 && (u64)(wave) < (u64)(nWaves))
 
 // returns 0, or -1 for an op it does not know (nothing is written then)
 QM_DEV int probe_wave(int op, int prm, const u64* a, const u64* b, const u64* c, const u64* d, const unsigned char* mem, u64* atom, u32* lds,
@@ -157,6 +170,33 @@ QM_DEV int probe_wave(int op, int prm, const u64* a, const u64* b, const u64* c,
     case QP_atomic_or_u64: { QM_LANES(l) { atomic_or_u64(atom, a[l]); } } break;
     case QP_atomic_add_u64: { QM_LANES(l) { (void)atomic_add_u64(atom, a[l]); } } break;
     case QP_key_count: { QP_LV(int, n, prm) QM_LANES(l) { key_count(a[l], b[l], c[l], d[l], n[l]); } QP_OUT(0, (u32)n[l]) } break;
+    // ---- the sweep frame (qm_sweep.h)
+    // mem: the n + 1 offsets as 64-bit values, n = prm; this wave is wavefront a[0] of b[0] and strides as a sweep does: trip k's bounds
+    // (off[u], off[u + 1]) go to rows 2 k and 2 k + 1, and a lane past n writes nothing
+    case QP_unit_bounds: {
+      const long long wave = (long long)uniform(a[0]), nWaves = (long long)uniform(b[0]);
+      if (!QP_UNIT_BOUNDS_OK(prm, wave, nWaves)) return -1;
+      const UnitSrc S{nullptr, 0, (const long long*)mem, prm, 0};
+      int k = 0;
+      for (long long base = wave * 64; base < S.n && k < QP_NOUT / 2; base += nWaves * 64, ++k) {
+        LV<long long> o0, o1;
+        unit_bounds(S, base, o0, o1);
+        QM_LANES(l) { if (base + l < S.n) { out[(2 * k) * 64 + l] = (u64)o0[l]; out[(2 * k + 1) * 64 + l] = (u64)o1[l]; } }
+      }
+    } break;
+    // 1, 7 and 16 accumulators and the classify sweep's 15 onto the pre-filled words of row 0
+    case QP_flush_counters_1: { const int word[1] = {3}; probe_flush(a, out, word); } break;
+    case QP_flush_counters_7: { const int word[7] = {0, 1, 2, 3, 4, 5, 6}; probe_flush(a, out, word); } break;
+    case QP_flush_counters_16: { const int word[16] = LIB_UNITS_WORDS; probe_flush(a, out, word); } break;
+    case QP_flush_counters_lib: { const int word[15] = LIB_CLASSIFY_WORDS; probe_flush(a, out, word); } break;
+    // a slab of QP_LDSB / 4 words: word i < prm holds (u32)(a[i % 64] >> (i / 64)), the others 0xA5A5A5A5; its first prm words go
+    // out onto the output taken as QP_NOUT * 64 bins
+    case QP_slab_flush: {
+      if (prm < 1 || prm > QP_LDSB / 4) return -1;
+      QM_LDS(u32)* slab = (QM_LDS(u32)*)lds;
+      QM_LANES(l) { for (int i = l; i < QP_LDSB / 4; i += 64) slab[i] = i < prm ? (u32)(a[l] >> (i >> 6)) : 0xA5A5A5A5u; }
+      slab_flush(slab, prm, out);
+    } break;
     default: return -1;
   }
   return 0;

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libqm_emu_fld.so")
 _SRC = [os.path.join(_HERE, "qm_emu_fld.cpp")] + [os.path.join(_HERE, "../../rapmap_amd/csrc", f) for f in
-                                                  ("qm_fld_host.inl", "qm_fld.inl", "qm_exec.h", "qm_grid.h", "qm_wave.h")] + \
+                                                  ("qm_fld_host.inl", "qm_fld.inl", "qm_tally_host.inl", "qm_sweep.h", "qm_exec.h", "qm_grid.h", "qm_wave.h")] + \
        [os.path.join(_HERE, "../../include/qmap_mi355.h")]
 SLAB, C_WORDS = 1024, 8
 STATS = ("units", "used", "unmapped", "multi", "not_paired", "same_strand", "out_of_range", "max_len", "folds", "last_fold_us")   # the order of QM_FLD_STAT_*

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libqm_emu_gcb.so")
 _SRC = [os.path.join(_HERE, "qm_emu_gcb.cpp")] + [os.path.join(_HERE, "../../rapmap_amd/csrc", f) for f in
-                                                  ("qm_gcb_host.inl", "qm_gcb.inl", "qm_fld.inl", "qm_exec.h", "qm_grid.h", "qm_wave.h")] + \
+                                                  ("qm_gcb_host.inl", "qm_gcb.inl", "qm_tally_host.inl", "qm_sweep.h", "qm_exec.h", "qm_grid.h", "qm_wave.h")] + \
        [os.path.join(_HERE, "../../include/qmap_mi355.h")]
 BINS, SLAB, C_WORDS = 25, 32, 8
 STATS = ("units", "used", "unmapped", "multi", "not_paired", "same_strand", "out_of_range", "overhang", "max_len", "folds", "last_fold_us",

@@ -11,7 +11,7 @@ from lib_cases import mask_of
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libqm_emu_lib.so")
 _SRC = [os.path.join(_HERE, "qm_emu_lib.cpp")] + [os.path.join(_HERE, "../../rapmap_amd/csrc", f) for f in
-                                                  ("qm_lib_host.inl", "qm_lib.inl", "qm_eqc_host.inl", "qm_eqc.inl", "qm_exec.h", "qm_grid.h", "qm_wave.h")] + \
+                                                  ("qm_lib_host.inl", "qm_lib.inl", "qm_eqc_host.inl", "qm_eqc.inl", "qm_tally_host.inl", "qm_sweep.h", "qm_exec.h", "qm_grid.h", "qm_wave.h")] + \
        [os.path.join(_HERE, "../../include/qmap_mi355.h")]
 
 

@@ -14,6 +14,8 @@ _SRC = [os.path.join(_HERE, "qm_emu_wave.cpp"),
         os.path.join(_HERE, "../../rapmap_amd/csrc/qm_mapper.inl"),
         os.path.join(_HERE, "../../rapmap_amd/csrc/qm_sel.inl"),
         os.path.join(_HERE, "../../rapmap_amd/csrc/qm_selpack.inl"),
+        os.path.join(_HERE, "../../rapmap_amd/csrc/qm_sweep.h"),
+        os.path.join(_HERE, "../../rapmap_amd/csrc/qm_lib.inl"),
         os.path.join(_HERE, "../../include/qmap_mi355.h")]
 
 

@@ -1,7 +1,7 @@
 // tests/emu/qm_emu_fld.cpp -- TEST-ONLY lane emulation of the fragment-length histogram: the driver of rapmap_amd/csrc/qm_fld_host.inl
 // and the device code of qm_fld.inl, both compiled with -DQM_EMU (an LV<T> is a 64-entry array, QM_LANES a loop: qm_exec.h), for 256
 // compute units.  What is here is a C face over the driver's object.  One wavefront after the other, one lane after the other, each on
-// a slab filled with 0xA5 (the driver's emulated launcher): this checks the driver and the logic of the sweep -- the parts of host
+// a slab filled with 0xA5 (qx::sweep's emulation, qm_exec.h): this checks the driver and the logic of the sweep -- the parts of host
 // arrays, offsets, categories, the slab, the flush, the grid's cap --, not the atomics.
 #define QM_EMU
 #include "../../rapmap_amd/csrc/qm_wave.h"

@@ -217,6 +217,46 @@ def test_stream(small, oracle_small, small_fastq):
         st.close()
 
 
+def test_stream_with_every_tally(small, small_fastq):
+    """one stream with all four kinds of per-context tally on gives, bit for bit, what the streams with one kind each give: the class table
+    of a stream with the classes and the library type alone, and the histogram, the GC counts and the library-type tallies of the
+    single-flag streams"""
+    import rapmap_amd as ra
+    f1, f2 = small_fastq
+
+    def run(**flags):
+        st = ra.MappedStream(small["qi"], f1, f2, batch_units=512, threads=3, names=False, **flags)
+        nb = sum(1 for _ in st)
+        assert nb == 9
+        return st
+
+    st = run(eq_classes=True, lib_type="IU")
+    table, lib_with_classes = st.eq_classes(), st.lib_counts()
+    st.close()
+    st = run(frag_len_dist=True)
+    fld = st.frag_len_dist()
+    st.close()
+    st = run(gc_bias=True)
+    gcb = st.gc_bias()
+    st.close()
+    st = run(lib_type="IU")
+    lib = st.lib_counts()
+    st.close()
+    assert np.array_equal(lib, lib_with_classes)                  # (tallied the same with and without the fold behind it)
+
+    st = run(eq_classes=True, hits=False, frag_len_dist=True, gc_bias=True, lib_type="IU")
+    for x, y in zip(st.eq_classes(), table):
+        assert x.dtype == y.dtype and x.tobytes() == y.tobytes()
+    counts, stats = st.frag_len_dist()
+    assert counts.tobytes() == fld[0].tobytes() and stats == fld[1]
+    obs, gstats = st.gc_bias()
+    assert obs.tobytes() == gcb[0].tobytes() and gstats == gcb[1]
+    assert st.lib_counts().tobytes() == lib.tobytes()
+    s = st.stats()
+    assert s["fold_s"] > 0 and s["fld_fold_s"] > 0 and s["gcb_sweep_s"] > 0
+    st.close()
+
+
 def _cli(args):
     import subprocess
     import sys

@@ -10,12 +10,12 @@ waves of one launch -- and `want`: per output row the [W, 64] array the comment 
 The cross-lane inputs: the 64 one-hot vectors (positive in zeros, and negative in zeros for the minima), permutations of distinct values,
 all-equal vectors, 16 seeded random vectors and the integer extremes -- with one-hot and distinct-per-lane inputs every output lane names the
 source lanes it read, so a wrong pairing, row mask or fill cannot pass.  The inputs stay inside the preconditions of the primitives:
-lane_scan_max values >= 0 (the device's identity is 0), lane_scan_add sums that fit an int, perm8 selectors 0 .. 7 and 0x0c, align_bytes
+the sweep frame's pieces (unit_bounds, flush_counters, slab_flush of qm_sweep.h) are probed the same way; lane_scan_max values >= 0 (the device's identity is 0), lane_scan_add sums that fit an int, perm8 selectors 0 .. 7 and 0x0c, align_bytes
 shifts 0 .. 3, read_lane and uniform wave-uniform arguments, group_min G a power of two, group_sum_f64 G 8 or 16."""
 import numpy as np
 
 MEMB = 4096          # bytes of read-only memory per wave (QP_MEMB)
-NOUT = 6             # output rows (QP_NOUT)
+NOUT = 16            # output rows (QP_NOUT)
 FILL = np.uint64(0xEEEEEEEEEEEEEEEE)
 L = np.arange(64)
 M32 = np.uint64(0xffffffff)
@@ -130,7 +130,7 @@ def halves(seed):
 
 
 class Case:
-    def __init__(self, name, a, b=None, c=None, d=None, prm=None, mem_seed=None, atom=None):
+    def __init__(self, name, a, b=None, c=None, d=None, prm=None, mem_seed=None, atom=None, mem=None):
         self.name = name
         self.op = name.split("[")[0]
         self.a = np.ascontiguousarray(a, dtype=np.uint64)
@@ -139,6 +139,9 @@ class Case:
         self.b, self.c, self.d = [z if x is None else np.ascontiguousarray(x, dtype=np.uint64) for x in (b, c, d)]
         self.prm = np.ascontiguousarray(np.zeros(w) if prm is None else np.broadcast_to(prm, (w,)), dtype=np.int32)
         self.mem = np.random.default_rng(mem_seed if mem_seed is not None else 1).integers(0, 256, (w, MEMB), dtype=np.uint8)
+        if mem is not None:                                                                       # (the start of each wave's memory as given)
+            mem = np.ascontiguousarray(mem, dtype=np.uint8)
+            self.mem[:, :mem.shape[1]] = mem
         self.atom = np.ascontiguousarray(np.zeros(w) if atom is None else atom, dtype=np.uint64)
         assert self.b.shape == self.a.shape == self.c.shape == self.d.shape == (w, 64)
         self.w = w
@@ -223,6 +226,43 @@ def _wide(k, n, lane):
     return _rows([_pick(x, lane) for x in (k.a, k.b, k.c, k.d)[:n]])
 
 
+# ---- the sweep frame (rapmap_amd/csrc/qm_sweep.h)
+FLUSH_WORDS = {"flush_counters_1": [3], "flush_counters_7": list(range(7)),
+               "flush_counters_16": list(range(12, 28)),                                          # the unit sweep's: single-hit codes, then words 24 .. 27
+               "flush_counters_lib": list(range(12)) + [30, 29, 28]}                              # the classify sweep's: codes, then other, kept hits, hits
+
+
+def _unit_bounds(k):
+    """wave w is wavefront a[w, 0] of b[w, 0] over n = prm[w] units whose offsets are the first n + 1 u64 of its memory: trip t covers units
+    (wavefront + t * wavefronts) * 64 + lane, (off[u], off[u + 1]) in rows 2 t and 2 t + 1, nothing for a unit past n"""
+    want = {r: np.full((k.w, 64), FILL, dtype=np.uint64) for r in range(NOUT)}
+    for w in range(k.w):
+        n, wave, nw = int(k.prm[w]), int(k.a[w, 0]), int(k.b[w, 0])
+        off = k.mem[w, :8 * (n + 1)].view(np.uint64)
+        for t in range(NOUT // 2):
+            u = (wave + t * nw) * 64 + L
+            ok = u < n
+            want[2 * t][w, ok] = off[u[ok]]; want[2 * t + 1][w, ok] = off[u[ok] + 1]
+    return want
+
+
+def _flush_counters(k):
+    """lane i adds accumulator a[w, i] to word FLUSH_WORDS[i] of row 0 when it is not 0; every other word keeps its fill"""
+    want = np.full((k.w, 64), FILL, dtype=np.uint64)
+    for i, word in enumerate(FLUSH_WORDS[k.op]):
+        want[:, word] += k.a[:, i]
+    return want
+
+
+def _slab_flush(k):
+    """bins 0 .. n - 1 (n = prm) of the output taken as NOUT * 64 bins get slab word i = (u32)(a[w, i % 64] >> (i // 64)) added; the bins
+    beyond n keep their fill, whatever the slab holds there"""
+    i = np.arange(NOUT * 64)
+    v = (k.a[:, i % 64] >> (i // 64).astype(np.uint64)) & M32
+    bins = np.where(i[None, :] < k.prm[:, None], FILL + v, FILL)
+    return _rows(list(bins.reshape(k.w, NOUT, 64).transpose(1, 0, 2)))
+
+
 EXPECT = {
     "ballot": lambda k: lanes(_ballot(k)),
     "half_ballot": lambda k: np.where(L < 32, lanes(_ballot(k) & M32), lanes(_ballot(k) >> np.uint64(32))),
@@ -287,6 +327,9 @@ EXPECT = {
     "atomic_max_u64": lambda k: (None, np.maximum(k.atom, k.a.max(axis=1))),
     "atomic_or_u64": lambda k: (None, k.atom | np.bitwise_or.reduce(k.a, axis=1)),
     "atomic_add_u64": lambda k: (None, k.atom + k.a.sum(axis=1, dtype=np.uint64)),
+    "unit_bounds": _unit_bounds,
+    "flush_counters_1": _flush_counters, "flush_counters_7": _flush_counters, "flush_counters_16": _flush_counters, "flush_counters_lib": _flush_counters,
+    "slab_flush": _slab_flush,
     "key_count": lambda k: as_u64((k.prm[:, None] + pyints(lambda c1, c2, a1, a2: (c1, c2 & 0xffffffff) < (a1, a2 & 0xffffffff), k.a, k.b, k.c, k.d).astype(np.int64)).astype(np.int32)),
 }
 
@@ -342,6 +385,38 @@ def _key_count_case():
     return Case("key_count", a, b, c, d, prm=(np.arange(a.shape[0]) * 1000003) % 50 - 3)
 
 
+def _unit_bounds_case():
+    """n in {1, 63, 64, 65, 130} units under 1 and under 3 wavefronts (one probe wave per wavefront: the stride and the ragged tail); the
+    offsets are 64-bit values from 2^32 - 5 on, units of 0, 1 and 2 hits mixed, so they pass 2^32 and the two-dword split carries"""
+    rng = np.random.default_rng(91)
+    prm, a, b, mem = [], [], [], []
+    for n in (1, 63, 64, 65, 130):
+        sizes = rng.integers(0, 3, n); sizes[:min(n, 6)] = [2, 0, 1, 2, 1, 0][:min(n, 6)]
+        off = (np.uint64((1 << 32) - 5) + np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)).astype(np.uint64)
+        assert n < 6 or (off[0] < 1 << 32 < off[-1])
+        m = np.zeros(MEMB, dtype=np.uint8); m[:8 * (n + 1)] = off.view(np.uint8)
+        for nw in (1, 3):
+            for wave in range(nw):
+                prm.append(n); a.append(np.full(64, wave)); b.append(np.full(64, nw)); mem.append(m)
+    return Case("unit_bounds", np.array(a, dtype=np.uint64), np.array(b, dtype=np.uint64), prm=np.array(prm), mem=np.array(mem))
+
+
+def _flush_cases():
+    """accumulators of every size, some of them 0 (no atomic then), also all 0 and all non-zero; 2^64 - 1 wraps the pre-filled word"""
+    rng = np.random.default_rng(92)
+    rows = [np.zeros(64, dtype=np.uint64), np.full(64, 1, dtype=np.uint64), np.full(64, 0xffffffffffffffff, dtype=np.uint64), (L + 1).astype(np.uint64),
+            np.where(L % 2 == 0, 0, L * 1000003 + 1).astype(np.uint64), np.where(L % 3 == 1, 0, np.uint64(1) << L.astype(np.uint64)).astype(np.uint64)]
+    rows += [rng.integers(0, 1 << 64, 64, dtype=np.uint64) * (rng.random(64) < 0.6) for _ in range(6)]
+    return [Case(n, np.array(rows, dtype=np.uint64)) for n in FLUSH_WORDS]
+
+
+def _slab_cases():
+    rng = np.random.default_rng(93)
+    rows = [np.zeros(64, dtype=np.uint64), np.full(64, 0xffffffffffffffff, dtype=np.uint64), (L + 1).astype(np.uint64)]
+    rows += [rng.integers(0, 1 << 64, 64, dtype=np.uint64) * (rng.random(64) < 0.7) for _ in range(5)]
+    return [Case("slab_flush[%d]" % n, np.array(rows, dtype=np.uint64), prm=n) for n in (1, 25, 1001)]
+
+
 def _build():
     I, U, D, S = ints_xlane(11), u64_xlane(12), doubles_xlane(13), scalars64(14)
     rng = np.random.default_rng(15)
@@ -391,6 +466,7 @@ def _build():
     a0[5:] = np.where(np.arange(at.shape[0] - 5) % 3 == 0, np.sort(at[5:], axis=1)[:, 32], a0[5:])
     cs += [Case(n, at, atom=a0) for n in ("atomic_min_u64", "atomic_max_u64", "atomic_or_u64", "atomic_add_u64")]
     cs.append(_key_count_case())
+    cs += [_unit_bounds_case()] + _flush_cases() + _slab_cases()
     return {k.name: k for k in cs}
 
 
