@@ -582,6 +582,100 @@ int qm_gcb_eff_lens_from_counts(int32_t max_len, const uint64_t* counts /*[max_l
  * where the window is empty or does not lie on the transcript. */
 int qm_gcb_window_gc(qm_gcb* g, int64_t n, const uint32_t* tids, const int32_t* starts, const int32_t* lens, int32_t* out /*[n]*/);
 
+/* ---- sequence-specific bias: the nucleotide contexts at the two ends of a fragment ------------------------------------------
+ * (No counterpart in the reference; consumer of the hit records and of the transcript text.  The names follow Salmon's --seqBias;
+ * parity with Salmon is NOT claimed: none was at hand to compare with.  The model is this project's own and every constant in it
+ * -- the context of 9 with 3 upstream, the order 2, the pseudo-count 1, the clamp [0.25, 4], the exponent 61 -- is a constant of
+ * this model.)
+ * CODES: A, a = 0; C, c = 1; G, g = 2; T, t = 3; any other byte is AMBIGUOUS.
+ * CONTEXTS: a fragment lies on transcript t of length L as [s, e), e = s + frag_len, s = min(max(pos, 0), max(mate_pos, 0)) as
+ * in the GC model above.  QM_SQB_CTX = 9 characters, QM_SQB_UP = 3 of them upstream of the end.
+ *     5' context of start s:              c_j = code(t[s - 3 + j]), j = 0 .. 8; it lies on the transcript when 3 <= s <= L - 6
+ *     3' context of last position i = e - 1 (the reverse strand): c_j = 3 - code(t[i + 3 - j]); when 5 <= i <= L - 4
+ * and a context is VALID when it lies on the transcript and none of its nine characters is ambiguous.
+ * WORDS (a position-specific model of order 2; every word is below 64):
+ *     w_0 = c_0;   w_1 = 4 c_0 + c_1;   w_j = 16 c_(j-2) + 4 c_(j-1) + c_j for j >= 2
+ * A table is [2 ends][QM_SQB_CTX][64] = QM_SQB_BINS = 1152 entries, end 0 the 5' end; entry (end, j, w) is at (end * 9 + j) * 64 + w.
+ * OBSERVED: obs[QM_SQB_BINS], unsigned 64-bit.  Every unit of a batch falls into exactly one of eight categories -- the first
+ * condition that holds --, each with a 64-bit counter; the eight always add up to the units swept.  The first five are qm_fld's
+ * (unmapped, multi, not_paired, same_strand, out_of_range).  Then
+ *     overhang      tid >= n_txps, or e > L, or one of the two contexts does not lie on the transcript
+ *     ambiguous     one of the two contexts holds an ambiguous character
+ *     used          otherwise: obs[end][j][w_j] += 1 for the nine words of each end (18 increments)
+ * WEIGHTS (qm_sqb_weights, a pure host function; float64 under fp contract(off), every operation on its own): from a first
+ * estimate alpha, the transcript lengths and a fragment-length histogram counts[0 .. m] (qm_fld's shape, counts[0] == 0), with
+ * P[d] = sum of counts[l] over l <= d and Q[d] = sum of l * counts[l], both integers:
+ *     S_t   = (L_t + 1) * P[m'] - Q[m'], m' = min(L_t, m): the (start, length) placements on t, an integer
+ *     rho_t = alpha_t / (double)S_t; 0 when alpha_t > 0 does not hold or S_t == 0
+ *     X     = sum over t ascending of rho_t * (double)L_t (a product and an addition each)
+ *     k     = 61 - ilogb(X * (double)P[m]);  q_t = (uint64) floor(ldexp(rho_t, k))
+ * When X * (double)P[m] is 0, k = 0 and every q_t = 0; when it is not finite: QM_E_ARG.  The rule keeps
+ * sum of q_t * L_t * P[m] below 2^62 (1 + T 2^-52) < 2^63, which is what the expected counts need.
+ * EXPECTED: exp[QM_SQB_BINS], unsigned 64-bit, on the device, integers only, hence order-free:
+ *     exp[0][j][w] = sum over t of q_t * sum over the valid 5' contexts of t, at start s, of P[min(m, L_t - s)] * [w_j == w]
+ *     exp[1][j][w] = sum over t of q_t * sum over the valid 3' contexts of t, at last position i, of P[min(m, i + 1)] * [w_j == w]
+ * -- P[min(m, L_t - s)]: the fragments that may start at s; P[min(m, i + 1)]: those that may end at i.  THE TWO ENDS ARE COUNTED
+ * INDEPENDENTLY: a start is not asked for a valid end and an end not for a valid start, while `used` needs both; the ratios below
+ * are taken within an end, so a common factor between the ends does not reach them.  For each end the sum over w of exp[end][j][w]
+ * is the same for all nine j.  sum of q_t * L_t * P[m] >= 2^63 (128-bit host arithmetic): QM_E_UNSUPPORTED.
+ * RATIOS (qm_sqb_ratios, a pure host function): per end, position j and group of the four words that share w >> 2 (the same
+ * two characters in front):
+ *     po = (double)(obs + 1) / (double)(sum of the group's obs + 4);   pe likewise from exp;   R = min(max(po / pe, 0.25), 4.0)
+ * Entries no context can produce (j = 0: w >= 4; j = 1: w >= 16) hold 1.0.
+ * EFFECTIVE LENGTHS, on the device, float64, nothing fused:
+ *     b5_t(s) = ((...((1.0 * R[0][0][w_0]) * R[0][1][w_1]) ...) * R[0][8][w_8]) for a valid 5' context at s, 1.0 otherwise
+ *     b3_t(i) the same over R[1] for the 3' context at last position i
+ *     N_t     = sum over l = 1 .. min(m, L_t) of counts[l] * sum over s = 0 .. L_t - l of b5(s) * b3(s + l - 1)
+ *     e'_t    = N_t / (double)P[min(L_t, m)]; (double)L_t when that P is 0
+ * in this order: per start s, a_s = the sum over ascending l (those with counts[l] != 0 and l <= min(m, L_t - s)) of
+ * (double)counts[l] * b3(s + l - 1), starting from 0.0, one product and one addition each; v_s = b5(s) * a_s; the v of 64
+ * consecutive starts 64 k .. 64 k + 63 (a tile; an absent start counts 0.0) are added by the tree
+ *     rows of 16: x0..x15 -> ((x0 + x1) + (x2 + x3)) + ((x4 + x5) + (x6 + x7)), plus the same over x8..x15; then (R0 + R1) + (R2 + R3)
+ * and a transcript's tiles are added in ascending order, starting from 0.0.  With R == 1 every term is an integer: N_t = S_t
+ * exactly while S_t < 2^53, and e' is qm_fld's effective length as one quotient.
+ * Not thread-safe (one per context / host thread; merge with qm_sqb_add_counts). */
+typedef struct qm_sqb qm_sqb;
+#define QM_SQB_CTX 9
+#define QM_SQB_UP 3
+#define QM_SQB_BINS 1152
+/* no counterpart in the reference.  max_len and flags as qm_gcb_create's. */
+int qm_sqb_create(qm_ctx* ctx, int32_t max_len, uint32_t flags, qm_sqb** out);
+/* no counterpart in the reference */
+int qm_sqb_destroy(qm_sqb* g);
+/* no counterpart in the reference.  Observed counts and counters back to zero. */
+int qm_sqb_clear(qm_sqb* g);
+/* no counterpart in the reference.  Sweeps the result of ctx's last map call where it lies, as qm_gcb_add does. */
+int qm_sqb_add(qm_sqb* g, qm_ctx* ctx);
+/* no counterpart in the reference.  The same kernel over arrays in HOST memory, uploaded in parts. */
+int qm_sqb_add_hits(qm_sqb* g, int64_t n_units, const int64_t* hit_offsets, const qm_hit* hits);
+/* no counterpart in the reference.  obs[i] += counts[i]: the merge primitive.  A used fragment brings 18 counts, one of them at (end 0,
+ * j = 0): the sum of counts[0][0][.] is added to `used` and to the units. */
+int qm_sqb_add_counts(qm_sqb* g, const uint64_t* obs /*[QM_SQB_BINS]*/);
+/* no counterpart in the reference */
+int qm_sqb_fetch(qm_sqb* g, uint64_t* obs /*[QM_SQB_BINS]*/);
+/* no counterpart in the reference.  Since creation / the last clear: the units swept, the eight categories, max_len, the folds and
+ * the kernels of the last fold, the last qm_sqb_expect and the last qm_sqb_eff_lens in microseconds (HIP events) */
+enum { QM_SQB_STAT_UNITS = 0, QM_SQB_STAT_USED = 1, QM_SQB_STAT_UNMAPPED = 2, QM_SQB_STAT_MULTI = 3, QM_SQB_STAT_NOT_PAIRED = 4, QM_SQB_STAT_SAME_STRAND = 5,
+       QM_SQB_STAT_OUT_OF_RANGE = 6, QM_SQB_STAT_OVERHANG = 7, QM_SQB_STAT_AMBIGUOUS = 8, QM_SQB_STAT_MAX_LEN = 9, QM_SQB_STAT_FOLDS = 10,
+       QM_SQB_STAT_LAST_FOLD_US = 11, QM_SQB_STAT_LAST_EXPECT_US = 12, QM_SQB_STAT_LAST_EFFLEN_US = 13 };
+int qm_sqb_stat(const qm_sqb* g, int which, int64_t* value);
+/* no counterpart in the reference.  exp[QM_SQB_BINS] from counts[0 .. max_len] and the weights q[n_txps] over every transcript of
+ * the index (n_txps must be the index's).  counts[0] != 0: QM_E_ARG; 2^63 fragments or more, or the bound above: QM_E_UNSUPPORTED. */
+int qm_sqb_expect(qm_sqb* g, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, const uint64_t* q /*[n_txps]*/, uint64_t* exp /*[QM_SQB_BINS]*/);
+/* no counterpart in the reference.  eff[n_txps] from counts[0 .. max_len] and the ratios R[QM_SQB_BINS].  counts[0] != 0: QM_E_ARG. */
+int qm_sqb_eff_lens(qm_sqb* g, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, const double* R /*[QM_SQB_BINS]*/, double* eff /*[n_txps]*/);
+/* no counterpart in the reference.  A probe of the contexts: question i asks for the context of end ends[i] (0: 5', 1: 3') at
+ * position positions[i] (the start s, or the last position i) of transcript tids[i]; out[9 i .. 9 i + 8] are its nine words, or
+ * all -1 where the context is not valid. */
+int qm_sqb_context(qm_sqb* g, int64_t n, const uint32_t* tids, const int32_t* positions, const int32_t* ends, int32_t* out /*[n*9]*/);
+/* no counterpart in the reference.  The weights above as a pure host function: q[n_txps] and the exponent k.  lens[i] == 0,
+ * counts[0] != 0, max_len < 1, X * P[m] not finite: QM_E_ARG; max_len > 1023, 2^63 fragments or more, or (the longest transcript
+ * + 1) * P[m] >= 2^63: QM_E_UNSUPPORTED. */
+int qm_sqb_weights(int32_t max_len, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, const uint32_t* lens, const double* alpha /*[n_txps]*/,
+                   uint64_t* q /*[n_txps]*/, int32_t* k);
+/* no counterpart in the reference.  The ratios above as a pure host function. */
+int qm_sqb_ratios(const uint64_t* obs /*[QM_SQB_BINS]*/, const uint64_t* exp /*[QM_SQB_BINS]*/, double* R /*[QM_SQB_BINS]*/);
+
 /* ---- library type: hit orientations tallied, compatible hits kept ------------------------------------------------------------
  * (No counterpart in the reference; consumer of the hit records.  The names follow Salmon's -l / --libType and its
  * lib_format_counts.json; parity with Salmon is NOT claimed: none was at hand to compare with.  The model is this project's own,
@@ -706,6 +800,11 @@ int qm_stream_open(const qm_index* ix, int device_id, uint32_t ctx_flags, const 
  * flags.  qm_stream_gcb_fetch sums the contexts' observed counts.  A stream without the flag creates no qm_gcb, builds no rank
  * structure and launches nothing of it. */
 #define QM_STREAM_GCB 32u
+/* QM_STREAM_SQB -- every map context owns a qm_sqb of QM_FLD_DEFAULT_MAX_LEN and sweeps each batch into it after mapping (after the
+ * QM_STREAM_GCB sweep, when there is one), on the context's stream, before the batch's buffers are reused; with or without the other
+ * flags.  qm_stream_sqb_fetch sums the contexts' observed counts.  A stream without the flag creates no qm_sqb and launches nothing
+ * of it. */
+#define QM_STREAM_SQB 64u
 int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devices, uint32_t ctx_flags, const qm_opts* opts,
                       const char* path1, const char* path2, int64_t batch_units, int32_t reader_threads, uint32_t stream_flags,
                       qm_stream** out);
@@ -731,14 +830,19 @@ int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]);
  * before that, and for a stream opened without QM_STREAM_GCB): the contexts' observed GC counts and counters summed, across devices.
  * stats8: the units, then used, unmapped, multi, not_paired, same_strand, out_of_range, overhang. */
 int qm_stream_gcb_fetch(qm_stream* s, uint64_t* obs /*[QM_GCB_BINS]*/, int64_t* stats8);
+/* No counterpart in the reference; consumer of the hit records.  Once qm_stream_next has returned the end of the input (QM_E_STATE
+ * before that, and for a stream opened without QM_STREAM_SQB): the contexts' observed sequence-bias counts and counters summed,
+ * across devices.  stats9: the units, then used, unmapped, multi, not_paired, same_strand, out_of_range, overhang, ambiguous. */
+int qm_stream_sqb_fetch(qm_stream* s, uint64_t* obs /*[QM_SQB_BINS]*/, int64_t* stats9);
 void qm_stream_close(qm_stream* s);
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
- * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 17) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
+ * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 18) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
  * [8] copy tasks, [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that went
  * to the device 2-bit packed, [13] qm_eqc_add of the batches (summed over the contexts), [14] contexts that folded at least one batch,
  * [15] qm_fld_add of the batches of a QM_STREAM_FLD stream (seconds, summed over the contexts; not part of [1], [2] or [13]),
- * [16] qm_gcb_add of the batches of a QM_STREAM_GCB stream (seconds, summed over the contexts; not part of [1], [2], [13] or [15]) */
+ * [16] qm_gcb_add of the batches of a QM_STREAM_GCB stream (seconds, summed over the contexts; not part of [1], [2], [13] or [15]),
+ * [17] qm_sqb_add of the batches of a QM_STREAM_SQB stream (seconds, summed over the contexts; not part of the others) */
 int qm_stream_stats(qm_stream* s, double* out6);
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n);
 const char* qm_stream_last_error(void);

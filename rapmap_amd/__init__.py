@@ -6,7 +6,9 @@ from .api import (QuasiIndex, QuasiMapper, QmError, QmOpts, default_opts, build_
                   FastxReader, ReadBatch, MappedStream, reserve_stream_memory, SamWriter, sam_header_text, sam_records_text,
                   HIT_DTYPE, INTERVAL_DTYPE, LIB_PATH, ABI_SYMBOLS, EqClasses, write_eq_classes, read_eq_classes,
                   Quant, exp_digamma, write_quant, read_quant, Bootstrap, write_bootstraps, read_bootstraps,
-                  FragLenDist, GCBias, gc_eff_lens_from_counts, write_gc_bias, read_gc_bias, GCB_BINS, GCB_STATS, eff_lens_from_counts, frag_len_mean, write_flen_dist, read_flen_dist, FLD_DEFAULT_MAX_LEN, FLD_STATS,
+                  FragLenDist, GCBias, gc_eff_lens_from_counts, write_gc_bias, read_gc_bias, GCB_BINS, GCB_STATS,
+                  SeqBias, seq_bias_weights, seq_bias_ratios, write_seq_bias, read_seq_bias, SQB_BINS, SQB_STATS,
+                  eff_lens_from_counts, frag_len_mean, write_flen_dist, read_flen_dist, FLD_DEFAULT_MAX_LEN, FLD_STATS,
                   LibFormat, lib_type_mask, infer_lib_type, lib_format_counts, write_lib_format_counts, read_lib_format_counts,
                   LIB_TYPES, LIB_CODES, LIB_TOTALS, LIB_ALL_CODES)
 from . import api

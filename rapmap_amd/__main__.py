@@ -89,6 +89,12 @@ def _quasimap(argv):
                     "over every window of every transcript under the run's fragment-length distribution is computed on the GPU (expected), "
                     "and a second estimate, started from the first, runs on effective lengths weighted by observed / expected; bins, "
                     "counts and ratios are written to FILE.gcBias.txt")
+    ap.add_argument("--quantSeqBias", action="store_true", help="[only with quantFLD, not with quantGCBias]: one round of sequence-specific bias "
+                    "correction: the nucleotide contexts (nine characters, three of them upstream) at the two ends of the run's uniquely and "
+                    "properly paired fragments are counted (observed), the same contexts over every place of every transcript a fragment "
+                    "could start or end at are counted on the GPU under the first estimate and the run's fragment-length distribution "
+                    "(expected), and a second estimate, started from the first, runs on effective lengths weighted by observed / expected, "
+                    "computed on the GPU; counts and ratios are written to FILE.seqBias.txt")
     ap.add_argument("--quantVB", action="store_true", help="[only with quant]: the variational Bayes EM in place of the EM: a transcript's weight is "
                     "exp(digamma(abundance + prior)) / effective length; the bootstrap replicates of --numBootstraps use it as well")
     ap.add_argument("--quantVBPrior", type=float, default=1e-2, metavar="P", help="[only with quantVB]: the prior, per nucleotide: P x effective length "
@@ -112,6 +118,10 @@ def _quasimap(argv):
         ap.error("--quantFLD needs --quant")
     if a.quantGCBias and not a.quantFLD:
         ap.error("--quantGCBias needs --quantFLD")
+    if a.quantSeqBias and not a.quantFLD:
+        ap.error("--quantSeqBias needs --quantFLD")
+    if a.quantSeqBias and a.quantGCBias:
+        ap.error("--quantSeqBias and --quantGCBias are two corrections of their own: the joint model is not there, give one of them")
     if a.quantVB and not a.quant:
         ap.error("--quantVB needs --quant")
     if not (a.quantVBPrior >= 0 and a.quantVBPrior < float("inf")):
@@ -234,11 +244,14 @@ def _quasimap(argv):
     # --quantGCBias: ... and sweeps them into observed GC counts; their sums (one per file) meet here
     gcb_obs = np.zeros(ra.GCB_BINS, dtype=np.uint64) if a.quantGCBias else None
     gcb_stats = dict.fromkeys(ra.GCB_STATS, 0); gcb_s = 0.0
+    # --quantSeqBias: ... or into the observed counts of the end contexts
+    sqb_obs = np.zeros((2, 9, 64), dtype=np.uint64) if a.quantSeqBias else None
+    sqb_stats = dict.fromkeys(ra.SQB_STATS, 0); sqb_s = 0.0
     for f1, f2 in pairs:
         os.environ.setdefault("QM_INGEST_PIN", "1")   # a whole-machine job with one ingest engine: its workers on the NUMA node that holds the files' pages
         st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None,
                              eq_classes=classes is not None, hits=out is not None or classes is None, frag_len_dist=a.quantFLD,
-                             lib_type=a.libType or None, gc_bias=a.quantGCBias)
+                             lib_type=a.libType or None, gc_bias=a.quantGCBias, seq_bias=a.quantSeqBias)
         for b in st:
             gpu_ms += b.gpu_ms
             for kk in tot:
@@ -265,6 +278,11 @@ def _quasimap(argv):
             gcb_obs += c_; gcb_s += st.stats()["gcb_sweep_s"]
             for kk in gcb_stats:
                 gcb_stats[kk] += s_[kk]
+        if a.quantSeqBias:
+            c_, s_ = st.seq_bias()
+            sqb_obs += c_; sqb_s += st.stats()["sqb_sweep_s"]
+            for kk in sqb_stats:
+                sqb_stats[kk] += s_[kk]
         log("stream: " + ", ".join("%s %.3f" % kv for kv in st.stats().items()))
         st.close()
     if a.libType:
@@ -309,6 +327,28 @@ def _quasimap(argv):
                 log("fragment GC: %s, swept in %.3f ms; expected counts in %.3f ms on the GPU (rank structure %.3f ms); ratios %g .. %g; wrote %s.gcBias.txt" % (
                     ", ".join("%s %d" % (kk, gcb_stats[kk]) for kk in ra.GCB_STATS), gcb_s * 1e3, expect_us / 1e3, rank_us / 1e3,
                     float(gc_ratio.min()), float(gc_ratio.max()), a.quant))
+                qn.close()
+                qn = ra.Quant(classes, qi.n_txps, eff)
+                if a.quantVB:
+                    qn.set_method("vbem", prior=a.quantVBPrior, per_transcript=a.quantPerTranscriptPrior)
+                qn.set_start(first)
+                it2, rel = qn.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
+                iters += it2
+            if a.quantSeqBias:
+                # --quantSeqBias: integer weights from the first estimate, the expected counts and the effective lengths on device 0,
+                # a second estimate over the same table started from the first; what follows (quant.sf, the bootstrap) takes the second
+                first = qn.fetch()
+                sq_q, sq_k = ra.seq_bias_weights(first, lens, fld_counts)
+                sb = ra.SeqBias(keep[0])
+                sq_exp = sb.expect(fld_counts, qi.n_txps, sq_q)
+                sq_ratio = ra.seq_bias_ratios(sqb_obs, sq_exp)
+                eff = sb.eff_lens(fld_counts, qi.n_txps, sq_ratio)
+                expect_us = sb.stat()["last_expect_us"]; efflen_us = sb.stat()["last_efflen_us"]
+                sb.close()
+                ra.write_seq_bias(a.quant + ".seqBias.txt", sqb_obs, sq_exp, sq_ratio)
+                log("sequence bias: %s, swept in %.3f ms; weights 2^%d; expected counts in %.3f ms and effective lengths in %.3f ms on the GPU; ratios %g .. %g; "
+                    "wrote %s.seqBias.txt" % (", ".join("%s %d" % (kk, sqb_stats[kk]) for kk in ra.SQB_STATS), sqb_s * 1e3, sq_k, expect_us / 1e3, efflen_us / 1e3,
+                                              float(sq_ratio.min()), float(sq_ratio.max()), a.quant))
                 qn.close()
                 qn = ra.Quant(classes, qi.n_txps, eff)
                 if a.quantVB:

@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "qm_fld_eff_lens_from_counts", "qm_fld_eff_lens", "qm_stream_fld_fetch",
     "qm_gcb_create", "qm_gcb_destroy", "qm_gcb_clear", "qm_gcb_add", "qm_gcb_add_hits", "qm_gcb_add_counts", "qm_gcb_fetch", "qm_gcb_stat",
     "qm_gcb_expect", "qm_gcb_eff_lens_from_counts", "qm_gcb_window_gc", "qm_stream_gcb_fetch",
+    "qm_sqb_create", "qm_sqb_destroy", "qm_sqb_clear", "qm_sqb_add", "qm_sqb_add_hits", "qm_sqb_add_counts", "qm_sqb_fetch", "qm_sqb_stat",
+    "qm_sqb_expect", "qm_sqb_eff_lens", "qm_sqb_context", "qm_sqb_weights", "qm_sqb_ratios", "qm_stream_sqb_fetch",
     "qm_lib_create", "qm_lib_destroy", "qm_lib_clear", "qm_lib_add", "qm_lib_add_hits", "qm_lib_compact_hits", "qm_lib_add_counts", "qm_lib_fetch",
     "qm_lib_stat", "qm_eqc_add_lib", "qm_lib_type_mask", "qm_lib_infer", "qm_stream_lib_fetch",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
@@ -241,6 +243,20 @@ def lib():
     L.qm_gcb_eff_lens_from_counts.argtypes = [C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 7
     L.qm_gcb_window_gc.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qm_stream_gcb_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_sqb_create.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.qm_sqb_destroy.argtypes = [C.c_void_p]
+    L.qm_sqb_clear.argtypes = [C.c_void_p]
+    L.qm_sqb_add.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_sqb_add_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_sqb_add_counts.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_sqb_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_sqb_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_sqb_expect.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_sqb_eff_lens.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_sqb_context.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_sqb_weights.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    L.qm_sqb_ratios.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_stream_sqb_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.qm_lib_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.qm_lib_destroy.argtypes = [C.c_void_p]
     L.qm_lib_clear.argtypes = [C.c_void_p]
@@ -1190,6 +1206,134 @@ def read_gc_bias(path):
     return obs, ex, ratio
 
 
+SQB_BINS = 1152                                                       # QM_SQB_BINS: [2 ends][9 positions][64 words]
+SQB_SHAPE = (2, 9, 64)
+SQB_STATS = ("units", "used", "unmapped", "multi", "not_paired", "same_strand", "out_of_range", "overhang", "ambiguous")
+
+
+def seq_bias_weights(alpha, lens, counts):
+    """qm_sqb_weights, a pure host function: (q uint64[T], k) -- the integer weights q_t = floor(rho_t * 2^k) of the expected counts from
+    a first estimate alpha float64[T], the transcript lengths and the fragment-length histogram counts uint64[max_len + 1]"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64); lens = _fld_lens(lens); alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    if alpha.size != lens.size:
+        raise ValueError("alpha must be [len(lens)]")
+    q = np.zeros(lens.size, dtype=np.uint64); k = C.c_int32(0)
+    some = lens.size > 0
+    _check(lib().qm_sqb_weights(int(counts.size) - 1, counts.ctypes.data if counts.size else None, int(lens.size), lens.ctypes.data if some else None,
+                                alpha.ctypes.data if some else None, q.ctypes.data if some else None, C.byref(k)))
+    return q, int(k.value)
+
+
+def seq_bias_ratios(obs, exp):
+    """qm_sqb_ratios, a pure host function: R float64[2][9][64] from the observed and the expected counts, uint64[2][9][64] each"""
+    obs = np.ascontiguousarray(obs, dtype=np.uint64).ravel(); exp = np.ascontiguousarray(exp, dtype=np.uint64).ravel()
+    if obs.size != SQB_BINS or exp.size != SQB_BINS:
+        raise ValueError("%d counts each" % SQB_BINS)
+    R = np.zeros(SQB_BINS, dtype=np.float64)
+    _check(lib().qm_sqb_ratios(obs.ctypes.data, exp.ctypes.data, R.ctypes.data))
+    return R.reshape(SQB_SHAPE)
+
+
+class SeqBias(_Object):
+    """qm_sqb_*: the sequence-specific bias model in the device memory of a mapper's GPU.  add(mapper) sweeps the mapper's last result
+    where it lies, add_hits sweeps arrays held on the host through the same kernel, add_counts adds another object's observed counts:
+    a unit with exactly one hit that is properly paired, on opposite strands, of 1 .. max_len bases, whose two nine-character end
+    contexts lie on its transcript and hold A, C, G, T only, counts once in each of its 18 words; stat() tells where the others went.
+    expect(counts, n_txps, q) is the same count over every place of every transcript a fragment could start or end at, weighted;
+    eff_lens(counts, n_txps, R) the effective lengths under a table of ratios; context probes single contexts.
+    max_blocks: at most that many workgroups per launch (0: as many as are resident)."""
+
+    STATS = SQB_STATS + ("max_len", "folds", "last_fold_us", "last_expect_us", "last_efflen_us")
+    DESTROY, STAT = "qm_sqb_destroy", "qm_sqb_stat"
+
+    def __init__(self, mapper, max_len=FLD_DEFAULT_MAX_LEN, max_blocks=0):
+        self._h = C.c_void_p()
+        if not 0 <= int(max_blocks) <= 0xffff:
+            raise ValueError("max_blocks must be 0 .. 65535")
+        _check(lib().qm_sqb_create(mapper._h, int(max_len), int(max_blocks), C.byref(self._h)))
+        self.device = mapper.device
+        self.max_len = int(max_len)
+
+    def add(self, mapper):
+        """sweep the result of the mapper's last map call"""
+        _check(lib().qm_sqb_add(self._h, mapper._h))
+
+    def add_hits(self, hit_offsets, hits):
+        n, hit_offsets, hits = _host_hits(hit_offsets, hits)
+        _check(lib().qm_sqb_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
+
+    def add_counts(self, obs):
+        obs = np.ascontiguousarray(obs, dtype=np.uint64).ravel()
+        if obs.size != SQB_BINS:
+            raise ValueError("%d counts" % SQB_BINS)
+        _check(lib().qm_sqb_add_counts(self._h, obs.ctypes.data))
+
+    def counts(self):
+        """the observed counts, uint64[2][9][64]"""
+        c = np.zeros(SQB_BINS, dtype=np.uint64)
+        _check(lib().qm_sqb_fetch(self._h, c.ctypes.data))
+        return c.reshape(SQB_SHAPE)
+
+    def expect(self, counts, n_txps, q):
+        """qm_sqb_expect: the expected counts uint64[2][9][64] of a fragment-length histogram counts uint64[max_len + 1] and weights q uint64[n_txps]"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64); q = np.ascontiguousarray(q, dtype=np.uint64)
+        if counts.size != self.max_len + 1 or q.size != int(n_txps):
+            raise ValueError("max_len + 1 counts and n_txps weights")
+        ex = np.zeros(SQB_BINS, dtype=np.uint64)
+        _check(lib().qm_sqb_expect(self._h, counts.ctypes.data, int(n_txps), q.ctypes.data if q.size else None, ex.ctypes.data))
+        return ex.reshape(SQB_SHAPE)
+
+    def eff_lens(self, counts, n_txps, R):
+        """qm_sqb_eff_lens: the effective lengths float64[n_txps] under the ratios R float64[2][9][64]"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64); R = np.ascontiguousarray(R, dtype=np.float64).ravel()
+        if counts.size != self.max_len + 1 or R.size != SQB_BINS:
+            raise ValueError("max_len + 1 counts and %d ratios" % SQB_BINS)
+        eff = np.zeros(int(n_txps), dtype=np.float64)
+        _check(lib().qm_sqb_eff_lens(self._h, counts.ctypes.data, int(n_txps), R.ctypes.data, eff.ctypes.data if eff.size else None))
+        return eff
+
+    def context(self, tids, positions, ends):
+        """qm_sqb_context: int32[n][9], the nine words of the context of end ends[i] (0: 5', 1: 3') at positions[i] of transcript tids[i];
+        a row of -1 where the context does not lie on the transcript or holds a character that is not A, C, G, T"""
+        tids = np.ascontiguousarray(tids, dtype=np.uint32); positions = np.ascontiguousarray(positions, dtype=np.int32); ends = np.ascontiguousarray(ends, dtype=np.int32)
+        if not tids.size == positions.size == ends.size:
+            raise ValueError("tids, positions and ends must be of one length")
+        out = np.zeros((tids.size, 9), dtype=np.int32)
+        if tids.size:
+            _check(lib().qm_sqb_context(self._h, int(tids.size), tids.ctypes.data, positions.ctypes.data, ends.ctypes.data, out.ctypes.data))
+        return out
+
+    def clear(self):
+        _check(lib().qm_sqb_clear(self._h))
+
+
+def write_seq_bias(path, obs, exp, ratio):
+    """FILE.seqBias.txt: a header line, then per entry `end<TAB>position<TAB>word<TAB>obs<TAB>exp<TAB>ratio` -- obs and exp integers, ratio
+    %.17g (every double comes back bit for bit)"""
+    obs = np.asarray(obs).reshape(SQB_SHAPE); exp = np.asarray(exp).reshape(SQB_SHAPE); ratio = np.asarray(ratio).reshape(SQB_SHAPE)
+    with open(path, "w") as f:
+        f.write("end\tposition\tword\tobs\texp\tratio\n")
+        for e in range(2):
+            for j in range(9):
+                for w in range(64):
+                    f.write("%d\t%d\t%d\t%d\t%d\t%.17g\n" % (e, j, w, int(obs[e, j, w]), int(exp[e, j, w]), float(ratio[e, j, w])))
+
+
+def read_seq_bias(path):
+    """the inverse of write_seq_bias: (obs uint64[2][9][64], exp uint64[2][9][64], ratio float64[2][9][64])"""
+    obs = np.zeros(SQB_SHAPE, dtype=np.uint64); ex = np.zeros(SQB_SHAPE, dtype=np.uint64); ratio = np.zeros(SQB_SHAPE, dtype=np.float64)
+    with open(path) as f:
+        if f.readline().rstrip("\n").split("\t") != ["end", "position", "word", "obs", "exp", "ratio"]:
+            raise ValueError("%s: not a seqBias file" % path)
+        for i in range(SQB_BINS):
+            w = f.readline().rstrip("\n").split("\t")
+            e, j, k = i // 576, (i // 64) % 9, i % 64
+            if len(w) != 6 or (int(w[0]), int(w[1]), int(w[2])) != (e, j, k):
+                raise ValueError("%s: line %d" % (path, i + 2))
+            obs[e, j, k] = int(w[3]); ex[e, j, k] = int(w[4]); ratio[e, j, k] = float(w[5])
+    return obs, ex, ratio
+
+
 LIB_TYPES = ("IU", "ISF", "ISR", "OU", "OSF", "OSR", "MU", "MSF", "MSR", "U", "SF", "SR", "A")
 LIB_CODES = ("ISF", "ISR", "OSF", "OSR", "MSF", "MSR", "LF", "LR", "RF", "RR", "SF", "SR")    # a hit's code: words 0 .. 11 of a tally
 LIB_TOTALS = ("units", "unmapped_units", "kept_units", "dropped_units", "hits", "kept_hits")  # words 24 .. 29; word 30: other_hits
@@ -1433,12 +1577,13 @@ class MappedStream:
     into equivalence classes on its device (eq_classes() after the last batch); with hits=False on top the hits stay on the
     device -- hit_offsets / hits of a batch are None, n_hits and counters as ever.  frag_len_dist=True: every batch is folded into a
     fragment-length histogram on its device as well (frag_len_dist() after the last batch).  gc_bias=True: every batch is swept into
-    the observed counts of the fragment GC bias model as well (gc_bias() after the last batch).  lib_type (a name of LIB_TYPES or a
+    the observed counts of the fragment GC bias model as well (gc_bias() after the last batch).  seq_bias=True: ... and into the observed
+    counts of the sequence-specific bias model (seq_bias() after the last batch).  lib_type (a name of LIB_TYPES or a
     12-bit mask): every batch is tallied by orientation code on its device (lib_counts() after the last batch), and with
     eq_classes=True the classes hold only the hits that type keeps."""
 
     def __init__(self, index: QuasiIndex, path1, path2=None, opts=None, device=0, batch_units=1 << 20, threads=None, ph_compact=False,
-                 names=True, eq_classes=False, hits=True, frag_len_dist=False, lib_type=None, gc_bias=False):
+                 names=True, eq_classes=False, hits=True, frag_len_dist=False, lib_type=None, gc_bias=False, seq_bias=False):
         self._h = C.c_void_p()
         self.paired = path2 is not None
         self.names = bool(names)
@@ -1453,7 +1598,7 @@ class MappedStream:
         rc = lib().qm_stream_open_ex(index._h, darr, len(devs), 1 if ph_compact else 0, C.byref(opts), os.fsencode(path1),
                                      os.fsencode(path2) if path2 else None, int(batch_units),
                                      int(threads or min(32, os.cpu_count() or 1)),
-                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0) | (32 if gc_bias else 0) |
+                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0) | (32 if gc_bias else 0) | (64 if seq_bias else 0) |
                                      (0 if lib_type is None else 16 | (lib_type_mask(lib_type) if isinstance(lib_type, str) else int(lib_type)) << 16), C.byref(self._h))
         if rc != 0:
             raise QmError("qm_stream_open failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
@@ -1515,6 +1660,13 @@ class MappedStream:
         self._call("qm_stream_gcb_fetch", c.ctypes.data, st.ctypes.data)
         return c, dict(zip(GCB_STATS, (int(x) for x in st)))
 
+    def seq_bias(self):
+        """after the last batch of a stream opened with seq_bias=True: (obs uint64[2][9][64], stats) summed over the stream's contexts and
+        devices -- stats: a dictionary of units and the eight categories (SQB_STATS)"""
+        c = np.zeros(SQB_BINS, dtype=np.uint64); st = np.zeros(9, dtype=np.int64)
+        self._call("qm_stream_sqb_fetch", c.ctypes.data, st.ctypes.data)
+        return c.reshape(SQB_SHAPE), dict(zip(SQB_STATS, (int(x) for x in st)))
+
     def lib_counts(self):
         """after the last batch of a stream opened with lib_type: the tallies uint64[32] (LibFormat.counts) summed over the stream's
         contexts and devices"""
@@ -1525,10 +1677,10 @@ class MappedStream:
     def stats(self):
         """seconds: read_s = open to the last batch packed (wall), map_s / fetch_s = upload + kernels / download summed over the
         contexts, parse_cpu_s / copy_cpu_s = the ingest workers' task time summed over the workers"""
-        a = (C.c_double * 17)()
-        _check(lib().qm_stream_stats_ex(self._h, a, 17))
+        a = (C.c_double * 18)()
+        _check(lib().qm_stream_stats_ex(self._h, a, 18))
         return dict(zip(("read_s", "map_s", "fetch_s", "caller_wait_s", "open_s", "alloc_s", "first_batch_s", "parse_cpu_s", "copy_cpu_s",
-                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts", "fld_fold_s", "gcb_sweep_s"), [float(x) for x in a]))
+                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts", "fld_fold_s", "gcb_sweep_s", "sqb_sweep_s"), [float(x) for x in a]))
 
     def close(self):
         if self._h:

@@ -1,5 +1,5 @@
-// qm_exec.h -- what the six drivers of the estimation objects (qm_eqc_host.inl, qm_quant_host.inl, qm_boot_host.inl, qm_fld_host.inl,
-// qm_lib_host.inl, qm_gcb_host.inl) run on: a buffer type, the launch of a wave body over a number of wavefronts, two scans and a sort, the host
+// qm_exec.h -- what the seven drivers of the estimation objects (qm_eqc_host.inl, qm_quant_host.inl, qm_boot_host.inl, qm_fld_host.inl,
+// qm_lib_host.inl, qm_gcb_host.inl, qm_sqb_host.inl) run on: a buffer type, the launch of a wave body over a number of wavefronts, two scans and a sort, the host
 // operations, and two things every object needs: Base -- device, stream and the two timer events, opened and closed in one place --
 // and feed -- host arrays in CSR form cut into parts, uploaded and handed to the caller's function part by part.  Like qm_wave.h it
 // has two definitions.  In the library (included by qm_host.hip, after DevBuf, PinBuf, fail and HIPCHK) a launch is a kernel on a
@@ -144,7 +144,7 @@ template <auto Body, int SLAB_WORDS, class... A>
 __global__ void __launch_bounds__(QX_BLOCK) sweep_kernel(A... a) {
   const long long w = uniform(((long long)blockIdx.x * QX_BLOCK + threadIdx.x) >> 6), nWaves = (long long)gridDim.x * (QX_BLOCK / 64);
   if constexpr (SLAB_WORDS > 0) {
-    __shared__ u32 slab[QX_BLOCK / 64][SLAB_WORDS];
+    __shared__ alignas(8) u32 slab[QX_BLOCK / 64][SLAB_WORDS];     // (a body may keep 64-bit words in an even SLAB_WORDS)
     Body(a..., w, nWaves, (QM_LDS(u32)*)&slab[threadIdx.x >> 6][0]);
   }
   else Body(a..., w, nWaves);

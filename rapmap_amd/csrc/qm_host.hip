@@ -2081,3 +2081,4 @@ int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
 #include "qm_fld_host.inl"
 #include "qm_lib_host.inl"
 #include "qm_gcb_host.inl"
+#include "qm_sqb_host.inl"
