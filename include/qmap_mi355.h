@@ -676,6 +676,78 @@ int qm_sqb_weights(int32_t max_len, const uint64_t* counts /*[max_len+1]*/, int6
 /* no counterpart in the reference.  The ratios above as a pure host function. */
 int qm_sqb_ratios(const uint64_t* obs /*[QM_SQB_BINS]*/, const uint64_t* exp /*[QM_SQB_BINS]*/, double* R /*[QM_SQB_BINS]*/);
 
+/* ---- positional bias: where along its transcript a fragment starts and where it ends ---------------------------------------------
+ * (No counterpart in the reference; consumer of the hit records.  The names follow Salmon's --posBias; parity with Salmon is NOT
+ * claimed: none was at hand to compare with.  The model is this project's own and every constant in it -- the five length classes
+ * and their bounds, the 20 bins, the pseudo-count 1, the clamp [0.25, 4] -- is a constant of this model.)
+ * FRAGMENT: a fragment lies on transcript t of length L as [s, e), e = s + frag_len, s = min(max(pos, 0), max(mate_pos, 0)) as in
+ * the GC model above; its last position is i = e - 1.  Everything is in transcript coordinates, as in the sequence model.
+ * CLASSES: QM_PSB_CLASSES = 5, by transcript length: class 0: L <= 791; 1: L <= 1265; 2: L <= 1707; 3: L <= 2433; 4: otherwise.
+ * BINS: QM_PSB_POS = 20.  Position x (0 <= x < L) falls in bin floor(20 x / L), exact integer arithmetic; equivalently bin b holds
+ * [B_b, B_(b+1)) with B_b = ceil(b L / 20).  A transcript shorter than 20 has empty bins.
+ * TABLE: [2 ends][5][20] = QM_PSB_BINS = 200 entries; entry (end, c, b) is at (end * 5 + c) * 20 + b.  End 0 is the start s, end 1
+ * the last position i.
+ * OBSERVED: obs[QM_PSB_BINS], unsigned 64-bit.  A unit falls into the first of seven categories that holds, each with a 64-bit
+ * counter; the seven always add up to the units swept.  The first five are qm_fld's (unmapped, multi, not_paired, same_strand,
+ * out_of_range).  Then
+ *     overhang      tid >= n_txps, or e > L
+ *     used          otherwise: obs[0][c][bin(s)] += 1 and obs[1][c][bin(i)] += 1, c the class of L
+ * WEIGHTS: qm_sqb_weights as it is (q_t and k); this model adds no function of its own.
+ * EXPECTED: exp[QM_PSB_BINS], unsigned 64-bit, on the device, integers only, hence order-free.  With P of the sequence model,
+ * W[0] = 0 and W[x] = W[x - 1] + P[min(m, x)] -- so W[x] = W[m] + (x - m) P[m] beyond m, and W[L_t] = S_t.  A start s carries
+ * P[min(m, L - s)], a last position i carries P[min(m, i + 1)]; summed over the positions of a bin:
+ *     exp[0][c_t][b] += q_t * (W[L_t - B_b] - W[L_t - B_(b+1)])
+ *     exp[1][c_t][b] += q_t * (W[B_(b+1)] - W[B_b])
+ * a closed form per (transcript, bin).  Each end sums to the sum over t of q_t * S_t.  sum of q_t * L_t * P[m] >= 2^63 (128-bit
+ * host arithmetic): QM_E_UNSUPPORTED, as in qm_sqb_expect.
+ * RATIOS (qm_psb_ratios, a pure host function; float64 under fp contract(off), every operation on its own): per (end, class), over
+ * its 20 bins,
+ *     po = (double)(obs + 1) / (double)(sum of the 20 obs + 20);   pe likewise from exp;   R = min(max(po / pe, 0.25), 4.0)
+ * and an (end, class) whose sum of obs or sum of exp is 0 holds 1.0 throughout.
+ * EFFECTIVE LENGTHS, on the device, float64, nothing fused: the sequence model's definition with
+ *     b5_t(s) = R[0][c_t][bin_t(s)]        b3_t(i) = R[1][c_t][bin_t(i)]
+ * and everything else as it stands there: N_t; e'_t = N_t / (double)P[min(L_t, m)], (double)L_t where that P is 0; the order -- per
+ * start ascending l, one product and one addition each, never fused; 64 starts by the tree; a transcript's tiles ascending.  With
+ * R == 1 it is qm_fld's effective length as one quotient, bit for bit.
+ * Not thread-safe (one per context / host thread; merge with qm_psb_add_counts). */
+typedef struct qm_psb qm_psb;
+#define QM_PSB_CLASSES 5
+#define QM_PSB_POS 20
+#define QM_PSB_BINS 200
+/* no counterpart in the reference.  max_len and flags as qm_gcb_create's. */
+int qm_psb_create(qm_ctx* ctx, int32_t max_len, uint32_t flags, qm_psb** out);
+/* no counterpart in the reference */
+int qm_psb_destroy(qm_psb* g);
+/* no counterpart in the reference.  Observed counts and counters back to zero. */
+int qm_psb_clear(qm_psb* g);
+/* no counterpart in the reference.  Sweeps the result of ctx's last map call where it lies, as qm_gcb_add does. */
+int qm_psb_add(qm_psb* g, qm_ctx* ctx);
+/* no counterpart in the reference.  The same kernel over arrays in HOST memory, uploaded in parts. */
+int qm_psb_add_hits(qm_psb* g, int64_t n_units, const int64_t* hit_offsets, const qm_hit* hits);
+/* no counterpart in the reference.  obs[i] += counts[i]: the merge primitive.  A used fragment brings two counts, one of them at
+ * end 0: the sum of counts[0][.][.] is added to `used` and to the units. */
+int qm_psb_add_counts(qm_psb* g, const uint64_t* obs /*[QM_PSB_BINS]*/);
+/* no counterpart in the reference */
+int qm_psb_fetch(qm_psb* g, uint64_t* obs /*[QM_PSB_BINS]*/);
+/* no counterpart in the reference.  Since creation / the last clear: the units swept, the seven categories, max_len, the folds and
+ * the kernels of the last fold, the last qm_psb_expect and the last qm_psb_eff_lens in microseconds (HIP events) */
+enum { QM_PSB_STAT_UNITS = 0, QM_PSB_STAT_USED = 1, QM_PSB_STAT_UNMAPPED = 2, QM_PSB_STAT_MULTI = 3, QM_PSB_STAT_NOT_PAIRED = 4, QM_PSB_STAT_SAME_STRAND = 5,
+       QM_PSB_STAT_OUT_OF_RANGE = 6, QM_PSB_STAT_OVERHANG = 7, QM_PSB_STAT_MAX_LEN = 8, QM_PSB_STAT_FOLDS = 9, QM_PSB_STAT_LAST_FOLD_US = 10,
+       QM_PSB_STAT_LAST_EXPECT_US = 11, QM_PSB_STAT_LAST_EFFLEN_US = 12 };
+int qm_psb_stat(const qm_psb* g, int which, int64_t* value);
+/* no counterpart in the reference.  exp[QM_PSB_BINS] from counts[0 .. max_len] and the weights q[n_txps] (qm_sqb_weights) over every
+ * transcript of the index (n_txps must be the index's).  counts[0] != 0: QM_E_ARG; 2^63 fragments or more, or the bound above:
+ * QM_E_UNSUPPORTED. */
+int qm_psb_expect(qm_psb* g, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, const uint64_t* q /*[n_txps]*/, uint64_t* exp /*[QM_PSB_BINS]*/);
+/* no counterpart in the reference.  eff[n_txps] from counts[0 .. max_len] and the ratios R[QM_PSB_BINS].  counts[0] != 0: QM_E_ARG. */
+int qm_psb_eff_lens(qm_psb* g, const uint64_t* counts /*[max_len+1]*/, int64_t n_txps, const double* R /*[QM_PSB_BINS]*/, double* eff /*[n_txps]*/);
+/* no counterpart in the reference.  A probe of classes and bins: question i asks for position positions[i] of transcript tids[i];
+ * out[2 i] is the transcript's class and out[2 i + 1] the position's bin, or both -1 where tids[i] is no transcript of the index or
+ * positions[i] no position of it. */
+int qm_psb_position(qm_psb* g, int64_t n, const uint32_t* tids, const int32_t* positions, int32_t* out /*[n*2]*/);
+/* no counterpart in the reference.  The ratios above as a pure host function. */
+int qm_psb_ratios(const uint64_t* obs /*[QM_PSB_BINS]*/, const uint64_t* exp /*[QM_PSB_BINS]*/, double* R /*[QM_PSB_BINS]*/);
+
 /* ---- library type: hit orientations tallied, compatible hits kept ------------------------------------------------------------
  * (No counterpart in the reference; consumer of the hit records.  The names follow Salmon's -l / --libType and its
  * lib_format_counts.json; parity with Salmon is NOT claimed: none was at hand to compare with.  The model is this project's own,
@@ -805,6 +877,11 @@ int qm_stream_open(const qm_index* ix, int device_id, uint32_t ctx_flags, const 
  * flags.  qm_stream_sqb_fetch sums the contexts' observed counts.  A stream without the flag creates no qm_sqb and launches nothing
  * of it. */
 #define QM_STREAM_SQB 64u
+/* QM_STREAM_PSB -- every map context owns a qm_psb of QM_FLD_DEFAULT_MAX_LEN and sweeps each batch into it after mapping (after the
+ * QM_STREAM_SQB sweep, when there is one), on the context's stream, before the batch's buffers are reused; with or without the other
+ * flags.  qm_stream_psb_fetch sums the contexts' observed counts.  A stream without the flag creates no qm_psb and launches nothing
+ * of it. */
+#define QM_STREAM_PSB 128u
 int qm_stream_open_ex(const qm_index* ix, const int32_t* devices, int32_t n_devices, uint32_t ctx_flags, const qm_opts* opts,
                       const char* path1, const char* path2, int64_t batch_units, int32_t reader_threads, uint32_t stream_flags,
                       qm_stream** out);
@@ -834,15 +911,20 @@ int qm_stream_gcb_fetch(qm_stream* s, uint64_t* obs /*[QM_GCB_BINS]*/, int64_t* 
  * before that, and for a stream opened without QM_STREAM_SQB): the contexts' observed sequence-bias counts and counters summed,
  * across devices.  stats9: the units, then used, unmapped, multi, not_paired, same_strand, out_of_range, overhang, ambiguous. */
 int qm_stream_sqb_fetch(qm_stream* s, uint64_t* obs /*[QM_SQB_BINS]*/, int64_t* stats9);
+/* No counterpart in the reference; consumer of the hit records.  Once qm_stream_next has returned the end of the input (QM_E_STATE
+ * before that, and for a stream opened without QM_STREAM_PSB): the contexts' observed positional-bias counts and counters summed,
+ * across devices.  stats8: the units, then used, unmapped, multi, not_paired, same_strand, out_of_range, overhang. */
+int qm_stream_psb_fetch(qm_stream* s, uint64_t* obs /*[QM_PSB_BINS]*/, int64_t* stats8);
 void qm_stream_close(qm_stream* s);
 /* seconds spent so far: [0] the ingest engine, open to its last batch packed (wall), [1] upload + kernels (summed over the
  * contexts), [2] download (summed), [3] the caller waiting in qm_stream_next, [4] qm_stream_open, [5] growing the pinned result
- * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 18) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
+ * buffers ([1] and [2] do not hold the folds of a QM_STREAM_EQ_CLASSES stream: those are [13]); qm_stream_stats_ex(n <= 19) adds [6] open to the first batch packed, [7] parse tasks (CPU seconds over all workers),
  * [8] copy tasks, [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that went
  * to the device 2-bit packed, [13] qm_eqc_add of the batches (summed over the contexts), [14] contexts that folded at least one batch,
  * [15] qm_fld_add of the batches of a QM_STREAM_FLD stream (seconds, summed over the contexts; not part of [1], [2] or [13]),
  * [16] qm_gcb_add of the batches of a QM_STREAM_GCB stream (seconds, summed over the contexts; not part of [1], [2], [13] or [15]),
- * [17] qm_sqb_add of the batches of a QM_STREAM_SQB stream (seconds, summed over the contexts; not part of the others) */
+ * [17] qm_sqb_add of the batches of a QM_STREAM_SQB stream (seconds, summed over the contexts; not part of the others),
+ * [18] qm_psb_add of the batches of a QM_STREAM_PSB stream (seconds, summed over the contexts; not part of the others) */
 int qm_stream_stats(qm_stream* s, double* out6);
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n);
 const char* qm_stream_last_error(void);

@@ -8,6 +8,7 @@ from .api import (QuasiIndex, QuasiMapper, QmError, QmOpts, default_opts, build_
                   Quant, exp_digamma, write_quant, read_quant, Bootstrap, write_bootstraps, read_bootstraps,
                   FragLenDist, GCBias, gc_eff_lens_from_counts, write_gc_bias, read_gc_bias, GCB_BINS, GCB_STATS,
                   SeqBias, seq_bias_weights, seq_bias_ratios, write_seq_bias, read_seq_bias, SQB_BINS, SQB_STATS,
+                  PosBias, pos_bias_ratios, write_pos_bias, read_pos_bias, PSB_BINS, PSB_STATS,
                   eff_lens_from_counts, frag_len_mean, write_flen_dist, read_flen_dist, FLD_DEFAULT_MAX_LEN, FLD_STATS,
                   LibFormat, lib_type_mask, infer_lib_type, lib_format_counts, write_lib_format_counts, read_lib_format_counts,
                   LIB_TYPES, LIB_CODES, LIB_TOTALS, LIB_ALL_CODES)

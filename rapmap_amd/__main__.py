@@ -95,6 +95,12 @@ def _quasimap(argv):
                     "could start or end at are counted on the GPU under the first estimate and the run's fragment-length distribution "
                     "(expected), and a second estimate, started from the first, runs on effective lengths weighted by observed / expected, "
                     "computed on the GPU; counts and ratios are written to FILE.seqBias.txt")
+    ap.add_argument("--quantPosBias", action="store_true", help="[only with quantFLD, not with quantGCBias or quantSeqBias]: one round of positional bias "
+                    "correction: where along their transcript the run's uniquely and properly paired fragments start and end is counted in 20 bins "
+                    "per class of transcript length (observed), the same bins over every place of every transcript a fragment could start or end "
+                    "at are counted on the GPU under the first estimate and the run's fragment-length distribution (expected), and a second "
+                    "estimate, started from the first, runs on effective lengths weighted by observed / expected, computed on the GPU; counts "
+                    "and ratios are written to FILE.posBias.txt")
     ap.add_argument("--quantVB", action="store_true", help="[only with quant]: the variational Bayes EM in place of the EM: a transcript's weight is "
                     "exp(digamma(abundance + prior)) / effective length; the bootstrap replicates of --numBootstraps use it as well")
     ap.add_argument("--quantVBPrior", type=float, default=1e-2, metavar="P", help="[only with quantVB]: the prior, per nucleotide: P x effective length "
@@ -122,6 +128,10 @@ def _quasimap(argv):
         ap.error("--quantSeqBias needs --quantFLD")
     if a.quantSeqBias and a.quantGCBias:
         ap.error("--quantSeqBias and --quantGCBias are two corrections of their own: the joint model is not there, give one of them")
+    if a.quantPosBias and not a.quantFLD:
+        ap.error("--quantPosBias needs --quantFLD")
+    if a.quantPosBias and (a.quantGCBias or a.quantSeqBias):
+        ap.error("--quantPosBias and %s are two corrections of their own: the joint model is not there, give one of them" % ("--quantGCBias" if a.quantGCBias else "--quantSeqBias"))
     if a.quantVB and not a.quant:
         ap.error("--quantVB needs --quant")
     if not (a.quantVBPrior >= 0 and a.quantVBPrior < float("inf")):
@@ -247,11 +257,14 @@ def _quasimap(argv):
     # --quantSeqBias: ... or into the observed counts of the end contexts
     sqb_obs = np.zeros((2, 9, 64), dtype=np.uint64) if a.quantSeqBias else None
     sqb_stats = dict.fromkeys(ra.SQB_STATS, 0); sqb_s = 0.0
+    # --quantPosBias: ... or into the observed counts of the positions of the fragments' ends
+    psb_obs = np.zeros((2, 5, 20), dtype=np.uint64) if a.quantPosBias else None
+    psb_stats = dict.fromkeys(ra.PSB_STATS, 0); psb_s = 0.0
     for f1, f2 in pairs:
         os.environ.setdefault("QM_INGEST_PIN", "1")   # a whole-machine job with one ingest engine: its workers on the NUMA node that holds the files' pages
         st = ra.MappedStream(qi, f1, f2, opts=opts, device=devices, batch_units=a.chunk, threads=nthr, names=out is not None,
                              eq_classes=classes is not None, hits=out is not None or classes is None, frag_len_dist=a.quantFLD,
-                             lib_type=a.libType or None, gc_bias=a.quantGCBias, seq_bias=a.quantSeqBias)
+                             lib_type=a.libType or None, gc_bias=a.quantGCBias, seq_bias=a.quantSeqBias, pos_bias=a.quantPosBias)
         for b in st:
             gpu_ms += b.gpu_ms
             for kk in tot:
@@ -283,6 +296,11 @@ def _quasimap(argv):
             sqb_obs += c_; sqb_s += st.stats()["sqb_sweep_s"]
             for kk in sqb_stats:
                 sqb_stats[kk] += s_[kk]
+        if a.quantPosBias:
+            c_, s_ = st.pos_bias()
+            psb_obs += c_; psb_s += st.stats()["psb_sweep_s"]
+            for kk in psb_stats:
+                psb_stats[kk] += s_[kk]
         log("stream: " + ", ".join("%s %.3f" % kv for kv in st.stats().items()))
         st.close()
     if a.libType:
@@ -349,6 +367,28 @@ def _quasimap(argv):
                 log("sequence bias: %s, swept in %.3f ms; weights 2^%d; expected counts in %.3f ms and effective lengths in %.3f ms on the GPU; ratios %g .. %g; "
                     "wrote %s.seqBias.txt" % (", ".join("%s %d" % (kk, sqb_stats[kk]) for kk in ra.SQB_STATS), sqb_s * 1e3, sq_k, expect_us / 1e3, efflen_us / 1e3,
                                               float(sq_ratio.min()), float(sq_ratio.max()), a.quant))
+                qn.close()
+                qn = ra.Quant(classes, qi.n_txps, eff)
+                if a.quantVB:
+                    qn.set_method("vbem", prior=a.quantVBPrior, per_transcript=a.quantPerTranscriptPrior)
+                qn.set_start(first)
+                it2, rel = qn.run(max_iter=a.quantMaxIter, rel_tol=a.quantRelTol)
+                iters += it2
+            if a.quantPosBias:
+                # --quantPosBias: the steps of --quantSeqBias over the positional model: integer weights from the first estimate, the
+                # expected counts and the effective lengths on device 0, a second estimate over the same table started from the first
+                first = qn.fetch()
+                ps_q, ps_k = ra.seq_bias_weights(first, lens, fld_counts)
+                pb = ra.PosBias(keep[0])
+                ps_exp = pb.expect(fld_counts, qi.n_txps, ps_q)
+                ps_ratio = ra.pos_bias_ratios(psb_obs, ps_exp)
+                eff = pb.eff_lens(fld_counts, qi.n_txps, ps_ratio)
+                expect_us = pb.stat()["last_expect_us"]; efflen_us = pb.stat()["last_efflen_us"]
+                pb.close()
+                ra.write_pos_bias(a.quant + ".posBias.txt", psb_obs, ps_exp, ps_ratio)
+                log("positional bias: %s, swept in %.3f ms; weights 2^%d; expected counts in %.3f ms and effective lengths in %.3f ms on the GPU; ratios %g .. %g; "
+                    "wrote %s.posBias.txt" % (", ".join("%s %d" % (kk, psb_stats[kk]) for kk in ra.PSB_STATS), psb_s * 1e3, ps_k, expect_us / 1e3, efflen_us / 1e3,
+                                              float(ps_ratio.min()), float(ps_ratio.max()), a.quant))
                 qn.close()
                 qn = ra.Quant(classes, qi.n_txps, eff)
                 if a.quantVB:

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "qm_gcb_expect", "qm_gcb_eff_lens_from_counts", "qm_gcb_window_gc", "qm_stream_gcb_fetch",
     "qm_sqb_create", "qm_sqb_destroy", "qm_sqb_clear", "qm_sqb_add", "qm_sqb_add_hits", "qm_sqb_add_counts", "qm_sqb_fetch", "qm_sqb_stat",
     "qm_sqb_expect", "qm_sqb_eff_lens", "qm_sqb_context", "qm_sqb_weights", "qm_sqb_ratios", "qm_stream_sqb_fetch",
+    "qm_psb_create", "qm_psb_destroy", "qm_psb_clear", "qm_psb_add", "qm_psb_add_hits", "qm_psb_add_counts", "qm_psb_fetch", "qm_psb_stat",
+    "qm_psb_expect", "qm_psb_eff_lens", "qm_psb_position", "qm_psb_ratios", "qm_stream_psb_fetch",
     "qm_lib_create", "qm_lib_destroy", "qm_lib_clear", "qm_lib_add", "qm_lib_add_hits", "qm_lib_compact_hits", "qm_lib_add_counts", "qm_lib_fetch",
     "qm_lib_stat", "qm_eqc_add_lib", "qm_lib_type_mask", "qm_lib_infer", "qm_stream_lib_fetch",
     "qm_sam_write", "qm_sam_writer_open", "qm_sam_writer_open_ex", "qm_sam_writer_header", "qm_sam_writer_put", "qm_sam_writer_close", "qm_buf_free",
@@ -257,6 +259,19 @@ def lib():
     L.qm_sqb_weights.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     L.qm_sqb_ratios.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.qm_stream_sqb_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_psb_create.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.qm_psb_destroy.argtypes = [C.c_void_p]
+    L.qm_psb_clear.argtypes = [C.c_void_p]
+    L.qm_psb_add.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_psb_add_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_psb_add_counts.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_psb_fetch.argtypes = [C.c_void_p, C.c_void_p]
+    L.qm_psb_stat.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.qm_psb_expect.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_psb_eff_lens.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.qm_psb_position.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_psb_ratios.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.qm_stream_psb_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.qm_lib_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.qm_lib_destroy.argtypes = [C.c_void_p]
     L.qm_lib_clear.argtypes = [C.c_void_p]
@@ -1334,6 +1349,121 @@ def read_seq_bias(path):
     return obs, ex, ratio
 
 
+PSB_BINS = 200                                                        # QM_PSB_BINS: [2 ends][5 length classes][20 bins]
+PSB_SHAPE = (2, 5, 20)
+PSB_STATS = ("units", "used", "unmapped", "multi", "not_paired", "same_strand", "out_of_range", "overhang")
+
+
+def pos_bias_ratios(obs, exp):
+    """qm_psb_ratios, a pure host function: R float64[2][5][20] from the observed and the expected counts, uint64[2][5][20] each"""
+    obs = np.ascontiguousarray(obs, dtype=np.uint64).ravel(); exp = np.ascontiguousarray(exp, dtype=np.uint64).ravel()
+    if obs.size != PSB_BINS or exp.size != PSB_BINS:
+        raise ValueError("%d counts each" % PSB_BINS)
+    R = np.zeros(PSB_BINS, dtype=np.float64)
+    _check(lib().qm_psb_ratios(obs.ctypes.data, exp.ctypes.data, R.ctypes.data))
+    return R.reshape(PSB_SHAPE)
+
+
+class PosBias(_Object):
+    """qm_psb_*: the positional bias model in the device memory of a mapper's GPU.  add(mapper) sweeps the mapper's last result where it
+    lies, add_hits sweeps arrays held on the host through the same kernel, add_counts adds another object's observed counts: a unit
+    with exactly one hit that is properly paired, on opposite strands, of 1 .. max_len bases and on its transcript counts once in the
+    bin of its start and once in the bin of its last position, in the class of its transcript's length; stat() tells where the others
+    went.  expect(counts, n_txps, q) is the same count over every place of every transcript a fragment could start or end at,
+    weighted (q: seq_bias_weights); eff_lens(counts, n_txps, R) the effective lengths under a table of ratios; position probes single
+    positions.  max_blocks: at most that many workgroups per launch (0: as many as are resident)."""
+
+    STATS = PSB_STATS + ("max_len", "folds", "last_fold_us", "last_expect_us", "last_efflen_us")
+    DESTROY, STAT = "qm_psb_destroy", "qm_psb_stat"
+
+    def __init__(self, mapper, max_len=FLD_DEFAULT_MAX_LEN, max_blocks=0):
+        self._h = C.c_void_p()
+        if not 0 <= int(max_blocks) <= 0xffff:
+            raise ValueError("max_blocks must be 0 .. 65535")
+        _check(lib().qm_psb_create(mapper._h, int(max_len), int(max_blocks), C.byref(self._h)))
+        self.device = mapper.device
+        self.max_len = int(max_len)
+
+    def add(self, mapper):
+        """sweep the result of the mapper's last map call"""
+        _check(lib().qm_psb_add(self._h, mapper._h))
+
+    def add_hits(self, hit_offsets, hits):
+        n, hit_offsets, hits = _host_hits(hit_offsets, hits)
+        _check(lib().qm_psb_add_hits(self._h, n, hit_offsets.ctypes.data, hits.ctypes.data if hits.size else None))
+
+    def add_counts(self, obs):
+        obs = np.ascontiguousarray(obs, dtype=np.uint64).ravel()
+        if obs.size != PSB_BINS:
+            raise ValueError("%d counts" % PSB_BINS)
+        _check(lib().qm_psb_add_counts(self._h, obs.ctypes.data))
+
+    def counts(self):
+        """the observed counts, uint64[2][5][20]"""
+        c = np.zeros(PSB_BINS, dtype=np.uint64)
+        _check(lib().qm_psb_fetch(self._h, c.ctypes.data))
+        return c.reshape(PSB_SHAPE)
+
+    def expect(self, counts, n_txps, q):
+        """qm_psb_expect: the expected counts uint64[2][5][20] of a fragment-length histogram counts uint64[max_len + 1] and weights q uint64[n_txps]"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64); q = np.ascontiguousarray(q, dtype=np.uint64)
+        if counts.size != self.max_len + 1 or q.size != int(n_txps):
+            raise ValueError("max_len + 1 counts and n_txps weights")
+        ex = np.zeros(PSB_BINS, dtype=np.uint64)
+        _check(lib().qm_psb_expect(self._h, counts.ctypes.data, int(n_txps), q.ctypes.data if q.size else None, ex.ctypes.data))
+        return ex.reshape(PSB_SHAPE)
+
+    def eff_lens(self, counts, n_txps, R):
+        """qm_psb_eff_lens: the effective lengths float64[n_txps] under the ratios R float64[2][5][20]"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64); R = np.ascontiguousarray(R, dtype=np.float64).ravel()
+        if counts.size != self.max_len + 1 or R.size != PSB_BINS:
+            raise ValueError("max_len + 1 counts and %d ratios" % PSB_BINS)
+        eff = np.zeros(int(n_txps), dtype=np.float64)
+        _check(lib().qm_psb_eff_lens(self._h, counts.ctypes.data, int(n_txps), R.ctypes.data, eff.ctypes.data if eff.size else None))
+        return eff
+
+    def position(self, tids, positions):
+        """qm_psb_position: int32[n][2], the class of transcript tids[i] and the bin of positions[i] on it; a row of -1 where there is no
+        such transcript or the position does not lie on it"""
+        tids = np.ascontiguousarray(tids, dtype=np.uint32); positions = np.ascontiguousarray(positions, dtype=np.int32)
+        if tids.size != positions.size:
+            raise ValueError("tids and positions must be of one length")
+        out = np.zeros((tids.size, 2), dtype=np.int32)
+        if tids.size:
+            _check(lib().qm_psb_position(self._h, int(tids.size), tids.ctypes.data, positions.ctypes.data, out.ctypes.data))
+        return out
+
+    def clear(self):
+        _check(lib().qm_psb_clear(self._h))
+
+
+def write_pos_bias(path, obs, exp, ratio):
+    """FILE.posBias.txt: a header line, then per entry `end<TAB>class<TAB>bin<TAB>obs<TAB>exp<TAB>ratio` -- obs and exp integers, ratio
+    %.17g (every double comes back bit for bit)"""
+    obs = np.asarray(obs).reshape(PSB_SHAPE); exp = np.asarray(exp).reshape(PSB_SHAPE); ratio = np.asarray(ratio).reshape(PSB_SHAPE)
+    with open(path, "w") as f:
+        f.write("end\tclass\tbin\tobs\texp\tratio\n")
+        for e in range(2):
+            for c in range(5):
+                for b in range(20):
+                    f.write("%d\t%d\t%d\t%d\t%d\t%.17g\n" % (e, c, b, int(obs[e, c, b]), int(exp[e, c, b]), float(ratio[e, c, b])))
+
+
+def read_pos_bias(path):
+    """the inverse of write_pos_bias: (obs uint64[2][5][20], exp uint64[2][5][20], ratio float64[2][5][20])"""
+    obs = np.zeros(PSB_SHAPE, dtype=np.uint64); ex = np.zeros(PSB_SHAPE, dtype=np.uint64); ratio = np.zeros(PSB_SHAPE, dtype=np.float64)
+    with open(path) as f:
+        if f.readline().rstrip("\n").split("\t") != ["end", "class", "bin", "obs", "exp", "ratio"]:
+            raise ValueError("%s: not a posBias file" % path)
+        for i in range(PSB_BINS):
+            w = f.readline().rstrip("\n").split("\t")
+            e, c, b = i // 100, (i // 20) % 5, i % 20
+            if len(w) != 6 or (int(w[0]), int(w[1]), int(w[2])) != (e, c, b):
+                raise ValueError("%s: line %d" % (path, i + 2))
+            obs[e, c, b] = int(w[3]); ex[e, c, b] = int(w[4]); ratio[e, c, b] = float(w[5])
+    return obs, ex, ratio
+
+
 LIB_TYPES = ("IU", "ISF", "ISR", "OU", "OSF", "OSR", "MU", "MSF", "MSR", "U", "SF", "SR", "A")
 LIB_CODES = ("ISF", "ISR", "OSF", "OSR", "MSF", "MSR", "LF", "LR", "RF", "RR", "SF", "SR")    # a hit's code: words 0 .. 11 of a tally
 LIB_TOTALS = ("units", "unmapped_units", "kept_units", "dropped_units", "hits", "kept_hits")  # words 24 .. 29; word 30: other_hits
@@ -1578,12 +1708,13 @@ class MappedStream:
     device -- hit_offsets / hits of a batch are None, n_hits and counters as ever.  frag_len_dist=True: every batch is folded into a
     fragment-length histogram on its device as well (frag_len_dist() after the last batch).  gc_bias=True: every batch is swept into
     the observed counts of the fragment GC bias model as well (gc_bias() after the last batch).  seq_bias=True: ... and into the observed
-    counts of the sequence-specific bias model (seq_bias() after the last batch).  lib_type (a name of LIB_TYPES or a
+    counts of the sequence-specific bias model (seq_bias() after the last batch).  pos_bias=True: ... and into those of the positional
+    bias model (pos_bias() after the last batch).  lib_type (a name of LIB_TYPES or a
     12-bit mask): every batch is tallied by orientation code on its device (lib_counts() after the last batch), and with
     eq_classes=True the classes hold only the hits that type keeps."""
 
     def __init__(self, index: QuasiIndex, path1, path2=None, opts=None, device=0, batch_units=1 << 20, threads=None, ph_compact=False,
-                 names=True, eq_classes=False, hits=True, frag_len_dist=False, lib_type=None, gc_bias=False, seq_bias=False):
+                 names=True, eq_classes=False, hits=True, frag_len_dist=False, lib_type=None, gc_bias=False, seq_bias=False, pos_bias=False):
         self._h = C.c_void_p()
         self.paired = path2 is not None
         self.names = bool(names)
@@ -1598,7 +1729,7 @@ class MappedStream:
         rc = lib().qm_stream_open_ex(index._h, darr, len(devs), 1 if ph_compact else 0, C.byref(opts), os.fsencode(path1),
                                      os.fsencode(path2) if path2 else None, int(batch_units),
                                      int(threads or min(32, os.cpu_count() or 1)),
-                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0) | (32 if gc_bias else 0) | (64 if seq_bias else 0) |
+                                     (0 if names else 1) | (2 if eq_classes else 0) | (0 if hits else 4) | (8 if frag_len_dist else 0) | (32 if gc_bias else 0) | (64 if seq_bias else 0) | (128 if pos_bias else 0) |
                                      (0 if lib_type is None else 16 | (lib_type_mask(lib_type) if isinstance(lib_type, str) else int(lib_type)) << 16), C.byref(self._h))
         if rc != 0:
             raise QmError("qm_stream_open failed (%d): %s" % (rc, lib().qm_stream_last_error().decode(errors="replace")))
@@ -1667,6 +1798,13 @@ class MappedStream:
         self._call("qm_stream_sqb_fetch", c.ctypes.data, st.ctypes.data)
         return c.reshape(SQB_SHAPE), dict(zip(SQB_STATS, (int(x) for x in st)))
 
+    def pos_bias(self):
+        """after the last batch of a stream opened with pos_bias=True: (obs uint64[2][5][20], stats) summed over the stream's contexts and
+        devices -- stats: a dictionary of units and the seven categories (PSB_STATS)"""
+        c = np.zeros(PSB_BINS, dtype=np.uint64); st = np.zeros(8, dtype=np.int64)
+        self._call("qm_stream_psb_fetch", c.ctypes.data, st.ctypes.data)
+        return c.reshape(PSB_SHAPE), dict(zip(PSB_STATS, (int(x) for x in st)))
+
     def lib_counts(self):
         """after the last batch of a stream opened with lib_type: the tallies uint64[32] (LibFormat.counts) summed over the stream's
         contexts and devices"""
@@ -1677,10 +1815,10 @@ class MappedStream:
     def stats(self):
         """seconds: read_s = open to the last batch packed (wall), map_s / fetch_s = upload + kernels / download summed over the
         contexts, parse_cpu_s / copy_cpu_s = the ingest workers' task time summed over the workers"""
-        a = (C.c_double * 18)()
-        _check(lib().qm_stream_stats_ex(self._h, a, 18))
+        a = (C.c_double * 19)()
+        _check(lib().qm_stream_stats_ex(self._h, a, 19))
         return dict(zip(("read_s", "map_s", "fetch_s", "caller_wait_s", "open_s", "alloc_s", "first_batch_s", "parse_cpu_s", "copy_cpu_s",
-                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts", "fld_fold_s", "gcb_sweep_s", "sqb_sweep_s"), [float(x) for x in a]))
+                         "inflate_s", "bytes_parsed", "last_mapped_s", "packed_batches", "fold_s", "fold_contexts", "fld_fold_s", "gcb_sweep_s", "sqb_sweep_s", "psb_sweep_s"), [float(x) for x in a]))
 
     def close(self):
         if self._h:

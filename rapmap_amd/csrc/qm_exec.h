@@ -1,5 +1,5 @@
-// qm_exec.h -- what the seven drivers of the estimation objects (qm_eqc_host.inl, qm_quant_host.inl, qm_boot_host.inl, qm_fld_host.inl,
-// qm_lib_host.inl, qm_gcb_host.inl, qm_sqb_host.inl) run on: a buffer type, the launch of a wave body over a number of wavefronts, two scans and a sort, the host
+// qm_exec.h -- what the eight drivers of the estimation objects (qm_eqc_host.inl, qm_quant_host.inl, qm_boot_host.inl, qm_fld_host.inl,
+// qm_lib_host.inl, qm_gcb_host.inl, qm_sqb_host.inl, qm_psb_host.inl) run on: a buffer type, the launch of a wave body over a number of wavefronts, two scans and a sort, the host
 // operations, and two things every object needs: Base -- device, stream and the two timer events, opened and closed in one place --
 // and feed -- host arrays in CSR form cut into parts, uploaded and handed to the caller's function part by part.  Like qm_wave.h it
 // has two definitions.  In the library (included by qm_host.hip, after DevBuf, PinBuf, fail and HIPCHK) a launch is a kernel on a

@@ -28,10 +28,15 @@
 //   sqb_obs_wave (sweep)        sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
 //   sqb_expect_wave (sweep)     sweep_grid: tiles of 64       4 (fixed)  no    1, then at most the caller's max_blocks
 //   sqb_efflen_wave (sweep)     sweep_grid: tiles of 64       4 (fixed)  no    1, then at most the caller's max_blocks
+//   psb_obs_wave (sweep)        sweep_grid: units / 64        8 (fixed)  no    1, then at most the caller's max_blocks
+//   psb_expect_wave (sweep)     sweep_grid: 20 n_txps / 64    8 (fixed)  no    1, then at most the caller's max_blocks
+//   psb_efflen_wave (sweep)     sweep_grid: tiles of 64       4 (fixed)  no    1, then at most the caller's max_blocks
 //
 // The fixed figures of the sweeps with an LDS slab come from the compute unit's 160 KiB: sqb_obs_wave keeps 1 152 32-bit words per
 // wavefront (18 KiB per workgroup: 8 workgroups are 144 KiB, and the CU's 32 wavefronts), sqb_expect_wave 1 152 64-bit accumulators
-// and sqb_efflen_wave a ring of 1 152 doubles (36 KiB per workgroup: 4 workgroups are 144 KiB, 16 wavefronts).
+// and sqb_efflen_wave a ring of 1 152 doubles (36 KiB per workgroup: 4 workgroups are 144 KiB, 16 wavefronts).  psb_obs_wave keeps
+// 200 32-bit words per wavefront (3 200 bytes per workgroup) and psb_expect_wave 200 64-bit accumulators (6 400 bytes per workgroup):
+// 8 workgroups are 25 and 50 KiB, and the CU's 32 wavefronts; psb_efflen_wave is sqb_efflen_wave's walk and keeps its ring.
 //
 // map_grid is the host's plan for the general kernels (the "caller's grid" above, and what their scratch and the bump allocators' slack
 // are sized by); resident_grid the one it falls back to when that scratch does not fit, and the size of the list kernels' -s scratch.
@@ -75,8 +80,8 @@ inline long long pair_iters(long long nreads) { return nreads >> 1; }
 inline int map_grid(long long nreads, int num_cu, bool ph_compact) { return grid_blocks(nreads, num_cu, GRID_NOMINAL_PER_CU, ph_compact ? grid_oversub_ph() : grid_oversub()); }
 inline int resident_grid(long long nreads, int num_cu) { return grid_blocks(nreads, num_cu, GRID_NOMINAL_PER_CU, 1); }
 
-// the sweeps of the estimation objects (qm_fld.inl, qm_lib.inl, qm_gcb.inl, qm_sqb.inl), one lane per unit, hit, window start or text position: the workgroups that are resident at
-// once (FLD_ / LIB_ / GCB_ / SQB_BLOCKS_PER_CU, no query), fewer when the lanes do not fill them, at most max_blocks when that is not 0
+// the sweeps of the estimation objects (qm_fld.inl, qm_lib.inl, qm_gcb.inl, qm_sqb.inl, qm_psb.inl), one lane per unit, hit, window start or text position: the workgroups that are resident at
+// once (FLD_ / LIB_ / GCB_ / SQB_ / PSB_*_BLOCKS_PER_CU, no query), fewer when the lanes do not fill them, at most max_blocks when that is not 0
 inline int sweep_grid(long long lanes, int num_cu, int resident_per_cu, int max_blocks) {
   const int g = grid_blocks((lanes + 63) / 64, num_cu > 0 ? num_cu : 1, resident_per_cu, 1);
   return max_blocks > 0 && g > max_blocks ? max_blocks : g;

@@ -2082,3 +2082,4 @@ int qm_last_kernel_ms(const qm_ctx* c, double* map_ms, double* total_ms) {
 #include "qm_lib_host.inl"
 #include "qm_gcb_host.inl"
 #include "qm_sqb_host.inl"
+#include "qm_psb_host.inl"

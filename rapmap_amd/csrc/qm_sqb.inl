@@ -11,7 +11,8 @@
 //   sqb_probe_wave     qm_sqb_context: one lane per question
 //   sqb_obs_wave       the observed sweep, on the frame of qm_sweep.h
 //   sqb_expect_wave    the expected counts: one lane per text position over the tile table of qm_gcb.inl (gcb_tiles_wave)
-//   sqb_efflen_wave    the hot path: a tile's 64 starts walk the fragment length upward over b3 values kept in LDS
+//   sqb_walk_wave      the hot path: a tile's 64 starts walk the fragment length upward over b3 values kept in LDS; a template over
+//                      the source of the end biases (sqb_efflen_wave: the sequence model's; psb_efflen_wave, qm_psb.inl: the positional)
 //   sqb_tilesum_wave   a transcript's tiles added in order, and the quotient
 #pragma once
 #include <stddef.h>
@@ -269,8 +270,15 @@ QM_DEV double sqb_bias(const double* R, const unsigned char* text, long long o, 
   return b;
 }
 
+// The walk is written once, over the source of the end biases: Bias(E.R, E.I.text, o, L, x, end) is b5 (end 0) of start x or b3
+// (end 1) of last position x on the transcript of L characters at text + o (o, L wave-uniform, 0 <= x < L).  It is asked in exactly
+// two places: the ring's fill and a tile's 64 starts.  The sequence model's source is sqb_bias, which reads the text; the positional
+// model's is a table lookup by position (psb_bias, qm_psb.inl) and leaves the text alone; a joint model is one more function of this
+// signature.  (The source is the function itself, called where sqb_bias was called: behind a functor, and behind a type with a
+// static member, the sequence instantiation took 47 VGPRs where it had taken 37 -- profiles/psb/results/resources.txt.)
 // wavefront `wave` of `nWaves` (both wave-uniform); slab: SQB_RING_WORDS words of its own
-QM_DEV void sqb_efflen_wave(const SqbEff& E, long long wave, long long nWaves, QM_LDS(u32)* slab) {
+template <auto Bias>
+QM_DEV void sqb_walk_wave(const SqbEff& E, long long wave, long long nWaves, QM_LDS(u32)* slab) {
   long long k0, k1, t;
   if (!sqb_tile_run(E.tileOff, E.I.nTxp, E.nTiles, wave, nWaves, k0, k1, t)) return;
   QM_LDS(double)* ring = (QM_LDS(double)*)slab;
@@ -290,7 +298,7 @@ QM_DEV void sqb_efflen_wave(const SqbEff& E, long long wave, long long nWaves, Q
       QM_LANES(l) {
         const long long p = p0 + l;
         if (p < need) {
-          const double b = sqb_bias(E.R, E.I.text, o, L, p, 1);
+          const double b = Bias(E.R, E.I.text, o, L, p, 1);
           const int ph = (int)(p % SQB_RING);
           ring[ph] = b;
           if (ph < 64) ring[SQB_RING + ph] = b;
@@ -320,10 +328,15 @@ QM_DEV void sqb_efflen_wave(const SqbEff& E, long long wave, long long nWaves, Q
       QM_LANES(l) { const double s = sqb_mul_add(c, ring[sqb_ring_at(u0, len) + l], a[l]); if (len <= lim[l]) a[l] = s; }
     }
     LV<double> v;
-    QM_LANES(l) { const long long x = base + l; v[l] = x < L ? sqb_bias(E.R, E.I.text, o, L, x, 0) * a[l] : 0.0; }
+    QM_LANES(l) { const long long x = base + l; v[l] = x < L ? Bias(E.R, E.I.text, o, L, x, 0) * a[l] : 0.0; }
     const double sum = wave_sum_f64(v);
     QM_LANES(l) if (l == 0) E.partial[k] = sum;
   }
+}
+
+// the sequence model's instantiation of the walk
+QM_DEV void sqb_efflen_wave(const SqbEff& E, long long wave, long long nWaves, QM_LDS(u32)* slab) {
+  sqb_walk_wave<sqb_bias>(E, wave, nWaves, slab);
 }
 
 // eff[t] = (partial[tileOff[t]] + ... in ascending order) / (double)P[min(L_t, max_len)], or (double)L_t where that P is 0: a lane per transcript

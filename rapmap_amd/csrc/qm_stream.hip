@@ -98,7 +98,7 @@ struct OutSlot {                 // the result side of ingest slot i
 
 // The per-context tallies of a stream: what a map context folds each batch into where it lies in device memory, one object per
 // context and kind.  The table is in the order the kinds run on a batch; a new kind is a row here, a flag and its fetch function.
-enum { K_EQC = 0, K_LIB = 1, K_FLD = 2, K_GCB = 3, K_SQB = 4, K_N = 5 };
+enum { K_EQC = 0, K_LIB = 1, K_FLD = 2, K_GCB = 3, K_SQB = 4, K_PSB = 5, K_N = 6 };
 struct TallyKind {
   uint32_t flag; const char* flagName;                     // the stream flag that turns it on
   int (*create)(qm_ctx* c, uint32_t stream_flags, void** out);
@@ -107,7 +107,7 @@ struct TallyKind {
   int (*fetch)(void* o, uint64_t* part);                   // the object's words (null: the kind has a fetch of its own) ...
   int (*counter)(void* o, int which, int64_t* value);      // ... and its counters, which = 0 .. (null: none)
 };
-static_assert(QM_FLD_STAT_UNITS == 0 && QM_GCB_STAT_UNITS == 0 && QM_SQB_STAT_UNITS == 0, "the counters a stream sums start at 0");
+static_assert(QM_FLD_STAT_UNITS == 0 && QM_GCB_STAT_UNITS == 0 && QM_SQB_STAT_UNITS == 0 && QM_PSB_STAT_UNITS == 0, "the counters a stream sums start at 0");
 const TallyKind KINDS[K_N] = {
   {QM_STREAM_EQ_CLASSES, "QM_STREAM_EQ_CLASSES", [](qm_ctx* c, uint32_t, void** o) { return qm_eqc_create(c, 1 << 16, 0, (qm_eqc**)o); },
    [](void* o) { qm_eqc_destroy((qm_eqc*)o); }, [](void* o, qm_ctx* c) { return qm_eqc_add((qm_eqc*)o, c); }, nullptr, nullptr},
@@ -124,6 +124,9 @@ const TallyKind KINDS[K_N] = {
   {QM_STREAM_SQB, "QM_STREAM_SQB", [](qm_ctx* c, uint32_t, void** o) { return qm_sqb_create(c, QM_FLD_DEFAULT_MAX_LEN, 0, (qm_sqb**)o); },
    [](void* o) { qm_sqb_destroy((qm_sqb*)o); }, [](void* o, qm_ctx* c) { return qm_sqb_add((qm_sqb*)o, c); },
    [](void* o, uint64_t* part) { return qm_sqb_fetch((qm_sqb*)o, part); }, [](void* o, int w, int64_t* v) { return qm_sqb_stat((qm_sqb*)o, w, v); }},
+  {QM_STREAM_PSB, "QM_STREAM_PSB", [](qm_ctx* c, uint32_t, void** o) { return qm_psb_create(c, QM_FLD_DEFAULT_MAX_LEN, 0, (qm_psb**)o); },
+   [](void* o) { qm_psb_destroy((qm_psb*)o); }, [](void* o, qm_ctx* c) { return qm_psb_add((qm_psb*)o, c); },
+   [](void* o, uint64_t* part) { return qm_psb_fetch((qm_psb*)o, part); }, [](void* o, int w, int64_t* v) { return qm_psb_stat((qm_psb*)o, w, v); }},
 };
 
 }  // namespace
@@ -424,6 +427,12 @@ int qm_stream_sqb_fetch(qm_stream* s, uint64_t* obs, int64_t* stats9) {
   return fetch_sum(s, K_SQB, "qm_stream_sqb_fetch", obs, QM_SQB_BINS, stats9, 9);
 }
 
+/* The contexts' observed positional-bias counts and counters summed on the host: 1 600 bytes and eight numbers per context. */
+int qm_stream_psb_fetch(qm_stream* s, uint64_t* obs, int64_t* stats8) {
+  if (!s || !obs || !stats8) return sfail(QM_E_ARG, "qm_stream_psb_fetch: bad argument");
+  return fetch_sum(s, K_PSB, "qm_stream_psb_fetch", obs, QM_PSB_BINS, stats8, 8);
+}
+
 /* The contexts' library-type tallies summed on the host: 256 bytes per context. */
 int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]) {
   if (!s || !counts) return sfail(QM_E_ARG, "qm_stream_lib_fetch: bad argument");
@@ -436,18 +445,19 @@ int qm_stream_lib_fetch(qm_stream* s, uint64_t counts[32]) {
  * (summed), [9] inflate threads, [10] bytes parsed, [11] open to the last batch mapped and downloaded (wall), [12] batches that
  * went to the device 2-bit packed, [13] qm_eqc_add of the batches (QM_STREAM_EQ_CLASSES; not part of [1] or [2]), [14] contexts that
  * folded at least one batch, [15] qm_fld_add of the batches (QM_STREAM_FLD; not part of [1], [2] or [13]), [16] qm_gcb_add of the
- * batches (QM_STREAM_GCB; not part of [1], [2], [13] or [15]), [17] qm_sqb_add of the batches (QM_STREAM_SQB; not part of the others) */
+ * batches (QM_STREAM_GCB; not part of [1], [2], [13] or [15]), [17] qm_sqb_add of the batches (QM_STREAM_SQB; not part of the others),
+ * [18] qm_psb_add of the batches (QM_STREAM_PSB; not part of the others) */
 int qm_stream_stats_ex(qm_stream* s, double* out, int32_t n) {
   if (!s || !out || n < 0) return sfail(QM_E_ARG, "qm_stream_stats: bad argument");
-  double v[18] = {0}; double ing[8] = {0};
+  double v[19] = {0}; double ing[8] = {0};
   qm_ingest_stats(s->g, ing);
   std::unique_lock<std::mutex> lk(s->mu);
   v[0] = ing[6]; v[1] = s->tMap; v[2] = s->tFetch; v[3] = s->tWait; v[4] = s->tOpen; v[5] = s->tAlloc;
   v[6] = ing[0]; v[7] = ing[1]; v[8] = ing[2]; v[9] = ing[3]; v[10] = ing[4]; v[11] = s->tLastMapped;
   v[12] = (double)__atomic_load_n(&s->nPacked, __ATOMIC_RELAXED);
   v[13] = s->seconds[K_EQC] + s->seconds[K_LIB]; for (int64_t f : s->eqcFolds) v[14] += f > 0 ? 1 : 0;
-  v[15] = s->seconds[K_FLD]; v[16] = s->seconds[K_GCB]; v[17] = s->seconds[K_SQB];
-  for (int i = 0; i < n && i < 18; ++i) out[i] = v[i];
+  v[15] = s->seconds[K_FLD]; v[16] = s->seconds[K_GCB]; v[17] = s->seconds[K_SQB]; v[18] = s->seconds[K_PSB];
+  for (int i = 0; i < n && i < 19; ++i) out[i] = v[i];
   return QM_OK;
 }
 int qm_stream_stats(qm_stream* s, double* out6) { return qm_stream_stats_ex(s, out6, 6); }

@@ -61,6 +61,18 @@ def all_reduce_seq_counts(obs, device):
     return t.cpu().numpy().view(np.uint64)
 
 
+def all_reduce_pos_counts(obs, device):
+    """the observed counts of the positional bias model (PosBias.counts, MappedStream.pos_bias) -> their sum over all ranks, in the
+    input's shape: one int64 all_reduce over the 200 entries (1 600 bytes on the wire).  Without a process group the input comes back
+    unchanged.  The sum goes into an object through PosBias.add_counts."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return obs
+    c = np.ascontiguousarray(obs, dtype=np.uint64)
+    t = torch.from_numpy(c.view(np.int64).copy()).to(device)    # (counts stay far below 2^63: the bits are the same either way)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().numpy().view(np.uint64)
+
+
 def all_reduce_lib_counts(counts, device):
     """the tallies of a library type (LibFormat.counts, MappedStream.lib_counts) -> their sum over all ranks: one int64 all_reduce over
     the 32 words (256 bytes on the wire).  Without a process group the input comes back unchanged.  The sum goes into an object through
