@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <cstdio>
 #include <cstdlib>
 #include "qm_grid.h"
 
@@ -29,6 +30,22 @@ inline int resident_per_cu() {
     return v;
   }();
   return nb;
+}
+// The same for the two headline kernels, in the unit their grids are counted in -- four waves (qm_grid.h) -- whatever QM_WG_WAVES their
+// workgroups have: the query counts workgroups, QM_BLOCKS_PER_CU lowers the units.  QM_GRID_TRACE=1: what the query said, on stderr.
+template <auto K, int FALLBACK>
+inline int resident_quads_per_cu(const char* name) {
+  static const int nq = [name] {
+    int v = 0;
+    const bool asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, K, 64 * QM_WG_WAVES, 0) == hipSuccess && v >= 1;
+    if (getenv("QM_GRID_TRACE")) fprintf(stderr, "[qm grid] %s: %d workgroups of %d wave(s) resident per CU%s\n", name, asked ? v : 0, QM_WG_WAVES, asked ? "" : " (the query failed)");
+    v = asked ? v * QM_WG_WAVES / 4 : FALLBACK;
+    if (v < 1) v = 1;
+    const char* ov = getenv("QM_BLOCKS_PER_CU");
+    if (ov && atoi(ov) > 0 && atoi(ov) < v) v = atoi(ov);
+    return v;
+  }();
+  return nq;
 }
 }  // namespace qm
 

@@ -26,6 +26,7 @@
 // left when an interval is wider than 32 suffixes or its intervals hold more than 32 together (a half has 32 lanes).
 #pragma once
 #include "qm_lean.inl"
+#include "qm_grid.h"
 
 namespace qm {
 
@@ -34,7 +35,7 @@ namespace qm {
 #endif
 #define QM_DUO_MAXIV 32          // intervals per read (a bit each)
 
-struct DuoMem {                                // one wave's LDS slab (4 656 bytes)
+struct DuoMem {                                // one wave's LDS slab (4 880 bytes)
   u64 pk[2][2][8];                             // as LeanMem::pk: [mate][0: the read, 1: mirrored reverse complement][word]; words 4-7 stay zero
   union {
     LeanSuf suf[2][QM_DUO_SUF];                // [mate]: suffixes of the intervals recorded for it
@@ -44,9 +45,11 @@ struct DuoMem {                                // one wave's LDS slab (4 656 byt
   U4 pf[3][34];                                // the next pair's first probe: the 48 bytes of the buckets of its mates' first and last k-mers (lanes 0, 1, 32, 33),
                                                // fetched straight into here (global_load_lds_dwordx4) while the pair before it is finished
   u32 stage[100];                              // raw characters of the next pair: dwords [0, 32) mate 0, [32, 64) mate 1, [64] / [96] the 33rd dword of mate 0 / 1
-  u32 ostage[2][8];                            // offsets of the next / the next but one pair: off1[u], off1[u + 1], off2[u], off2[u + 1]
+  u32 orun[2][2 * QM_ORUN_H];                  // offsets of the pairs of this run / of the wave's next run (then of the one after it): off1[u0 .. u0 + R] as dwords
+                                               // [0, 2 R + 2), off2[u0 .. u0 + R] from dword QM_ORUN_H on (duo_stage_offsets)
 };
 typedef PairCtr DuoCtr;
+static_assert(32 * sizeof(DuoMem) <= 160 * 1024 && 32 * sizeof(LeanMem) <= 160 * 1024, "a compute unit's 32 waves, each with its slab, fit its LDS");
 
 // khash.find for one POSITION per lane: w the k-mer as the read has it, wr its reverse complement.  One bucket of the canonical
 // table holds both; fh / (flb, fub): the k-mer is in the index / its interval, ch / (clb, cub): the same for the reverse complement.
@@ -207,19 +210,23 @@ QM_DEV void duo_probe(const DevIndex& ix, const QM_LDS(u64)* pkw, int k, const L
   }
 }
 
-// offsets of pair `it` into ostage[par] (lean_stage_offsets<true>)
-QM_DEV void duo_stage_offsets(const ReadBatch& B, int it, int nit, DuoMem& M, int par) {
-  if (it >= nit) return;
+// offsets of the run that starts at pair u0 (a multiple of the run length 1 << rs; lean_stage_offsets) into orun[par], one request for
+// both arrays: the run's n pairs (the batch's last run may be short) need off[u0 .. u0 + n], which the arrays hold (nit + 1 entries)
+QM_DEV void duo_stage_offsets(const ReadBatch& B, int u0, int nit, int rs, DuoMem& M, int par) {
+  if (u0 >= nit) return;
+  const int left = nit - u0, n = left < (1 << rs) ? left : (1 << rs);
   QM_LANES(l) {
-    if (l < 8) { const long long* o = (l < 4 ? B.off1 : B.off2) + it; lds_dma_u32((const u32*)o + (l & 3), M.ostage[par], l); }
+    const int h = l >= QM_ORUN_H ? 1 : 0, d = l - QM_ORUN_H * h;
+    if (l < 2 * QM_ORUN_H && d < 2 * n + 2) lds_dma_u32((const u32*)((h ? B.off2 : B.off1) + u0) + d, M.orun[par], l);
   }
 }
-// the offsets in ostage[par] (landed) into the request for the two mates' characters: every lane works out its own mate's address
-QM_DEV void duo_stage_chars(const ReadBatch& B, int it, int nit, DuoMem& M, int par) {
+// the offsets of pair `it`'s run in orun[par] (landed) into the request for the two mates' characters: every lane works out its own mate's address
+QM_DEV void duo_stage_chars(const ReadBatch& B, int it, int nit, int rs, DuoMem& M, int par) {
   if (it >= nit) return;
+  const int j2 = 2 * (it & ((1 << rs) - 1));
   QM_LANES(l) {
     const int h = l >> 5, j = l & 31;
-    const QM_LDS(u32)* os = (const QM_LDS(u32)*)&M.ostage[par][4 * h];
+    const QM_LDS(u32)* os = (const QM_LDS(u32)*)&M.orun[par][QM_ORUN_H * h + j2];
     const u32 olo = os[0], ohi = os[1], o1 = os[2];
     int len = (int)(o1 - olo);
     if (len > QM_LEAN_MAXLEN) len = QM_LEAN_MAXLEN;
@@ -233,7 +240,7 @@ QM_DEV void duo_stage_chars(const ReadBatch& B, int it, int nit, DuoMem& M, int 
 }
 
 // What duo_prepare leaves in registers for the iteration that maps the pair
-struct DuoNext { LV<int> Lv, defv; LV<u64> ck; LV<u32> flg; };    // flg: bit 0 the lane asked (first / last k-mer of its mate), bit 1 its k-mer is the larger of the two orientations
+struct DuoNext { LV<int> Lv, defv; LV<u64> ck; LV<u32> flg; int nx, last; };   // nx / last: the pair the wave maps behind this one, and whether this one ends its run (worked out once per pair)    // flg: bit 0 the lane asked (first / last k-mer of its mate), bit 1 its k-mer is the larger of the two orientations
 
 // Pair `it`, first half: the two mates' characters (staged by the iteration before) -> 2-bit images of both strands, four characters
 // per lane (lean_iter); the staging of the pairs behind it; and the FIRST PROBE's requests -- lane 0 of a half = its mate's position 0,
@@ -241,9 +248,10 @@ struct DuoNext { LV<int> Lv, defv; LV<u64> ck; LV<u32> flg; };    // flg: bit 0 
 // reverse-complement pass asks for), both orientations each: one canonical bucket per lane, its 48 bytes sent straight to LDS.
 // Runs BEFORE the pair ahead of it is finished (hits -> mappings, merge, write-out), so that trip is over when duo_iter starts.
 template <bool PH>
-QM_DEV void duo_prepare(const DevIndex& ix, const ReadBatch& B, int it, int nit, int nw, int par, DuoMem& M, DuoNext& N) {
+QM_DEV void duo_prepare(const DevIndex& ix, const ReadBatch& B, int it, int nit, const WaveRuns& S, int par, DuoMem& M, DuoNext& N) {
   if (it >= nit) return;
   const int k = ix.k;
+  const int j2 = 2 * (it & ((1 << S.rs) - 1));
   const QM_LDS(u64)* pkw = (const QM_LDS(u64)*)&M.pk[0][0][0];
   LV<int> rawv;
   LV<bool> bad, rep;
@@ -251,7 +259,7 @@ QM_DEV void duo_prepare(const DevIndex& ix, const ReadBatch& B, int it, int nit,
     QM_LDS(unsigned char)* PKb = (QM_LDS(unsigned char)*)&M.pk[0][0][0];
     QM_LANES(l) {
       const int h = l >> 5, jj = l & 31, base = 4 * jj;
-      const QM_LDS(u32)* os = (const QM_LDS(u32)*)&M.ostage[par][4 * h];
+      const QM_LDS(u32)* os = (const QM_LDS(u32)*)&M.orun[par][QM_ORUN_H * h + j2];
       const u32 a0 = os[0], a1 = os[2];
       const int raw = (int)(a1 - a0), len = raw > QM_LEAN_MAXLEN ? QM_LEAN_MAXLEN : raw;
       const int mis = (int)(((u32)(unsigned long long)(h ? B.seq2 : B.seq1) + a0) & 3u);
@@ -279,9 +287,12 @@ QM_DEV void duo_prepare(const DevIndex& ix, const ReadBatch& B, int it, int nit,
   LV<u32> dirty, reps;
   half_ballot(bad, dirty); half_ballot(rep, reps);
   wave_fence();
-  // the staging rows are free again: the next pair's characters, and the offsets of the one after it
-  duo_stage_chars(B, it + nw, nit, M, par ^ 1);
-  duo_stage_offsets(B, it + 2 * nw, nit, M, par);
+  // the staging rows are free again: the next pair's characters -- of this run, or the first pair of the wave's next run, whose offsets
+  // the other buffer holds -- and, behind a run's last pair, the offsets of the run after the next one where this run's were
+  const int last = run_ends(it, nit, S.rs), nx = last ? run_ahead(it, nit, S.nw, S.rs, 1) : it + 1;
+  N.nx = nx; N.last = last;
+  duo_stage_chars(B, nx, nit, S.rs, M, par ^ last);
+  if (last) duo_stage_offsets(B, run_ahead(it, nit, S.nw, S.rs, 2), nit, S.rs, M, par);
   // what this kernel takes: no character but A C G T, no window of k equal bases, at most 128 characters (lean_iter)
   // 1: a character that is not A C G T or too many characters, 2: a window of k equal bases
   QM_LANES(l) { N.defv[l] = (rawv[l] > QM_LEAN_MAXLEN || dirty[l] != 0) ? 1 : (4 * popc32(reps[l]) + 6 >= k ? 2 : 0); }
@@ -306,7 +317,7 @@ QM_DEV void duo_prepare(const DevIndex& ix, const ReadBatch& B, int it, int nit,
 // Pair `it` (reads 2 it and 2 it + 1), second half: the first probe's answers, the two walks in lockstep, hits -> mappings, the merge.
 // Between the walks and the rest it runs duo_prepare for the pair the wave maps next.
 template <bool PH, bool COV>
-QM_DEV void duo_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, int nw, int par, DuoMem& M, WaveAlloc& wa, DuoCtr& ctr, DuoNext& N) {
+QM_DEV void duo_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, const WaveRuns& S, int par, int nx, int last, DuoMem& M, WaveAlloc& wa, DuoCtr& ctr, DuoNext& N) {
   const int k = ix.k;
   const QM_LDS(u64)* pkw = (const QM_LDS(u64)*)&M.pk[0][0][0];
   LV<int> Lv, Pv, defv;
@@ -521,7 +532,7 @@ QM_DEV void duo_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, in
   }
   // ---- the pair this wave maps next: its images and its first probe's requests, under way while this pair is finished (the images
   // of this pair are not needed any more: what follows works on the suffix stashes)
-  duo_prepare<PH>(ix, B, it + nw, nit, nw, par ^ 1, M, N);
+  duo_prepare<PH>(ix, B, nx, nit, S, par ^ last, M, N);
   // ---- hitsToMappingsSimple (HitManager.cpp:691-882) for both mates at once, lane j of a half = suffix j of its stash (lean_h2m): a
   // transcript survives when it was seen in every interval, represented by the entry with the smallest position (the earlier interval
   // in processing order on ties); survivors go out in ascending transcript order
@@ -621,26 +632,34 @@ QM_DEV void duo_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, in
   }
 }
 
-// The wave body of qm_duo_kernel: wave gw of nw maps pairs gw, gw + nw, ... (lean_wave's pipeline, plus duo_prepare one pair ahead) and
-// adds the HitCounters of the pairs it merged to B.cursor[1 .. 6] (stage B's count pass adds the others').
+// The wave body of qm_duo_kernel: wave gw of nw maps the runs gw, gw + nw, ... of 1 << rs neighbouring pairs (qm_grid.h; rs = 0: pairs
+// gw, gw + nw, ...), each run's pairs in order (lean_wave's pipeline, plus duo_prepare one pair ahead -- behind a run's last pair that is
+// the first pair of the wave's next run), and adds the HitCounters of the pairs it merged to B.cursor[1 .. 6] (stage B's count pass adds
+// the others').  A run's offsets are fetched once, two runs ahead; what a pair's requests need of them is read from LDS.
 template <bool PH, bool COV>
-QM_DEV void duo_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, DuoMem& M) {
+QM_DEV void duo_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, DuoMem& M, int rs = 0) {
   const int nit = (int)(B.nreads >> 1);                     // pairs (reads per launch < 2^31)
+  const WaveRuns S = {nw, rs};
+  const long long t0 = run_trip(0, gw, nw, rs);
+  const int it0 = t0 < nit ? (int)t0 : nit;
   QM_LANES(l) { if (l < 16) M.pk[l >> 3][(l >> 2) & 1][4 + (l & 3)] = 0; }   // the words behind the images stay zero
   WaveAlloc wa;
   DuoCtr ctr = {0, 0, 0, 0, 0, 0};
-  duo_stage_offsets(B, gw, nit, M, 0);
+  duo_stage_offsets(B, it0, nit, rs, M, 0);
   lds_dma_wait();
-  duo_stage_chars(B, gw, nit, M, 0);
-  duo_stage_offsets(B, gw + nw, nit, M, 1);
+  duo_stage_chars(B, it0, nit, rs, M, 0);
+  duo_stage_offsets(B, run_ahead(it0, nit, nw, rs, 1), nit, rs, M, 1);
   lds_dma_wait();
   int par = 0;
   DuoNext N;
   QM_LANES(l) { N.Lv[l] = 0; N.defv[l] = 0; N.ck[l] = 0; N.flg[l] = 0; }
-  duo_prepare<PH>(ix, B, gw, nit, nw, 0, M, N);             // (every later pair is prepared by the iteration before it)
-  for (int it = gw; it < nit; it += nw) {
-    duo_iter<PH, COV>(ix, B, it, nit, nw, par, M, wa, ctr, N);
-    par ^= 1;
+  N.nx = nit; N.last = 0;
+  duo_prepare<PH>(ix, B, it0, nit, S, 0, M, N);             // (every later pair is prepared by the iteration before it)
+  for (int it = it0; it < nit;) {
+    const int nx = N.nx, last = N.last;                     // of pair `it`, as its duo_prepare left them; duo_iter's duo_prepare writes the next pair's
+    duo_iter<PH, COV>(ix, B, it, nit, S, par, nx, last, M, wa, ctr, N);
+    par ^= last;                                            // the offsets' two buffers alternate by run
+    it = nx;
   }
   QM_LANES(l) {
     const u32 v = l == 0 ? ctr.pe : (l == 1 ? ctr.se : (l == 2 ? ctr.tot : (l == 3 ? ctr.reads : (l == 4 ? ctr.tooMany : ctr.mapped))));

@@ -1,6 +1,7 @@
 // qm_grid.h -- the grid of a persistent kernel: plain arithmetic, no HIP (tests/test_launch_grid.py compiles it with g++).
 //
-// Every stage-A kernel is a persistent grid of four-wave workgroups whose waves stride over the work.  Launched with exactly the
+// Every stage-A kernel is a persistent grid whose waves stride over the work, in four-wave workgroups (the two headline kernels: in
+// workgroups of one wave, see "the two headline kernels" below; their grids are counted in four-wave units all the same).  Launched with exactly the
 // blocks that are resident at once, the work is divided statically and the launch lasts as long as its slowest wave (13 % longer
 // than the average one on config 2); launched with `oversub` times that many, the hardware hands the blocks out as slots free up:
 // 41.6 -> 36.1 ms at 4 (profiles/r04/grid_oversub.txt; 8: the same).  So
@@ -15,6 +16,9 @@
 //   qm_read_kernel<NS, WPS, F>  the caller's grid (blocks)    WPS        yes   F & QM_F_PH ? P : G
 //   qm_lean_kernel              lean_iters(nreads, WIDE)      8          yes   NQ ? 1 : PH ? P : SEL ? G : 2 G
 //   qm_duo_kernel               pair_iters(nreads)            8          yes   QM_DUO_OVERSUB if set, else PH ? P : 2 G
+//     (both: wave_grid -- 4 / QM_WG_WAVES workgroups of QM_WG_WAVES waves (default 1) per unit; resident: resident_quads_per_cu, the
+//      occupancy query in workgroups x QM_WG_WAVES / 4 -- 32 one-wave workgroups per CU on gfx950 for both; runs of QM_WAVE_RUN trips
+//      (default 8; 1, 2, 4, 8) per wave, fewer while the batch has not num_cu x 4 x resident runs of them)
 //   qm_h2m_kernel<0 / SEL>      the caller's grid (blocks)    2          no    1
 //   qm_h2m_pack_kernel          the caller's grid (blocks)    2          no    G
 //   qm_h2m_packw_kernel         the caller's grid (blocks)    1          no    G
@@ -79,6 +83,59 @@ inline long long pair_iters(long long nreads) { return nreads >> 1; }
 // oversubscription (kernels that own per-wave scratch in device memory: the list kernels)
 inline int map_grid(long long nreads, int num_cu, bool ph_compact) { return grid_blocks(nreads, num_cu, GRID_NOMINAL_PER_CU, ph_compact ? grid_oversub_ph() : grid_oversub()); }
 inline int resident_grid(long long nreads, int num_cu) { return grid_blocks(nreads, num_cu, GRID_NOMINAL_PER_CU, 1); }
+
+// ---- the two headline kernels (qm_lean_kernel, qm_duo_kernel): workgroups of QM_WG_WAVES waves, runs of neighbouring trips per wave.
+//
+// The grid is still counted in units of four waves (grid_blocks, and QM_BLOCKS_PER_CU / the oversubscription knobs with it): a launch
+// has 4 x grid_blocks(..) WAVES, in workgroups of QM_WG_WAVES (1, 2 or 4; a compile-time choice, because a block's LDS slabs are).
+// Wave gw of nw takes RUNS gw, gw + nw, .. of R = 1 << rs consecutive trips (pairs, iterations) and maps each run's trips in order:
+// neighbouring pairs' offsets and characters share sectors, and the wave that fetched a sector is the one that asks for it again.
+// Static and deterministic; R = 1 is the strided order gw, gw + nw, ..  R comes from QM_WAVE_RUN (wave_run) and shrinks until the batch
+// has at least as many runs as waves can be resident (run_shift), so that a small batch still fills the device.
+#ifndef QM_WG_WAVES
+#define QM_WG_WAVES 1
+#endif
+#if defined(__HIPCC__) && !defined(QM_EMU)
+#define QM_GRID_FN __host__ __device__ inline
+#else
+#define QM_GRID_FN inline
+#endif
+constexpr int WAVE_RUN_MAX = 8;            // the longest run: the kernels stage a run's offsets in LDS (DuoMem / LeanMem::orun)
+constexpr int WAVE_RUN_DEFAULT = 8;
+
+// R as asked for: QM_WAVE_RUN = 1, 2, 4 or 8 (anything else: the default)
+inline int wave_run() {
+  static const int r = [] { const char* e = getenv("QM_WAVE_RUN"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 || v == 4 || v == 8 ? v : WAVE_RUN_DEFAULT; }();
+  return r;
+}
+// blocks of wg_waves waves for a grid of `quads` four-wave units
+inline int wave_blocks(int quads, int wg_waves) { return quads * (4 / wg_waves); }
+// runs of 1 << rs trips that `trips` trips make (the last one may be short)
+QM_GRID_FN long long run_count(long long trips, int rs) { return (trips + (1LL << rs) - 1) >> rs; }
+// log2 of the run length of a batch: the largest power of two up to `want` that leaves at least resident_waves runs; 0 when none does
+inline int run_shift(long long trips, long long resident_waves, int want) {
+  int rs = 0;
+  while ((2 << rs) <= want && (2 << rs) <= WAVE_RUN_MAX && run_count(trips, rs + 1) >= resident_waves) ++rs;
+  return rs;
+}
+// a headline kernel's launch over `trips` trips: workgroups of QM_WG_WAVES waves (4 x grid_blocks(..) waves in all) and log2 of the run
+// length; quads_per_cu: resident four-wave units per CU (resident_quads_per_cu, qm_device.h)
+struct WaveGrid { int blocks, rs; };
+inline WaveGrid wave_grid(long long trips, int num_cu, int quads_per_cu, int oversub) {
+  const WaveGrid g = {wave_blocks(grid_blocks(trips, num_cu, quads_per_cu, oversub), QM_WG_WAVES), run_shift(trips, 4LL * num_cu * quads_per_cu, wave_run())};
+  return g;
+}
+// the t-th trip of wave gw of nw; at or beyond the number of trips of the batch: the wave is through (a wave's trips ascend)
+QM_GRID_FN long long run_trip(long long t, int gw, int nw, int rs) { return ((((t >> rs) * nw) + gw) << rs) + (t & ((1LL << rs) - 1)); }
+// trip `it` (< trips) is the last one of its run
+QM_GRID_FN int run_ends(int it, int trips, int rs) { return (it + 1 >= trips || ((it + 1) & ((1 << rs) - 1)) == 0) ? 1 : 0; }
+// the first trip of the run `ahead` runs of the same wave behind the run of trip `it`; `trips` when the batch has no such run
+QM_GRID_FN int run_ahead(int it, int trips, int nw, int rs, int ahead) {
+  const unsigned n = ((unsigned)(it >> rs) + (unsigned)ahead * (unsigned)nw) << rs;   // (below 2^32: trips < 2^31, runs of at most eight, waves < 2^20)
+  return n < (unsigned)trips ? (int)n : trips;
+}
+// the trip that wave maps behind `it`; `trips` when there is none
+QM_GRID_FN int run_next(int it, int trips, int nw, int rs) { return run_ends(it, trips, rs) ? run_ahead(it, trips, nw, rs, 1) : it + 1; }
 
 // the sweeps of the estimation objects (qm_fld.inl, qm_lib.inl, qm_gcb.inl, qm_sqb.inl, qm_psb.inl), one lane per unit, hit, window start or text position: the workgroups that are resident at
 // once (FLD_ / LIB_ / GCB_ / SQB_ / PSB_*_BLOCKS_PER_CU, no query), fewer when the lanes do not fill them, at most max_blocks when that is not 0

@@ -8,11 +8,11 @@
 namespace qm {
 
 template <bool PH, bool COV>
-__global__ __launch_bounds__(256, 8) void qm_duo_kernel(DevIndex ix_, ReadBatch B_) {
+__global__ __launch_bounds__(64 * QM_WG_WAVES, 8) void qm_duo_kernel(DevIndex ix_, ReadBatch B_, int rs) {
   const DevIndex& ix = stage_args().ix; const ReadBatch& B = stage_args().B;   // (through the kernarg segment, not ix_ / B_: see stage_args)
-  __shared__ __attribute__((aligned(16))) DuoMem mem[4];
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  duo_wave<PH, COV>(ix, B, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, mem[wave]);
+  __shared__ __attribute__((aligned(16))) DuoMem mem[QM_WG_WAVES];
+  const int wave = QM_WG_WAVES == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  duo_wave<PH, COV>(ix, B, (int)blockIdx.x * QM_WG_WAVES + wave, (int)gridDim.x * QM_WG_WAVES, mem[wave], rs);
 }
 
 }  // namespace qm
@@ -26,8 +26,8 @@ hipError_t qmk_launch_duo(const DevIndex& ix, const ReadBatch& B, int num_cu, hi
   return duo_dispatch(ix.ph != nullptr, B.quasi_cov > 0.0, [&](auto ph, auto cov) {
     constexpr bool PH = decltype(ph)::value, COV = decltype(cov)::value;
     const int over = knob ? knob : (PH ? grid_oversub_ph() : 2 * grid_oversub());
-    const int g = grid_blocks(pair_iters(B.nreads), num_cu, resident_per_cu<qm_duo_kernel<PH, COV>, 256, 8, true>(), over);
-    hipLaunchKernelGGL((qm_duo_kernel<PH, COV>), dim3((unsigned)g), dim3(256), 0, st, ix, B);
+    const WaveGrid g = wave_grid(pair_iters(B.nreads), num_cu, resident_quads_per_cu<qm_duo_kernel<PH, COV>, 8>("qm_duo_kernel"), over);
+    hipLaunchKernelGGL((qm_duo_kernel<PH, COV>), dim3((unsigned)g.blocks), dim3(64 * QM_WG_WAVES), 0, st, ix, B, g.rs);
     return hipGetLastError();
   });
 }

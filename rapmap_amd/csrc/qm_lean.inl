@@ -32,8 +32,13 @@
 #pragma once
 #include <type_traits>
 #include "qm_mapper.inl"
+#include "qm_grid.h"
 
 namespace qm {
+
+// What a wave of the two headline kernels knows of its schedule (qm_grid.h): nw waves, runs of 1 << rs neighbouring trips
+struct WaveRuns { int nw, rs; };
+#define QM_ORUN_H (2 * WAVE_RUN_MAX + 2)   // dwords of one offsets array in a run's staging row: R + 1 offsets of 64 bits
 
 #define QM_LEAN_MAXLEN 128       // two reads per wavefront (32 lanes x 4 characters each); the wide edition -- one read over all 64 lanes -- takes 256
 #define QM_LEAN_SUF 64           // suffixes a strand's intervals may hold together
@@ -48,7 +53,7 @@ namespace qm {
 
 struct LeanSuf { u32 tid, pos, qp, iv; };      // one suffix of a recorded interval: transcript, offset in it, queryPos and index of the interval
 
-struct LeanMem {                               // one wave's LDS slab (1 632 bytes)
+struct LeanMem {                               // one wave's LDS slab (1 856 bytes)
   u64 pk[2][2][8];                             // [read of the iteration][0: the read, 1: mirrored reverse complement][word]: 2 bits per base, first
                                                // base in the top bits of word 0; words 4-7 stay zero (extension queries read past the image)
   union {
@@ -56,7 +61,10 @@ struct LeanMem {                               // one wave's LDS slab (1 632 byt
     IntRec ints[QM_LEAN_MAXIV];                // -s collector: the interval records themselves (SAIntervalHit)
   };
   u32 stage[2][36];                            // raw characters of the next iteration's two reads (global_load_lds target)
-  u32 ostage[2][8];                            // offsets (dwords) of the next / the next but one iteration
+  union {
+    u32 ostage[2][8];                          // offsets (dwords) of the next / the next but one iteration
+    u32 orun[2][2 * QM_ORUN_H];                // the edition that stages offsets by run (lean_by_run): of this run / the wave's next run, as DuoMem::orun
+  };
   u32 nm[2][2][QM_LEAN_NMW];                   // [read][strand]: a bit per position that holds an N (round 6; words 4 .. stay zero), written for
   u32 nmz[QM_LEAN_NMW];                        // reads with N's only; every other read's walks look at nmz: all zero
 };
@@ -461,10 +469,35 @@ QM_DEV void lean_stage_offsets(const ReadBatch& B, int it, int nit, LeanMem& M, 
     }
   }
 }
+// The edition the headline runs -- pairs of up to 128 characters, straight from the batch -- stages offsets once per RUN of iterations
+// (qm_grid.h): iteration `it` is pair `it`, so a run needs off1[u0 .. u0 + n] and off2[u0 .. u0 + n].  The others (single-end reads, the wide
+// edition, the N-aware pass over a queue) keep a request per iteration, two iterations ahead.
+template <bool PAIRED, bool WIDE, bool NQ> constexpr bool lean_by_run() { return PAIRED && !WIDE && !NQ; }
+// offsets of the run that starts at iteration u0 (a multiple of 1 << rs) into orun[par]: one request for both arrays; the arrays hold
+// off[u0 + n] for the n iterations of the run (the batch's last run may be short)
+QM_DEV void lean_stage_run_offsets(const ReadBatch& B, int u0, int nit, int rs, LeanMem& M, int par) {
+  if (u0 >= nit) return;
+  const int left = nit - u0, n = left < (1 << rs) ? left : (1 << rs);
+  QM_LANES(l) {
+    const int h = l >= QM_ORUN_H ? 1 : 0, d = l - QM_ORUN_H * h;
+    if (l < 2 * QM_ORUN_H && d < 2 * n + 2) lds_dma_u32((const u32*)((h ? B.off2 : B.off1) + u0) + d, M.orun[par], l);
+  }
+}
+// the eight offset dwords of iteration `it` (landed), lane l: dword l & 7 of lean_stage_offsets' layout -- out of ostage[par], or out of
+// the row of the iteration's run
+template <bool PAIRED, bool WIDE, bool NQ>
+QM_DEV void lean_offsets(const LeanMem& M, int par, int it, int rs, LV<u32>& ov) {
+  if (lean_by_run<PAIRED, WIDE, NQ>()) {
+    const int j2 = 2 * (it & ((1 << rs) - 1));
+    QM_LANES(l) { ov[l] = M.orun[par][QM_ORUN_H * ((l >> 2) & 1) + (l & 3) + j2]; }
+  } else {
+    QM_LANES(l) { ov[l] = M.ostage[par][l & 7]; }
+  }
+}
 QM_DEV long long lean_off64(const LV<u32>& ov, int d) { return (long long)(((u64)read_lane(ov, d + 1) << 32) | (u64)read_lane(ov, d)); }
 // the offsets in ostage[par] (landed) into the request for the two reads' characters
 template <bool PAIRED, bool WIDE = false, bool NQ = false>
-QM_DEV void lean_stage_chars(const ReadBatch& B, int it, int nit, LeanMem& M, int par) {
+QM_DEV void lean_stage_chars(const ReadBatch& B, int it, int nit, int rs, LeanMem& M, int par) {
   if (it >= nit) return;
   if (WIDE) {
     LV<u32> ovw;
@@ -483,7 +516,7 @@ QM_DEV void lean_stage_chars(const ReadBatch& B, int it, int nit, LeanMem& M, in
   }
   const bool have1 = 2 * it + 1 < (int)B.nreads;
   LV<u32> ov;
-  QM_LANES(l) { ov[l] = M.ostage[par][l & 7]; }
+  lean_offsets<PAIRED, WIDE, NQ>(M, par, it, rs, ov);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     if (h && !have1) break;
@@ -507,7 +540,7 @@ QM_DEV void lean_stage_chars(const ReadBatch& B, int it, int nit, LeanMem& M, in
 // words apart instead of 8, the MMP extension reads the 224-character table (SaExt2).  The window probes, the walk and hits->mappings
 // are the same code.
 template <bool PAIRED, bool SEL, bool PH, bool WIDE = false, bool NQ = false>
-QM_DEV void lean_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, int nw, int par, LeanMem& M, WaveAlloc& wa) {
+QM_DEV void lean_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, const WaveRuns& S, int par, LeanMem& M, WaveAlloc& wa) {
   constexpr int IW = WIDE ? 16 : 8;                        // words between the two images of a read
   constexpr int HW = WIDE ? 64 : 32;                       // lanes per read
   constexpr int MAXLEN = WIDE ? 2 * QM_LEAN_MAXLEN : QM_LEAN_MAXLEN;
@@ -517,7 +550,7 @@ QM_DEV void lean_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, i
   const int have1 = (!WIDE && r0 + 1 < (int)B.nreads) ? 1 : 0;
   // ---- the two reads' characters -> 2-bit images of both strands, four characters per lane
   LV<u32> ov;
-  QM_LANES(l) { ov[l] = M.ostage[par][l & 7]; }
+  lean_offsets<PAIRED, WIDE, NQ>(M, par, it, S.rs, ov);
   const u32 a0 = read_lane(ov, 0), a1 = read_lane(ov, 2);
   const u32 b0 = read_lane(ov, (PAIRED || NQ) ? 4 : 2), b1 = read_lane(ov, (PAIRED || NQ) ? 6 : 4);
   // the reads of the iteration: 2 it and 2 it + 1, or (NQ: the N-aware pass over the queue of the reads the first pass left) what those slots name
@@ -587,9 +620,20 @@ QM_DEV void lean_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, i
     }
   }
   wave_fence();
-  // the staging rows are free again: the next iteration's characters, and the offsets of the one after it
-  lean_stage_chars<PAIRED, WIDE, NQ>(B, it + nw, nit, M, par ^ 1);
-  lean_stage_offsets<PAIRED, WIDE, NQ>(B, it + 2 * nw, nit, M, par);
+  // the staging rows are free again: the next iteration's characters, and the offsets of the one after it -- by run: behind a run's last
+  // iteration the next one is the first of the wave's next run, whose offsets the other row holds, and the offsets of the run after that
+  // one go where this run's were
+  {
+    const int nx = run_next(it, nit, S.nw, S.rs);
+    if (lean_by_run<PAIRED, WIDE, NQ>()) {
+      const int last = run_ends(it, nit, S.rs);
+      lean_stage_chars<PAIRED, WIDE, NQ>(B, nx, nit, S.rs, M, par ^ last);
+      if (last) lean_stage_run_offsets(B, run_ahead(it, nit, S.nw, S.rs, 2), nit, S.rs, M, par);
+    } else {
+      lean_stage_chars<PAIRED, WIDE, NQ>(B, nx, nit, S.rs, M, par ^ 1);
+      lean_stage_offsets<PAIRED, WIDE, NQ>(B, nx < nit ? run_next(nx, nit, S.nw, S.rs) : nit, nit, M, par);
+    }
+  }
 #if defined(QM_LEAN_ABLATE) && QM_LEAN_ABLATE == 1    // profiling builds (profiles/r05/ablate_build.sh): the phases up to here, empty lists out
   lds_dma_wait();
   QM_LANES(l) { if (l < 2 && r0 + l < (int)B.nreads) { B.lcnt[r0 + l] = (u32)(dirty & reps & 1); B.loff[r0 + l] = 0; } }
@@ -1064,10 +1108,12 @@ QM_DEV void lean_iter(const DevIndex& ix, const ReadBatch& B, int it, int nit, i
   }
 }
 
-// The wave body of qm_lean_kernel: wave gw of nw maps iterations gw, gw + nw, ... with the software pipeline of the general kernel
-// (characters of the next iteration and offsets of the one after staged in LDS meanwhile).  The slab holds whatever it held.
+// The wave body of qm_lean_kernel: wave gw of nw maps the runs gw, gw + nw, ... of 1 << rs neighbouring iterations (qm_grid.h; rs = 0:
+// iterations gw, gw + nw, ...), each run's iterations in order, with the software pipeline of the general kernel (characters of the
+// next iteration and offsets of the one after it -- lean_by_run: of the run after the next -- staged in LDS meanwhile).  The slab holds
+// whatever it held.
 template <bool PAIRED, bool SEL, bool PH, bool WIDE = false, bool NQ = false>
-QM_DEV void lean_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, LeanMem& M) {
+QM_DEV void lean_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, LeanMem& M, int rs = 0) {
   const int nit = WIDE ? (int)B.nreads : (int)((B.nreads + 1) >> 1);   // iterations: two reads each, one in the wide edition (reads per launch < 2^31)
   QM_LANES(l) {                                              // the words behind the images stay zero
     if (WIDE) { if (l < 16) (&M.pk[0][0][0])[16 * (l >> 3) + 8 + (l & 7)] = 0; }
@@ -1075,15 +1121,20 @@ QM_DEV void lean_wave(const DevIndex& ix, const ReadBatch& B, int gw, int nw, Le
     if (l < 5 * QM_LEAN_NMW) (&M.nm[0][0][0])[l] = 0;        // the N flags (and nmz behind them): lean_iter writes words 0-3 of a read with N's, the rest stays zero
   }
   WaveAlloc wa;
-  lean_stage_offsets<PAIRED, WIDE, NQ>(B, gw, nit, M, 0);
+  constexpr bool BYRUN = lean_by_run<PAIRED, WIDE, NQ>();
+  const WaveRuns S = {nw, rs};
+  const long long t0 = run_trip(0, gw, nw, rs);
+  const int it0 = t0 < nit ? (int)t0 : nit;
+  if (BYRUN) lean_stage_run_offsets(B, it0, nit, rs, M, 0); else lean_stage_offsets<PAIRED, WIDE, NQ>(B, it0, nit, M, 0);
   lds_dma_wait();
-  lean_stage_chars<PAIRED, WIDE, NQ>(B, gw, nit, M, 0);
-  lean_stage_offsets<PAIRED, WIDE, NQ>(B, gw + nw, nit, M, 1);
+  lean_stage_chars<PAIRED, WIDE, NQ>(B, it0, nit, rs, M, 0);
+  if (BYRUN) lean_stage_run_offsets(B, run_ahead(it0, nit, nw, rs, 1), nit, rs, M, 1);
+  else lean_stage_offsets<PAIRED, WIDE, NQ>(B, it0 < nit ? run_next(it0, nit, nw, rs) : nit, nit, M, 1);
   lds_dma_wait();
   int par = 0;
-  for (int it = gw; it < nit; it += nw) {
-    lean_iter<PAIRED, SEL, PH, WIDE, NQ>(ix, B, it, nit, nw, par, M, wa);
-    par ^= 1;
+  for (int it = it0; it < nit; it = run_next(it, nit, nw, rs)) {
+    lean_iter<PAIRED, SEL, PH, WIDE, NQ>(ix, B, it, nit, S, par, M, wa);
+    par ^= BYRUN ? run_ends(it, nit, rs) : 1;               // the offsets' two rows alternate by run, or by iteration
   }
 }
 
