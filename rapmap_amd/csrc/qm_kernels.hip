@@ -144,49 +144,7 @@ __global__ __launch_bounds__(256) void qm_sel_sides_kernel(PairBatch P, SelBatch
   if (m > 0) sel_unit_sides_write(P, A, u, (long long)base + incl - m);
   sel_flush_counters(sc, uc, P.counters);
 }
-// plan, step 2: a group of lanes per question (qm_sel_score_kernel<G>); the groups' sums / xors by DPP
-struct SelRed16 {                       // all-reduce over a row of 16 lanes by rotations (DPP row_ror:8, 4, 2, 1): every lane ends up with the result
-  template <int CTRL> static QM_DEV int rot(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-  QM_DEV int add(int v) const { v += rot<0x128>(v); v += rot<0x124>(v); v += rot<0x122>(v); v += rot<0x121>(v); return v; }
-  QM_DEV int min(int v) const { int o; o = rot<0x128>(v); v = o < v ? o : v; o = rot<0x124>(v); v = o < v ? o : v; o = rot<0x122>(v); v = o < v ? o : v; o = rot<0x121>(v); v = o < v ? o : v; return v; }
-  QM_DEV int max(int v) const { int o; o = rot<0x128>(v); v = o > v ? o : v; o = rot<0x124>(v); v = o > v ? o : v; o = rot<0x122>(v); v = o > v ? o : v; o = rot<0x121>(v); v = o > v ? o : v; return v; }
-  QM_DEV u64 bxor(u64 v) const {
-    int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-    lo ^= rot<0x128>(lo); hi ^= rot<0x128>(hi); lo ^= rot<0x124>(lo); hi ^= rot<0x124>(hi);
-    lo ^= rot<0x122>(lo); hi ^= rot<0x122>(hi); lo ^= rot<0x121>(lo); hi ^= rot<0x121>(hi);
-    return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32);
-  }
-};
-// ... or over the eight lanes of a half row: row_half_mirror (lane i <-> 7 - i), then the two quad permutations
-struct SelRed8 {
-  template <int CTRL> static QM_DEV int dpp(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-  QM_DEV int add(int v) const { v += dpp<0x141>(v); v += dpp<0xB1>(v); v += dpp<0x4E>(v); return v; }
-  QM_DEV int min(int v) const { int o; o = dpp<0x141>(v); v = o < v ? o : v; o = dpp<0xB1>(v); v = o < v ? o : v; o = dpp<0x4E>(v); v = o < v ? o : v; return v; }
-  QM_DEV int max(int v) const { int o; o = dpp<0x141>(v); v = o > v ? o : v; o = dpp<0xB1>(v); v = o > v ? o : v; o = dpp<0x4E>(v); v = o > v ? o : v; return v; }
-  QM_DEV u64 bxor(u64 v) const {
-    int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-    lo ^= dpp<0x141>(lo); hi ^= dpp<0x141>(hi); lo ^= dpp<0xB1>(lo); hi ^= dpp<0xB1>(hi); lo ^= dpp<0x4E>(lo); hi ^= dpp<0x4E>(hi);
-    return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32);
-  }
-};
-struct SelRed4 {                       // ... or the four lanes of a quad
-  template <int CTRL> static QM_DEV int dpp(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-  QM_DEV int add(int v) const { v += dpp<0xB1>(v); v += dpp<0x4E>(v); return v; }
-  QM_DEV int min(int v) const { int o; o = dpp<0xB1>(v); v = o < v ? o : v; o = dpp<0x4E>(v); v = o < v ? o : v; return v; }
-  QM_DEV int max(int v) const { int o; o = dpp<0xB1>(v); v = o > v ? o : v; o = dpp<0x4E>(v); v = o > v ? o : v; return v; }
-  QM_DEV u64 bxor(u64 v) const {
-    int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-    lo ^= dpp<0xB1>(lo); hi ^= dpp<0xB1>(hi); lo ^= dpp<0x4E>(lo); hi ^= dpp<0x4E>(hi);
-    return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32);
-  }
-};
-struct SelRed2 {                       // ... or a pair of lanes
-  template <int CTRL> static QM_DEV int dpp(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-  QM_DEV int add(int v) const { return v + dpp<0xB1>(v); }
-  QM_DEV int min(int v) const { const int o = dpp<0xB1>(v); return o < v ? o : v; }
-  QM_DEV int max(int v) const { const int o = dpp<0xB1>(v); return o > v ? o : v; }
-  QM_DEV u64 bxor(u64 v) const { int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32); lo ^= dpp<0xB1>(lo); hi ^= dpp<0xB1>(hi); return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32); }
-};
+// plan, step 2: a group of lanes per question (qm_sel_score_kernel<G>); the groups' sums / xors by DPP (SelRed2 / 4 / 8 / 16, qm_sel.inl)
 // Lanes per alignment question (measured on 2 x 100 bp, ms per chunk of 10.7 M questions: 16 lanes 4.08, 8 lanes 3.07, 4 lanes 2.42, 2 lanes 2.09,
 // 1 lane 4.12): the geometry and bookkeeping of a question is per lane whatever the group, so few lanes with several 8-character words each
 // beat one word per lane -- until a lane's loads no longer share lines with its neighbours'.  Longer reads take wider groups.

@@ -1271,6 +1271,51 @@ QM_DEV u64 sel_read_word(const unsigned char* r, int len, bool fwd, int j0) {
   return nv >= 8 ? w : (w & ((1ULL << (8 * nv)) - 1ULL));
 }
 struct SelRedOne { QM_DEV int add(int v) const { return v; } QM_DEV int min(int v) const { return v; } QM_DEV int max(int v) const { return v; } QM_DEV u64 bxor(u64 v) const { return v; } };   // a group of one lane (emulation)
+#ifndef QM_EMU
+// the groups of qm_sel_score_kernel<G> (qm_kernels.hip; tests/device/qm_probe.hip instantiates the same ones): sums / xors by DPP
+struct SelRed16 {                       // all-reduce over a row of 16 lanes by rotations (DPP row_ror:8, 4, 2, 1): every lane ends up with the result
+  template <int CTRL> static QM_DEV int rot(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
+  QM_DEV int add(int v) const { v += rot<0x128>(v); v += rot<0x124>(v); v += rot<0x122>(v); v += rot<0x121>(v); return v; }
+  QM_DEV int min(int v) const { int o; o = rot<0x128>(v); v = o < v ? o : v; o = rot<0x124>(v); v = o < v ? o : v; o = rot<0x122>(v); v = o < v ? o : v; o = rot<0x121>(v); v = o < v ? o : v; return v; }
+  QM_DEV int max(int v) const { int o; o = rot<0x128>(v); v = o > v ? o : v; o = rot<0x124>(v); v = o > v ? o : v; o = rot<0x122>(v); v = o > v ? o : v; o = rot<0x121>(v); v = o > v ? o : v; return v; }
+  QM_DEV u64 bxor(u64 v) const {
+    int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    lo ^= rot<0x128>(lo); hi ^= rot<0x128>(hi); lo ^= rot<0x124>(lo); hi ^= rot<0x124>(hi);
+    lo ^= rot<0x122>(lo); hi ^= rot<0x122>(hi); lo ^= rot<0x121>(lo); hi ^= rot<0x121>(hi);
+    return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32);
+  }
+};
+// ... or over the eight lanes of a half row: row_half_mirror (lane i <-> 7 - i), then the two quad permutations
+struct SelRed8 {
+  template <int CTRL> static QM_DEV int dpp(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
+  QM_DEV int add(int v) const { v += dpp<0x141>(v); v += dpp<0xB1>(v); v += dpp<0x4E>(v); return v; }
+  QM_DEV int min(int v) const { int o; o = dpp<0x141>(v); v = o < v ? o : v; o = dpp<0xB1>(v); v = o < v ? o : v; o = dpp<0x4E>(v); v = o < v ? o : v; return v; }
+  QM_DEV int max(int v) const { int o; o = dpp<0x141>(v); v = o > v ? o : v; o = dpp<0xB1>(v); v = o > v ? o : v; o = dpp<0x4E>(v); v = o > v ? o : v; return v; }
+  QM_DEV u64 bxor(u64 v) const {
+    int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    lo ^= dpp<0x141>(lo); hi ^= dpp<0x141>(hi); lo ^= dpp<0xB1>(lo); hi ^= dpp<0xB1>(hi); lo ^= dpp<0x4E>(lo); hi ^= dpp<0x4E>(hi);
+    return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32);
+  }
+};
+struct SelRed4 {                       // ... or the four lanes of a quad
+  template <int CTRL> static QM_DEV int dpp(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
+  QM_DEV int add(int v) const { v += dpp<0xB1>(v); v += dpp<0x4E>(v); return v; }
+  QM_DEV int min(int v) const { int o; o = dpp<0xB1>(v); v = o < v ? o : v; o = dpp<0x4E>(v); v = o < v ? o : v; return v; }
+  QM_DEV int max(int v) const { int o; o = dpp<0xB1>(v); v = o > v ? o : v; o = dpp<0x4E>(v); v = o > v ? o : v; return v; }
+  QM_DEV u64 bxor(u64 v) const {
+    int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    lo ^= dpp<0xB1>(lo); hi ^= dpp<0xB1>(hi); lo ^= dpp<0x4E>(lo); hi ^= dpp<0x4E>(hi);
+    return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32);
+  }
+};
+struct SelRed2 {                       // ... or a pair of lanes
+  template <int CTRL> static QM_DEV int dpp(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
+  QM_DEV int add(int v) const { return v + dpp<0xB1>(v); }
+  QM_DEV int min(int v) const { const int o = dpp<0xB1>(v); return o < v ? o : v; }
+  QM_DEV int max(int v) const { const int o = dpp<0xB1>(v); return o > v ? o : v; }
+  QM_DEV u64 bxor(u64 v) const { int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32); lo ^= dpp<0xB1>(lo); hi ^= dpp<0xB1>(hi); return (u64)(unsigned)lo | ((u64)(unsigned)hi << 32); }
+};
+#endif
 
 // step 2: question x, by lane l of a group of G lanes (lane l takes the 8-character words l, l + G, ...); red sums / xors over the group
 template <int G, typename Red>
@@ -1315,7 +1360,10 @@ QM_DEV void sel_side_score(const PairBatch& P, const SelBatch& A, long long x, i
     // less than 2M (q + L e, or q + L (e + a) with the query characters of the run: one and two skipped target characters and one
     // skipped query character under the default scores); the target has to reach past the longest of them, so that ending in
     // the target's last column is no option, and the band has to hold them.  The diagonals next to the main one cost a funnel
-    // shift of the words already loaded.
+    // shift of the words already loaded.  The query has to be at least as long as the longest run of skipped target characters -- the
+    // characters the main diagonal and diagonal +Ld look at then cover target[0 .. rlen + Ld), so an N anywhere a one-gap path could meet it is
+    // seen -- and longer than the longest run of skipped query characters: a path that skips every query character ends in no cell of the
+    // query's last row, ksw2 does not score it (tests/test_sel_side.py found both on alignments of two characters).
     int a = (signed char)A.match, b = (signed char)A.mismatch;
     a = a < 0 ? -a : a; b = b > 0 ? -b : b;
     const int gq = (int)(signed char)A.gap_open, ge = (int)(signed char)A.gap_extend, qe = gq + ge, M = a - b;
@@ -1323,7 +1371,7 @@ QM_DEV void sel_side_score(const PairBatch& P, const SelBatch& A, long long x, i
     int Ld = 0, Li = 0;
     while (Ld < 4 && gq + (Ld + 1) * ge < 2 * M) ++Ld;
     while (Li < 3 && gq + (Li + 1) * (ge + a) < 2 * M) ++Li;
-    const bool rule2 = diag && A.no_diag != 2 && M <= qe && Ld <= 3 && Li <= 2 && (A.bandwidth < 0 || A.bandwidth >= 8) && tlen1 >= rlen + Ld + 1;
+    const bool rule2 = diag && A.no_diag != 2 && M <= qe && Ld <= 3 && Li <= 2 && (A.bandwidth < 0 || A.bandwidth >= 8) && tlen1 >= rlen + Ld + 1 && rlen >= Ld && rlen > Li;
     const int alnLen = rlen < tlen1 ? rlen : tlen1;
     const int cmpLen = doUngapped ? alnLen : (diag ? rlen : 0);
     const int hashLen = multiMapping ? keyLen : 0;

@@ -1,5 +1,6 @@
 """tests/device/probe.py -- ctypes face of the TEST-ONLY device probes (libqm_probe.so, tests/device/qm_probe.hip): single wave bodies of the
-product's source run by themselves on the GPU -- the primitives of qm_wave.h, lean_h2m and the ksw2 row kernels -- so that the device edition of
+product's source run by themselves on the GPU -- the primitives of qm_wave.h, lean_h2m, the ksw2 row kernels, the -s question scorer and the
+strip alignments -- so that the device edition of
 each can be held to its lane emulation (tests/emu).  The library is rebuilt when a source is newer; a missing library that cannot be built is
 an error, not a skip.  Load it after torch has opened the device (the `lib_built` fixture of tests/conftest.py)."""
 import ctypes as C
@@ -144,6 +145,37 @@ def ksw_rows(groups, scheme, ring=-1):
                             C.c_int(a), C.c_int(b), C.c_int(q_), C.c_int(e_), C.c_int(w), C.c_void_p(out.ctypes.data))
     _check(rc, "qp_ksw_rows(ring %d, %d waves, scheme %r)" % (ring, nw, scheme))
     return _first_copies([[int(x) for x in out[i, :len(g)]] for i, g in enumerate(groups)], asked, "qp_ksw_rows")
+
+
+def sel_side(G, batch, policy, scheme):
+    """every question of the batch (tests/sel_side_cases.py: Batch) through sel_side_score<G> in ONE launch, G = 2 / 4 / 8 / 16 lanes per question
+    -> (kind[n] int32, tsc[n] int32, key[n] uint64, task[n, 9] int64 rows of emu_sel.TASK_FIELDS) -- what emu_sel.sel_side(.., strip=False) gives"""
+    import emu_sel
+    reads, roffs, text, txp_off, txp_len, qd = emu_sel.flat(batch)
+    n = len(qd)
+    prm = np.array([policy] + list(scheme), dtype=np.int32)
+    kind = np.zeros(n, dtype=np.int32); tsc = np.zeros(n, dtype=np.int32); key = np.zeros(n, dtype=np.uint64); task = np.zeros((n, 9), dtype=np.int64)
+    rc = _lib().qp_sel_side(C.c_int(G), C.c_int(n), C.c_void_p(reads.ctypes.data), C.c_void_p(roffs.ctypes.data), C.c_void_p(text.ctypes.data),
+                            C.c_longlong(len(text)), C.c_int(len(txp_off)), C.c_void_p(txp_off.ctypes.data), C.c_void_p(txp_len.ctypes.data),
+                            C.c_void_p(qd.ctypes.data), C.c_void_p(prm.ctypes.data), C.c_void_p(kind.ctypes.data), C.c_void_p(tsc.ctypes.data),
+                            C.c_void_p(key.ctypes.data), C.c_void_p(task.ctypes.data))
+    _check(rc, "qp_sel_side(%d lanes, %d questions, policy %d, scheme %r)" % (G, n, policy, scheme))
+    return kind, tsc, key, task
+
+
+def sel_strip(tasks, batch, scheme):
+    """tasks: (n, 9) rows of emu_sel.TASK_FIELDS as sel_side leaves them for the questions with kind & 4, run four per wavefront in this order in ONE
+    launch of sel_tasks_strip -> scores[n] int32"""
+    import emu_sel
+    reads, roffs, text, txp_off, txp_len, qd = emu_sel.flat(batch)
+    t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int64)[:, [1, 4, 5, 6, 2, 7, 8]])       # {read offset, rl, roff, rlen, target offset, tlen1, fwd}
+    n = len(t)
+    prm = np.array(scheme[:4], dtype=np.int32)
+    out = np.zeros(n, dtype=np.int32)
+    rc = _lib().qp_sel_strip(C.c_int(n), C.c_void_p(t.ctypes.data), C.c_void_p(reads.ctypes.data), C.c_longlong(len(reads)), C.c_void_p(text.ctypes.data),
+                             C.c_longlong(len(text)), C.c_void_p(prm.ctypes.data), C.c_void_p(out.ctypes.data))
+    _check(rc, "qp_sel_strip(%d alignments, scheme %r)" % (n, scheme))
+    return out
 
 
 def ksw_rows8(groups, scheme):

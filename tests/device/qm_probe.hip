@@ -5,6 +5,8 @@
 //   qp_h2m        lean_h2m, lean_h2m_loop, lean_h2m_tiles<false / true> of qm_lean.inl on a stash in LDS          (tests/emu/qm_emu_h2m.cpp)
 //   qp_ksw_rows   sel_ksw_extz2_rows<RING> of qm_sel.inl, four alignments per wavefront                           (tests/emu/qm_emu.cpp)
 //   qp_ksw_rows8  sel_ksw_extz2_rows_reg<.., true, 2>, eight alignments of one shape per wavefront
+//   qp_sel_side   sel_side_score<G> with SelRed2 / 4 / 8 / 16, 256 / G questions per block as qm_sel_score_kernel launches it    (tests/emu/qm_emu_sel.cpp)
+//   qp_sel_strip  sel_tasks_strip, four alignments per wavefront as qm_sel_strip_kernel launches it
 // An entry point is self-contained: host arrays in, hipSetDevice(0), allocate, copy, ONE launch, synchronise, copy back, free; it returns the
 // hipError_t (hipErrorInvalidValue for an argument outside what the body is written for -- checked here, before anything is launched).
 // One wave of the caller's = one wavefront; blocks of four wavefronts (the ksw2 kernels: as many as the product's launch wrapper gives that
@@ -12,6 +14,8 @@
 #include "../../rapmap_amd/csrc/qm_lean.inl"
 #include "qm_wave_probe.inl"
 
+#include <string.h>
+#include <type_traits>
 #include <vector>
 
 using namespace qm;
@@ -166,6 +170,27 @@ __global__ __launch_bounds__(256) void qp_ksw_rows8_kernel(int nw, const int* hd
   if ((lane & 15) == 0) for (int s = 0; s < 2; ++s) out[(size_t)wave * 8 + 4 * s + (lane >> 4)] = sc[s].v[0];
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the -s question scorer, the strip alignments
+// qm_sel_score_kernel<G> and qm_sel_strip_kernel of qm_kernels.hip, word for word: 256-thread blocks, 256 / G questions per block and trip with the
+// product's own group reductions (SelRed2 / 4 / 8 / 16, qm_sel.inl); four strip tasks per wavefront on __shared__ StripMem[4]
+template <int G>
+__global__ __launch_bounds__(256) void qp_sel_side_kernel(PairBatch P, SelBatch A) {
+  const unsigned long long n = *A.nsides;
+  constexpr int PER = 256 / G;
+  const int l = (int)(threadIdx.x & (G - 1));
+  typename std::conditional<G == 16, SelRed16, typename std::conditional<G == 8, SelRed8, typename std::conditional<G == 4, SelRed4, SelRed2>::type>::type>::type red;
+  for (unsigned long long x = (unsigned long long)blockIdx.x * PER + (threadIdx.x / G); x < n; x += (unsigned long long)gridDim.x * PER)
+    sel_side_score<G>(P, A, (long long)x, l, red);
+}
+__global__ __launch_bounds__(256) void qp_sel_strip_kernel(SelBatch A) {
+  __shared__ StripMem mem[4];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned long long nt = *A.ntasks2;
+  for (unsigned long long t = ((unsigned long long)blockIdx.x * 4 + wave) * 4; t < nt; t += (unsigned long long)gridDim.x * 16) sel_tasks_strip(A, t, nt, mem[wave]);
+}
+// blocks for n items, `per` of them per block and trip: at least two, and about half as many as one trip would take (the stride loop runs)
+unsigned blocks_two_trips(long long n, int per) { const long long b = ((n + per - 1) / per + 1) / 2; return (unsigned)(b < 2 ? 2 : b); }
+
 // a sequence [off, off + len) must lie inside the nseq bytes the caller passed
 bool seq_ok(long long off, long long len, long long nseq) { return off >= 0 && len >= 0 && off + len <= nseq; }
 
@@ -288,6 +313,114 @@ int qp_ksw_rows8(int nw, const int* hdr, const unsigned char* seq, long long nse
   hipLaunchKernelGGL(qp_ksw_rows8_kernel, dim3(blocks_for(nw, 4)), dim3(256), 0, 0, nw, dhdr, dseq, K, dout);
   B.sync();
   B.get(out, dout, (size_t)nw * 8);
+  return (int)B.err;
+}
+
+int qp_sel_max_read_len(void) { return QM_MAX_READ_LEN; }
+
+// nq questions in ONE launch of qp_sel_side_kernel<G> (G: 2, 4, 8 or 16 lanes per question), one unit and one hit per question -- the arguments and
+// the answers of tests/emu/qm_emu_sel.cpp's qe_sel_side (its strip pass is qp_sel_strip here).  reads[roffs[nq]]: question x asks about
+// reads[roffs[x] .. roffs[x + 1]); text[ntext] with ntx transcripts txp_off / txp_len; qd: nq x {tid, pos, fwd, chain status, multi-mapping unit};
+// prm: {policy, match, mismatch, gap open, gap extend, band}.  Out, per question: kind, tsc (0x5A5A5A5A: never written), key, task[9] = {written,
+// read offset, target offset, gslot, rl, roff, rlen, tlen1, fwd} (written 0: tasks[x] still holds the 0xEE it was filled with; the rest is 0 then).
+int qp_sel_side(int G, int nq, const unsigned char* reads, const long long* roffs, const unsigned char* text, long long ntext, int ntx, const u32* txp_off,
+                const int* txp_len, const int* qd, const int* prm, int* kind, int* tsc, u64* key, long long* task) {
+  if (!(G == 2 || G == 4 || G == 8 || G == 16) || nq < 1 || ntx < 1 || roffs[0] < 0) return (int)hipErrorInvalidValue;
+  for (int t = 0; t < ntx; ++t) if (txp_len[t] < 0 || (long long)txp_off[t] + txp_len[t] > ntext) return (int)hipErrorInvalidValue;
+  for (int x = 0; x < nq; ++x) {
+    const int* d = qd + 5 * x;
+    if (roffs[x + 1] < roffs[x] || roffs[x + 1] - roffs[x] > QM_MAX_LONG_READ_LEN || d[0] < 0 || d[0] >= ntx || d[1] < -(1 << 24) || d[1] > (1 << 24)) return (int)hipErrorInvalidValue;
+  }
+  hipError_t e = hipSetDevice(0);
+  if (e != hipSuccess) return (int)e;
+  const size_t n = (size_t)nq;
+  std::vector<u32> cnt(n + 1, 0);
+  std::vector<qm_hit> tmp(n);
+  std::vector<SelSide> sides(n);
+  memset(sides.data(), 0xEE, sizeof(SelSide) * n);
+  for (size_t x = 0; x < n; ++x) {
+    const int* d = qd + 5 * x;
+    qm_hit h; memset(&h, 0, sizeof(h));
+    h.tid = (u32)d[0]; h.pos = d[1]; h.fwd = d[2] ? 1 : 0; h.mate_is_fwd = 1; h.read_len = (u32)(roffs[x + 1] - roffs[x]); h.aln_score = d[3];
+    tmp[x] = h;
+    cnt[x] = d[4] ? 2u : 1u;
+    sides[x].u = (long long)x; sides[x].g = 2 * (long long)x; sides[x].nth = 0;
+  }
+  // (the sequences with sixteen bytes of 0xA5 behind them: the word loads stay inside [0, len), and if one did not it would stay inside the allocation)
+  std::vector<unsigned char> hr(reads, reads + roffs[nq]), ht(text, text + ntext);
+  hr.resize(hr.size() + 16, 0xA5); ht.resize(ht.size() + 16, 0xA5);
+  const u64 nsides = (u64)n;
+  ProbeBufs B;
+  const unsigned char* dreads = B.put(hr.data(), hr.size()); const unsigned char* dtext = B.put(ht.data(), ht.size());
+  const long long* droffs = B.put(roffs, n + 1);
+  const u32* dtoff = B.put(txp_off, (size_t)ntx); const int* dtlen = B.put(txp_len, (size_t)ntx);
+  u32* dcnt = B.put(cnt.data(), n + 1); qm_hit* dtmp = B.put(tmp.data(), n); SelSide* dsides = B.put(sides.data(), n);
+  u64* dnsides = B.put(&nsides, 1);
+  SelTask* dtasks = B.fill<SelTask>(n, 0xEE);
+  int* dtsc = B.fill<int>(2 * n, 0x5A); int* dtref = B.fill<int>(2 * n, 0x5A);
+  u64* dtorder2 = B.fill<u64>(n, 0); u64* dntasks2 = B.fill<u64>(1, 0);
+  if (B.err != hipSuccess) return (int)B.err;
+  PairBatch P; memset(&P, 0, sizeof(P));
+  P.n = nq; P.paired = 0; P.off1 = droffs; P.off2 = droffs; P.cnt = dcnt; P.max_num_hits = 200;
+  SelBatch A; memset(&A, 0, sizeof(A));
+  A.seq1 = dreads; A.seq2 = dreads; A.text = dtext; A.txp_off = dtoff; A.txp_len = dtlen; A.tmp = dtmp;
+  A.tsc = dtsc; A.tref = dtref; A.sides = dsides; A.nsides = dnsides; A.tasks = dtasks; A.torder2 = dtorder2; A.ntasks2 = dntasks2; A.u0 = 0; A.u1 = nq;
+  A.policy = prm[0]; A.match = prm[1]; A.mismatch = prm[2]; A.gap_open = prm[3]; A.gap_extend = prm[4]; A.bandwidth = prm[5];
+  A.min_score_fraction = 0.65;
+  const unsigned nb = blocks_two_trips(nq, 256 / G);
+  switch (G) {
+    case 2: hipLaunchKernelGGL(qp_sel_side_kernel<2>, dim3(nb), dim3(256), 0, 0, P, A); break;
+    case 4: hipLaunchKernelGGL(qp_sel_side_kernel<4>, dim3(nb), dim3(256), 0, 0, P, A); break;
+    case 8: hipLaunchKernelGGL(qp_sel_side_kernel<8>, dim3(nb), dim3(256), 0, 0, P, A); break;
+    default: hipLaunchKernelGGL(qp_sel_side_kernel<16>, dim3(nb), dim3(256), 0, 0, P, A); break;
+  }
+  B.sync();
+  std::vector<SelTask> tasks(n); std::vector<int> tscv(2 * n);
+  B.get(sides.data(), dsides, n); B.get(tasks.data(), dtasks, n); B.get(tscv.data(), dtsc, 2 * n);
+  if (B.err != hipSuccess) return (int)B.err;
+  std::vector<unsigned char> fill(sizeof(SelTask), 0xEE);
+  for (size_t x = 0; x < n; ++x) {
+    kind[x] = sides[x].kind; key[x] = sides[x].key; tsc[x] = tscv[2 * x];
+    long long* o = task + 9 * x;
+    for (int i = 0; i < 9; ++i) o[i] = 0;
+    if (memcmp(&tasks[x], fill.data(), sizeof(SelTask)) == 0) continue;
+    const SelTask& t = tasks[x];
+    o[0] = 1; o[1] = (long long)(t.rd - dreads); o[2] = (long long)(t.tx - dtext); o[3] = t.gslot; o[4] = t.rl; o[5] = t.roff; o[6] = t.rlen; o[7] = t.tlen1; o[8] = t.fwd;
+  }
+  return (int)B.err;
+}
+
+// nt strip alignments in ONE launch of qp_sel_strip_kernel, four per wavefront in the order given: task[nt * 7] = {read offset, rl, roff, rlen, target
+// offset, tlen1, fwd} into reads[nreads] / text[ntext] (characters); prm: {match, mismatch, gap open, gap extend}.  out[nt]: the scores.
+int qp_sel_strip(int nt, const long long* task, const unsigned char* reads, long long nreads, const unsigned char* text, long long ntext, const int* prm, int* out) {
+  if (nt < 1) return (int)hipErrorInvalidValue;
+  for (int i = 0; i < nt; ++i) {
+    const long long* t = task + 7 * i;
+    if (!seq_ok(t[0], t[1], nreads) || t[2] < 0 || t[3] < 0 || t[2] + t[3] > t[1] || t[3] > QM_MAX_READ_LEN || !seq_ok(t[4], t[5], ntext) || t[5] > QM_MAX_READ_LEN + 48) return (int)hipErrorInvalidValue;
+  }
+  hipError_t e = hipSetDevice(0);
+  if (e != hipSuccess) return (int)e;
+  const size_t n = (size_t)nt;
+  std::vector<unsigned char> hr(reads, reads + nreads), ht(text, text + ntext);
+  hr.resize(hr.size() + 16, 0xA5); ht.resize(ht.size() + 16, 0xA5);
+  ProbeBufs B;
+  const unsigned char* dreads = B.put(hr.data(), hr.size()); const unsigned char* dtext = B.put(ht.data(), ht.size());
+  std::vector<SelTask> tasks(n); std::vector<u64> order(n);
+  for (size_t i = 0; i < n; ++i) {
+    const long long* t = task + 7 * i;
+    SelTask s; s.rd = dreads + t[0]; s.rl = (int)t[1]; s.roff = (int)t[2]; s.rlen = (int)t[3]; s.tx = dtext + t[4]; s.tlen1 = (int)t[5]; s.fwd = t[6] ? 1 : 0; s.gslot = (int)i;
+    tasks[i] = s; order[i] = (u64)i;
+  }
+  const u64 ntasks2 = (u64)n;
+  SelTask* dtasks = B.put(tasks.data(), n); u64* dorder = B.put(order.data(), n); u64* dnt = B.put(&ntasks2, 1);
+  int* dtsc = B.fill<int>(n, 0x5A);
+  if (B.err != hipSuccess) return (int)B.err;
+  SelBatch A; memset(&A, 0, sizeof(A));
+  A.seq1 = dreads; A.seq2 = dreads; A.text = dtext; A.tasks = dtasks; A.torder2 = dorder; A.ntasks2 = dnt; A.tsc = dtsc;
+  A.match = prm[0]; A.mismatch = prm[1]; A.gap_open = prm[2]; A.gap_extend = prm[3];
+  hipLaunchKernelGGL(qp_sel_strip_kernel, dim3(blocks_two_trips(nt, 16)), dim3(256), 0, 0, A);
+  B.sync();
+  B.get(out, dtsc, n);
   return (int)B.err;
 }
 

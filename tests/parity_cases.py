@@ -44,6 +44,45 @@ def sel_reads(synth_small, which):
     return sam.read_fastq(os.path.join(nx, "reads_indel_1.fastq.gz"))[1], sam.read_fastq(os.path.join(nx, "reads_indel_2.fastq.gz"))[1]
 
 
+def _edited_pairs(txps, n, seed):
+    """pairs of 100-bp reads (mate 2 from the other strand, 150 bases downstream) with the edits that decide between the gapless
+    path and a path with one gap: two substitutions anywhere, or a one- / two-base deletion or a one-base insertion a few
+    characters from either end of the read (behind it the diagonal has a handful of mismatches, often exactly two)"""
+    rng = np.random.default_rng(seed)
+    B = np.frombuffer(b"ACGT", dtype=np.uint8)
+    comp = np.zeros(256, np.uint8); comp[list(b"ACGT")] = list(b"TGCA")
+    long_enough = [t for t in txps if len(t) >= 400]
+
+    def edit(frag):                                         # frag: 104 characters of transcript, the read is (about) its first 100
+        kind = int(rng.integers(0, 6))
+        r = frag.copy()
+        if kind == 0:
+            for p in rng.choice(100, 2, replace=False): r[p] = B[(np.searchsorted(B, r[p]) + 1 + rng.integers(0, 3)) % 4]
+            return r[:100]
+        near = int(rng.integers(1, 7))
+        p = near if rng.random() < 0.5 else 100 - near
+        if kind in (1, 2): return np.concatenate([r[:p], r[p + 1:]])[:100]                   # one base missing from the read
+        if kind == 3: return np.concatenate([r[:p], r[p + 2:]])[:100]                        # two
+        if kind == 4: return np.concatenate([r[:p], B[rng.integers(0, 4, 1)], r[p:]])[:100]  # one extra
+        for p in rng.choice(100, 3, replace=False): r[p] = B[(np.searchsorted(B, r[p]) + 1) % 4]
+        return r[:100]
+    r1, r2 = [], []
+    for i in range(n):
+        t = long_enough[int(rng.integers(0, len(long_enough)))]
+        p = int(rng.integers(0, len(t) - 360))
+        a = edit(t[p:p + 104]); b = edit(t[p + 150:p + 254])
+        b = comp[b[::-1]]
+        if i % 2: a, b = b, a
+        r1.append(a.tobytes()); r2.append(b.tobytes())
+    return r1, r2
+
+
+# the schemes of test_selective_alignment_answers_known_without_ksw2 (emulation and device), as oracle options
+KNOWN_ANSWER_SCHEMES = [dict(), dict(gapOpen=4, gapExtend=2), dict(matchScore=1, mismatchPenalty=-1, gapOpen=1, gapExtend=1),
+                        dict(dpBandwidth=5), dict(matchScore=2, mismatchPenalty=-4, gapOpen=6, gapExtend=1, dpBandwidth=-1)]
+KNOWN_ANSWER_OPTS = {"gapOpen": "gap_open", "gapExtend": "gap_extend", "matchScore": "match_score", "mismatchPenalty": "mismatch_penalty", "dpBandwidth": "dp_bandwidth"}
+
+
 def ksw_mutate(rng, q, tlen, sub=0.05, indel=0.02, nfrac=0.01):
     """a target of tlen codes: the query (repeated as needed) with substitutions, insertions, deletions and N's"""
     out = []

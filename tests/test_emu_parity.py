@@ -10,7 +10,7 @@ import pytest
 import emu
 import mapping_harness as mh
 from conftest import load_oracle
-from parity_cases import SEL_VARIANTS, dollar_reads, sel_reads
+from parity_cases import KNOWN_ANSWER_SCHEMES, SEL_VARIANTS, _edited_pairs, dollar_reads, sel_reads   # (_edited_pairs: profiles/fuzz_more.py takes it from here)
 from util import assert_hits_equal, pack
 
 
@@ -442,41 +442,7 @@ def test_one_diagonal_chaining_editions_equal_the_doubles():
     assert agreed[8] > 4000 and agreed[0] > 9000
 
 
-def _edited_pairs(txps, n, seed):
-    """pairs of 100-bp reads (mate 2 from the other strand, 150 bases downstream) with the edits that decide between the gapless
-    path and a path with one gap: two substitutions anywhere, or a one- / two-base deletion or a one-base insertion a few
-    characters from either end of the read (behind it the diagonal has a handful of mismatches, often exactly two)"""
-    rng = np.random.default_rng(seed)
-    B = np.frombuffer(b"ACGT", dtype=np.uint8)
-    comp = np.zeros(256, np.uint8); comp[list(b"ACGT")] = list(b"TGCA")
-    long_enough = [t for t in txps if len(t) >= 400]
-
-    def edit(frag):                                         # frag: 104 characters of transcript, the read is (about) its first 100
-        kind = int(rng.integers(0, 6))
-        r = frag.copy()
-        if kind == 0:
-            for p in rng.choice(100, 2, replace=False): r[p] = B[(np.searchsorted(B, r[p]) + 1 + rng.integers(0, 3)) % 4]
-            return r[:100]
-        near = int(rng.integers(1, 7))
-        p = near if rng.random() < 0.5 else 100 - near
-        if kind in (1, 2): return np.concatenate([r[:p], r[p + 1:]])[:100]                   # one base missing from the read
-        if kind == 3: return np.concatenate([r[:p], r[p + 2:]])[:100]                        # two
-        if kind == 4: return np.concatenate([r[:p], B[rng.integers(0, 4, 1)], r[p:]])[:100]  # one extra
-        for p in rng.choice(100, 3, replace=False): r[p] = B[(np.searchsorted(B, r[p]) + 1) % 4]
-        return r[:100]
-    r1, r2 = [], []
-    for i in range(n):
-        t = long_enough[int(rng.integers(0, len(long_enough)))]
-        p = int(rng.integers(0, len(t) - 360))
-        a = edit(t[p:p + 104]); b = edit(t[p + 150:p + 254])
-        b = comp[b[::-1]]
-        if i % 2: a, b = b, a
-        r1.append(a.tobytes()); r2.append(b.tobytes())
-    return r1, r2
-
-
-@pytest.mark.parametrize("scheme", [dict(), dict(gapOpen=4, gapExtend=2), dict(matchScore=1, mismatchPenalty=-1, gapOpen=1, gapExtend=1),
-                                    dict(dpBandwidth=5), dict(matchScore=2, mismatchPenalty=-4, gapOpen=6, gapExtend=1, dpBandwidth=-1)])
+@pytest.mark.parametrize("scheme", KNOWN_ANSWER_SCHEMES)
 def test_selective_alignment_answers_known_without_ksw2(synth_medium, oracle_mod, scheme):
     """sel_side_score's two rules -- the gapless path when it loses no more than one gap, and with two mismatches the best of the
     gapless path and the few one-gap paths that could beat it -- on reads whose edits sit where those paths differ: every

@@ -10,7 +10,7 @@ import pytest
 import mapping_harness as mh
 import rapmap_amd as ra
 from conftest import GOLD, load_oracle
-from parity_cases import SEL_VARIANTS, dollar_reads, sel_reads
+from parity_cases import KNOWN_ANSWER_OPTS, KNOWN_ANSWER_SCHEMES, SEL_VARIANTS, _edited_pairs, dollar_reads, sel_reads
 from util import assert_hits_equal, pack
 
 pytestmark = pytest.mark.gpu
@@ -506,7 +506,7 @@ def test_perfect_hash_index(synth_small, synth_small_ph, oracle_mod, compact, gp
         assert r2.counters == g2.counters
 
 
-@pytest.mark.parametrize("case", range(6))
+@pytest.mark.parametrize("case", range(len(SEL_VARIANTS)))
 def test_selective_alignment(synth_small, oracle_mod, case, gpu):
     """config 5 (-s) through the C ABI: hits incl. alignment scores and counters == oracle, paired and single-end"""
     which, oo, go = SEL_VARIANTS[case]
@@ -522,6 +522,23 @@ def test_selective_alignment(synth_small, oracle_mod, case, gpu):
     gs = mp.map_reads(q2, o2, opts=ra.default_opts(**go))
     assert_hits_equal(rs.hit_offsets, rs.hits, gs.hit_offsets, gs.hits, "selAln single-end %s" % oo)
     assert rs.counters == gs.counters
+
+
+@pytest.mark.parametrize("scheme", KNOWN_ANSWER_SCHEMES)
+def test_selective_alignment_answers_known_without_ksw2(synth_medium, oracle_mod, scheme, gpu):
+    """the device twin of test_emu_parity's test of that name: sel_side_score's two rules and the strip alignments on reads whose edits sit where
+    the gapless path and the one-gap paths differ (parity_cases._edited_pairs, the one data set built to reach rule 2's gap-wins branch) --
+    every alignment score equals the oracle's, which runs ksw2 for all of them"""
+    ix, orc = load_oracle(synth_medium["idx"])
+    qi, mp = gpu(synth_medium["idx"], debug=False)
+    r1, r2 = _edited_pairs(synth_medium["txps"], 3000, 99)
+    q1, o1 = pack(r1); q2, o2 = pack(r2)
+    oo = dict(selAln=1, minScoreFraction=0.5, **scheme); go = dict(sel_aln=1, min_score_fraction=0.5, **{KNOWN_ANSWER_OPTS[k]: v for k, v in scheme.items()})
+    res = orc.map_pairs(q1, o1, q2, o2, opts=oracle_mod.default_opts(**oo), nthreads=8)
+    gr = mp.map_pairs(q1, o1, q2, o2, opts=ra.default_opts(**go))
+    assert res.counters["peHits"] > 1000
+    assert_hits_equal(res.hit_offsets, res.hits, gr.hit_offsets, gr.hits, "known answers %s" % scheme)
+    assert res.counters == gr.counters
 
 
 def test_selective_alignment_in_chunks(synth_small, oracle_mod, monkeypatch, gpu):

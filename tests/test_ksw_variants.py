@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, os.path.join(HERE,
 from oracle import oracle  # noqa: E402
 import emu  # noqa: E402
 import ksw_rows_cases as kc  # noqa: E402
+from sel_side_cases import _known_answer_rule, _strip_dp  # noqa: E402  (the restatements of sel_side_score's rules and of sel_tasks_strip)
 
 
 def _rows(el, grp, a, b, q_, e_, w, ring=-1):
@@ -115,41 +116,6 @@ def test_gapless_path_wins_when_it_loses_no_more_than_one_gap(scheme):
     assert hits > 500
 
 
-def _known_answer_rule(q, t, a, b, q_, e_, w):
-    """returns score or None (ask ksw2)"""
-    qlen, tlen = len(q), len(t)
-    aa, bb = abs(a), -abs(b)
-    M = aa - bb; qe = q_ + e_
-    if not (w != 0 and tlen >= qlen and qlen > 0 and aa >= 1 and q_ >= 0 and e_ >= 1 and aa - bb + qe <= 96): return None
-    sc = np.where((q < 4) & (t[:qlen] < 4), np.where(q == t[:qlen], aa, bb), 0)
-    smax = int(np.where(q < 4, aa, 0).sum()); U = int(sc.sum()); loss = smax - U
-    if loss <= qe: return U
-    # extension
-    if M > qe or loss != 2 * M: return None
-    Ld = 0
-    while q_ + (Ld + 1) * e_ < 2 * M: Ld += 1
-    Li = 0
-    while q_ + (Li + 1) * (e_ + aa) < 2 * M: Li += 1
-    if Ld > 3 or Li > 2: return None
-    if not (w < 0 or w >= 8): return None
-    if tlen < qlen + Ld + 1: return None
-    if (q >= 4).any() or (t[:qlen + Ld] >= 4).any(): return None
-    mm = np.nonzero(q != t[:qlen])[0]
-    assert len(mm) == 2
-    m1 = int(mm[0])
-    best = 2 * M
-    for L in range(1, Ld + 1):
-        d = np.nonzero(q != t[L:L + qlen])[0]
-        hm = int(d[-1]) if len(d) else -1
-        if hm <= m1 - 1: best = min(best, q_ + L * e_)
-    for L in range(1, Li + 1):
-        idx = np.arange(L, qlen)
-        d = idx[q[L:] != t[:qlen - L]]
-        hm = int(d[-1]) if len(d) else L - 1
-        if hm <= m1 + L - 1: best = min(best, q_ + L * (e_ + aa))
-    return smax - best
-
-
 @pytest.mark.parametrize("scheme", [(2, -4, 5, 3, 15), (2, -4, 4, 2, 15), (2, -4, 4, 2, 8), (1, -1, 1, 1, 15), (2, -6, 5, 3, 33), (4, -4, 6, 2, 20),
                                     (2, -4, 4, 2, -1), (3, -2, 2, 1, 15), (2, -4, 5, 3, 9), (1, -3, 2, 1, 15), (2, -4, 6, 1, 15)])
 def test_two_mismatches_lose_to_at_most_one_gap_run(scheme):
@@ -196,49 +162,6 @@ def test_two_mismatches_lose_to_at_most_one_gap_run(scheme):
     if M <= q_ + e_: assert tot > 1000
     if M <= q_ + e_ and (w < 0 or w >= 8) and q_ + 4 * e_ >= 2 * M and q_ + 3 * (e_ + abs(a)) >= 2 * M:   # (the rule's own limits)
         assert ext > 300 and gapwin > 0, (tot, ext, gapwin)
-
-
-NEG = -(1 << 28)
-
-def _strip_dp(q, t, a, b, go, ge, half=7):
-    """extension alignment from (0,0), affine gaps go + L*ge, score-only, max(mqe, mte); diagonals -half .. half+1"""
-    qlen, tlen = len(q), len(t)
-    aa, bb = abs(a), -abs(b)
-    W = 2 * half + 2
-    Hp = [NEG] * W; Fp = [NEG] * W
-    for c in range(W):
-        j = c - (half + 1)
-        if j == -1: Hp[c] = 0
-        elif 0 <= j < tlen: Hp[c] = -(go + ge * (j + 1))
-    mqe = NEG; mte = NEG
-    for i in range(qlen):
-        Ht = [NEG] * W; F = [NEG] * W
-        for c in range(W):
-            j = i + c - half
-            if j == -1:
-                Ht[c] = -(go + ge * (i + 1)); continue
-            if j < 0 or j >= tlen: continue
-            s = (aa if q[i] == t[j] else bb) if (q[i] < 4 and t[j] < 4) else 0
-            M = Hp[c] + s if Hp[c] > NEG else NEG
-            f = NEG
-            if c + 1 < W:
-                if Hp[c + 1] > NEG: f = Hp[c + 1] - go - ge
-                if Fp[c + 1] > NEG: f = max(f, Fp[c + 1] - ge)
-            F[c] = f
-            Ht[c] = max(M, f)
-        H = [NEG] * W
-        run = NEG
-        for c in range(W):
-            j = i + c - half
-            E = run - go - ge * c if run > NEG else NEG
-            if j == -1: H[c] = Ht[c]
-            elif 0 <= j < tlen: H[c] = max(Ht[c], E)
-            if Ht[c] > NEG: run = max(run, Ht[c] + ge * c)
-            if 0 <= j < tlen:
-                if i == qlen - 1: mqe = max(mqe, H[c])
-                if j == tlen - 1: mte = max(mte, H[c])
-        Hp, Fp = H, F
-    return max(mqe, mte)
 
 
 @pytest.mark.parametrize("scheme", [(2, -4, 4, 2, 15), (2, -4, 5, 3, 15), (1, -1, 1, 1, 15), (2, -6, 5, 3, 33), (2, -4, 4, 2, -1), (3, -2, 2, 1, 15), (2, -4, 6, 1, 15)])
